@@ -24,7 +24,6 @@ cross-check of the GPU result.
 import argparse
 import json
 import os
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # before the process's first HIP call (PyTorch's, here): what dgpu_runtime_hints(DGPU_HINT_EIGHT_HW_QUEUES) does for a host whose first HIP call is the library's (include/dock_gpu.h)
 import sys
 import time
 
@@ -158,6 +157,15 @@ def single_gpu_2p24(ca, FB, gen1, pool):
             "table_build_ms": round(tab24, 1), "bit_exact_vs_closed_form": ok}
 
 
+def dump_outputs(d, point):
+    """--dump-outputs: the timed step's result as the caller receives it — the 18 u64 words of the normalised Jacobian G1 point (X, Y, Z, six
+    little-endian Montgomery limbs each, include/dock_gpu.h) — written losslessly as float64: each word split into its low and high 32-bit halves,
+    shape (3, 12) = one row per coordinate, 32-bit words least significant first.  The inputs are seeded, so two builds compare file for file."""
+    os.makedirs(d, exist_ok=True)
+    words = np.ascontiguousarray(point, dtype=np.uint64).reshape(18).view(np.uint32)     # (x86-64: little-endian, low half first)
+    np.save(os.path.join(d, "msm_g1.npy"), words.astype(np.float64).reshape(3, 12))
+
+
 def timed(fn, k=5, warm=1):
     for _ in range(warm):
         fn()
@@ -181,7 +189,10 @@ def main():
     ap.add_argument("--reduce-shift", type=int, default=-1, help="development: dgpu_set_reduce_shift (log2 buckets per lane of the bucket reduction; -1 = automatic)")
     ap.add_argument("--reduce-lanes", type=int, default=-1, help="development: dgpu_set_reduce_lanes (0 = bit marginals, the default; 1 / 4 = the scan form of rounds 1-4)")
     ap.add_argument("--miller-pipeline", type=int, default=-1, help="development: dgpu_set_miller_pipeline (forms of the Miller kernels; -1 = the library's default, 31)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's result to DIR/msm_g1.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     sys.setswitchinterval(1e-4)            # (a host thread that returns from the library gets the interpreter within 0.1 ms instead of CPython's default 5)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -315,6 +326,8 @@ def main():
             print("call %3d: %8.2f -> %8.2f ms" % (i, (a_ - t0) * 1e3, (b_ - t0) * 1e3), file=sys.stderr)
     allocs_timed = ca.device_alloc_count() - allocs0
     assert (last == res).all(), "result changed between runs"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     per_rank_table_ms = [round(table_ms, 1)]
     collective = None
     if world > 1:

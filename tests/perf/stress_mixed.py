@@ -4,7 +4,6 @@ result compared with the one the same call gave single-threaded at start-up.  Us
 import os, sys, time, threading
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch  # noqa: F401
 import oracle_c as O, util as U, crypto_amd as ca

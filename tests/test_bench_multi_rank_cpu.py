@@ -48,3 +48,21 @@ def test_default_size_at_two_ranks_is_config_5s_share():
     # (2^23 terms per rank in pure Python integers would take minutes: the rule is asserted on the source, the flow on the small run above)
     out = _run(2, env_small + ["--log2n", "8"])
     assert out["config"]["terms_per_step"] == 512
+
+
+def test_dump_outputs_holds_the_last_timed_result(tmp_path):
+    """--dump-outputs DIR: the last timed step's (folded) result as DIR/msm_g1.npy — float64, the 18 result words as 36 exact 32-bit halves — and
+    that result is the closed form over both ranks' seeded terms, so two builds given the same arguments compare file for file"""
+    import importlib.util
+    import numpy as np
+    out = _run(2, ["--steps", "3", "--warmup", "0", "--log2n", "8", "--inflight", "2", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 3
+    a = np.load(tmp_path / "msm_g1.npy")
+    assert a.dtype == np.float64 and a.shape == (3, 12)
+    assert (a == np.floor(a)).all() and (a >= 0).all() and (a < 2.0 ** 32).all()
+    w = a.reshape(18, 2).astype(np.uint64)
+    words = w[:, 0] | (w[:, 1] << np.uint64(32))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    B = importlib.util.module_from_spec(spec); spec.loader.exec_module(B)
+    tot = sum(B.dot_mod_r(B.seeded_scalars(0x5EED2000 + r, 1 << 8), B.seeded_scalars(0x5EED1000 + r, 1 << 8)) for r in range(2)) % B.R_MOD
+    assert sum(int(words[i]) << (64 * i) for i in range(4)) == tot and int(words[12]) == 1      # (tests/bench_stub.py: a "point" is its integer, z = 1)

@@ -2,7 +2,6 @@
 # to stderr when it is built with them and DGPU_AGG_TRACE is set)
 import sys, os, time, numpy as np
 R_ = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path[:0] = [R_ + "/oracle", R_ + "/tests", R_]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import oracle_c as O, util as U, crypto_amd as ca
 from crypto_amd import aggregation as AG

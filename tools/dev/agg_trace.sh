@@ -4,7 +4,6 @@ cd /tmp && export TMPDIR=/tmp
 cat > /tmp/agg_one.py <<'PY'
 import sys, os, time, numpy as np
 R_ = "/root/repo"; sys.path[:0] = [R_ + "/oracle", R_ + "/tests", R_]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import oracle_c as O, util as U, crypto_amd as ca
 from crypto_amd import aggregation as AG

@@ -2,7 +2,6 @@
 system ROCm runtime instead of the one bundled with the torch wheel (crypto_amd/_native.py loads torch first when it is importable).  NOTORCH=1 T=6 python tools/dev/inflight_probe3.py"""
 import os, sys, time, threading, itertools
 sys.path[:0] = ["/root/repo"]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 if os.environ.get("NOTORCH"): sys.modules["torch"] = None
 import numpy as np
 import crypto_amd as ca

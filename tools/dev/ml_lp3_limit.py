@@ -3,7 +3,6 @@
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT + "/oracle", ROOT]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import oracle_c as O, crypto_amd as ca
 from crypto_amd import pairing
 from crypto_amd._native import lib

@@ -4,7 +4,6 @@ pairs), scale (dgpu_g1_scale_batch, 1024 points: k_g1_scale_oct), one (dgpu_lego
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch  # noqa: F401
 import crypto_amd as ca
