@@ -256,8 +256,9 @@ __global__ void __launch_bounds__(64) k_fold_affine_g2(const uint32_t *__restric
 // deep each: 1280 product-depths.  Here the four lanes of a point run ONE chain over both halves of the GLV split through the round forms of ec29.hip.h
 // (a doubling three products deep, an addition four) with TWO bits of each half per addition: the addend of a step is T[d1 + 4 d2] = d1 P + d2 phi(P),
 // d1, d2 < 4, from a table of fifteen sums the quad builds first (one doubling, ten additions, three products by beta) and keeps in LDS —
-// 64 x (2 x 3 + 4) = 640 product-depths, and the additions fall on the same steps for every point of the wave.  13 x 30-bit signed field.  Points are
-// elements of the prime-order subgroup (phi(P) = lambda P holds there, and no table entry is the identity).
+// 64 x (2 x 3 + 4) = 640 product-depths, and the additions fall on the same steps for every point of the wave.  13 x 30-bit signed field.  The result
+// is k1 P + k2 phi(P): [m] P for P in the prime-order subgroup (phi(P) = lambda P holds there, and no table entry is the identity).  Any other point of
+// the curve gets the same k1 P + k2 phi(P); table entries that are the identity there (P of order 3: phi(P) = P, 3 P = O) carry a bit of `tinf`.
 // 53 KB of LDS per 64-lane block: three blocks per CU, i.e. 12 288 points in one round of the chip — the call sites scale hundreds to a few thousand points.
 constexpr int SCQ_ENTRY = 4 * SN, SCQ_STRIDE = 16 * SCQ_ENTRY + 1;          // words per entry / per quad (odd: the sixteen quads of a wave read different banks)
 __global__ void __launch_bounds__(64) k_g1_scale_quad(const uint32_t *__restrict__ p_abi, const uint8_t *__restrict__ is_inf, const uint32_t *__restrict__ scalars, int scalar_stride,
@@ -286,6 +287,7 @@ __global__ void __launch_bounds__(64) k_g1_scale_quad(const uint32_t *__restrict
         for (int j = 0; j < SCQ_ENTRY; j++) o[j] = src[j];
     };
     Xyzz<F> acc;
+    uint32_t tinf = 0;                                                       // bit e: entry e is the identity (only for a P outside the subgroup)
     if (!pinf) {
         F beta;
         {   // beta (ec29_two_lane.hip.h xyzz_phi's constant) from the 29-bit form into this field
@@ -300,17 +302,20 @@ __global__ void __launch_bounds__(64) k_g1_scale_quad(const uint32_t *__restrict
         fs_from_abi(P1.x, p_abi + i * 24); fs_from_abi(P1.y, p_abi + i * 24 + 12); fset_one(P1.zz); fset_one(P1.zzz);
         park(1, P1);
         xyzz_dbl_rounds(M, P1, q4); park(2, M);                              // 2 P
-        { bool f = false; xyzz_add_rounds(M, f, P1, false, q4); } park(3, M); // 3 P
+        { bool f = false; xyzz_add_rounds(M, f, P1, false, q4); tinf |= (uint32_t)f << 3; } park(3, M); // 3 P
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // (one wave per block: the table is written and read by the same wave, in order)
 #pragma unroll 1
         for (int d2 = 1; d2 < 4; d2++) {                                     // d2 phi(P) = phi(d2 P): x times beta
             Xyzz<F> Q; fetch(Q, d2);
             { F xn; fnorm(xn, Q.x); fmul(Q.x, xn, beta); }
             park(4 * d2, Q);
+            const bool qinf = (tinf >> d2) & 1u;
+            tinf |= (uint32_t)qinf << (4 * d2);
 #pragma unroll 1
             for (int d1 = 1; d1 < 4; d1++) {
                 Xyzz<F> S; fetch(S, d1);
-                bool f = false; xyzz_add_rounds(S, f, Q, false, q4);         // (d1 + d2 lambda) P: never the identity, and d1 P != +- d2 phi(P)
+                bool f = (tinf >> d1) & 1u; xyzz_add_rounds(S, f, Q, qinf, q4);  // (d1 + d2 lambda) P: never the identity in the subgroup
+                tinf |= (uint32_t)f << (4 * d2 + d1);
                 park(4 * d2 + d1, S);
             }
         }
@@ -325,7 +330,7 @@ __global__ void __launch_bounds__(64) k_g1_scale_quad(const uint32_t *__restrict
             { Xyzz<F> d; xyzz_dbl_rounds(d, acc, q4); xyzz_dbl_rounds(acc, d, q4); }        // (on an identity accumulator: zeros in, zeros out)
             const uint32_t sel = ((s[b >> 5] >> (b & 31)) & 3u) | (((s[4 + (b >> 5)] >> (b & 31)) & 3u) << 2);
             Xyzz<F> B; fetch(B, sel ? (int)sel : 1);
-            xyzz_add_rounds(acc, inf, B, sel == 0, q4);
+            xyzz_add_rounds(acc, inf, B, sel == 0 || ((tinf >> sel) & 1u), q4);
         }
     }
     if (add_abi) {
@@ -365,6 +370,7 @@ __global__ void __launch_bounds__(64 * SCO_WAVES) k_g1_scale_oct(const uint32_t 
     constexpr int HW = SCQ_ENTRY + 1;
     __shared__ uint32_t tab[16 * SCQ_STRIDE];
     __shared__ uint32_t hand[(SCO_WAVES - 1) * 16 * HW];                     // the pieces of waves 0 .. 2 of every point (+ identity flags)
+    __shared__ uint32_t rowinf[16 * SCO_WAVES];                              // identity bits of the table row each wave builds (see k_g1_scale_quad)
     const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6), pq = lane >> 2;
     const size_t i_raw = (size_t)blockIdx.x * 16 + pq;
     const bool live = i_raw < n;                                             // (padding quads follow the barriers and write nothing)
@@ -385,12 +391,14 @@ __global__ void __launch_bounds__(64 * SCO_WAVES) k_g1_scale_oct(const uint32_t 
 #pragma unroll
         for (int j = 0; j < SCQ_ENTRY; j++) o[j] = src[j];
     };
+    uint32_t rinf = 0;                                                       // this wave's row of identity bits
     if (!pinf) {
         Xyzz<F> P1, P2, P3;
         fs_from_abi(P1.x, p_abi + i * 24); fs_from_abi(P1.y, p_abi + i * 24 + 12); fset_one(P1.zz); fset_one(P1.zzz);
         xyzz_dbl_rounds(P2, P1, q4);
-        P3 = P2; { bool f = false; xyzz_add_rounds(P3, f, P1, false, q4); }
-        if (wave == 0) { park_at(mine + 1 * SCQ_ENTRY, P1); park_at(mine + 2 * SCQ_ENTRY, P2); park_at(mine + 3 * SCQ_ENTRY, P3); }
+        bool p3inf = false;
+        P3 = P2; xyzz_add_rounds(P3, p3inf, P1, false, q4);                  // (3 P = O: P of order 3, outside the subgroup)
+        if (wave == 0) { park_at(mine + 1 * SCQ_ENTRY, P1); park_at(mine + 2 * SCQ_ENTRY, P2); park_at(mine + 3 * SCQ_ENTRY, P3); rinf = (uint32_t)p3inf << 3; }
         else {                                                               // row d2 = wave: phi(d2 P) (x times beta), then + d1 P
             F beta;
             {
@@ -402,17 +410,24 @@ __global__ void __launch_bounds__(64 * SCO_WAVES) k_g1_scale_oct(const uint32_t 
                 fp_to_abi(w, b29); fs_from_abi(beta, w);
             }
             Xyzz<F> Q = wave == 1 ? P1 : (wave == 2 ? P2 : P3);
+            const bool qinf = wave == 3 && p3inf;
             { F xn; fnorm(xn, Q.x); fmul(Q.x, xn, beta); }
             park_at(mine + 4 * wave * SCQ_ENTRY, Q);
+            rinf = (uint32_t)qinf << (4 * wave);
 #pragma unroll 1
             for (int d1 = 1; d1 < 4; d1++) {
                 Xyzz<F> S = d1 == 1 ? P1 : (d1 == 2 ? P2 : P3);
-                bool f = false; xyzz_add_rounds(S, f, Q, false, q4);         // (d1 + d2 lambda) P: never the identity, and d1 P != +- d2 phi(P)
+                bool f = d1 == 3 && p3inf; xyzz_add_rounds(S, f, Q, qinf, q4); // (d1 + d2 lambda) P: never the identity in the subgroup
+                rinf |= (uint32_t)f << (4 * wave + d1);
                 park_at(mine + (4 * wave + d1) * SCQ_ENTRY, S);
             }
         }
     }
+    if (q4.role == 0) rowinf[wave * 16 + pq] = rinf;
     __syncthreads();                                                         // (the table is complete; every lane of the block is here)
+    uint32_t tinf = 0;
+#pragma unroll
+    for (int w = 0; w < SCO_WAVES; w++) tinf |= rowinf[w * 16 + pq];
     Xyzz<F> acc; bool inf = true;
     fzero(acc.x); fzero(acc.y); fzero(acc.zz); fzero(acc.zzz);
     const uint32_t *s = scalars + i * (size_t)scalar_stride;                 // (k1 | k2), four words each
@@ -424,7 +439,7 @@ __global__ void __launch_bounds__(64 * SCO_WAVES) k_g1_scale_oct(const uint32_t 
             const int b = 2 * j;
             const uint32_t sel = ((s[b >> 5] >> (b & 31)) & 3u) | (((s[4 + (b >> 5)] >> (b & 31)) & 3u) << 2);
             Xyzz<F> B; fetch_at(B, mine + (sel ? (int)sel : 1) * SCQ_ENTRY);
-            xyzz_add_rounds(acc, inf, B, sel == 0, q4);
+            xyzz_add_rounds(acc, inf, B, sel == 0 || ((tinf >> sel) & 1u), q4);
         }
 #pragma unroll 1
         for (int k = 0; k < lo; k++) { Xyzz<F> d; xyzz_dbl_rounds(d, acc, q4); xyzz_dbl_rounds(acc, d, q4); }

@@ -111,7 +111,9 @@ uint64_t dgpu_device_alloc_count(void);
  * scalar, and what arkworks computes).  A scalar with bit 255 set has no meaning that is independent of arkworks' window width — its
  * `make_digits` reads bit 255 in the top window unless the width divides 255 (n <= 32, 2^18 < n <= 2^20, 2^21 < n <= 2^23
  * ignore it, every other n multiplies by the full 256-bit integer) — so every MSM entry point REFUSES such input with DGPU_E_BADARG and the
- * caller stays on its CPU path; `Fr::into_bigint()` never produces it.  (tests/test_gpu_msm.py::test_scalars_with_bit_255) */
+ * caller stays on its CPU path; `Fr::into_bigint()` never produces it.  (tests/test_gpu_msm.py::test_scalars_with_bit_255)
+ * Bases may be any points of the curve, in the prime-order subgroup or not (every MSM entry point, handles, tables and the resident-bases
+ * cache included: tests/test_gpu_off_subgroup.py). */
 int32_t dgpu_msm_g1(const uint64_t *bases_xy /* n*12 */, const uint8_t *is_inf /* n or NULL */,
                     const uint64_t *scalars /* n*4, canonical */, size_t n, uint64_t out_xyz[18]);
 /* replaces <G1Projective as VariableBaseMSM>::msm_unchecked(bases, &[Fr]) (Fr in Montgomery form, R = 2^256)
@@ -252,7 +254,9 @@ int32_t dgpu_lincomb_g2(const uint64_t *points_xy, const uint8_t *is_inf, const 
 /* ---- pairings ----
  * replaces Bls12_381::multi_miller_loop(a, b) — utils/src/randomized_pairing_check.rs:207,
  * legogroth16/src/verifier.rs:69-76.  skip[i] != 0 marks a pair with an identity member (arkworks
- * filters those out).  Output: raw MillerLoopOutput, Fp12 as c0.c0.c0 ... c1.c2.c1 (72 u64). */
+ * filters those out).  Output: raw MillerLoopOutput, Fp12 as c0.c0.c0 ... c1.c2.c1 (72 u64).
+ * Every Miller-loop entry point accepts any P on E(Fp) and any Q of order greater than the loop's doubling chain on E'(Fp2), in the
+ * prime-order subgroups or not; only all-zero words or a skip flag mark an identity member (P = (0, 2) is a point). */
 int32_t dgpu_multi_miller_loop(const uint64_t *p_xy /* n*12 */, const uint64_t *q_xy /* n*24 */,
                                const uint8_t *skip /* n or NULL */, size_t n, uint64_t out_f12[72]);
 /* E::G2Prepared — the form in which the reference's verifier and pairing checker HOLD their G2 operands
@@ -284,7 +288,8 @@ int32_t dgpu_multi_miller_loop_mixed(const uint64_t *p_aff /* n_aff x 12 */, con
  * and the scaling chains of the P_i run side by side and the scaled points never visit the host (1024 pairs: 1.64 -> 1.34 ms).
  * scalars: n_aff x 4 canonical words (scalar_stride = 4) or ONE scalar for every pair (scalar_stride = 0), reduced mod r; a pair whose
  * scaled point is the identity (m = 0 mod r, P all zero), whose Q is all zero or whose skip flag is set contributes one.  P_i in the
- * prime-order subgroup (the invariant of arkworks' G1Affine: the scaling uses the endomorphism). */
+ * prime-order subgroup (the invariant of arkworks' G1Affine: the scaling uses the endomorphism); any other P is scaled as dgpu_g1_scale_batch
+ * scales it, and a pair whose scaled point turns out to be the identity on the device contributes one in both forms of the call. */
 int32_t dgpu_multi_miller_loop_scaled(const uint64_t *p_aff /* n_aff x 12 */, const uint64_t *scalars, size_t scalar_stride, const uint64_t *q_aff /* n_aff x 24 */,
                                       const uint8_t *skip_aff, size_t n_aff,
                                       const uint64_t *p_prep /* n_prep x 12 */, const uint64_t *coeffs /* n_prep x DGPU_G2_PREPARED_WORDS */, const uint8_t *skip_prep, size_t n_prep,
@@ -308,7 +313,9 @@ int32_t dgpu_final_exponentiation(const uint64_t in_f12[72], uint64_t out_f12[72
 /* ---- pieces of utils::randomized_pairing_check::RandomizedPairingChecker (utils/src/randomized_pairing_check.rs:24-215) ----
  * out_i = s_i * P_i as affine points (the per-equation `a.mul_bigint(m)` scalings, :125-127,152-158), batched on the GPU.
  * scalar_stride = 4: one canonical scalar per point; scalar_stride = 0: the same scalar for every point.
- * negate[i] != 0 returns -(s_i P_i) (the `-c.mul_bigint(m)` of add_multiple_sources, :156-158). */
+ * negate[i] != 0 returns -(s_i P_i) (the `-c.mul_bigint(m)` of add_multiple_sources, :156-158).
+ * P_i in G1: the scaling computes k1 P + k2 phi(P) for the GLV split s mod r = k1 + k2 lambda, which is [s] P there only; for any other
+ * point of the curve it returns that same k1 P + k2 phi(P) (e.g. ((k1 + k2) mod 3) P for P of order 3), the identity flagged as usual. */
 int32_t dgpu_g1_scale_batch(const uint64_t *p_xy /* n*12 */, const uint8_t *is_inf, const uint64_t *scalars, size_t scalar_stride,
                             const uint8_t *negate, size_t n, uint64_t *out_xy /* n*12 */, uint8_t *out_inf /* n */);
 /* GT arithmetic on the host: PairingOutput `+` is the Fp12 product, `mul_bigint` the power (:136 `self.right += out.mul_bigint(m)`) */

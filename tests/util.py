@@ -110,3 +110,118 @@ def on_both_paths(fn):
     with bucket_pipeline():
         b = fn()
     return a, b
+
+
+# ---- points of the curves outside the prime-order subgroups (tests/test_gpu_off_subgroup.py) ----------------------------------------------------
+H1 = 0x396C8C005555E1568C00AAAB0000AAAB          # #E(Fp) = H1 * R       (y^2 = x^3 + 4)
+H2 = 0x5D543A95414E7F1091D50792876A202CD91DE4547085ABAA68A205B2E5A7DDFA628F1CB4D9E82EF21537E293A6691AE1616EC6E786F0C70CF1C38E31C7238E5   # #E'(Fp2) = H2 * R
+GLV_LAMBDA = 0xAC45A4010001A40200000000FFFFFFFF   # lambda^2 + lambda + 1 = 0 mod R: the host's split of the G1 scalings (k mod R = k1 + k2 lambda)
+
+
+def glv_split(k):
+    """(k1, k2) with k mod R = k1 + k2 GLV_LAMBDA, k1 < GLV_LAMBDA (what the G1 scaling kernels are fed with)"""
+    k2, k1 = divmod(k % R, GLV_LAMBDA)
+    return k1, k2
+
+
+def small_primes_dividing(n, bound=1 << 16):
+    out, p = [], 2
+    while p < bound:
+        if n % p == 0:
+            out.append(p)
+            while n % p == 0:
+                n //= p
+        p += 1
+    return out
+
+
+def fp_sqrt(a):
+    s = pow(a % P, (P + 1) // 4, P)
+    return s if s * s % P == a % P else None
+
+
+def fp2_sqrt(a):
+    """a square root in Fp2 (p = 3 mod 4), None if there is none"""
+    a1 = M.f2_pow(a, (P - 3) // 4)
+    alpha = M.f2_mul(a1, M.f2_mul(a1, a))
+    x0 = M.f2_mul(a1, a)
+    if alpha == (P - 1, 0):
+        x = M.f2_mul((0, 1), x0)
+    else:
+        x = M.f2_mul(M.f2_pow(M.f2_add(M.F2_ONE, alpha), (P - 1) // 2), x0)
+    return x if M.f2_sqr(x) == a else None
+
+
+def g1_lift(x):
+    y = fp_sqrt(x ** 3 + 4)
+    return None if y is None else (x % P, y)
+
+
+def g2_lift(x):
+    y = fp2_sqrt(M.f2_add(M.f2_mul(M.f2_sqr(x), x), M.B_TWIST))
+    return None if y is None else (x, y)
+
+
+def _first(lift, xs, ok):
+    for x in xs:
+        pt = lift(x)
+        if pt is not None and ok(pt):
+            return pt
+    raise AssertionError("no point found")
+
+
+def _order_ell(mul, pt, n, ell):
+    """a point of order exactly ell from pt (n: the group order): the ell-part of pt, then times ell until the next step would be the identity"""
+    while n % ell == 0:
+        n //= ell
+    q = mul(pt, n)
+    if q is None:
+        return None
+    while mul(q, ell) is not None:
+        q = mul(q, ell)
+    return q
+
+
+def off_subgroup_points():
+    """Model points (ints) outside the prime-order subgroups, with the order each is built to have (None: a multiple of R, not R itself):
+    G1: S = (0, 2) and -S (order 3: every point with x = 0 is 3-torsion), T (order divisible by R and by a cofactor prime), S11 (order 11);
+    G2: T2 (like T), S2 (order ELL2, the smallest prime dividing the G2 cofactor)."""
+    global _OFF
+    if _OFF is None:
+        S = (0, 2)
+        T = _first(g1_lift, range(1, 100), lambda t: M.g1_mul(t, R) is not None)
+        S11 = _order_ell(M.g1_mul, _first(g1_lift, range(1, 100), lambda t: _order_ell(M.g1_mul, t, H1 * R, 11) is not None), H1 * R, 11)
+        ell2 = small_primes_dividing(H2)[0]
+        T2 = _first(g2_lift, ((a, 1) for a in range(100)), lambda t: M.g2_mul(t, R) is not None)
+        S2 = _order_ell(M.g2_mul, _first(g2_lift, ((a, 1) for a in range(100)), lambda t: _order_ell(M.g2_mul, t, H2 * R, ell2) is not None), H2 * R, ell2)
+        _OFF = {"S": (S, 3), "-S": (M.g1_neg(S), 3), "T": (T, None), "S11": (S11, 11), "T2": (T2, None), "S2": (S2, ell2)}
+    return _OFF
+
+
+_OFF = None
+
+
+def jac_abi(G, aff):
+    """affine ABI words -> the oracle's Jacobian (Z = one)"""
+    one = O.fp_to_mont(np.array([[1, 0, 0, 0, 0, 0]], np.uint64)).reshape(-1)
+    z = np.zeros(G.AW // 2, np.uint64); z[:6] = one
+    return np.concatenate([np.asarray(aff, np.uint64), z])
+
+
+def plus_multiples(G, bases, e, T_abi, threads=8):
+    """B_i = bases_i + e_i T (affine ABI words; e_i = 0 leaves the base as it is), on `threads` host threads"""
+    from concurrent.futures import ThreadPoolExecutor
+    out = np.array(bases, dtype=np.uint64, copy=True)
+    mult = {}
+    for k in sorted(set(int(v) for v in e) - {0}):
+        mult[k] = G.mul(T_abi, O.int_to_limbs(k, 4))
+    idx = np.nonzero(np.asarray(e))[0]
+
+    def work(part):
+        for i in part:
+            a, inf = G.to_affine(G.add(jac_abi(G, out[i]), mult[int(e[i])]))
+            assert not inf
+            out[i] = a
+    with ThreadPoolExecutor(threads) as ex:
+        list(ex.map(work, np.array_split(idx, threads)))
+    return out
