@@ -918,6 +918,16 @@ int32_t msm_oneshot(const RawBases &rb, const uint64_t *scalars, size_t n, bool 
     return msm_oneshot_ctx<C, HF>(rb, scalars, n, mont, out);
 }
 
+// prepared records p (n of them, on the current context, written) become a plain handle of `kind`; the caller holds no slot
+template <class C>
+void bases_register(void *p, size_t n, uint64_t *handle, int kind) {
+    *handle = register_handle(p, n, kind);
+    (void)reserve_slots<C>(2, n, 0, nullptr);       // every slot is ready for an MSM over this query before the first proof arrives
+    if (n && n <= SMALL_MSM_MAX_N && n <= gs.small_max.load()) {     // ... and a handle the small path will serve gets its table now (best effort: ~1 ms once, no allocation at its calls)
+        HandleRef ref(*handle);
+        if (ref.ok) { SlotLock L; if (L.ok && hipSetDevice(cur().device) == hipSuccess) { SmallSub sub; (void)small_sub_for<C>(*L.s, *handle, ref.h, 0, 0, sub, true); } }
+    }
+}
 // rec_hash != nullptr (the resident-bases cache, bases_cache.hpp): the fingerprint of every raw record, computed on the device from the staged bytes
 template <class C>
 int32_t bases_upload(const RawBases &rb, size_t n, uint64_t *handle, int kind, std::vector<uint64_t> *rec_hash = nullptr) {
@@ -941,12 +951,7 @@ int32_t bases_upload(const RawBases &rb, size_t n, uint64_t *handle, int kind, s
         if (gs.prof) prof_flush(sl);
         if (rc) { (void)hipFree(p); return rc; }
     }
-    *handle = register_handle(p, n, kind);
-    (void)reserve_slots<C>(2, n, 0, nullptr);       // every slot is ready for an MSM over this query before the first proof arrives
-    if (n && n <= SMALL_MSM_MAX_N && n <= gs.small_max.load()) {     // ... and a handle the small path will serve gets its table now (best effort: ~1 ms once, no allocation at its calls)
-        HandleRef ref(*handle);
-        if (ref.ok) { SlotLock L; if (L.ok && hipSetDevice(cur().device) == hipSuccess) { SmallSub sub; (void)small_sub_for<C>(*L.s, *handle, ref.h, 0, 0, sub, true); } }
-    }
+    bases_register<C>(p, n, handle, kind);
     return DGPU_OK;
 }
 

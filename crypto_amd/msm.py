@@ -259,6 +259,24 @@ class DeviceBases:
         return cls.from_handle(curve, h.value, len(structs))
 
     @classmethod
+    def from_serialized(cls, curve, data, compressed=True, validate=True):
+        """dgpu_bases_upload_*_serialized: a resident query straight from arkworks' encoded points, decoded and validated on the device.  A
+        refused key raises DockGpuError whose `index` is the lowest refused point (and leaves nothing on the device)."""
+        _ensure()
+        sz = (48 if compressed else 96) * (1 if curve.tag == "g1" else 2)
+        if len(data) % sz:
+            raise ValueError("length is not a multiple of %d" % sz)
+        n = len(data) // sz
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        h, bad = C.c_uint64(0), C.c_size_t(0)
+        rc = curve.fn("dgpu_bases_upload_%s_serialized")(_p(buf), n, int(compressed) | (0 if validate else 2), None, None, C.byref(h), C.byref(bad))
+        if rc:
+            err = DockGpuError(rc, "dgpu_bases_upload_serialized")
+            err.index = bad.value if rc == -3 else None
+            raise err
+        return cls.from_handle(curve, h.value, n)
+
+    @classmethod
     def from_handle(cls, curve, handle, n):
         """adopt a bases handle produced on the device (WindowTable.multiply_many_to_bases)"""
         self = cls.__new__(cls)

@@ -540,6 +540,21 @@ int32_t dgpu_g1_deserialize(const uint8_t *in, size_t n, int32_t mode, uint64_t 
 int32_t dgpu_g2_serialize(const uint64_t *xy /* n*24 */, const uint8_t *is_inf, size_t n, int32_t compressed, uint8_t *out);
 int32_t dgpu_g2_deserialize(const uint8_t *in, size_t n, int32_t mode, uint64_t *xy /* n*24 */, uint8_t *is_inf /* n */);
 
+/* ---- the same decoding and validation on the device (one point per lane; the calling thread's context, dgpu_set_device) ----
+ * dgpu_g1/g2_deserialize_device: the mode bits, verdict and (when accepted) words and flags of dgpu_g1/g2_deserialize.  first_bad (may be NULL):
+ * n on success, else the LOWEST refused index (DGPU_E_BADARG).  Outputs are unspecified on refusal.  n = 0: DGPU_OK.
+ * dgpu_bases_upload_g1/g2_serialized: bytes -> a resident plain bases handle, what dgpu_bases_upload_* makes of the decoded points (MSMs, precompute,
+ * dgpu_handle_len as for those); xy / is_inf (may be NULL): the decoded words too.  On refusal or error no handle exists and no device memory is kept.
+ * dgpu_g1/g2_validate_batch: Validate::Yes of affine ABI words already in memory: ok[i] = 1 iff point i is the identity (is_inf[i] or all-zero
+ * words) or reduced (< p), on the curve and in G1 / G2 — the checks an aggregate proof's points get on the host (g1_words_valid / g2_words_valid).
+ * Argument checks come first (DGPU_E_BADARG); without a device n >= 1 is DGPU_E_NODEVICE, never a host result. */
+int32_t dgpu_g1_deserialize_device(const uint8_t *in, size_t n, int32_t mode, uint64_t *xy /* n*12 */, uint8_t *is_inf /* n */, size_t *first_bad);
+int32_t dgpu_g2_deserialize_device(const uint8_t *in, size_t n, int32_t mode, uint64_t *xy /* n*24 */, uint8_t *is_inf /* n */, size_t *first_bad);
+int32_t dgpu_bases_upload_g1_serialized(const uint8_t *in, size_t n, int32_t mode, uint64_t *xy, uint8_t *is_inf, uint64_t *handle, size_t *first_bad);
+int32_t dgpu_bases_upload_g2_serialized(const uint8_t *in, size_t n, int32_t mode, uint64_t *xy, uint8_t *is_inf, uint64_t *handle, size_t *first_bad);
+int32_t dgpu_g1_validate_batch(const uint64_t *xy /* n*12 */, const uint8_t *is_inf, size_t n, uint8_t *ok /* n */);
+int32_t dgpu_g2_validate_batch(const uint64_t *xy /* n*24 */, const uint8_t *is_inf, size_t n, uint8_t *ok /* n */);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

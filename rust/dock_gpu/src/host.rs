@@ -357,6 +357,24 @@ pub fn deserialize_g1(bytes: &[u8], n: usize, compressed: bool, validate: bool) 
     if unsafe { dgpu_g1_deserialize(bytes.as_ptr(), n, mode, xy.as_mut_ptr(), inf.as_mut_ptr()) } != DGPU_OK { return None; }
     Some((0..n).map(|i| g1_affine(xy[12 * i..12 * i + 12].try_into().unwrap(), inf[i])).collect())
 }
+/// deserialize_g1 decoded and validated on the current device.  Err(Some(i)): point i is the lowest refused one; Err(None): a length that does not
+/// match, no device, or another error
+pub fn deserialize_g1_device(bytes: &[u8], n: usize, compressed: bool, validate: bool) -> Result<Vec<G1Affine>, Option<usize>> {
+    if bytes.len() != n * if compressed { 48 } else { 96 } { return Err(None); }
+    let (mut xy, mut inf, mut bad) = (ark_std::vec![0u64; n * 12], ark_std::vec![0u8; n], 0usize);
+    let mode = (compressed as i32) | if validate { 0 } else { DGPU_SERDE_NO_VALIDATE };
+    let rc = unsafe { dgpu_g1_deserialize_device(bytes.as_ptr(), n, mode, xy.as_mut_ptr(), inf.as_mut_ptr(), &mut bad) };
+    if rc == DGPU_E_BADARG { return Err(Some(bad)); }
+    if rc != DGPU_OK { return Err(None); }
+    Ok((0..n).map(|i| g1_affine(xy[12 * i..12 * i + 12].try_into().unwrap(), inf[i])).collect())
+}
+/// `Valid::check` of every point on the current device (on the curve and in G1; the identity passes); None: no device or another error
+pub fn validate_g1_batch(points: &[G1Affine]) -> Option<Vec<bool>> {
+    let (xy, inf) = pack_g1(points);
+    let mut ok = ark_std::vec![0u8; points.len()];
+    if unsafe { dgpu_g1_validate_batch(xy.as_ptr(), inf.as_ptr(), points.len(), ok.as_mut_ptr()) } != DGPU_OK { return None; }
+    Some(ok.iter().map(|&v| v != 0).collect())
+}
 pub fn serialize_g2(points: &[G2Affine], compressed: bool) -> Option<Vec<u8>> {
     let (xy, inf) = pack_g2(points);
     let mut out = ark_std::vec![0u8; points.len() * if compressed { 96 } else { 192 }];
@@ -369,4 +387,21 @@ pub fn deserialize_g2(bytes: &[u8], n: usize, compressed: bool, validate: bool) 
     let mode = (compressed as i32) | if validate { 0 } else { DGPU_SERDE_NO_VALIDATE };
     if unsafe { dgpu_g2_deserialize(bytes.as_ptr(), n, mode, xy.as_mut_ptr(), inf.as_mut_ptr()) } != DGPU_OK { return None; }
     Some((0..n).map(|i| g2_affine(xy[24 * i..24 * i + 24].try_into().unwrap(), inf[i])).collect())
+}
+/// deserialize_g2 decoded and validated on the current device (see deserialize_g1_device)
+pub fn deserialize_g2_device(bytes: &[u8], n: usize, compressed: bool, validate: bool) -> Result<Vec<G2Affine>, Option<usize>> {
+    if bytes.len() != n * if compressed { 96 } else { 192 } { return Err(None); }
+    let (mut xy, mut inf, mut bad) = (ark_std::vec![0u64; n * 24], ark_std::vec![0u8; n], 0usize);
+    let mode = (compressed as i32) | if validate { 0 } else { DGPU_SERDE_NO_VALIDATE };
+    let rc = unsafe { dgpu_g2_deserialize_device(bytes.as_ptr(), n, mode, xy.as_mut_ptr(), inf.as_mut_ptr(), &mut bad) };
+    if rc == DGPU_E_BADARG { return Err(Some(bad)); }
+    if rc != DGPU_OK { return Err(None); }
+    Ok((0..n).map(|i| g2_affine(xy[24 * i..24 * i + 24].try_into().unwrap(), inf[i])).collect())
+}
+/// `Valid::check` of every point on the current device (on the twist and in G2; the identity passes)
+pub fn validate_g2_batch(points: &[G2Affine]) -> Option<Vec<bool>> {
+    let (xy, inf) = pack_g2(points);
+    let mut ok = ark_std::vec![0u8; points.len()];
+    if unsafe { dgpu_g2_validate_batch(xy.as_ptr(), inf.as_ptr(), points.len(), ok.as_mut_ptr()) } != DGPU_OK { return None; }
+    Some(ok.iter().map(|&v| v != 0).collect())
 }

@@ -150,6 +150,20 @@ impl ResidentG1 {
         g1_from_xyz(&out)
     }
 }
+impl ResidentG1 {
+    /// a resident query straight from arkworks' encoded points (`CanonicalSerialize` of each), decoded and validated on the current device; the host
+    /// copy is the decoded points.  Err(Some(i)): point i is the lowest refused one (nothing stays on the device); Err(None): no device or another error
+    pub fn from_serialized(bytes: &[u8], n: usize, compressed: bool, validate: bool) -> Result<Self, Option<usize>> {
+        if bytes.len() != n * if compressed { 48 } else { 96 } { return Err(None); }
+        let (mut xy, mut inf, mut bad, mut handle) = (ark_std::vec![0u64; n * 12], ark_std::vec![0u8; n], 0usize, 0u64);
+        let mode = (compressed as i32) | if validate { 0 } else { DGPU_SERDE_NO_VALIDATE };
+        let rc = unsafe { dgpu_bases_upload_g1_serialized(bytes.as_ptr(), n, mode, xy.as_mut_ptr(), inf.as_mut_ptr(), &mut handle, &mut bad) };
+        if rc == DGPU_E_BADARG { return Err(Some(bad)); }
+        if rc != DGPU_OK { return Err(None); }
+        let host = (0..n).map(|i| g1_affine(xy[12 * i..12 * i + 12].try_into().unwrap(), inf[i])).collect();
+        Ok(ResidentG1 { handle, host })
+    }
+}
 impl Drop for ResidentG1 { fn drop(&mut self) { if self.handle != 0 { unsafe { dgpu_bases_free(self.handle); } } } }
 
 /// the same for G2 (b_g2_query)
@@ -168,6 +182,20 @@ impl ResidentG2 {
         let rc = if self.handle == 0 { -1 } else { unsafe { dgpu_msm_g2_handle(self.handle, offset, scalars.as_ptr() as *const u64, n, 0, out.as_mut_ptr()) } };
         if rc != DGPU_OK { return G2Projective::msm_bigint(&self.host[offset..offset + n], &scalars[..n]); }
         g2_from_xyz(&out)
+    }
+}
+impl ResidentG2 {
+    /// a resident query straight from arkworks' encoded points (`CanonicalSerialize` of each), decoded and validated on the current device; the host
+    /// copy is the decoded points.  Err(Some(i)): point i is the lowest refused one (nothing stays on the device); Err(None): no device or another error
+    pub fn from_serialized(bytes: &[u8], n: usize, compressed: bool, validate: bool) -> Result<Self, Option<usize>> {
+        if bytes.len() != n * if compressed { 96 } else { 192 } { return Err(None); }
+        let (mut xy, mut inf, mut bad, mut handle) = (ark_std::vec![0u64; n * 24], ark_std::vec![0u8; n], 0usize, 0u64);
+        let mode = (compressed as i32) | if validate { 0 } else { DGPU_SERDE_NO_VALIDATE };
+        let rc = unsafe { dgpu_bases_upload_g2_serialized(bytes.as_ptr(), n, mode, xy.as_mut_ptr(), inf.as_mut_ptr(), &mut handle, &mut bad) };
+        if rc == DGPU_E_BADARG { return Err(Some(bad)); }
+        if rc != DGPU_OK { return Err(None); }
+        let host = (0..n).map(|i| g2_affine(xy[24 * i..24 * i + 24].try_into().unwrap(), inf[i])).collect();
+        Ok(ResidentG2 { handle, host })
     }
 }
 impl Drop for ResidentG2 { fn drop(&mut self) { if self.handle != 0 { unsafe { dgpu_bases_free(self.handle); } } } }

@@ -450,3 +450,43 @@ fn verifier_batch_verifier_and_aggregation() {
     assert_ne!(verify_aggregate_proof_gpu(&g.into_affine(), &h.into_affine(), &g_alpha[1], &g_beta[1], &h_alpha[1], &h_beta[1], n, &alpha_g1, &beta_g2, &gamma_g2, &delta_g2, &gamma_abc,
                                           &inputs, &tampered, 0, None, Fr::rand(&mut rng), &mut tv2, true), Some(true));
 }
+
+#[test]
+fn device_deserialization_and_validation() {
+    setup();
+    use ark_serialize::{CanonicalDeserialize, CanonicalSerialize, Valid};
+    let mut rng = StdRng::seed_from_u64(0x5EED00DE);
+    let (b1, b2) = (g1s(&mut rng, 300), g2s(&mut rng, 60));
+    for compressed in [true, false] {
+        let (mut e1, mut e2) = (Vec::new(), Vec::new());
+        for p in b1.iter() { if compressed { p.serialize_compressed(&mut e1).unwrap() } else { p.serialize_uncompressed(&mut e1).unwrap() } }
+        for p in b2.iter() { if compressed { p.serialize_compressed(&mut e2).unwrap() } else { p.serialize_uncompressed(&mut e2).unwrap() } }
+        let want1: Vec<G1Affine> = e1.chunks(e1.len() / b1.len()).map(|c| if compressed { G1Affine::deserialize_compressed(c).unwrap() } else { G1Affine::deserialize_uncompressed(c).unwrap() }).collect();
+        assert_eq!(deserialize_g1_device(&e1, b1.len(), compressed, true).unwrap(), want1);
+        assert_eq!(deserialize_g1_device(&e1, b1.len(), compressed, false).unwrap(), want1);
+        let want2: Vec<G2Affine> = e2.chunks(e2.len() / b2.len()).map(|c| if compressed { G2Affine::deserialize_compressed(c).unwrap() } else { G2Affine::deserialize_uncompressed(c).unwrap() }).collect();
+        assert_eq!(deserialize_g2_device(&e2, b2.len(), compressed, true).unwrap(), want2);
+        // resident bases from bytes == resident bases from the points
+        let s: Vec<BigInt<4>> = frs(&mut rng, b1.len()).iter().map(|f| f.into_bigint()).collect();
+        let r1 = ResidentG1::from_serialized(&e1, b1.len(), compressed, true).ok().unwrap();
+        assert_eq!(r1.msm_bigint(0, &s), G1Projective::msm_bigint(&b1, &s));
+        let r2 = ResidentG2::from_serialized(&e2, b2.len(), compressed, true).ok().unwrap();
+        assert_eq!(r2.msm_bigint(0, &s[..b2.len()]), G2Projective::msm_bigint(&b2, &s[..b2.len()]));
+    }
+    // a point on the curve outside G1 (x = 0: order 3): refused with validation at its index, accepted without, as arkworks does
+    let mut e = Vec::new();
+    for p in b1[..5].iter() { p.serialize_compressed(&mut e).unwrap(); }
+    let mut off = [0u8; 48]; off[0] = 0x80;                                 // x = 0, y = 2 (not the largest root)
+    let unchecked = G1Affine::deserialize_compressed_unchecked(&off[..]).unwrap();
+    assert!(unchecked.is_on_curve() && !unchecked.is_in_correct_subgroup_assuming_on_curve() && unchecked.check().is_err());
+    e[96..144].copy_from_slice(&off);
+    assert_eq!(deserialize_g1_device(&e, 5, true, true), Err(Some(2)));
+    assert_eq!(ResidentG1::from_serialized(&e, 5, true, true).err(), Some(Some(2)));
+    assert_eq!(deserialize_g1_device(&e, 5, true, false).unwrap()[2], unchecked);
+    // Valid::check on points in memory
+    let mut pts = b1[..4].to_vec(); pts.push(unchecked); pts.push(G1Affine::identity());
+    let want: Vec<bool> = pts.iter().map(|p| p.check().is_ok()).collect();
+    assert_eq!(validate_g1_batch(&pts).unwrap(), want);
+    let q: Vec<G2Affine> = b2[..3].to_vec();
+    assert_eq!(validate_g2_batch(&q).unwrap(), q.iter().map(|p| p.check().is_ok()).collect::<Vec<bool>>());
+}
