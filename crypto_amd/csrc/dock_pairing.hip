@@ -17,6 +17,7 @@
 #include "fp2_pair.hip.h"
 #include "sort_launch.hip.h"
 #include "fixed_launch.hip.h"
+#include "gt_launch.hip.h"
 #include <thread>
 #include <functional>
 #include <atomic>
@@ -647,19 +648,21 @@ __global__ void __launch_bounds__(256) k_prepared_from_lines(const uint32_t *__r
 // thread (s, i), i fastest: ark-ec `ell` (c1 *= px, c2 *= py) on coefficient triple s of pair i, written in K10's layout
 // pxy_one != nullptr (a mixed call whose product kernel evaluates the affine pairs' lines): these pairs' lines are evaluated HERE, so their
 // (px, py) for the product kernel is (1, 1) — pxy_one points at this kernel's first pair
+// shared: every pair takes the ONE coefficient block at `coeffs` (dgpu_legogroth16_verify_each: -delta / -gamma of the key beside every proof's C / d)
 __global__ void __launch_bounds__(256) k_lines_from_prepared(const uint32_t *__restrict__ p_abi, const uint32_t *__restrict__ coeffs, const uint8_t *__restrict__ skip, size_t n, uint32_t *__restrict__ lines, size_t stride,
-                                                              uint32_t *__restrict__ pxy_one = nullptr) {
+                                                              uint32_t *__restrict__ pxy_one = nullptr, bool shared = false) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * N_LINES) return;
     const size_t s = t / n, i = t % n;
     if (pxy_one && s == 0) { Fp one; fp_set_one(one); for (int k = 0; k < NL; k++) { pxy_one[(size_t)k * stride + i] = one.l[k]; pxy_one[(size_t)(NL + k) * stride + i] = one.l[k]; } }
     uint32_t pw[24], anyp = 0;
     for (int k = 0; k < 24; k += 4) { uint4 v = *reinterpret_cast<const uint4 *>(p_abi + i * 24 + k); pw[k] = v.x; pw[k + 1] = v.y; pw[k + 2] = v.z; pw[k + 3] = v.w; anyp |= v.x | v.y | v.z | v.w; }
-    const uint32_t *src = coeffs + (i * N_LINES + s) * (size_t)CW;
+    const size_t ci = shared ? 0 : i;
+    const uint32_t *src = coeffs + (ci * N_LINES + s) * (size_t)CW;
     uint32_t cw[CW], anyc = 0;
     for (int k = 0; k < CW; k += 4) { uint4 v = *reinterpret_cast<const uint4 *>(src + k); cw[k] = v.x; cw[k + 1] = v.y; cw[k + 2] = v.z; cw[k + 3] = v.w; anyc |= v.x | v.y | v.z | v.w; }
     uint32_t any0 = 0;                                               // an identity Q is an all-zero block: its first triple decides (a real doubling line has c1 = 3 x^2 != 0)
-    for (int k = 0; k < CW; k += 4) { uint4 v = *reinterpret_cast<const uint4 *>(coeffs + i * (size_t)(N_LINES * CW) + k); any0 |= v.x | v.y | v.z | v.w; }
+    for (int k = 0; k < CW; k += 4) { uint4 v = *reinterpret_cast<const uint4 *>(coeffs + ci * (size_t)(N_LINES * CW) + k); any0 |= v.x | v.y | v.z | v.w; }
     (void)anyc;
     const bool sk = (skip && skip[i]) || !anyp || !any0;
     uint32_t *dst = lines + (s * LW) * stride + i;
@@ -1684,6 +1687,116 @@ int32_t dgpu_g1_scale_batch(const uint64_t *p, const uint8_t *is_inf, const uint
     if (gs.prof) prof_flush(sl);
     return DGPU_OK;
 }
+// ---- many independent GT elements: the Fp12 chains on the device (k_gt.hip, gt_kernels.hip.h) ----
+constexpr size_t FE_CHUNK = 16384;        // elements per launch: 9.4 MB of device memory in and out
+int32_t dgpu_final_exponentiation_batch(const uint64_t *in, size_t n, uint64_t *out, uint8_t *is_zero) {
+    if (n == 0) return DGPU_OK;
+    if (!in || !out || !is_zero) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    SLOT_ACQUIRE(slot_lock, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    int32_t rc;
+    const size_t ch = std::min(n, FE_CHUNK);
+    if ((rc = sl.ml_out.ensure(ch * 576 * 2))) return rc;
+    if ((rc = sl.flags.ensure(ch))) return rc;
+    hipStream_t s = sl.stream;
+    uint32_t *din = sl.ml_out.as<uint32_t>(), *dout = din + ch * 144;
+    for (size_t lo = 0; lo < n; lo += ch) {
+        const size_t m = std::min(ch, n - lo);
+        HIPCHK(hipMemcpyAsync(din, in + lo * 72, m * 576, hipMemcpyHostToDevice, s));
+        { StageTimer st(sl, "gt.final_exp"); gtk::launch_final_exp(s, din, m, dout, sl.flags.as<uint8_t>(), nullptr, nullptr); }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out + lo * 72, dout, m * 576, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(is_zero + lo, sl.flags.p, m, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (gs.prof) prof_flush(sl);
+    return DGPU_OK;
+}
+
+// ---- one verdict per LegoGroth16 proof (verifier.rs:62-99 `verify_proof` once per statement) ----
+// Per chunk of up to VE_CHUNK proofs:
+//   d_i = gamma_abc[0] + sum_j x_ij gamma_abc[1 + j] + D_i    n_pub + 1 calls of dgpu_g1_mul_add_batch (one shared point each)
+//   lines: (A_i, B_i) affine in columns [0, m), (C_i, -delta) in [m, 2m), (d_i, -gamma) in [2m, 3m) — the two prepared points' coefficients
+//          uploaded ONCE and shared by every column (k_lines_from_prepared, shared)
+//   k_line_products over one "segment" of 3m pairs with slices of 3: slice j is the pairs j, j + m, j + 2 m, i.e. partial (s, j) = L_s of proof j
+//   k_miller_tail, k_final_exp against e(alpha, beta): only the m verdict bytes come back.
+// Device memory of a chunk: 68 x 84 x 4 B x 3m of lines + 68 x 672 B x m of per-step products + 576 B x m ~ 115 KB per proof (0.47 GB at 4096).
+constexpr size_t VE_CHUNK = 4096;
+int32_t dgpu_legogroth16_verify_each(const uint64_t alpha_beta_gt[72], const uint64_t *delta_neg_pc, const uint64_t *gamma_neg_pc, const uint64_t *gamma_abc_g1, size_t gamma_abc_len,
+                                     const uint64_t *proofs_a, const uint64_t *proofs_b, const uint64_t *proofs_c, const uint64_t *proofs_d, size_t n,
+                                     const uint64_t *public_inputs, size_t n_pub, int32_t montgomery, uint8_t *ok) {
+    if (!alpha_beta_gt || !delta_neg_pc || !gamma_neg_pc || !gamma_abc_g1) return DGPU_E_BADARG;
+    if (n && (!proofs_a || !proofs_b || !proofs_c || !proofs_d || !ok)) return DGPU_E_BADARG;
+    if (n_pub + 1 > gamma_abc_len || (n && n_pub && !public_inputs)) return DGPU_E_BADARG;          // MalformedVerifyingKey (verifier.rs:101-109)
+    if (n == 0) return DGPU_OK;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    auto zero_words = [](const uint64_t *w, int k) { uint64_t o = 0; for (int i = 0; i < k; i++) o |= w[i]; return o == 0; };
+    const size_t cw = (size_t)DGPU_G2_PREPARED_WORDS;
+    for (size_t lo = 0; lo < n; lo += VE_CHUNK) {
+        const size_t m = std::min(VE_CHUNK, n - lo), np = 3 * m;
+        // d_i on the device, before a slot is taken (the mul-add calls take their own)
+        std::vector<uint64_t> rep(m * 12), d(m * 12), d2(m * 12), sc(m * 4);
+        std::vector<uint8_t> dinf(m), dinf2(m);
+        const uint64_t one[4] = {1, 0, 0, 0};
+        for (size_t i = 0; i < m; i++) memcpy(&rep[i * 12], gamma_abc_g1, 96);
+        int32_t rc = dgpu_g1_mul_add_batch(rep.data(), nullptr, one, 0, proofs_d + lo * 12, nullptr, m, d.data(), dinf.data());
+        if (rc) return rc;
+        for (size_t j = 0; j < n_pub; j++) {
+            for (size_t i = 0; i < m; i++) {
+                memcpy(&rep[i * 12], gamma_abc_g1 + 12 * (1 + j), 96);
+                const uint64_t *x = public_inputs + 4 * ((lo + i) * n_pub + j);
+                if (montgomery) hostf::fr_from_mont(&sc[4 * i], x); else memcpy(&sc[4 * i], x, 32);
+            }
+            if ((rc = dgpu_g1_mul_add_batch(rep.data(), nullptr, sc.data(), 4, d.data(), dinf.data(), m, d2.data(), dinf2.data()))) return rc;
+            d.swap(d2); dinf.swap(dinf2);
+        }
+        std::vector<uint8_t> sk(np);
+        for (size_t i = 0; i < m; i++) {
+            sk[i] = (zero_words(proofs_a + (lo + i) * 12, 12) || zero_words(proofs_b + (lo + i) * 24, 24)) ? 1 : 0;
+            sk[m + i] = zero_words(proofs_c + (lo + i) * 12, 12) ? 1 : 0;
+            sk[2 * m + i] = (dinf[i] || zero_words(&d[i * 12], 12)) ? 1 : 0;
+        }
+        SLOT_ACQUIRE(slot_lock, sl);
+        HIPCHK(hipSetDevice(cur().device));
+        if ((rc = sl.in_bases.ensure(np * 96))) return rc;
+        if ((rc = sl.in_scalars.ensure(m * 192 + 16))) return rc;
+        if ((rc = sl.in_inf.ensure(np + 16))) return rc;
+        if ((rc = sl.ml_coeffs.ensure(2 * cw * 8 + 16))) return rc;
+        if ((rc = sl.ml_lines.ensure((size_t)N_LINES * LW * np * 4))) return rc;
+        if ((rc = sl.ml_partial.ensure((size_t)N_LINES * m * F12W * 4))) return rc;
+        if ((rc = sl.ml_out.ensure(m * 576 + 576))) return rc;
+        if ((rc = sl.flags.ensure(m))) return rc;
+        hipStream_t s = sl.stream;
+        uint32_t *dp = sl.in_bases.as<uint32_t>(), *lines = sl.ml_lines.as<uint32_t>(), *fout = sl.ml_out.as<uint32_t>(), *want = fout + m * 144;
+        uint8_t *dsk = sl.in_inf.as<uint8_t>();
+        HIPCHK(hipMemcpyAsync(dp, proofs_a + lo * 12, m * 96, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dp + m * 24, proofs_c + lo * 12, m * 96, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dp + 2 * m * 24, d.data(), m * 96, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sl.in_scalars.p, proofs_b + lo * 24, m * 192, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dsk, sk.data(), np, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sl.ml_coeffs.p, delta_neg_pc, cw * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sl.ml_coeffs.as<uint64_t>() + cw, gamma_neg_pc, cw * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(want, alpha_beta_gt, 576, hipMemcpyHostToDevice, s));
+        { StageTimer st(sl, "ve.lines");
+          hipLaunchKernelGGL(k_miller_lines_quad<true>, dim3((unsigned)((4 * m + 63) / 64)), dim3(64), 0, s, dp, sl.in_scalars.as<uint32_t>(), (const uint8_t *)dsk, m, lines, np,
+                             62, 0, 0, (uint32_t *)nullptr, (uint32_t *)nullptr);
+          for (int k = 0; k < 2; k++)
+              hipLaunchKernelGGL(k_lines_from_prepared, dim3((unsigned)((m * N_LINES + 255) / 256)), dim3(256), 0, s, dp + (1 + k) * m * 24, sl.ml_coeffs.as<uint32_t>() + k * cw * 2,
+                                 (const uint8_t *)(dsk + (1 + k) * m), m, lines + (1 + k) * m, np, (uint32_t *)nullptr, true); }
+        { StageTimer st(sl, "ve.products");
+          hipLaunchKernelGGL(k_line_products, dim3((unsigned)((2 * (size_t)N_LINES * m + 63) / 64)), dim3(64), 0, s, (const uint32_t *)lines, np, 3, (int)m, sl.ml_partial.as<uint32_t>(),
+                             (const uint32_t *)nullptr, 1, 0, N_LINES, (const uint32_t *)nullptr); }
+        { StageTimer st(sl, "ve.tail"); gtk::launch_miller_tail(s, sl.ml_partial.as<uint32_t>(), m, fout); }
+        { StageTimer st(sl, "ve.final_exp"); gtk::launch_final_exp(s, fout, m, (uint32_t *)nullptr, (uint8_t *)nullptr, want, sl.flags.as<uint8_t>()); }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ok + lo, sl.flags.p, m, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (gs.prof) prof_flush(sl);
+    }
+    return DGPU_OK;
+}
+
 // E::final_exponentiation: once per batch, host code
 int32_t dgpu_final_exponentiation(const uint64_t *in, uint64_t *out) {
     if (!in || !out) return DGPU_E_BADARG;

@@ -705,6 +705,31 @@ def verify_proofs_batch_abi(pvk, proofs, public_inputs, random, montgomery=False
     return ok.value == 1
 
 
+def verify_proofs_each_abi(pvk, proofs, public_inputs, montgomery=False, packed=None):
+    """N proofs of one verifying key, one verdict each, through ONE call of the C ABI (dgpu_legogroth16_verify_each): verify_proof per statement
+    (verifier.rs:62-99) with the Miller loops, their tails and the final exponentiations on the device.  Returns a bool array; a proof whose Miller
+    output is zero (UnexpectedIdentity) is rejected.  packed: pack_proofs(proofs, public_inputs) made ahead."""
+    import ctypes as C
+    from ._native import lib, DockGpuError
+    vk = pvk["vk"]
+    a, b, c, d, pubs = packed if packed is not None else pack_proofs(proofs, public_inputs)
+    n = len(a)
+    k = pubs.shape[1] if n else 0
+    gabc = np.ascontiguousarray(vk.gamma_abc_g1, dtype=np.uint64).reshape(-1, 12)
+    p_ = lambda x: np.ascontiguousarray(x, dtype=np.uint64).ctypes.data_as(C.c_void_p)
+    dn, gn = np.ascontiguousarray(pvk["delta_g2_neg_pc"].coeffs.reshape(-1)), np.ascontiguousarray(pvk["gamma_g2_neg_pc"].coeffs.reshape(-1))
+    ab = np.ascontiguousarray(pvk["alpha_g1_beta_g2"], dtype=np.uint64)
+    ok = np.zeros(n, dtype=np.uint8)
+    pubs = np.ascontiguousarray(pubs, dtype=np.uint64)
+    rc = lib().dgpu_legogroth16_verify_each(p_(ab), p_(dn), p_(gn), p_(gabc), len(gabc), p_(a), p_(b), p_(c), p_(d), n,
+                                            pubs.ctypes.data_as(C.c_void_p), k, int(montgomery), ok.ctypes.data_as(C.c_void_p))
+    if rc == -3 and k + 1 > len(gabc):
+        raise ValueError("MalformedVerifyingKey")
+    if rc:
+        raise DockGpuError(rc, "dgpu_legogroth16_verify_each")
+    return ok.astype(bool)
+
+
 def verify_proof(pvk, proof, public_inputs):
     """verifier.rs:62-99: e(A, B) e(C, -delta) e(d, -gamma) == e(alpha, beta)"""
     d = calculate_d(pvk, proof, public_inputs)

@@ -215,5 +215,17 @@ def final_exponentiation(f):
     return out
 
 
+def final_exponentiation_batch(fs):
+    """n independent final exponentiations on the device (dgpu_final_exponentiation_batch): (gts, is_zero), gts (n, 72) words with zero rows where
+    is_zero[i] (arkworks' None)"""
+    fs = np.ascontiguousarray(fs, dtype=np.uint64).reshape(-1, 72)
+    n = len(fs)
+    out, zero = np.zeros((n, 72), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+    rc = lib().dgpu_final_exponentiation_batch(_p(fs), n, _p(out), _p(zero))
+    if rc:
+        raise DockGpuError(rc, "dgpu_final_exponentiation_batch")
+    return out, zero.astype(bool)
+
+
 def multi_pairing(ps, qs, skip=None):
     return final_exponentiation(multi_miller_loop(ps, qs, skip))

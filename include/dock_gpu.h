@@ -309,6 +309,11 @@ int32_t dgpu_multi_pairing_segments(const uint64_t *p_xy, const uint64_t *q_xy, 
 int32_t dgpu_multi_miller_loop_sharded(const uint64_t *p_xy, const uint64_t *q_xy, const uint8_t *skip, size_t n, int32_t ngpus, uint64_t out_f12[72]);
 /* replaces Bls12_381::final_exponentiation — utils/src/randomized_pairing_check.rs:213 (host code, once per batch) */
 int32_t dgpu_final_exponentiation(const uint64_t in_f12[72], uint64_t out_f12[72]);
+/* the same for n independent elements, on the device (crypto_amd/csrc/gt_kernels.hip.h: one element per group of six lanes), whatever n: one verdict
+ * per statement needs one final exponentiation per proof (dgpu_legogroth16_verify_each).  out_gt: n x 72 words, for canonical input words equal to what
+ * dgpu_final_exponentiation returns; is_zero[i] = 1 where element i is zero (arkworks' None, dgpu_final_exponentiation's DGPU_E_ZERO), its words are
+ * then zero.  Large n runs in chunks of bounded device memory.  n = 0: DGPU_OK without a device; NULL pointers with n > 0: DGPU_E_BADARG. */
+int32_t dgpu_final_exponentiation_batch(const uint64_t *in_f12 /* n*72 */, size_t n, uint64_t *out_gt /* n*72 */, uint8_t *is_zero /* n */);
 
 /* ---- pieces of utils::randomized_pairing_check::RandomizedPairingChecker (utils/src/randomized_pairing_check.rs:24-215) ----
  * out_i = s_i * P_i as affine points (the per-equation `a.mul_bigint(m)` scalings, :125-127,152-158), batched on the GPU.
@@ -476,6 +481,17 @@ int32_t dgpu_legogroth16_verify(const uint64_t alpha_beta_gt[72], const uint64_t
 int32_t dgpu_legogroth16_verify_batch(const uint64_t alpha_beta_gt[72], const uint64_t *delta_neg_pc, const uint64_t *gamma_neg_pc, const uint64_t *gamma_abc_g1, size_t gamma_abc_len,
                                       const uint64_t *proofs_a, const uint64_t *proofs_b, const uint64_t *proofs_c, const uint64_t *proofs_d, size_t n,
                                       const uint64_t *public_inputs, size_t n_pub, int32_t montgomery, const uint64_t random[4], int32_t *ok);
+/* n proofs of ONE verifying key, one verdict EACH: verify_proof (legogroth16/src/verifier.rs:62-99) per statement, as the reference's
+ * proof_system runs it without a pairing checker (proof_system/src/sub_protocols/r1cs_legogorth16.rs:187, bound_check_legogroth16.rs:205).
+ * Arguments as dgpu_legogroth16_verify_batch without `random`; ok[i] = 1: proof i verifies, 0: it does not (a zero Miller output, the
+ * reference's UnexpectedIdentity, is a rejection too).  Identities are all-zero words; a pair with an identity member is skipped per proof as in
+ * dgpu_legogroth16_verify.  Any n_pub (no DGPU_MAX_LINCOMB limit); DGPU_E_BADARG: n_pub + 1 > gamma_abc_len or a NULL pointer.  n = 0: DGPU_OK.
+ * Everything runs on the device: d_i through dgpu_g1_mul_add_batch, one segmented Miller loop with the key's two prepared points shared by every
+ * proof, the tails, final exponentiations and comparisons with alpha_beta_gt in k_gt.hip; only the verdicts come back.  Chunks of 4096 proofs
+ * (~0.5 GB of device memory). */
+int32_t dgpu_legogroth16_verify_each(const uint64_t alpha_beta_gt[72], const uint64_t *delta_neg_pc, const uint64_t *gamma_neg_pc, const uint64_t *gamma_abc_g1, size_t gamma_abc_len,
+                                     const uint64_t *proofs_a, const uint64_t *proofs_b, const uint64_t *proofs_c, const uint64_t *proofs_d, size_t n,
+                                     const uint64_t *public_inputs, size_t n_pub, int32_t montgomery, uint8_t *ok /* n */);
 /* ---- SnarkPack aggregation of Groth16 / LegoGroth16 proofs (crypto_amd/csrc/dock_aggregation.cpp) ----
  * replaces aggregate_proofs (legogroth16/src/aggregation/groth16/prover.rs:47-147; legogroth16/prover.rs:38-127 when `d` is given) and
  * verify_aggregate_proof (groth16/verifier.rs:36-100, legogroth16/verifier.rs:34-96, legogroth16/using_groth16.rs:45-128) as the reference

@@ -276,6 +276,16 @@ pub fn final_exponentiation(f: MillerLoopOutput<Bls12_381>) -> Option<PairingOut
         _ => Bls12_381::final_exponentiation(f),
     }
 }
+/// `Bls12_381::final_exponentiation` of many independent Miller outputs at once, on the device (dgpu_final_exponentiation_batch).  One entry per
+/// input: None where arkworks returns None (a zero input).  None for the whole batch when the library declined.
+pub fn final_exponentiation_batch(fs: &[MillerLoopOutput<Bls12_381>]) -> Option<Vec<Option<PairingOutput<Bls12_381>>>> {
+    let w: Vec<u64> = fs.iter().flat_map(|f| fq12_to_words(&f.0)).collect();
+    let mut out = ark_std::vec![0u64; fs.len() * 72];
+    let mut zero = ark_std::vec![0u8; fs.len()];
+    let rc = unsafe { dgpu_final_exponentiation_batch(w.as_ptr(), fs.len(), out.as_mut_ptr(), zero.as_mut_ptr()) };
+    if rc != DGPU_OK { return None; }
+    Some((0..fs.len()).map(|i| if zero[i] != 0 { None } else { Some(PairingOutput(fq12_from_words(out[72 * i..72 * i + 72].try_into().unwrap()))) }).collect())
+}
 /// `a.mul_bigint(m)` (or its negative) for every point of a batch, ONE scalar — utils/src/randomized_pairing_check.rs:125-129,152-158.
 /// None when the library declined (the caller then scales on the CPU).
 pub fn g1_scale_batch(points: &[G1Affine], m: &BigInt<4>, negate: bool) -> Option<Vec<G1Affine>> {
@@ -388,6 +398,25 @@ pub fn verify_proofs_batch_gpu(pvk: &GpuPreparedVerifyingKey, proofs: &[(G1Affin
                                                     a.as_ptr(), b.as_ptr(), c.as_ptr(), d.as_ptr(), n, if k == 0 { core::ptr::null() } else { pubs.as_ptr() }, k, 0, rnd.0.as_ptr(), &mut ok) };
     if rc != DGPU_OK { return None; }
     Some(ok == 1)
+}
+
+/// Many proofs of ONE verifying key, one verdict each: `verify_proof` (legogroth16/src/verifier.rs:62-99) per statement, as proof_system runs it
+/// without a pairing checker (sub_protocols/r1cs_legogorth16.rs:187, bound_check_legogroth16.rs:205).  Some(verdicts) or None when the library declined.
+pub fn verify_proofs_each_gpu(pvk: &GpuPreparedVerifyingKey, proofs: &[(G1Affine, G2Affine, G1Affine, G1Affine)], public_inputs: &[Vec<Fr>]) -> Option<Vec<bool>> {
+    let n = proofs.len();
+    if public_inputs.len() != n { return None; }
+    let k = public_inputs.first().map_or(0, |r| r.len());
+    if public_inputs.iter().any(|r| r.len() != k) { return None; }
+    let a = pack_g1(&proofs.iter().map(|p| p.0).collect::<Vec<_>>()).0;
+    let b = pack_g2(&proofs.iter().map(|p| p.1).collect::<Vec<_>>()).0;
+    let c = pack_g1(&proofs.iter().map(|p| p.2).collect::<Vec<_>>()).0;
+    let d = pack_g1(&proofs.iter().map(|p| p.3).collect::<Vec<_>>()).0;
+    let pubs: Vec<u64> = public_inputs.iter().flat_map(|r| r.iter().flat_map(|x| x.into_bigint().0)).collect();
+    let mut ok = ark_std::vec![0u8; n];
+    let rc = unsafe { dgpu_legogroth16_verify_each(pvk.alpha_beta.as_ptr(), pvk.delta_neg.as_ptr(), pvk.gamma_neg.as_ptr(), pvk.gamma_abc.as_ptr(), pvk.gamma_abc_len,
+                                                   a.as_ptr(), b.as_ptr(), c.as_ptr(), d.as_ptr(), n, if k == 0 { core::ptr::null() } else { pubs.as_ptr() }, k, 0, ok.as_mut_ptr()) };
+    if rc != DGPU_OK { return None; }
+    Some(ok.iter().map(|&v| v == 1).collect())
 }
 
 // ---- SnarkPack aggregation as one call each way (legogroth16/src/aggregation/groth16/prover.rs:47-147, verifier.rs:36-100) -----------------------

@@ -61,6 +61,9 @@ fn pairing_equals_arkworks() {
         assert_eq!(f.0, g.0, "raw Miller output, n = {n}");
         assert_eq!(final_exponentiation(f).unwrap().0, Bls12_381::final_exponentiation(g).unwrap().0);
         assert_eq!(multi_pairing(&p, &q), Bls12_381::multi_pairing(p.iter().copied(), q.iter().copied()));
+        let batch = final_exponentiation_batch(&[f, ark_ec::pairing::MillerLoopOutput(<Bls12_381 as Pairing>::TargetField::zero()), f]).unwrap();
+        let want = Bls12_381::final_exponentiation(g);
+        assert_eq!((batch[0], batch[1], batch[2]), (want, None, want), "final_exponentiation_batch, n = {n}");
     }
     let q = g2s(&mut rng, 7);
     let (mine, theirs): (Vec<G2Prepared>, Vec<G2Prepared>) = (g2_prepare(&q), q.iter().map(|x| G2Prepared::from(*x)).collect());
@@ -429,6 +432,8 @@ fn verifier_batch_verifier_and_aggregation() {
     assert_eq!(verify_proofs_batch_gpu(&pvk, &proofs, &inputs, Fr::rand(&mut rng)), Some(true));
     let mut bad = proofs.clone(); bad[3].2 = bad[2].2;
     assert_eq!(verify_proofs_batch_gpu(&pvk, &bad, &inputs, Fr::rand(&mut rng)), Some(false));
+    let mut each = ark_std::vec![true; n]; each[3] = false;
+    assert_eq!(verify_proofs_each_gpu(&pvk, &bad, &inputs), Some(each));
     // SnarkPack: aggregate the n proofs under a fake SRS (known alpha, beta), verify the aggregate
     let (sa, sb) = (Fr::rand(&mut rng), Fr::rand(&mut rng));
     let pow = |base: Fr, k: usize| { let mut v = Vec::with_capacity(k); let mut c = Fr::from(1u64); for _ in 0..k { v.push(c); c *= base; } v };
