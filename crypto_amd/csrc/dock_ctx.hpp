@@ -253,6 +253,9 @@ template <class Pred> inline bool take_handle(uint64_t id, Pred kind_ok, Handle 
     }
 }
 void free_r1cs_object(void *p);      // dock_qap.hip
+// the device arrays of a resident circuit (kind 4) for the key generator (dock_setup.hip): CSR per matrix, values limb-major with stride vstride
+struct R1csView { const uint64_t *rowptr[3]; const uint32_t *cols[3]; const uint32_t *vals[3]; size_t vstride[3]; size_t num_vars, num_inputs, num_constraints; };
+R1csView r1cs_view(const void *p);    // dock_qap.hip
 // contexts a sharded call runs on: the first `ngpus` initialised ones (0 = all)
 inline std::vector<int> ready_contexts(int ngpus) {
     std::vector<int> v;

@@ -261,6 +261,31 @@ int32_t fold_apply(bool g2, uint64_t handle, const uint64_t *scalar, const uint6
 
 }  // namespace
 
+namespace dock {
+// table_mul with the scalars already on the slot's device (canonical words: the key generator's, dock_setup.hip): the products go to a new bases
+// allocation (*keep: the records dgpu_window_table_mul_to_bases_* registers; the caller registers it) and / or to the host (affine ABI words and
+// identity flags).  On failure nothing is left allocated.
+template <class C> int32_t table_mul_device(Slot &sl, const void *table, const uint32_t *d_scalars, size_t n, void **keep, uint64_t *out, uint8_t *out_inf) {
+    if (n >= (1ull << 31)) return DGPU_E_BADARG;
+    const size_t pt_bytes = 2 * C::ABI_W * 4;
+    if (keep && dev_malloc(keep, std::max<size_t>(n, 1) * C::AFF_STRIDE * 4) != hipSuccess) { (void)hipGetLastError(); *keep = nullptr; return DGPU_E_OOM; }
+    auto fail = [&](int32_t rc) { if (keep && *keep) { (void)hipStreamSynchronize(sl.stream); (void)hipFree(*keep); *keep = nullptr; } return rc; };
+    if (n == 0) return DGPU_OK;
+    int32_t rc;
+    if ((rc = sl.in_bases.ensure(n * pt_bytes + n))) return fail(rc);
+    uint8_t *dinf = sl.in_bases.as<uint8_t>() + n * pt_bytes;
+    { StageTimer st(sl, "fixed.mul");
+      msm::launch_fb_mul<C>(sl.stream, (const uint32_t *)table, d_scalars, n, sl.in_bases.as<uint32_t>(), dinf); }
+    if (keep) msm::launch_prep_bases<C>(sl.stream, sl.in_bases.as<uint32_t>(), dinf, n, (uint32_t *)*keep);
+    if (out && hipMemcpyAsync(out, sl.in_bases.p, n * pt_bytes, hipMemcpyDeviceToHost, sl.stream) != hipSuccess) { (void)hipGetLastError(); return fail(DGPU_E_HIP); }
+    if (out_inf && hipMemcpyAsync(out_inf, dinf, n, hipMemcpyDeviceToHost, sl.stream) != hipSuccess) { (void)hipGetLastError(); return fail(DGPU_E_HIP); }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(sl.stream) != hipSuccess) { (void)hipGetLastError(); return fail(DGPU_E_HIP); }   // in_bases is reused by the next query
+    return DGPU_OK;
+}
+template int32_t table_mul_device<G1>(Slot &, const void *, const uint32_t *, size_t, void **, uint64_t *, uint8_t *);
+template int32_t table_mul_device<G2>(Slot &, const void *, const uint32_t *, size_t, void **, uint64_t *, uint8_t *);
+}  // namespace dock
+
 extern "C" {
 int32_t dgpu_g1_mul_add_batch(const uint64_t *p, const uint8_t *p_inf, const uint64_t *sc, size_t stride, const uint64_t *add, const uint8_t *add_inf, size_t n, uint64_t *out, uint8_t *out_inf) {
     return mul_add<G1>(p, p_inf, sc, stride, add, add_inf, n, out, out_inf);

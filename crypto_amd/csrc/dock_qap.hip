@@ -137,7 +137,16 @@ int32_t build_r1cs(Slot &sl, const Csr mats[3], size_t num_vars, size_t num_inpu
 }
 
 }  // namespace
-namespace dock { void free_r1cs_object(void *p) { free_r1cs((DevR1cs *)p); } }
+namespace dock {
+void free_r1cs_object(void *p) { free_r1cs((DevR1cs *)p); }
+R1csView r1cs_view(const void *p) {
+    const DevR1cs *r = (const DevR1cs *)p;
+    R1csView v;
+    for (int k = 0; k < 3; k++) { v.rowptr[k] = r->m[k].rowptr; v.cols[k] = r->m[k].cols; v.vals[k] = r->m[k].vals; v.vstride[k] = r->m[k].nnz; }
+    v.num_vars = r->num_vars; v.num_inputs = r->num_inputs; v.num_constraints = r->num_constraints;
+    return v;
+}
+}  // namespace dock
 
 extern "C" {
 

@@ -18,6 +18,12 @@
 #else
 #define FRD inline
 #endif
+// With -DFP29_CHECK (host only) fr_mul asserts its operand contract on the actual operands (limbs and value product), so that the
+// routines below can be run on the host over adversarial inputs (tests/test_setup_device_code_on_host.py).
+#ifdef FP29_CHECK
+#include <cassert>
+#include <cmath>
+#endif
 
 namespace fr29 {
 
@@ -94,8 +100,18 @@ FRD void fr_norm(Fr &r, const Fr &a) {
     r.l[0] = t0; r.l[NL - 1] = tl;
 }
 // Montgomery product a * b / 2^290 mod r (product scanning, reduction interleaved)
+#ifdef FP29_CHECK
+inline double fr_value_over_r(const Fr &a) {      // value(a) / r, approximately (a bound check, not arithmetic)
+    double v = 0; for (int i = NL - 1; i >= 0; i--) v = v * 536870912.0 + (double)a.l[i];
+    return v / 5.2435875175126190479447740508185965837690552500527637822603658699938581184513e76;
+}
+#endif
 FRD void fr_mul(Fr &r, const Fr &a, const Fr &b) {
     constexpr uint32_t P_[NL] = FR29_R;
+#ifdef FP29_CHECK
+    for (int i = 0; i < NL; i++) assert(a.l[i] < (1u << 31) && b.l[i] <= (1u << 29) + 7);
+    assert(fr_value_over_r(a) * fr_value_over_r(b) < 17179869184.0);     // value(a) value(b) < 2^34 r^2
+#endif
     uint32_t m[NL], t[NL];
     uint64_t acc = 0;
 #pragma unroll
@@ -184,6 +200,67 @@ FRD void fr_to_words(uint32_t w[8], const Fr &a, bool mont) {
     }
 #pragma unroll
     for (int i = 0; i < 8; i++) w[i] = o[i];
+}
+
+// ---- inversion and the two pieces of the key generator's scalar half (k_setup.hip) ----
+// r - 2 as eight little-endian words: a^(r-2) = a^-1 for a != 0 (Fermat)
+#define FR29_RM2_WORDS {0xffffffffu, 0xfffffffeu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u}
+// r = a^-1 (a = 0 gives 0).  a: limbs < 2^32 with value < 2^34 r (a product, or a short sum of products); returns limbs < 2^29, value < 2 r.
+// 254 squarings and 177 products, left to right: the exponent is a constant, so every lane of a wave takes the same branch.
+FRD void fr_inv(Fr &r, const Fr &a) {
+    constexpr uint32_t E_[8] = FR29_RM2_WORDS;
+    Fr x, acc, one; fr_one(one);
+    fr_norm(x, a);
+    fr_mul(x, x, one);                 // < 2 r, limbs < 2^29: the operand of every product below
+    acc = x;                           // the top bit (254) of r - 2
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+    for (int bit = 253; bit >= 0; bit--) {
+        fr_mul(acc, acc, acc);
+        if ((E_[bit >> 5] >> (bit & 31)) & 1) fr_mul(acc, acc, x);
+    }
+    r = acc;
+}
+// Montgomery's trick over one chunk of n non-zero elements: out(k) = x(k)^-1 for k < n, with ONE fr_inv.
+//   x(k, Fr &)          loads element k (limbs < 2^31, value < 2^10 r: the operand of a product)
+//   ld(k, Fr &) / st(k, const Fr &)   the output slot of element k, which holds the prefix product in between
+// Outputs: limbs < 2^29, value < 2 r.  The caller picks the chunk (a lane's strided share of an array on the device, a plain array on the host).
+template <class X, class LD, class ST> FRD void fr_batch_inv(size_t n, X x, LD ld, ST st) {
+    Fr acc, v; fr_one(acc);
+    for (size_t k = 0; k < n; k++) { st(k, acc); x(k, v); fr_mul(acc, v, acc); }
+    Fr inv; fr_inv(inv, acc);
+    for (size_t k = n; k-- > 0;) {
+        Fr pre, o; ld(k, pre); x(k, v);
+        fr_mul(o, inv, pre); fr_mul(inv, v, inv);
+        st(k, o);
+    }
+}
+// One lane's share [lo, hi) of a segmented sum over a key-sorted list of n entries (keys[], values through val(k, Fr &): limbs < 2^29,
+// value < 2 r).  Runs of equal keys are summed (hi - lo <= 2^10: a run's sum then stays an operand of a product) and
+// reduced below 2 r.  A run that lies strictly inside the chunk is complete (its neighbours differ): done(key, sum).  The first and last
+// runs may continue in the neighbouring chunks: they go to part(0, key, sum) and part(1, key, sum) — a chunk of one run writes (key, 0) as
+// its second partial — so that the 2 x nchunks partials form a key-sorted list of their own for the next pass.  final_pass (one chunk
+// covers the whole list): every run is complete.  The result does not depend on the order of the entries inside a run.
+template <class V, class Done, class Part> FRD void fr_fold_chunk(const uint32_t *keys, size_t lo, size_t hi, bool final_pass, V val, Done done, Part part) {
+    if (lo >= hi) return;
+    Fr one, acc, v; fr_one(one);
+    uint32_t key = keys[lo];
+    bool first = true;
+    fr_zero(acc);
+    for (size_t k = lo; k < hi; k++) {
+        const uint32_t kk = keys[k];
+        if (kk != key) {                               // the run of `key` ends inside the chunk
+            fr_mul(acc, acc, one);
+            if (first && !final_pass) part(0, key, acc); else done(key, acc);
+            first = false; key = kk; fr_zero(acc);
+        }
+        val(k, v); fr_add(acc, acc, v); fr_norm(acc, acc);
+    }
+    fr_mul(acc, acc, one);
+    if (final_pass) { done(key, acc); return; }
+    if (first) { part(0, key, acc); fr_zero(acc); }   // one run: the whole chunk is the first partial, the second adds nothing
+    part(1, key, acc);
 }
 
 }  // namespace fr29

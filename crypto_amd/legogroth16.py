@@ -167,6 +167,48 @@ def generate_parameters(A, B, C, num_instance_variables, num_witness_variables, 
     return pk, num_instance_variables
 
 
+def generate_parameters_r1cs(circuit, commit_witness_count, alpha, beta, gamma, delta, eta, t, g1_generator, g2_generator, queries_to_host=False):
+    """generate_parameters (above) on a resident circuit (qap.DeviceR1cs) as ONE call of the C ABI, dgpu_legogroth16_setup: the instance map, the key
+    scalars and every FixedBase::msm run on the device.  Same key, word for word.  queries_to_host: the five queries also come back as affine ABI
+    words and identity flags, in pk.host_queries {"a_query": (xy, inf), ...}.  Returns (pk, num_instance_variables)."""
+    nv, n_inst, n_cons = circuit.num_vars, circuit.num_inputs, circuit.num_constraints
+    if nv - n_inst < commit_witness_count:
+        raise ValueError("InsufficientWitnessesForCommitment(%d, %d)" % (nv - n_inst, commit_witness_count))   # generator.rs:289-294
+    D = 1
+    while D < n_cons + n_inst:
+        D *= 2
+    n = n_inst + commit_witness_count
+    waste = np.concatenate([_sc(x) for x in (alpha, beta, gamma, delta, eta, t)])
+    g1 = np.ascontiguousarray(g1_generator, dtype=np.uint64).reshape(12)
+    g2 = np.ascontiguousarray(g2_generator, dtype=np.uint64).reshape(24)
+    handles = np.zeros(5, np.uint64)
+    o1, o2 = np.zeros((7, 12), np.uint64), np.zeros((4, 24), np.uint64)
+    gabc = np.zeros((max(n, 1), 12), np.uint64)
+    names = ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query")
+    lens = (nv, nv, nv, D - 1, nv - n)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    xy_arr = inf_arr = None
+    host = {}
+    if queries_to_host:
+        for q, (name, k) in enumerate(zip(names, lens)):
+            host[name] = (np.zeros((max(k, 1), 24 if q == 2 else 12), np.uint64), np.zeros(max(k, 1), np.uint8))
+        xy_arr = (C.c_void_p * 5)(*[host[nm][0].ctypes.data for nm in names])
+        inf_arr = (C.c_void_p * 5)(*[host[nm][1].ctypes.data for nm in names])
+    dsize = C.c_size_t(0)
+    rc = M.lib().dgpu_legogroth16_setup(circuit.handle, commit_witness_count, p(waste), p(g1), p(g2), 0, p(handles), p(o1), p(o2), p(gabc), len(gabc),
+                                        None if xy_arr is None else C.cast(xy_arr, C.c_void_p), None if inf_arr is None else C.cast(inf_arr, C.c_void_p), C.byref(dsize))
+    if rc:
+        raise M.DockGpuError(rc, "dgpu_legogroth16_setup")
+    assert dsize.value == D
+    q = [M.DeviceBases.from_handle(M.G2 if k == 2 else M.G1, int(handles[k]), lens[k]) for k in range(5)]
+    # out_g1: alpha, beta, delta, eta/gamma, eta/delta, a0, b1_0; out_g2: beta, delta, gamma, b2_0 (generate_parameters' small1 / small2)
+    vk = VerifyingKey(o1[0], o2[0], o2[2], o2[1], gabc[:n], o1[3], commit_witness_count)
+    pk = ProvingKey.from_device(vk, o1[1], o1[2], o1[4], o1[5], o1[6], o2[3], q[0], q[1], q[2], q[3], q[4])
+    if queries_to_host:
+        pk.host_queries = {nm: (host[nm][0][:k], host[nm][1][:k]) for nm, k in zip(names, lens)}
+    return pk, n_inst
+
+
 _POOL = None
 
 

@@ -107,6 +107,19 @@ class DeviceR1cs:
             ds.n, ds.handle = olen.value, handle.value
         return out, ds
 
+    def instance_map(self, t, montgomery=False):
+        """instance_map_with_evaluation (legogroth16/src/r1cs_to_qap.rs:105-147) on the resident circuit (dgpu_qap_instance_map): what
+        legogroth16.instance_map_with_evaluation returns, (a, b, c, zt, qap_num_variables, domain_size), with a, b, c as (num_vars, 4) limb arrays
+        and zt as 4 limbs.  `t`: an int or 4 limbs; montgomery: t and the outputs are ark-ff Fr limbs instead of canonical."""
+        tw = np.array([(int(t) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64) if not isinstance(t, np.ndarray) else np.ascontiguousarray(t, dtype=np.uint64).reshape(4)
+        out = [np.zeros((self.num_vars, 4), dtype=np.uint64) for _ in range(3)]
+        zt = np.zeros(4, dtype=np.uint64)
+        D = C.c_size_t(0)
+        rc = lib().dgpu_qap_instance_map(self.handle, tw.ctypes.data_as(C.c_void_p), int(bool(montgomery)), *[_p(o) for o in out], zt.ctypes.data_as(C.c_void_p), C.byref(D))
+        if rc:
+            raise DockGpuError(rc, "dgpu_qap_instance_map")
+        return out[0], out[1], out[2], zt, self.num_vars - 1, D.value
+
     def free(self):
         if self.handle:
             lib().dgpu_r1cs_free(self.handle)

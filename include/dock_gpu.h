@@ -407,6 +407,38 @@ int32_t dgpu_witness_map_r1cs(uint64_t r1cs, const uint64_t *assignment, size_t 
  * per proof then serves the witness map and — at scalar offset 1 — the prover's `assignment` = z[1..] of the a / b_g1 / b_g2 / l MSMs */
 int32_t dgpu_witness_map_r1cs_resident(uint64_t r1cs, uint64_t assignment, uint64_t *out_h, uint64_t *out_handle, size_t *out_len);
 
+/* ---- LegoGroth16 key generation from a resident circuit ----
+ * dgpu_qap_instance_map replaces LibsnarkReduction::instance_map_with_evaluation (legogroth16/src/r1cs_to_qap.rs:105-147) on a dgpu_r1cs_upload circuit:
+ * D = the witness map's domain (the next power of two >= num_constraints + num_inputs), u_i = Z(t) w^i / (D (t - w^i)) for i < D (one batch inversion
+ * on the device), then a_j = u_{num_constraints + j} (j < num_inputs) plus the column sums of u_i * A[i][j]; b, c the same over B, C (no instance
+ * terms).  t: 4 words (montgomery != 0: an ark-ff Fr, else canonical).  out_a / out_b / out_c: num_vars x 4 words each, out_zt: Z(t) = t^D - 1, all
+ * canonical or (montgomery != 0) Fr limbs; any output may be NULL.  *out_domain_size = D.  DGPU_E_BADARG: a bad handle, or Z(t) = 0 (t in the
+ * domain; the reference draws t with sample_element_outside_domain, generator.rs:284). */
+int32_t dgpu_qap_instance_map(uint64_t r1cs, const uint64_t t[4], int32_t montgomery, uint64_t *out_a, uint64_t *out_b, uint64_t *out_c,
+                              uint64_t out_zt[4], size_t *out_domain_size);
+/* dgpu_legogroth16_setup replaces generate_parameters_and_extra_info_with_qap (legogroth16/src/generator.rs:245-442) with the toxic waste passed
+ * in (the reference draws it from `rng`, :220-232, :283) and the QAP reduction's key scalars (r1cs_to_qap.rs:212-223): the instance map above,
+ * mix_j = beta a_j + alpha b_j + c_j, gamma_abc = mix[..n] / gamma (n = num_inputs + commit_witness_count), l = mix[n..] / delta, h_i = Z(t) / delta
+ * t^i (i < D - 1), then every FixedBase::msm (:335-406) as a window-table product from the scalars on the device: the five queries become resident
+ * bases handles exactly as dgpu_window_table_mul_to_bases_* makes them (an identity where a scalar is zero).
+ *   waste          alpha, beta, gamma, delta, eta, t: 6 x 4 words (montgomery != 0: ark-ff Fr limbs, else canonical)
+ *   g1_xy / g2_xy  the generators (affine ABI words)
+ *   out_handles    a_query, b_g1_query, b_g2_query, h_query (D - 1 points), l_query: bases handles the caller frees with dgpu_bases_free
+ *   out_g1         7 x 12 words: alpha_g1, beta_g1, delta_g1, eta_gamma_inv_g1, eta_delta_inv_g1, a_query[0], b_g1_query[0]
+ *   out_g2         4 x 24 words: beta_g2, delta_g2, gamma_g2, b_g2_query[0]
+ *   gamma_abc_g1   gamma_abc_cap x 12 words of the caller's; the first num_inputs + commit_witness_count rows are written
+ *   query_xy / query_inf   NULL, or five pointers each (same order as out_handles; any may be NULL): host copies of the queries as affine ABI
+ *                  words and one identity flag per point (a, b_g1, b_g2: num_vars points, h: D - 1, l: num_vars - n) — what a caller that holds
+ *                  keys as Vec<G1Affine> or serializes them needs
+ *   out_domain_size  D (may be NULL)
+ * A dgpu_lego_pk whose handles are out_handles and whose point members point into out_g1 / out_g2 / gamma_abc_g1 proves with dgpu_legogroth16_prove
+ * on the same r1cs.  DGPU_E_BADARG: a bad handle or NULL pointer, commit_witness_count > num_vars - num_inputs (InsufficientWitnessesForCommitment,
+ * :289-294), gamma or delta = 0 (UnexpectedIdentity), Z(t) = 0, gamma_abc_cap < num_inputs + commit_witness_count.  A refused or failing call
+ * leaves no handle and no device allocation behind.  Runs on the circuit's device; stage timers setup.instance_map and setup.fixed_base. */
+int32_t dgpu_legogroth16_setup(uint64_t r1cs, size_t commit_witness_count, const uint64_t waste[24], const uint64_t g1_xy[12], const uint64_t g2_xy[24],
+                               int32_t montgomery, uint64_t out_handles[5], uint64_t *out_g1, uint64_t *out_g2, uint64_t *gamma_abc_g1, size_t gamma_abc_cap,
+                               uint64_t **query_xy, uint8_t **query_inf, size_t *out_domain_size);
+
 /* ---- the LegoGroth16 prover as one call ----
  * replaces create_proof_and_committed_witnesses_with_assignment (legogroth16/src/prover.rs:267-383, with calculate_coeff :585-594) and — when
  * the circuit is resident (r1cs != 0) — the QAP::witness_map call in front of it (create_proof_with_reduction, :153-180): the whole schedule

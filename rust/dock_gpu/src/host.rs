@@ -260,6 +260,17 @@ impl R1cs {
         if rc != DGPU_OK || len != d { return None; }
         Some(h)
     }
+    /// `instance_map_with_evaluation(cs, t)` (r1cs_to_qap.rs:105-147) on the resident circuit: (a, b, c, Z(t), domain size), the three vectors of
+    /// num_vars entries each as `Vec<Fr>`; None for a t inside the domain
+    pub fn instance_map(&self, t: Fr) -> Option<(Vec<Fr>, Vec<Fr>, Vec<Fr>, Fr, usize)> {
+        let zero = Fr::from(0u64);
+        let (mut a, mut b, mut c, mut zt) = (ark_std::vec![zero; self.num_vars], ark_std::vec![zero; self.num_vars], ark_std::vec![zero; self.num_vars], zero);
+        let mut d = 0usize;
+        let rc = unsafe { dgpu_qap_instance_map(self.handle, &t as *const Fr as *const u64, 1, a.as_mut_ptr() as *mut u64, b.as_mut_ptr() as *mut u64,
+                                                c.as_mut_ptr() as *mut u64, &mut zt as *mut Fr as *mut u64, &mut d) };
+        if rc != DGPU_OK { return None; }
+        Some((a, b, c, zt, d))
+    }
 }
 impl Drop for R1cs { fn drop(&mut self) { unsafe { dgpu_r1cs_free(self.handle); } } }
 

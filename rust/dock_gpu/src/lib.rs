@@ -338,6 +338,52 @@ impl GpuProvingKey {
                      a0: g1(5), b1_0: g1(6), b2_0: g2(2), gamma_abc_g1: g1(7), gamma_abc_len: self.gamma_abc_len, commit_witness_count: self.commit_witness_count }
     }
 }
+/// the verifying key `generate_parameters_gpu` made alongside the proving key (legogroth16/src/data_structures.rs VerifyingKey's members)
+pub struct GpuSetupVk { pub alpha_g1: G1Affine, pub beta_g2: G2Affine, pub gamma_g2: G2Affine, pub delta_g2: G2Affine, pub gamma_abc_g1: Vec<G1Affine>, pub eta_gamma_inv_g1: G1Affine }
+/// `generate_parameters_and_extra_info_with_qap` (legogroth16/src/generator.rs:245-442) on a resident circuit with the toxic waste passed in
+/// (alpha, beta, gamma, delta, eta, t — what the reference draws from `rng`): the instance map, the key scalars and every FixedBase::msm on the device
+/// (dgpu_legogroth16_setup).  The proving key's queries stay resident (and come back to the host as the `Vec<G1Affine>` the key also holds);
+/// None when the library declined (InsufficientWitnessesForCommitment, a zero gamma / delta, t in the domain, no device).
+#[allow(clippy::too_many_arguments)]
+pub fn generate_parameters_gpu(circuit: &host::R1cs, commit_witness_count: usize, alpha: Fr, beta: Fr, gamma: Fr, delta: Fr, eta: Fr, t: Fr,
+                               g1_generator: G1Affine, g2_generator: G2Affine) -> Option<(GpuProvingKey, GpuSetupVk)> {
+    let mut waste = [0u64; 24];
+    for (k, x) in [alpha, beta, gamma, delta, eta, t].iter().enumerate() { waste[4 * k..4 * k + 4].copy_from_slice(&x.into_bigint().0); }
+    let (g1w, _) = pack_g1(&[g1_generator]);
+    let (g2w, _) = pack_g2(&[g2_generator]);
+    let nv = circuit.num_vars;
+    let d = (circuit.num_constraints + circuit.num_inputs).next_power_of_two();
+    let n_abc = circuit.num_inputs + commit_witness_count;
+    if commit_witness_count > nv - circuit.num_inputs { return None; }
+    let lens = [nv, nv, nv, d - 1, nv - n_abc];
+    let mut xy: Vec<Vec<u64>> = lens.iter().enumerate().map(|(q, &n)| ark_std::vec![0u64; n * if q == 2 { 24 } else { 12 }]).collect();
+    let mut inf: Vec<Vec<u8>> = lens.iter().map(|&n| ark_std::vec![0u8; n]).collect();
+    let mut xp: Vec<*mut u64> = xy.iter_mut().map(|v| v.as_mut_ptr()).collect();
+    let mut ip: Vec<*mut u8> = inf.iter_mut().map(|v| v.as_mut_ptr()).collect();
+    let (mut hs, mut o1, mut o2) = ([0u64; 5], [0u64; 7 * 12], [0u64; 4 * 24]);
+    let mut abc = ark_std::vec![0u64; n_abc * 12];
+    let mut dsize = 0usize;
+    // waste holds canonical limbs (`into_bigint`): montgomery = 0
+    let rc = unsafe { dgpu_legogroth16_setup(circuit.handle(), commit_witness_count, waste.as_ptr(), g1w.as_ptr(), g2w.as_ptr(), 0, hs.as_mut_ptr(), o1.as_mut_ptr(), o2.as_mut_ptr(),
+                                             abc.as_mut_ptr(), n_abc, xp.as_mut_ptr(), ip.as_mut_ptr(), &mut dsize) };
+    if rc != DGPU_OK { return None; }
+    debug_assert_eq!(dsize, d);
+    let g1_at = |w: &[u64], i: &[u8], k: usize| g1_affine(w[12 * k..12 * k + 12].try_into().unwrap(), i[k]);
+    let g1s = |q: usize| (0..lens[q]).map(|k| g1_at(&xy[q], &inf[q], k)).collect::<Vec<G1Affine>>();
+    let zero = |w: &[u64]| if w.iter().all(|&x| x == 0) { 1u8 } else { 0u8 };
+    let p1 = |k: usize| g1_affine(o1[12 * k..12 * k + 12].try_into().unwrap(), zero(&o1[12 * k..12 * k + 12]));
+    let p2 = |k: usize| g2_affine(o2[24 * k..24 * k + 24].try_into().unwrap(), zero(&o2[24 * k..24 * k + 24]));
+    let gamma_abc_g1: Vec<G1Affine> = (0..n_abc).map(|k| g1_affine(abc[12 * k..12 * k + 12].try_into().unwrap(), zero(&abc[12 * k..12 * k + 12]))).collect();
+    let mut s1 = ark_std::vec![p1(0), p1(1), p1(2), p1(4), p1(3), p1(5), p1(6)];      // alpha, beta, delta, eta/delta, eta/gamma, a0, b1_0
+    s1.extend_from_slice(&gamma_abc_g1);
+    let pk = GpuProvingKey {
+        a: ResidentG1 { handle: hs[0], host: g1s(0) }, b_g1: ResidentG1 { handle: hs[1], host: g1s(1) },
+        h: ResidentG1 { handle: hs[3], host: g1s(3) }, l: ResidentG1 { handle: hs[4], host: g1s(4) },
+        b_g2_handle: hs[2], small_g1: pack_g1(&s1).0, small_g2: pack_g2(&[p2(0), p2(1), p2(3)]).0,
+        gamma_abc_len: n_abc, commit_witness_count,
+    };
+    Some((pk, GpuSetupVk { alpha_g1: p1(0), beta_g2: p2(0), gamma_g2: p2(2), delta_g2: p2(1), gamma_abc_g1, eta_gamma_inv_g1: p1(3) }))
+}
 impl Drop for GpuProvingKey { fn drop(&mut self) { if self.b_g2_handle != 0 { unsafe { dgpu_bases_free(self.b_g2_handle); } } } }
 
 fn g1_affine(w: &[u64; 12], inf: u8) -> G1Affine { if inf != 0 { G1Affine::identity() } else { G1Affine::new_unchecked(fq(&w[0..6]), fq(&w[6..12])) } }
