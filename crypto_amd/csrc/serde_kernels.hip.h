@@ -9,10 +9,16 @@
 // Square roots use one exponentiation t = a^((p - 3) / 4) in Fq: sqrt(a) = t a, and 1 / sqrt(a) = t when a is a square.  The Fq2 root is the
 // complex method with its inversion replaced by t (see fq2_sqrt_dev): two Fq exponentiations per G2 point, no inversion.
 // Every lane runs the same instruction stream whatever its point (identity, malformed or not): the verdict only selects what is written.
+//
+// The other direction, dgpu_g1_serialize / dgpu_g2_serialize's bytes: encode_point takes affine ABI words, record_to_abi reads a resident base
+// record (what k_prep_bases writes, also row 0 of a precomputed table) back to ABI words.  Canonical values come from fp_from_abi + fp_int, the
+// "largest" flag from int_is_high (Fq2: c1, or c0 when c1 = 0, as dock_serde.cpp is_high2), the bytes from the inverses of be48_to_u64 and
+// fp_from_canonical's split.
 #pragma once
 #include "fp29.hip.h"
 #include "fp2_29.hip.h"
 #include "ec29.hip.h"
+#include "fp30s.hip.h"
 
 namespace serde {
 using namespace bls29;
@@ -291,6 +297,79 @@ FD bool words_valid(const uint32_t *w, bool inf_flag) {
     return inf_flag || any == 0 || (reduced && on_curve && sub);
 }
 
+
+// ---- encoding (dgpu_g*_serialize on the device) -----------------------------------------------------------------------------------------------
+// canonical 29-bit limbs (fp_int) -> six little-endian 64-bit limbs: the inverse of fp_from_canonical's split
+FD void int_to_u64(uint64_t c[6], const Fp &a) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) c[i] = 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        const int bit = i * LB, wi = bit >> 6, sh = bit & 63;
+        c[wi] |= (uint64_t)a.l[i] << sh;
+        if (sh + LB > 64 && wi + 1 < 6) c[wi + 1] |= (uint64_t)a.l[i] >> (64 - sh);
+    }
+}
+// six little-endian 64-bit limbs -> 48 big-endian bytes as 12 native-order 32-bit words: the inverse of be48_to_u64
+FD void u64_to_be48(uint32_t *w, const uint64_t c[6]) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) { w[2 * (5 - i)] = bswap32((uint32_t)(c[i] >> 32)); w[2 * (5 - i) + 1] = bswap32((uint32_t)c[i]); }
+}
+// the canonical value in [0, p) of one coordinate component given as ABI words (Montgomery limbs, R = 2^384)
+FD void abi_int(Fp &c, const uint32_t *w) { Fp a; fp_from_abi(a, w); fp_int(c, a); }
+
+// Affine ABI words w (2 NFP x 12 words: x then y, c0 before c1) -> the point's record (12 / 24 NFP native-order words) in the compressed (COMP)
+// or uncompressed form: the bytes of dgpu_g*_serialize.  The identity (inf_flag, or all-zero words) is the flag byte followed by zeros.
+template <class F, bool COMP>
+FD void encode_point(const uint32_t *w, bool inf_flag, uint32_t *rec) {
+    constexpr int K = Curve<F>::NFP, RW = (COMP ? 12 : 24) * K;
+    uint32_t any = 0;
+#pragma unroll
+    for (int k = 0; k < 24 * K; k++) any |= w[k];
+    const bool inf = inf_flag || any == 0;
+    Fp c[2 * K];                                                     // in byte order: x, then y; on Fq2 c1 before c0
+#pragma unroll
+    for (int j = 0; j < 2 * K; j++) abi_int(c[j], w + 12 * (K * (j / K) + (K == 2 ? 1 - j % K : 0)));
+    bool high;
+    if constexpr (K == 1) high = int_is_high(c[1]);
+    else high = fp_int_is_zero(c[2]) ? int_is_high(c[3]) : int_is_high(c[2]);       // y.c1, or y.c0 when y.c1 = 0
+#pragma unroll
+    for (int j = 0; j < (COMP ? K : 2 * K); j++) { uint64_t u[6]; int_to_u64(u, c[j]); u64_to_be48(rec + 12 * j, u); }
+    uint32_t top = (COMP ? FLAG_COMPRESSED : 0u) | (COMP && high ? FLAG_LARGEST : 0u);
+    if (inf) {
+#pragma unroll
+        for (int k = 0; k < RW; k++) rec[k] = 0;
+        top = (COMP ? FLAG_COMPRESSED : 0u) | FLAG_INF;
+    }
+    rec[0] |= bswap32(top);
+}
+
+// A resident base record (msm_kernels.hip.h, the MSM form of the curve: G1 -> G1S, G2 -> G2S) -> affine ABI words and the identity flag; an
+// identity comes back as zero words.  The coordinates are the signed 30-bit field's Montgomery form (fp30s.hip.h) as fs_from_abi / the table
+// construction's products left them (balanced digits).  G1: x[13] y[13] pad[2] flag pad[3]; G2: x.c0 x.c1 y.c0 y.c1 in slots of 14 words, flag
+// in word 56.  dock_serde_dev.hip checks these numbers against msm::G1S / G2S.
+template <class F> struct Rec;
+template <> struct Rec<Fp> { static constexpr int WORDS = 32, SLOT = SN, FLAGW = 28; };
+template <> struct Rec<Fp2> { static constexpr int WORDS = 64, SLOT = 14, FLAGW = 56; };
+template <class F>
+FD void record_to_abi(const uint32_t *rec, uint32_t *w, uint8_t *inf) {
+    constexpr int K = Curve<F>::NFP;
+    const bool id = rec[Rec<F>::FLAGW] != 0;
+#pragma unroll
+    for (int j = 0; j < 2 * K; j++) {
+        Fs f;
+#pragma unroll
+        for (int i = 0; i < SN; i++) f.l[i] = (int32_t)rec[j * Rec<F>::SLOT + i];
+        SCHK(schk_set_B(f, 1.0);)
+        fs_to_abi(w + 12 * j, f);
+    }
+    if (id) {
+#pragma unroll
+        for (int k = 0; k < 24 * K; k++) w[k] = 0;
+    }
+    *inf = id ? 1 : 0;
+}
+
 #if defined(__HIPCC__)
 constexpr int SERDE_BLOCK = 64;
 // points [lo, hi) of `raw` (records of 12 / 24 NFP 32-bit words); the lowest refused index goes to *first_bad (atomic min; the caller sets it to ~0u)
@@ -321,6 +400,44 @@ __global__ void __launch_bounds__(SERDE_BLOCK) k_validate_words(const uint32_t *
 #pragma unroll
     for (int k = 0; k < 24 * K; k += 4) { const uint4 v = *reinterpret_cast<const uint4 *>(xy + i * 24 * K + k); w[k] = v.x; w[k + 1] = v.y; w[k + 2] = v.z; w[k + 3] = v.w; }
     ok[i] = words_valid<F>(w, is_inf && is_inf[i]) ? 1 : 0;
+}
+// encoding: the ABI words of points [lo, hi) (is_inf may be null) -> their records in out (12 / 24 NFP words per point)
+template <class F, bool COMP>
+__global__ void __launch_bounds__(SERDE_BLOCK) k_serialize_words(const uint32_t *__restrict__ xy, const uint8_t *__restrict__ is_inf, size_t lo, size_t hi, uint32_t *__restrict__ out) {
+    constexpr int K = Curve<F>::NFP, RW = (COMP ? 12 : 24) * K;
+    const size_t i = lo + (size_t)blockIdx.x * SERDE_BLOCK + threadIdx.x;
+    if (i >= hi) return;
+    uint32_t w[24 * K], rec[RW];
+#pragma unroll
+    for (int k = 0; k < 24 * K; k += 4) { const uint4 v = *reinterpret_cast<const uint4 *>(xy + i * 24 * K + k); w[k] = v.x; w[k + 1] = v.y; w[k + 2] = v.z; w[k + 3] = v.w; }
+    encode_point<F, COMP>(w, is_inf && is_inf[i], rec);
+#pragma unroll
+    for (int k = 0; k < RW; k += 4) *reinterpret_cast<uint4 *>(out + i * RW + k) = make_uint4(rec[k], rec[k + 1], rec[k + 2], rec[k + 3]);
+}
+// resident base records of points [lo, hi) (recs: the first record of the range read) -> ABI words into xy and flags into is_inf (either may be
+// null) when ENC = 0, else their records in out (ENC = 1 compressed, 2 uncompressed)
+template <class F, int ENC>
+__global__ void __launch_bounds__(SERDE_BLOCK) k_read_records(const uint32_t *__restrict__ recs, size_t lo, size_t hi, uint32_t *__restrict__ xy, uint8_t *__restrict__ is_inf,
+                                                              uint32_t *__restrict__ out) {
+    constexpr int K = Curve<F>::NFP, RW = (ENC == 1 ? 12 : 24) * K, RECW = Rec<F>::WORDS;
+    const size_t i = lo + (size_t)blockIdx.x * SERDE_BLOCK + threadIdx.x;
+    if (i >= hi) return;
+    uint32_t r[RECW], w[24 * K]; uint8_t inf;
+#pragma unroll
+    for (int k = 0; k < RECW; k += 4) { const uint4 v = *reinterpret_cast<const uint4 *>(recs + i * RECW + k); r[k] = v.x; r[k + 1] = v.y; r[k + 2] = v.z; r[k + 3] = v.w; }
+    record_to_abi<F>(r, w, &inf);
+    if constexpr (ENC == 0) {
+        if (xy) {
+#pragma unroll
+            for (int k = 0; k < 24 * K; k += 4) *reinterpret_cast<uint4 *>(xy + i * 24 * K + k) = make_uint4(w[k], w[k + 1], w[k + 2], w[k + 3]);
+        }
+        if (is_inf) is_inf[i] = inf;
+    } else {
+        uint32_t rec[RW];
+        encode_point<F, ENC == 1>(w, inf != 0, rec);
+#pragma unroll
+        for (int k = 0; k < RW; k += 4) *reinterpret_cast<uint4 *>(out + i * RW + k) = make_uint4(rec[k], rec[k + 1], rec[k + 2], rec[k + 3]);
+    }
 }
 #endif
 

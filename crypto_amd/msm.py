@@ -284,6 +284,16 @@ class DeviceBases:
         return self
 
 
+    def read(self, offset=0, n=None):
+        """(words, is_inf) of points [offset, offset + n) read back from the device (dgpu_bases_read_*): identities as zero words with is_inf = 1"""
+        from . import serde
+        return serde.read_handle(self.curve, self.handle, offset, self.n - offset if n is None else n)
+
+    def to_bytes(self, compressed=True, offset=0, n=None):
+        """arkworks' encoding of points [offset, offset + n), made on the device (dgpu_bases_serialize_*): the inverse of from_serialized"""
+        from . import serde
+        return serde.serialize_handle(self.curve, self.handle, offset, self.n - offset if n is None else n, compressed)
+
     def precompute(self, window_bits=0):
         """dgpu_bases_precompute_*: in place; later MSMs on this handle run over the precomputed-multiples table"""
         rc = self.curve.fn("dgpu_bases_precompute_%s")(self.handle, window_bits)
@@ -368,6 +378,16 @@ class ShardedDeviceBases:
             raise DockGpuError(rc, "dgpu_bases_upload_sharded")
         self.handle = h.value
 
+
+    def read(self, offset=0, n=None):
+        """(words, is_inf) of points [offset, offset + n) read back from the device (dgpu_bases_read_*): identities as zero words with is_inf = 1"""
+        from . import serde
+        return serde.read_handle(self.curve, self.handle, offset, self.n - offset if n is None else n)
+
+    def to_bytes(self, compressed=True, offset=0, n=None):
+        """arkworks' encoding of points [offset, offset + n), made on the device (dgpu_bases_serialize_*): the inverse of from_serialized"""
+        from . import serde
+        return serde.serialize_handle(self.curve, self.handle, offset, self.n - offset if n is None else n, compressed)
 
     def precompute(self, window_bits=0):
         """dgpu_bases_precompute_*: in place; later MSMs on this handle run over the precomputed-multiples table"""

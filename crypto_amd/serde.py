@@ -18,6 +18,37 @@ def serialize(curve, points, is_inf=None, compressed=True):
     return out.tobytes()
 
 
+def serialize_device(curve, points, is_inf=None, compressed=True):
+    """serialize() on the device (dgpu_*_serialize_device): the same bytes"""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, curve.AW)
+    inf = None if is_inf is None else np.ascontiguousarray(is_inf, dtype=np.uint8)
+    out = np.zeros(len(pts) * _SZ[(curve.tag, compressed)], dtype=np.uint8)
+    fn = lib().dgpu_g1_serialize_device if curve.tag == "g1" else lib().dgpu_g2_serialize_device
+    rc = fn(pts.ctypes.data_as(C.c_void_p), None if inf is None else inf.ctypes.data_as(C.c_void_p), len(pts), int(compressed), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise DockGpuError(rc, "serialize_device")
+    return out.tobytes()
+
+
+def read_handle(curve, handle, offset, n):
+    """dgpu_bases_read_*: (words, is_inf) of points [offset, offset + n) of a resident bases handle"""
+    pts = np.zeros((n, curve.AW), dtype=np.uint64)
+    inf = np.zeros(n, dtype=np.uint8)
+    rc = getattr(lib(), "dgpu_bases_read_%s" % curve.tag)(handle, offset, n, pts.ctypes.data_as(C.c_void_p), inf.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise DockGpuError(rc, "dgpu_bases_read")
+    return pts, inf
+
+
+def serialize_handle(curve, handle, offset, n, compressed=True):
+    """dgpu_bases_serialize_*: the encoded points [offset, offset + n) of a resident bases handle"""
+    out = np.zeros(n * _SZ[(curve.tag, compressed)], dtype=np.uint8)
+    rc = getattr(lib(), "dgpu_bases_serialize_%s" % curve.tag)(handle, offset, n, int(compressed), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise DockGpuError(rc, "dgpu_bases_serialize")
+    return out.tobytes()
+
+
 def deserialize(curve, data, compressed=True, validate=True):
     """CanonicalDeserialize: validate=True is Validate::Yes (curve + prime-order subgroup), False is Validate::No (curve only)"""
     sz = _SZ[(curve.tag, compressed)]

@@ -603,6 +603,26 @@ int32_t dgpu_bases_upload_g2_serialized(const uint8_t *in, size_t n, int32_t mod
 int32_t dgpu_g1_validate_batch(const uint64_t *xy /* n*12 */, const uint8_t *is_inf, size_t n, uint8_t *ok /* n */);
 int32_t dgpu_g2_validate_batch(const uint64_t *xy /* n*24 */, const uint8_t *is_inf, size_t n, uint8_t *ok /* n */);
 
+/* ---- the encoding on the device, and resident bases read back (one point per lane) ----
+ * dgpu_g1/g2_serialize_device: the contract and the bytes of dgpu_g1/g2_serialize, on the calling thread's context (dgpu_set_device).  Argument checks
+ * come first (DGPU_E_BADARG); without a device n >= 1 is DGPU_E_NODEVICE, never a host result.  n = 0: DGPU_OK.
+ * dgpu_bases_read_g1/g2: the affine ABI words (xy, may be NULL) and identity flags (is_inf, may be NULL; not both) of points [offset, offset + n) of
+ * a G1 / G2 bases handle: a plain one (dgpu_bases_upload_*, *_serialized, *_strided, dgpu_window_table_mul_to_bases_*, the queries of
+ * dgpu_legogroth16_setup), its precomputed table (dgpu_bases_precompute_*) or a sharded set (dgpu_bases_upload_*_sharded: every part is read on its
+ * own context, the results land in global index order).  An identity comes back as zero words with is_inf = 1.
+ * dgpu_bases_serialize_g1/g2: the same points as the bytes dgpu_g1/g2_serialize writes for them (compressed: 48 / 96 B per point, else 96 / 192 B):
+ * the inverse of dgpu_bases_upload_g1/g2_serialized.
+ * The handle calls run on the context that owns the handle and pin it for the call (a racing dgpu_bases_free waits).  DGPU_E_BADARG: an unknown or
+ * freed handle, another kind (window table, scalars, circuit, ...), the other curve's handle, offset + n > its length, NULL out / both xy and is_inf
+ * NULL (n >= 1).  n = 0 on a valid handle: DGPU_OK.  A refused or failing call keeps no device memory of its own.  The results leave in pieces of
+ * STAGE_CHUNK_BYTES, each copied to the host while the next one encodes (stage timer serde.encode). */
+int32_t dgpu_g1_serialize_device(const uint64_t *xy /* n*12 */, const uint8_t *is_inf, size_t n, int32_t compressed, uint8_t *out);
+int32_t dgpu_g2_serialize_device(const uint64_t *xy /* n*24 */, const uint8_t *is_inf, size_t n, int32_t compressed, uint8_t *out);
+int32_t dgpu_bases_read_g1(uint64_t handle, size_t offset, size_t n, uint64_t *xy /* n*12 or NULL */, uint8_t *is_inf /* n or NULL */);
+int32_t dgpu_bases_read_g2(uint64_t handle, size_t offset, size_t n, uint64_t *xy /* n*24 or NULL */, uint8_t *is_inf /* n or NULL */);
+int32_t dgpu_bases_serialize_g1(uint64_t handle, size_t offset, size_t n, int32_t compressed, uint8_t *out);
+int32_t dgpu_bases_serialize_g2(uint64_t handle, size_t offset, size_t n, int32_t compressed, uint8_t *out);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

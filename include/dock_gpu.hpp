@@ -68,6 +68,9 @@ struct G1 {
     static int32_t upload_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, size_t n, uint64_t *h) { return dgpu_bases_upload_g1_strided(b, st, xo, yo, io, n, h); }
     static int32_t table(const uint64_t *b, uint64_t *h) { return dgpu_window_table_g1(b, h); }
     static int32_t table_mul(uint64_t t, const uint64_t *s, size_t n, int32_t mont, uint64_t *o, uint8_t *oi) { return dgpu_window_table_mul_g1(t, s, n, mont, o, oi); }
+    static int32_t serialize_device(const uint64_t *xy, const uint8_t *i, size_t n, int32_t c, uint8_t *o) { return dgpu_g1_serialize_device(xy, i, n, c, o); }
+    static int32_t bases_read(uint64_t h, size_t off, size_t n, uint64_t *xy, uint8_t *i) { return dgpu_bases_read_g1(h, off, n, xy, i); }
+    static int32_t bases_serialize(uint64_t h, size_t off, size_t n, int32_t c, uint8_t *o) { return dgpu_bases_serialize_g1(h, off, n, c, o); }
 };
 struct G2 {
     static constexpr size_t AW = 24;
@@ -81,6 +84,9 @@ struct G2 {
     static int32_t upload_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, size_t n, uint64_t *h) { return dgpu_bases_upload_g2_strided(b, st, xo, yo, io, n, h); }
     static int32_t table(const uint64_t *b, uint64_t *h) { return dgpu_window_table_g2(b, h); }
     static int32_t table_mul(uint64_t t, const uint64_t *s, size_t n, int32_t mont, uint64_t *o, uint8_t *oi) { return dgpu_window_table_mul_g2(t, s, n, mont, o, oi); }
+    static int32_t serialize_device(const uint64_t *xy, const uint8_t *i, size_t n, int32_t c, uint8_t *o) { return dgpu_g2_serialize_device(xy, i, n, c, o); }
+    static int32_t bases_read(uint64_t h, size_t off, size_t n, uint64_t *xy, uint8_t *i) { return dgpu_bases_read_g2(h, off, n, xy, i); }
+    static int32_t bases_serialize(uint64_t h, size_t off, size_t n, int32_t c, uint8_t *o) { return dgpu_bases_serialize_g2(h, off, n, c, o); }
 };
 
 // ark-ec's Affine { x, y, infinity } is not a flat array.  The MSM entry points take the array of structs as it is (dgpu_msm_*_strided:
@@ -164,7 +170,29 @@ public:
         check(G::msm_handle(h_, offset, n ? bigints[0].data() : nullptr, n, 0, out.data()), "msm_handle");
         return projective_from_abi<G>(out.data());
     }
+    // points [offset, offset + n) read back from the device (dgpu_bases_read_*; n = SIZE_MAX: to the end)
+    std::vector<typename G::Affine> read(size_t offset = 0, size_t n = SIZE_MAX) const {
+        if (n == SIZE_MAX) n = offset <= n_ ? n_ - offset : 0;
+        std::vector<uint64_t> xy(n * G::AW); std::vector<uint8_t> inf(n);
+        check(G::bases_read(h_, offset, n, xy.data(), inf.data()), "bases_read");
+        return affine_from_abi<G>(xy, inf);
+    }
+    // `CanonicalSerialize` of the same points, encoded on the device (dgpu_bases_serialize_*): the bytes serialize_compressed / _uncompressed write
+    std::vector<uint8_t> to_bytes(bool compressed = true, size_t offset = 0, size_t n = SIZE_MAX) const {
+        if (n == SIZE_MAX) n = offset <= n_ ? n_ - offset : 0;
+        std::vector<uint8_t> out(n * (compressed ? 48 : 96) * (G::AW / 12));
+        check(G::bases_serialize(h_, offset, n, compressed, out.data()), "bases_serialize");
+        return out;
+    }
 };
+
+// the points' `CanonicalSerialize` bytes, encoded on the current device (dgpu_g*_serialize_device; same bytes as dgpu_g*_serialize)
+template <class G> std::vector<uint8_t> serialize_device(const std::vector<typename G::Affine> &points, bool compressed = true) {
+    Packed<G> p(points, points.size());
+    std::vector<uint8_t> out(points.size() * (compressed ? 48 : 96) * (G::AW / 12));
+    check(G::serialize_device(p.xy.data(), p.inf.data(), points.size(), compressed, out.data()), "serialize_device");
+    return out;
+}
 
 // utils/src/msm.rs:8-52.  `num_multiplications` only sizes arkworks' window; the device table is fixed (accepted, ignored).
 template <class G> class WindowTable {

@@ -416,3 +416,44 @@ pub fn validate_g2_batch(points: &[G2Affine]) -> Option<Vec<bool>> {
     if unsafe { dgpu_g2_validate_batch(xy.as_ptr(), inf.as_ptr(), points.len(), ok.as_mut_ptr()) } != DGPU_OK { return None; }
     Some(ok.iter().map(|&v| v != 0).collect())
 }
+
+// ---- the encoding on the device, and resident bases read back --------------------------------------------------------------------------------------------
+/// serialize_g1 encoded on the current device (the same bytes); None: no device or another error.  The public names of these six are in src/encode.rs
+pub(crate) fn device_serialize_g1(points: &[G1Affine], compressed: bool) -> Option<Vec<u8>> {
+    let (xy, inf) = pack_g1(points);
+    let mut out = ark_std::vec![0u8; points.len() * if compressed { 48 } else { 96 }];
+    if unsafe { dgpu_g1_serialize_device(xy.as_ptr(), inf.as_ptr(), points.len(), compressed as i32, out.as_mut_ptr()) } != DGPU_OK { return None; }
+    Some(out)
+}
+/// serialize_g2 encoded on the current device (the same bytes)
+pub(crate) fn device_serialize_g2(points: &[G2Affine], compressed: bool) -> Option<Vec<u8>> {
+    let (xy, inf) = pack_g2(points);
+    let mut out = ark_std::vec![0u8; points.len() * if compressed { 96 } else { 192 }];
+    if unsafe { dgpu_g2_serialize_device(xy.as_ptr(), inf.as_ptr(), points.len(), compressed as i32, out.as_mut_ptr()) } != DGPU_OK { return None; }
+    Some(out)
+}
+/// the affine ABI words of points [offset, offset + n) of a G1 bases handle (plain, precomputed table or sharded set); an identity is all-zero words.
+/// None: not a G1 bases handle, a range past its end, or another error
+pub(crate) fn handle_read_g1(handle: u64, offset: usize, n: usize) -> Option<Vec<[u64; 12]>> {
+    let mut xy = ark_std::vec![[0u64; 12]; n];
+    if unsafe { dgpu_bases_read_g1(handle, offset, n, xy.as_mut_ptr() as *mut u64, core::ptr::null_mut()) } != DGPU_OK { return None; }
+    Some(xy)
+}
+/// bases_read_g1 for a G2 bases handle
+pub(crate) fn handle_read_g2(handle: u64, offset: usize, n: usize) -> Option<Vec<[u64; 24]>> {
+    let mut xy = ark_std::vec![[0u64; 24]; n];
+    if unsafe { dgpu_bases_read_g2(handle, offset, n, xy.as_mut_ptr() as *mut u64, core::ptr::null_mut()) } != DGPU_OK { return None; }
+    Some(xy)
+}
+/// `CanonicalSerialize` of points [offset, offset + n) of a G1 bases handle, encoded on the device that holds it
+pub(crate) fn handle_serialize_g1(handle: u64, offset: usize, n: usize, compressed: bool) -> Option<Vec<u8>> {
+    let mut out = ark_std::vec![0u8; n * if compressed { 48 } else { 96 }];
+    if unsafe { dgpu_bases_serialize_g1(handle, offset, n, compressed as i32, out.as_mut_ptr()) } != DGPU_OK { return None; }
+    Some(out)
+}
+/// bases_serialize_g1 for a G2 bases handle
+pub(crate) fn handle_serialize_g2(handle: u64, offset: usize, n: usize, compressed: bool) -> Option<Vec<u8>> {
+    let mut out = ark_std::vec![0u8; n * if compressed { 96 } else { 192 }];
+    if unsafe { dgpu_bases_serialize_g2(handle, offset, n, compressed as i32, out.as_mut_ptr()) } != DGPU_OK { return None; }
+    Some(out)
+}

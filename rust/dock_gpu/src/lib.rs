@@ -26,6 +26,7 @@ use ark_ec::{AffineRepr, VariableBaseMSM};
 use ark_ff::{BigInt, PrimeField};
 use ark_std::vec::Vec;
 
+pub mod encode;
 pub mod generic;
 pub mod host;
 
@@ -34,6 +35,7 @@ pub type G2Prepared = ArkG2Prepared<ark_bls12_381::Config>;
 pub mod ffi;
 pub use ffi::*;
 pub use host::*;          // (devices, cache, sharded MSMs, window tables, witness map, the host-key prover, serde: src/host.rs)
+pub use encode::*;        // (encoding on the device, resident bases read back: src/encode.rs)
 
 pub const G2_PREPARED_WORDS: usize = DGPU_G2_PREPARED_WORDS;
 
