@@ -66,5 +66,11 @@ int32_t dgpu_selftest_glv_decompose(const uint64_t k[4], uint64_t k1[2], uint64_
     hostf::glv_decompose(k, k1, k2);
     return DGPU_OK;
 }
+// host self-test hook: the GLS split the G2 scaling and fold kernels are fed with (k mod r = d0 + d1 |x| + d2 |x|^2 + d3 |x|^3, d0 .. d2 < |x|)
+int32_t dgpu_selftest_gls4_decompose(const uint64_t k[4], uint64_t d[4]) {
+    if (!k || !d) return DGPU_E_BADARG;
+    hostf::gls4_decompose(k, d);
+    return DGPU_OK;
+}
 
 }  // extern "C"

@@ -338,8 +338,10 @@ int32_t dgpu_fp12_multi_pow(const uint64_t *a /* n*72 */, const uint64_t *e /* n
  * multiply_field_elems_with_same_group_elem (utils/src/msm.rs:8-62) and the six query computations of the LegoGroth16 CRS
  * generator followed by normalize_batch (legogroth16/src/generator.rs:335-399,424-431).
  * out_i = scalars_i * base as affine points (x, y Montgomery limbs; zeros and out_inf[i] = 1 for the identity).
- * montgomery != 0: scalars are Fr Montgomery limbs (what &[Fr] holds), else canonical.  The table handle keeps
- * 32 x 255 multiples of the base in device memory (1 MiB for G1, 2 MiB for G2). */
+ * montgomery != 0: scalars are Fr Montgomery limbs (what &[Fr] holds), else canonical.  Canonical scalars may be any 256-bit integer,
+ * r and above included: all 32 bytes are digits of the table, so the product is the integer times the base (the same point as the scalar
+ * reduced mod r; a multiple of r gives the identity).  The table handle keeps 32 x 255 multiples of the base in device memory (1 MiB for G1,
+ * 2 MiB for G2). */
 int32_t dgpu_window_table_g1(const uint64_t base_xy[12], uint64_t *handle);
 int32_t dgpu_window_table_g2(const uint64_t base_xy[24], uint64_t *handle);
 int32_t dgpu_window_table_free(uint64_t handle);
@@ -371,7 +373,8 @@ int32_t dgpu_g2_mul_add_batch(const uint64_t *p_xy /* n*24 */, const uint8_t *p_
  * (identity: zero words and out_inf[i] = 1).  One handle serves any number of applies; dgpu_fold_free releases it.  crypto_amd/csrc/fold_kernels.hip.h */
 int32_t dgpu_g1_fold_prepare(const uint64_t *p_xy /* n*12 */, size_t n, uint64_t *handle);
 int32_t dgpu_g2_fold_prepare(const uint64_t *p_xy /* n*24 */, size_t n, uint64_t *handle);
-/* both groups' point sets of a round in ONE launch (two prepare calls can land on one hardware queue and run one after the other); a set may be empty */
+/* both groups' point sets of a round in ONE launch (two prepare calls can land on one hardware queue and run one after the other); a set may be empty
+ * (n = 0: its pointers are not read and its handle comes back 0), not both (DGPU_E_BADARG, both handles 0) */
 int32_t dgpu_fold_prepare_pair(const uint64_t *g1_xy, size_t n1, uint64_t *g1_handle, const uint64_t *g2_xy, size_t n2, uint64_t *g2_handle);
 int32_t dgpu_g1_fold_apply(uint64_t handle, const uint64_t scalar[4], const uint64_t *addend_xy /* n*12 or NULL */, uint64_t *out_xy, uint8_t *out_inf);
 int32_t dgpu_g2_fold_apply(uint64_t handle, const uint64_t scalar[4], const uint64_t *addend_xy /* n*24 or NULL */, uint64_t *out_xy, uint8_t *out_inf);

@@ -263,6 +263,26 @@ def test_glv_decomposition_on_host():
         assert O.limbs_to_int(k1) == rem and O.limbs_to_int(k2) == q, hex(k)
 
 
+def test_gls4_decomposition_on_host():
+    """k mod r = d0 + d1 |x| + d2 |x|^2 + d3 |x|^3 with d0 .. d2 < |x| (what the G2 scaling and fold kernels are fed with) against Python's repeated
+    divmod (util.gls4_split, from which tests/test_gpu_fold_shapes.py builds scalars with a chosen number of set bits per digit)"""
+    import random
+    L = dev_lib()                        # (a self-test hook: include/dock_gpu_dev.h)
+    x = U.GLS_X
+    assert U.R == x ** 4 - x ** 2 + 1
+    random.seed(6)
+    edge = [0, 1, x - 1, x, x + 1, x * x - 1, x * x, x * x + 1, x ** 3 - 1, x ** 3, x ** 3 + x, (x - 1) * (1 + x + x * x), (x ** 3) * (U.R // x ** 3), 2 ** 64 - 1, 2 ** 64,
+            2 ** 128 - 1, 2 ** 128, 2 ** 192 - 1, 2 ** 192, sum((2 ** 63 - 1) * x ** j for j in range(4)), U.R - 1, U.R, U.R + 1, U.R + 5, 2 * U.R - 1, 2 * U.R, 2 * U.R + 1,
+            2 ** 255, (1 << 256) - 1]
+    for k in edge + [random.randrange(1 << 256) for _ in range(3000)] + [random.randrange(1 << random.randrange(1, 257)) for _ in range(1000)]:
+        a = O.int_to_limbs(k, 4); d = np.zeros(4, np.uint64)
+        assert L.dgpu_selftest_gls4_decompose(a.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p)) == 0
+        want = U.gls4_split(k)
+        assert [int(v) for v in d] == want, hex(k)
+        assert sum(v * x ** j for j, v in enumerate(want)) == k % U.R and all(v < x for v in want[:3]) and want[3] < 2 ** 64, hex(k)
+    assert L.dgpu_selftest_gls4_decompose(None, None) == -3
+
+
 def test_prepared_batches_do_not_pose_as_arrays():
     """A G2Prepared batch indexes to a G2Prepared batch; numpy used to walk such an object as an endless sequence of sequences when a mixed
     operand list reached np.asarray (a batch verifier that passed [b, delta_pc, gamma_pc] per proof to the pairing checker never returned

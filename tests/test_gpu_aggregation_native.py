@@ -107,6 +107,37 @@ def test_native_aggregate_equals_python(n):
     assert rejects(lambda: V(proof=NA.aggregate_proofs(pk, AG.MerlinTranscript(label), wrong)))
 
 
+@pytest.mark.parametrize("n", [512, 1024])
+def test_native_aggregate_where_the_fold_changes_form(n):
+    """The GIPA rounds fold right halves of n / 2, n / 4, ... points with dgpu_fold_prepare_pair / dgpu_g*_fold_apply: up to 256 points a block per
+    point, above four points per block (crypto_amd/csrc/k_fixed.hip launch_fold_apply).  512 proofs fold 256-point halves (the border), 1024 — the
+    size the benchmark reports — 512-point halves, the first inside the protocol that reach the four-points-per-block form.  The native aggregate
+    verifies; one flipped word in one A, one B or one C makes the verifier reject; every element equals the Python mirror's, which folds through
+    ops.mul_add — the chain kernels, not the fold tree (measured on an MI355X at 1024 proofs: the mirror's aggregation 0.1 s, the whole case 1.0 s)."""
+    import time
+    t0 = time.time()
+    vk, proofs, inputs, _ = make_statement(n, 1, seed=300 + n)
+    pk, vsrs = AG.setup_fake_srs(0xA11CE5EED + n, 0xBE7A5EED, n, O.G1.generator(), O.G2.generator()).specialize(n)
+    label = b"native-aggregation-large"
+    pvk = {"vk": vk}
+    rnd = 0x5EED7654321
+    t1 = time.time()
+    words = NA.aggregate_proofs_words(pk, AG.MerlinTranscript(label), proofs)
+    NA.verify_aggregate_proof(vsrs, pvk, inputs, words, rnd, AG.MerlinTranscript(label))
+    t2 = time.time()
+    for key, i in (("a", 0), ("b", n // 2 + 5), ("c", n - 1)):
+        bad = list(proofs); bad[i] = dict(bad[i])
+        w = bad[i][key].copy(); w[0] ^= np.uint64(1); bad[i][key] = w
+        tampered = NA.aggregate_proofs_words(pk, AG.MerlinTranscript(label), bad)
+        assert not (tampered == words).all(), (key, i)
+        assert rejects(lambda: NA.verify_aggregate_proof(vsrs, pvk, inputs, tampered, rnd, AG.MerlinTranscript(label))), (key, i)
+    t3 = time.time()
+    py = AG.aggregate_proofs(pk, AG.MerlinTranscript(label), proofs)
+    assert same_proof(py, NA.proof_from_words(words))
+    print("n = %d: statement and SRS %.1f s, aggregate + verify %.2f s, three tampered aggregates %.2f s, Python mirror %.1f s" %
+          (n, t1 - t0, t2 - t1, t3 - t2, time.time() - t3))
+
+
 def test_native_transcript_in_c_gives_the_same_proof():
     """the caller's transcript as C callbacks (merlin_native.c: no interpreter inside the library call) — the same proof words as with the Python
     transcript called back, each verifier accepts the other's transcript form, a wrong label is rejected"""

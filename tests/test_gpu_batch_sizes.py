@@ -14,7 +14,6 @@ A batch verifier that gives two proofs the same weight accepts errors that cance
 A_i + E with A_j - E where B_i = B_j): those batches are rejected at random batching scalars, and — the check that the construction cancels — accepted
 at the scalar 1, where every weight is one."""
 import ctypes as C
-from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 import torch
@@ -25,6 +24,7 @@ from crypto_amd import legogroth16 as LG
 from crypto_amd import pairing
 from crypto_amd import fixed_base as FB
 from crypto_amd._native import lib
+from util import mul_add_oracle, first_bad      # (shared with tests/test_gpu_fold_shapes.py and tests/test_gpu_fixed_base.py)
 
 pytestmark = pytest.mark.gpu
 R = U.R
@@ -57,11 +57,6 @@ def ints(rng, k):
     return [int.from_bytes(rng.bytes(40), "little") % (R - 1) + 1 for _ in range(k)]
 
 
-def pmap(fn, items):
-    with ThreadPoolExecutor(16) as ex:
-        return list(ex.map(fn, items))
-
-
 def g1(k):
     return O.G1.to_affine(O.G1.mul(O.G1.generator(), O.int_to_limbs(k % R, 4)))[0]
 
@@ -88,10 +83,6 @@ def near(n, ends, border_offsets):
     """indices at the ends (offsets >= 0 from the first index, < 0 from one past the last) and at the given offsets from every border, inside [0, n)"""
     cand = {o if o >= 0 else n + o for o in ends} | {b + o for b in BORDERS for o in border_offsets}
     return sorted(i for i in cand if 0 <= i < n)
-
-
-def first_bad(got, got_inf, want, want_inf):
-    return np.nonzero((got != want).any(axis=1) | (np.asarray(got_inf) != np.asarray(want_inf)))[0][:8]
 
 
 # ============================================ 1. dgpu_g1_scale_batch vs the oracle ============================================
@@ -157,21 +148,6 @@ def mul_add_case(G, n, seed, edge):
         else:
             p_inf[i] = 1
     return P, p_inf, sc, A, a_inf, cls
-
-
-def mul_add_oracle(G, P, p_inf, sc, A, a_inf):
-    n = len(P)
-    pid = (p_inf | ~P.any(axis=1)).astype(bool)
-    aid = (a_inf | ~A.any(axis=1)).astype(bool)
-
-    def one(i):
-        e = G.mul(P[i], sc[i], inf=bool(pid[i]))
-        if not aid[i]:
-            e = G.add(e, U.jac_abi(G, A[i]))
-        a, inf = G.to_affine(e)
-        return (np.zeros(G.AW, np.uint64) if inf else a), inf
-    res = pmap(one, range(n))
-    return np.stack([r[0] for r in res]), np.array([r[1] for r in res], np.uint8)
 
 
 def mul_add_abi(G, P, p_inf, sc, A, a_inf):

@@ -124,6 +124,19 @@ def glv_split(k):
     return k1, k2
 
 
+GLS_X = 0xD201000000010000                        # |x| of BLS12-381: the base of the host's split of the G2 scalings (k mod R = d0 + d1 |x| + d2 |x|^2 + d3 |x|^3)
+
+
+def gls4_split(k):
+    """[d0, d1, d2, d3] with k mod R = sum d_j GLS_X^j, d0 .. d2 < GLS_X (what the G2 scaling and fold kernels are fed with)"""
+    k %= R
+    d = []
+    for _ in range(3):
+        k, rem = divmod(k, GLS_X)
+        d.append(rem)
+    return d + [k]
+
+
 def small_primes_dividing(n, bound=1 << 16):
     out, p = [], 2
     while p < bound:
@@ -225,3 +238,41 @@ def plus_multiples(G, bases, e, T_abi, threads=8):
     with ThreadPoolExecutor(threads) as ex:
         list(ex.map(work, np.array_split(idx, threads)))
     return out
+
+
+# ---- every row of a batched scaling against the oracle's double-and-add, on a pool of host threads ---------------------------------------------
+def pmap(fn, items):
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(16) as ex:
+        return list(ex.map(fn, items))
+
+
+def scaled_jac(G, P, p_inf, sc):
+    """the oracle's s_i P_i (Jacobian), one scalar per point or ((4,) limbs) one for all; identity points by the flag or by all-zero words"""
+    sc = np.asarray(sc, np.uint64)
+    pid = ~P.any(axis=1) if p_inf is None else (np.asarray(p_inf, bool) | ~P.any(axis=1))
+    return pmap(lambda i: G.mul(P[i], sc if sc.ndim == 1 else sc[i], inf=bool(pid[i])), range(len(P)))
+
+
+def plus_addends(G, jac, A, a_inf):
+    """(rows, flags) of jac_i + A_i as affine ABI words (A None: no addends; identity addends by the flag or by all-zero words); an identity row is
+    zero words with the flag set"""
+    n = len(jac)
+    aid = np.ones(n, bool) if A is None else (~A.any(axis=1) if a_inf is None else (np.asarray(a_inf, bool) | ~A.any(axis=1)))
+
+    def one(i):
+        e = jac[i] if aid[i] else G.add(jac[i], jac_abi(G, A[i]))
+        a, inf = G.to_affine(e)
+        return (np.zeros(G.AW, np.uint64) if inf else a), inf
+    res = pmap(one, range(n))
+    return np.stack([r[0] for r in res]), np.array([r[1] for r in res], np.uint8)
+
+
+def mul_add_oracle(G, P, p_inf, sc, A, a_inf):
+    """out_i = A_i + s_i P_i by the oracle's mul, add and to_affine: (rows, identity flags)"""
+    return plus_addends(G, scaled_jac(G, P, p_inf, sc), A, a_inf)
+
+
+def first_bad(got, got_inf, want, want_inf):
+    """the first rows (at most eight) whose words or identity flag differ"""
+    return np.nonzero((got != want).any(axis=1) | (np.asarray(got_inf) != np.asarray(want_inf)))[0][:8]
