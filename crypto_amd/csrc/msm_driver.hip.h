@@ -982,6 +982,119 @@ int32_t msm_handle(uint64_t bases, size_t offset, const uint64_t *scalars, size_
     return rc;
 }
 
+// ---- many rows of scalars over one plain handle in one call (many_kernels.hip.h) -----------------------------------------------------------
+// rows per launch: 2^17 terms' worth, at most 4096 rows — the scalars, 16 window sums per row and (rows of more than 128 terms) up to 64 partials per
+// window stay below ~70 MB of the slot's grow-only buffers whatever m; dgpu_set_many_chunk_rows (development surface) overrides it
+inline size_t many_chunk_rows(size_t n) {
+    const int forced = gs.many_chunk.load();
+    if (forced > 0) return (size_t)forced;
+    const size_t r = ((size_t)1 << 17) / std::max<size_t>(n, 1);
+    return std::min<size_t>(4096, std::max<size_t>(r, 1));
+}
+template <class C> int32_t ws_many(Slot &sl, size_t n, size_t rows, const ManyGeom &g) {
+    int32_t rc;
+    typedef typename C::ACC A;
+    constexpr size_t WPS = SMALL_MSM_W / SMALL_MSM_S;
+    if ((rc = sl.flags.ensure(64))) return rc;
+    if ((rc = sl.in_scalars.ensure(rows * n * 32))) return rc;
+    if ((rc = sl.bucket.ensure(rows * WPS * A::XW * 4))) return rc;                      // the window sums and their flags
+    if ((rc = sl.bucket_inf.ensure(rows * WPS))) return rc;
+    if (g.nblk > 1) {
+        if ((rc = sl.head.ensure(rows * WPS * g.nblk * A::XW * 4))) return rc;          // the blocks' partials, their flags, the per-window block counters
+        if ((rc = sl.part_inf.ensure(rows * WPS * g.nblk))) return rc;
+        if ((rc = sl.cnt.ensure(rows * WPS * 4))) return rc;
+    }
+    if ((rc = sl.win.ensure(rows * 3 * C::ABI_W * 4))) return rc;                        // the rows' results and their identity flags
+    return sl.win_inf.ensure(rows);
+}
+// the rows on the device, chunk by chunk: scalars up (rows packed: what lies between them in the caller's memory never crosses), tree, fold, results down
+template <class C>
+int32_t msm_device_many(Slot &sl, const SmallSub &sub, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, bool mont, uint64_t *out, uint8_t *out_inf) {
+    int32_t rc;
+    constexpr size_t JW = 3 * C::ABI_W / 2;                                               // u64 words per result
+    const ManyGeom g = many_geometry(n);
+    const size_t chunk = std::min(m, many_chunk_rows(n));
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws_many<C>(sl, n, chunk, g))) return rc;
+    if (g_dev_allocs.load() != allocs0) {                 // a new shape: the caller's other host threads come with it next (reserve_idle_slots: the one-shot calls do the same)
+        Ctx &cx = cur();
+        for (int k = 0; k < N_SLOTS; k++) {
+            Slot &o = cx.slots[k];
+            if (&o == &sl || !o.mu.try_lock()) continue;
+            (void)ws_many<C>(o, n, chunk, g);
+            o.mu.unlock();
+        }
+    }
+    hipStream_t s = sl.stream;
+    uint32_t *const d_sc = sl.in_scalars.as<uint32_t>(), *const d_bad = sl.flags.as<uint32_t>();
+    HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
+    uint32_t *const hbad = (uint32_t *)sl.hpin;
+    for (size_t r0 = 0; r0 < m; r0 += chunk) {
+        const size_t rows = std::min(chunk, m - r0);
+        const uint64_t *src = scalars + r0 * row_stride * 4;
+        hipEvent_t ev = sl.copy_ev[sl.ev_next++ % (Slot::N_COPY_EV + 1)];
+        if (row_stride == n) HIPCHK(hipMemcpyAsync(d_sc, src, rows * n * 32, hipMemcpyHostToDevice, sl.cstream));
+        else HIPCHK(hipMemcpy2DAsync(d_sc, n * 32, src, row_stride * 32, n * 32, rows, hipMemcpyHostToDevice, sl.cstream));
+        HIPCHK(hipEventRecord(ev, sl.cstream));
+        HIPCHK(hipStreamWaitEvent(s, ev, 0));
+        if (mont) ntt::launch_fr_mont_to_canonical(s, d_sc, rows * n);
+        if (g.nblk > 1) HIPCHK(hipMemsetAsync(sl.cnt.p, 0, rows * (SMALL_MSM_W / SMALL_MSM_S) * 4, s));
+        {
+            StageTimer st(sl, "msm.many_tree");
+            launch_many_tree<C>(s, sub.tab, sub.tab_inf, d_sc, n, n, rows, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(), sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_bad);
+        }
+        {
+            StageTimer st(sl, "msm.many_fold");
+            launch_many_fold<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), rows, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out + r0 * JW, sl.win.p, rows * JW * 8, hipMemcpyDeviceToHost, s));
+        if (out_inf) HIPCHK(hipMemcpyAsync(out_inf + r0, sl.win_inf.p, rows, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hbad, d_bad, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));                  // (the next chunk's scalars overwrite this one's)
+        if (gs.prof) prof_flush(sl);
+        if (*hbad) return DGPU_E_BADARG;                  // a scalar >= 2^255 somewhere in the block: the whole call is refused
+    }
+    return DGPU_OK;
+}
+template <class C, class HF>
+int32_t msm_handle_many(uint64_t bases, size_t offset, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, int mont, uint64_t *out, uint8_t *out_inf, int kind) {
+    if (m == 0) return DGPU_OK;
+    constexpr size_t JW = 3 * sizeof(HF) / 8;
+    if (!out || (n && (!scalars || row_stride < n)) || m >= (1ull << 31) || n >= (1ull << 31) || row_stride >= (1ull << 31)) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;             // (before the size threshold, like the single call)
+    if (!tl_no_min && m * n < std::min<size_t>(gs.min_gpu_n, DGPU_MIN_GPU_N_HANDLE)) return DGPU_E_TOO_SMALL;      // the batch is the unit: many one-term rows are device work
+    bool served = false;
+    int32_t rc = DGPU_OK;
+    {
+        HandleRef hb(bases);
+        if (!hb.ok || (hb.h.kind != kind && hb.h.kind != kind + 9) || offset > hb.h.n || n > hb.h.n - offset) return DGPU_E_BADARG;
+        if (n == 0) {                                     // every row is the empty sum
+            for (size_t j = 0; j < m; j++) { write_identity<HF>(out + j * JW); if (out_inf) out_inf[j] = 1; }
+            return DGPU_OK;
+        }
+        // the new kernels serve plain handles within the small path's reach; anything else (a precomputed table, more than 8192 bases, the small path switched
+        // off, no memory for the table) runs its rows through the single-row driver below
+        if (hb.h.kind == kind && hb.h.n <= SMALL_MSM_MAX_N && n <= gs.small_max.load()) {
+            CtxScope on_owner(hb.h.ctx);
+            SLOT_ACQUIRE(L, sl);
+            HIPCHK(hipSetDevice(cur().device));
+            SmallSub sub;
+            if (small_sub_for<C>(sl, bases, hb.h, offset, n, sub, true)) {
+                served = true;
+                rc = msm_device_many<C>(sl, sub, scalars, row_stride, n, m, mont != 0, out, out_inf);
+                if (rc) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); }      // nothing of ours may still read the caller's scalars
+            }
+        }
+    }
+    if (served) return rc;
+    for (size_t j = 0; j < m; j++) {
+        if ((rc = msm_handle<C, HF>(bases, offset, scalars + 4 * row_stride * j, n, mont, out + j * JW, kind, false))) return rc;
+        if (out_inf) { uint64_t z = 0; for (size_t k = 2 * JW / 3; k < JW; k++) z |= out[j * JW + k]; out_inf[j] = z == 0; }
+    }
+    return DGPU_OK;
+}
+
 // ---- the resident-bases cache (bases_cache.hpp) --------------------------------------------------------------------------------------------
 // device bytes of an entry of n points as a table of width c (0: the automatic choice; a handle too short for a table stays plain)
 template <class C> inline size_t cache_entry_bytes(size_t n, int c) {

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "msm_kernels.hip.h"
+#include "many_fold.hip.h"
 
 namespace msm {
 
@@ -37,6 +38,12 @@ template <class C> void launch_small_table(hipStream_t s, const uint32_t *bases,
 template <class C> void launch_small_subtable(hipStream_t s, const uint32_t *bases, size_t n, uint32_t *tab, uint8_t *tab_inf);
 template <class C> void launch_small_tree(hipStream_t s, const uint32_t *tab, const uint8_t *tab_inf, int subtables, const uint32_t *scalars, size_t n, uint32_t *partial, uint8_t *partial_inf,
                                           uint32_t *count, uint32_t *win_abi, uint8_t *win_inf, uint8_t *win_bad);
+
+// many rows of scalars over one resident table in one call (many_kernels.hip.h; k_g1_many.hip / k_g2_many.hip): the tree over a chunk of rows (geometry:
+// many_fold.hip.h many_geometry; window sums in the accumulator's own form, 16 per row; *bad_flag |= a scalar >= 2^255), then Horner + normalisation per row
+template <class C> void launch_many_tree(hipStream_t s, const uint32_t *tab, const uint8_t *tab_inf, const uint32_t *scalars, size_t n, size_t row_stride, size_t rows, uint32_t *partial,
+                                         uint8_t *partial_inf, uint32_t *count, uint32_t *win, uint8_t *win_inf, uint32_t *bad_flag);
+template <class C> void launch_many_fold(hipStream_t s, const uint32_t *win, const uint8_t *win_inf, size_t rows, uint32_t *out_xyz, uint8_t *out_inf);
 
 // precomputed-multiples tables (pre_kernels.hip.h; k_g1_pre.hip / k_g2_pre.hip)
 template <class C> void launch_pre_step(hipStream_t s, const uint32_t *prev, size_t n, int c, uint32_t *tmp, uint32_t *out);

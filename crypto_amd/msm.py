@@ -331,6 +331,24 @@ class DeviceBases:
             raise DockGpuError(rc, "dgpu_msm_handle")
         return out
 
+    def msm_many(self, scalars, offset=0, montgomery=False, flags=False):
+        """dgpu_msm_*_handle_many: one MSM per row of `scalars` (m, n, 4) over bases [offset, offset + n), in one call -> (m, 18 | 36), each row
+        what msm_bigint gives for it; flags=True also returns the (m,) identity flags.  The rows may be a strided view along the first axis
+        (rows of a wider matrix): what lies between them is not read."""
+        scalars = np.asarray(scalars, dtype=np.uint64)
+        if scalars.ndim != 3 or scalars.shape[2] != 4:
+            raise ValueError("scalars must have shape (m, n, 4)")
+        m, n = scalars.shape[:2]
+        if m and n and not (scalars.strides[2] == 8 and scalars.strides[1] == 32 and scalars.strides[0] % 32 == 0 and scalars.strides[0] >= 32 * n):
+            scalars = np.ascontiguousarray(scalars)
+        row_stride = scalars.strides[0] // 32 if m and n else n
+        out = np.zeros((m, self.curve.JW), dtype=np.uint64)
+        inf = np.zeros(m, dtype=np.uint8)
+        rc = self.curve.fn("dgpu_msm_%s_handle_many")(self.handle, offset, scalars.ctypes.data_as(C.c_void_p) if m and n else None, row_stride, n, m, int(montgomery), _p(out), _p(inf))
+        if rc:
+            raise DockGpuError(rc, "dgpu_msm_handle_many")
+        return (out, inf) if flags else out
+
     def msm_resident(self, dscalars, n=None, base_offset=0, scalar_offset=0):
         if n is None:
             n = min(self.n - base_offset, dscalars.n - scalar_offset)

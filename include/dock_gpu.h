@@ -185,6 +185,27 @@ int32_t dgpu_scalars_free(uint64_t handle);
 int32_t dgpu_scalars_upload_parts(const uint64_t *const *parts, const size_t *counts, size_t n_parts, int32_t montgomery, uint64_t *handle);
 int32_t dgpu_msm_g1_handle(uint64_t bases, size_t offset, const uint64_t *scalars, size_t n, int32_t montgomery, uint64_t out_xyz[18]);
 int32_t dgpu_msm_g2_handle(uint64_t bases, size_t offset, const uint64_t *scalars, size_t n, int32_t montgomery, uint64_t out_xyz[36]);
+/* MANY small MSMs over ONE resident base set in one call: row j multiplies bases [offset, offset + n) of the handle by the n scalars at
+ * scalars + 4 * row_stride * j (row_stride >= n scalars between rows; what lies between two rows is never read) and writes out_xyz[j] (18 / 36 words) —
+ * bit for bit what dgpu_msm_g*_handle(bases, offset, scalars + 4 * row_stride * j, n, montgomery, ..) writes, identity rows included — and out_inf[j] = 1
+ * for an identity row (out_inf may be NULL).  The reference issues its small MSMs this way: verifiable_encryption/src/tz_21/dkgith.rs:174-192,368
+ * (NUM_REPETITIONS x NUM_PARTIES msm_unchecked(comm_key, ..)), rdkgith.rs:140-147, bbs_plus/src/setup.rs:128-146,176-193, kvac/src/bbdt_2016/setup.rs:109,
+ * kvac/src/bbs_sharp/setup.rs:122, schnorr_pok/src/pok_generalized_pedersen.rs:97,153.
+ * Refusals: a scalar with bit 255 set ANYWHERE in the m x n block refuses the whole call (DGPU_E_BADARG; no row of out_xyz is then defined); m = 0 is
+ * DGPU_OK without touching a device or the pointers; n = 0 answers every row as the single call answers n = 0; NULL scalars / out_xyz with m, n > 0,
+ * row_stride < n, offset + n beyond the handle, a bad or busy handle: DGPU_E_BADARG; DGPU_E_TOO_SMALL only when m * n (the batch, not the row) is below
+ * min(dgpu_get_min_gpu_n(), DGPU_MIN_GPU_N_HANDLE): 300 one-term rows are device work.
+ * Paths: a PLAIN handle of at most 8192 bases with n <= dgpu_set_small_msm_max takes the many-row kernels (crypto_amd/csrc/many_kernels.hip.h) over the
+ * handle's small-path table (built on the spot if the handle has none yet): per chunk of rows ONE launch of the 16 trees of every row — rows of up to 32
+ * terms share blocks — and ONE launch that folds and normalises every row on the device; the host only copies.  Any other handle the single call accepts
+ * (a precomputed-multiples table, more than 8192 bases, dgpu_set_small_msm_max(0), no memory for the table) runs its rows through the single-row driver inside
+ * the call: correct, not faster than the caller's own loop.  Sharded handles are refused like dgpu_msm_*_handle refuses them.
+ * Memory: the call owns one slot; rows go in chunks of min(4096, 2^17 / n) rows, so the slot's grow-only workspace stays below ~70 MB whatever m, and a
+ * second call of a shape already seen allocates nothing.  Thread-safe like every entry point: several calls may be in flight. */
+int32_t dgpu_msm_g1_handle_many(uint64_t bases, size_t offset, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, int32_t montgomery,
+                                uint64_t *out_xyz /* m * 18 */, uint8_t *out_inf /* m or NULL */);
+int32_t dgpu_msm_g2_handle_many(uint64_t bases, size_t offset, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, int32_t montgomery,
+                                uint64_t *out_xyz /* m * 36 */, uint8_t *out_inf /* m or NULL */);
 /* Precomputed-multiples mode for a resident query (in place; the handle keeps its id): the device builds table[w][i] = 2^(c w) P_i for the
  * W = 255 / c + 1 windows (W x the memory: 1.7 GB for a 2^20-point G1 query at c = 20 — sized for 288 GB of HBM), after which every MSM on
  * the handle adds digit w of scalar i into ONE bucket set shared by all windows: wider windows (13 instead of 16 additions per term at

@@ -64,6 +64,7 @@ struct G1 {
     static int32_t msm_mont(const uint64_t *b, const uint8_t *i, const uint64_t *s, size_t n, uint64_t *o) { return dgpu_msm_g1_mont(b, i, s, n, o); }
     static int32_t upload(const uint64_t *b, const uint8_t *i, size_t n, uint64_t *h) { return dgpu_bases_upload_g1(b, i, n, h); }
     static int32_t msm_handle(uint64_t h, size_t off, const uint64_t *s, size_t n, int32_t mont, uint64_t *o) { return dgpu_msm_g1_handle(h, off, s, n, mont, o); }
+    static int32_t msm_handle_many(uint64_t h, size_t off, const uint64_t *s, size_t rs, size_t n, size_t m, int32_t mont, uint64_t *o, uint8_t *oi) { return dgpu_msm_g1_handle_many(h, off, s, rs, n, m, mont, o, oi); }
     static int32_t msm_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, const uint64_t *s, size_t n, int32_t mont, uint64_t *o) { return dgpu_msm_g1_strided(b, st, xo, yo, io, s, n, mont, o); }
     static int32_t upload_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, size_t n, uint64_t *h) { return dgpu_bases_upload_g1_strided(b, st, xo, yo, io, n, h); }
     static int32_t table(const uint64_t *b, uint64_t *h) { return dgpu_window_table_g1(b, h); }
@@ -80,6 +81,7 @@ struct G2 {
     static int32_t msm_mont(const uint64_t *b, const uint8_t *i, const uint64_t *s, size_t n, uint64_t *o) { return dgpu_msm_g2_mont(b, i, s, n, o); }
     static int32_t upload(const uint64_t *b, const uint8_t *i, size_t n, uint64_t *h) { return dgpu_bases_upload_g2(b, i, n, h); }
     static int32_t msm_handle(uint64_t h, size_t off, const uint64_t *s, size_t n, int32_t mont, uint64_t *o) { return dgpu_msm_g2_handle(h, off, s, n, mont, o); }
+    static int32_t msm_handle_many(uint64_t h, size_t off, const uint64_t *s, size_t rs, size_t n, size_t m, int32_t mont, uint64_t *o, uint8_t *oi) { return dgpu_msm_g2_handle_many(h, off, s, rs, n, m, mont, o, oi); }
     static int32_t msm_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, const uint64_t *s, size_t n, int32_t mont, uint64_t *o) { return dgpu_msm_g2_strided(b, st, xo, yo, io, s, n, mont, o); }
     static int32_t upload_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, size_t n, uint64_t *h) { return dgpu_bases_upload_g2_strided(b, st, xo, yo, io, n, h); }
     static int32_t table(const uint64_t *b, uint64_t *h) { return dgpu_window_table_g2(b, h); }
@@ -169,6 +171,20 @@ public:
         std::array<uint64_t, G::AW * 3 / 2> out{};
         check(G::msm_handle(h_, offset, n ? bigints[0].data() : nullptr, n, 0, out.data()), "msm_handle");
         return projective_from_abi<G>(out.data());
+    }
+    // one MSM per row of scalars over the same bases, in one call (dgpu_msm_*_handle_many): rows[j] against bases [offset, offset + n), n = the rows' common
+    // length — the NUM_REPETITIONS x NUM_PARTIES commitments of verifiable_encryption/src/tz_21/dkgith.rs:174-192, one per credential in bbs_plus/src/setup.rs:128-146
+    std::vector<typename G::Projective> msm_many(const std::vector<std::vector<BigInt256>> &rows, size_t offset = 0) const {
+        const size_t m = rows.size(), n = m ? rows[0].size() : 0;
+        std::vector<uint64_t> flat(m * n * 4 + 1), out(m * (G::AW * 3 / 2) + 1);
+        for (size_t j = 0; j < m; j++) {
+            if (rows[j].size() != n) check(DGPU_E_BADARG, "msm_many: rows of different lengths");
+            if (n) std::memcpy(&flat[j * n * 4], rows[j][0].data(), n * 32);
+        }
+        check(G::msm_handle_many(h_, offset, flat.data(), n, n, m, 0, out.data(), nullptr), "msm_handle_many");
+        std::vector<typename G::Projective> res(m);
+        for (size_t j = 0; j < m; j++) res[j] = projective_from_abi<G>(&out[j * (G::AW * 3 / 2)]);
+        return res;
     }
     // points [offset, offset + n) read back from the device (dgpu_bases_read_*; n = SIZE_MAX: to the end)
     std::vector<typename G::Affine> read(size_t offset = 0, size_t n = SIZE_MAX) const {

@@ -17,6 +17,9 @@ extern "C" {
 int32_t dgpu_set_window_bits(int32_t c);
 /* terms per lane of the bucket accumulation (16..4096; 0 = automatic).  Any value gives the same point (tests sweep it). */
 int32_t dgpu_set_chunk(int32_t terms);
+/* rows per launch of dgpu_msm_g*_handle_many (1..65535; 0 = automatic from the row length: 2^17 terms' worth, at most 4096 rows).  Any value gives the
+ * same rows (tests compare chunked against unchunked). */
+int32_t dgpu_set_many_chunk_rows(int32_t rows);
 /* log2 of the buckets one lane of the bucket reduction sums serially on the table pipeline (0..6; -1 = automatic: 3 for a 2^19-bucket table when the
  * call runs alone, 4 when three or more calls are in flight on the device context).  Any value gives the same point. */
 int32_t dgpu_set_reduce_shift(int32_t log2_buckets_per_lane);

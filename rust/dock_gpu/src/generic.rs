@@ -71,6 +71,23 @@ pub fn msm_bigint<G: AffineRepr>(bases: &[G], bigints: &[<G::ScalarField as Prim
     }
     G::Group::msm_bigint(bases, bigints)
 }
+/// `rows.iter().map(|r| G::Group::msm_unchecked(bases, r))` as ONE call (`dgpu_msm_*_handle_many`): the batches of small MSMs over one commitment key —
+/// verifiable_encryption/src/tz_21/dkgith.rs:174-192,368; rdkgith.rs:140-147; bbs_plus/src/setup.rs:128-146,176-193; kvac/src/bbdt_2016/setup.rs:109;
+/// kvac/src/bbs_sharp/setup.rs:122; schnorr_pok/src/pok_generalized_pedersen.rs:97,153.  The bases are uploaded for the call (a caller that keeps its key
+/// should keep a `ResidentG1` and call its `msm_many_unchecked`); arkworks row by row for every other curve.
+pub fn msm_many<G: AffineRepr>(bases: &[G], rows: &[&[G::ScalarField]]) -> Vec<G::Group> {
+    if same::<G, G1Affine>() {
+        let key = crate::ResidentG1::upload(unsafe { cast_slice::<G, G1Affine>(bases) }, None);
+        let r: Vec<&[Fr]> = rows.iter().map(|r| unsafe { cast_slice::<G::ScalarField, Fr>(r) }).collect();
+        return unsafe { cast_val::<Vec<G1Projective>, Vec<G::Group>>(key.msm_many_unchecked(0, &r)) };
+    }
+    if same::<G, G2Affine>() {
+        let key = crate::ResidentG2::upload(unsafe { cast_slice::<G, G2Affine>(bases) }, None);
+        let r: Vec<&[Fr]> = rows.iter().map(|r| unsafe { cast_slice::<G::ScalarField, Fr>(r) }).collect();
+        return unsafe { cast_val::<Vec<G2Projective>, Vec<G::Group>>(key.msm_many_unchecked(0, &r)) };
+    }
+    rows.iter().map(|r| G::Group::msm_unchecked(bases, r)).collect()
+}
 /// the name `north_star` uses for the same thing (`variable_base_msm(&[G], &[G::ScalarField]) -> G::Group`)
 #[inline]
 pub fn variable_base_msm<G: AffineRepr>(bases: &[G], scalars: &[G::ScalarField]) -> G::Group { msm_unchecked(bases, scalars) }

@@ -166,6 +166,31 @@ impl ResidentG1 {
         Ok(ResidentG1 { handle, host })
     }
 }
+impl ResidentG1 {
+    /// one MSM per row over the same bases in ONE call (`dgpu_msm_g1_handle_many`): `rows[j]` against `&query[offset..offset + n]`, n = the rows' common length —
+    /// the `NUM_REPETITIONS x NUM_PARTIES` calls of `msm_unchecked(comm_key, &shares_j)` in verifiable_encryption/src/tz_21/dkgith.rs:174-192,368, the
+    /// coefficient rows of rdkgith.rs:140-147, one commitment per credential in bbs_plus/src/setup.rs:128-146.  Element j is what `msm_bigint(offset, rows[j])` returns.
+    pub fn msm_many(&self, offset: usize, rows: &[&[BigInt<4>]]) -> ark_std::vec::Vec<G1Projective> {
+        let n = rows.first().map_or(0, |r| r.len()).min(self.host.len().saturating_sub(offset));
+        let flat: ark_std::vec::Vec<BigInt<4>> = rows.iter().flat_map(|r| r[..n.min(r.len())].iter().copied()).collect();
+        if rows.iter().all(|r| r.len() >= n) { if let Some(v) = self.many_raw(offset, flat.as_ptr() as *const u64, n, rows.len(), 0) { return v; } }
+        rows.iter().map(|r| { let k = n.min(r.len()); G1Projective::msm_bigint(&self.host[offset..offset + k], &r[..k]) }).collect()
+    }
+    /// the same for `&[Fr]` rows (`msm_unchecked`): the Montgomery limbs go over as they are
+    pub fn msm_many_unchecked(&self, offset: usize, rows: &[&[Fr]]) -> ark_std::vec::Vec<G1Projective> {
+        let n = rows.first().map_or(0, |r| r.len()).min(self.host.len().saturating_sub(offset));
+        let flat: ark_std::vec::Vec<Fr> = rows.iter().flat_map(|r| r[..n.min(r.len())].iter().copied()).collect();
+        if rows.iter().all(|r| r.len() >= n) { if let Some(v) = self.many_raw(offset, flat.as_ptr() as *const u64, n, rows.len(), 1) { return v; } }
+        rows.iter().map(|r| { let k = n.min(r.len()); G1Projective::msm_unchecked(&self.host[offset..offset + k], &r[..k]) }).collect()
+    }
+    fn many_raw(&self, offset: usize, scalars: *const u64, n: usize, m: usize, montgomery: i32) -> Option<ark_std::vec::Vec<G1Projective>> {
+        if self.handle == 0 { return None; }
+        let mut out = ark_std::vec![0u64; m * 18];
+        let rc = unsafe { dgpu_msm_g1_handle_many(self.handle, offset, scalars, n, n, m, montgomery, out.as_mut_ptr(), core::ptr::null_mut()) };
+        if rc != DGPU_OK { return None; }
+        Some(out.chunks_exact(18).map(|w| g1_from_xyz(w.try_into().unwrap())).collect())
+    }
+}
 impl Drop for ResidentG1 { fn drop(&mut self) { if self.handle != 0 { unsafe { dgpu_bases_free(self.handle); } } } }
 
 /// the same for G2 (b_g2_query)
@@ -198,6 +223,31 @@ impl ResidentG2 {
         if rc != DGPU_OK { return Err(None); }
         let host = (0..n).map(|i| g2_affine(xy[24 * i..24 * i + 24].try_into().unwrap(), inf[i])).collect();
         Ok(ResidentG2 { handle, host })
+    }
+}
+impl ResidentG2 {
+    /// one MSM per row over the same bases in ONE call (`dgpu_msm_g2_handle_many`): `rows[j]` against `&query[offset..offset + n]`, n = the rows' common length —
+    /// the `NUM_REPETITIONS x NUM_PARTIES` calls of `msm_unchecked(comm_key, &shares_j)` in verifiable_encryption/src/tz_21/dkgith.rs:174-192,368, the
+    /// coefficient rows of rdkgith.rs:140-147, one commitment per credential in bbs_plus/src/setup.rs:128-146.  Element j is what `msm_bigint(offset, rows[j])` returns.
+    pub fn msm_many(&self, offset: usize, rows: &[&[BigInt<4>]]) -> ark_std::vec::Vec<G2Projective> {
+        let n = rows.first().map_or(0, |r| r.len()).min(self.host.len().saturating_sub(offset));
+        let flat: ark_std::vec::Vec<BigInt<4>> = rows.iter().flat_map(|r| r[..n.min(r.len())].iter().copied()).collect();
+        if rows.iter().all(|r| r.len() >= n) { if let Some(v) = self.many_raw(offset, flat.as_ptr() as *const u64, n, rows.len(), 0) { return v; } }
+        rows.iter().map(|r| { let k = n.min(r.len()); G2Projective::msm_bigint(&self.host[offset..offset + k], &r[..k]) }).collect()
+    }
+    /// the same for `&[Fr]` rows (`msm_unchecked`): the Montgomery limbs go over as they are
+    pub fn msm_many_unchecked(&self, offset: usize, rows: &[&[Fr]]) -> ark_std::vec::Vec<G2Projective> {
+        let n = rows.first().map_or(0, |r| r.len()).min(self.host.len().saturating_sub(offset));
+        let flat: ark_std::vec::Vec<Fr> = rows.iter().flat_map(|r| r[..n.min(r.len())].iter().copied()).collect();
+        if rows.iter().all(|r| r.len() >= n) { if let Some(v) = self.many_raw(offset, flat.as_ptr() as *const u64, n, rows.len(), 1) { return v; } }
+        rows.iter().map(|r| { let k = n.min(r.len()); G2Projective::msm_unchecked(&self.host[offset..offset + k], &r[..k]) }).collect()
+    }
+    fn many_raw(&self, offset: usize, scalars: *const u64, n: usize, m: usize, montgomery: i32) -> Option<ark_std::vec::Vec<G2Projective>> {
+        if self.handle == 0 { return None; }
+        let mut out = ark_std::vec![0u64; m * 36];
+        let rc = unsafe { dgpu_msm_g2_handle_many(self.handle, offset, scalars, n, n, m, montgomery, out.as_mut_ptr(), core::ptr::null_mut()) };
+        if rc != DGPU_OK { return None; }
+        Some(out.chunks_exact(36).map(|w| g2_from_xyz(w.try_into().unwrap())).collect())
     }
 }
 impl Drop for ResidentG2 { fn drop(&mut self) { if self.handle != 0 { unsafe { dgpu_bases_free(self.handle); } } } }

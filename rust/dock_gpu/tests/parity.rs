@@ -279,6 +279,53 @@ fn sharded_msm_window_tables_and_serde() {
 }
 
 #[test]
+fn many_small_msms_over_one_key() {
+    // m rows against m arkworks calls: the shapes of dkgith.rs:174-192 (many short rows), one row of the key's full length, an identity row, &[Fr] and BigInt rows
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5EED0A11);
+    let (b, b2) = (g1s(&mut rng, 600), g2s(&mut rng, 200));
+    let (k1, k2) = (ResidentG1::upload(&b, None), ResidentG2::upload(&b2, None));
+    for (m, n, off) in [(1usize, 1usize, 0usize), (300, 1, 5), (64, 24, 1), (17, 33, 0), (5, 600, 0), (3, 129, 7)] {
+        let mut rows: Vec<Vec<Fr>> = (0..m).map(|_| frs(&mut rng, n)).collect();
+        if m > 2 { for x in rows[m / 2].iter_mut() { *x = Fr::from(0u64); } }
+        let big: Vec<Vec<BigInt<4>>> = rows.iter().map(|r| r.iter().map(|x| x.into_bigint()).collect()).collect();
+        let (rf, rb): (Vec<&[Fr]>, Vec<&[BigInt<4>]>) = (rows.iter().map(|r| &r[..]).collect(), big.iter().map(|r| &r[..]).collect());
+        let got = k1.msm_many_unchecked(off, &rf);
+        let gotb = k1.msm_many(off, &rb);
+        assert_eq!(got.len(), m);
+        for j in 0..m {
+            let want = G1Projective::msm_unchecked(&b[off..off + n], &rows[j]);
+            assert_eq!(got[j].into_affine(), want.into_affine(), "G1 row {} of {} x {}", j, m, n);
+            assert_eq!(gotb[j].into_affine(), want.into_affine());
+            assert_eq!(k1.msm_bigint(off, &big[j]).into_affine(), want.into_affine());
+        }
+        if off + n <= 200 {
+            let got2 = k2.msm_many_unchecked(off, &rf);
+            let got2b = k2.msm_many(off, &rb);
+            for j in 0..m {
+                let want = G2Projective::msm_unchecked(&b2[off..off + n], &rows[j]);
+                assert_eq!(got2[j].into_affine(), want.into_affine(), "G2 row {} of {} x {}", j, m, n);
+                assert_eq!(got2b[j].into_affine(), want.into_affine());
+            }
+        }
+        if off == 0 {
+            let gen = dock_gpu::generic::msm_many::<G1Affine>(&b[..n], &rf);
+            for j in 0..m { assert_eq!(gen[j].into_affine(), got[j].into_affine()); }
+        }
+    }
+    // the raw entry point: row_stride > n, identity flags
+    let (m, n, stride) = (9usize, 20usize, 23usize);
+    let s: Vec<BigInt<4>> = frs(&mut rng, m * stride).iter().map(|x| x.into_bigint()).collect();
+    let (mut out, mut inf) = (vec![0u64; m * 18], vec![7u8; m]);
+    assert_eq!(unsafe { dgpu_msm_g1_handle_many(k1.handle(), 2, s.as_ptr() as *const u64, stride, n, m, 0, out.as_mut_ptr(), inf.as_mut_ptr()) }, DGPU_OK);
+    for j in 0..m {
+        assert_eq!(inf[j], 0);
+        assert_eq!(k1.msm_bigint(2, &s[j * stride..j * stride + n]).into_affine(), G1Projective::msm_bigint(&b[2..2 + n], &s[j * stride..j * stride + n]).into_affine());
+    }
+    assert_eq!(unsafe { dgpu_msm_g2_handle_many(k2.handle(), 0, s.as_ptr() as *const u64, stride, n, 0, 0, core::ptr::null_mut(), core::ptr::null_mut()) }, DGPU_OK);
+}
+
+#[test]
 fn scalings_and_the_scaled_miller_loop() {
     setup();
     let mut rng = StdRng::seed_from_u64(0x5EED000B);
