@@ -6,7 +6,7 @@ There is no CPU fallback: every call goes through the HIP library and raises if 
 """
 from ._native import lib, DockGpuError, build_native, twin, dev_lib  # noqa: F401
 from .msm import (  # noqa: F401
-    G1, G2, msm_bigint, msm_unchecked, msm, Pairs, OwnedPairs, DeviceBases, DeviceScalars, SortedScalars, init, prof, init_devices, msm_bigint_sharded, ShardedDeviceBases,
+    G1, G2, msm_bigint, msm_unchecked, msm_segments, msm, Pairs, OwnedPairs, DeviceBases, DeviceScalars, SortedScalars, init, prof, init_devices, msm_bigint_sharded, ShardedDeviceBases,
     msm_strided, to_affine_structs, affine_struct_dtype, reserve, device_alloc_count, TABLE_C_WITNESS,
     bases_cache, bases_cache_stats, bases_cache_clear, bases_cache_invalidate, CACHE_VERIFY_FULL,
 )

@@ -31,6 +31,7 @@ int32_t dgpu_reserve_g1(size_t n) { CtxScope here(cur_index()); return reserve_s
 int32_t dgpu_bases_upload_g1(const uint64_t *b, const uint8_t *inf, size_t n, uint64_t *h) { return bases_upload<G1>(RawBases::packed<G1>(b, inf), n, h, 1); }
 int32_t dgpu_msm_g1_handle(uint64_t b, size_t off, const uint64_t *s, size_t n, int32_t mont, uint64_t out[18]) { return msm_handle<G1, hostf::Fq>(b, off, s, n, mont, out, 1); }
 int32_t dgpu_msm_g1_handle_many(uint64_t b, size_t off, const uint64_t *s, size_t row_stride, size_t n, size_t m, int32_t mont, uint64_t *out, uint8_t *out_inf) { return msm_handle_many<G1, hostf::Fq>(b, off, s, row_stride, n, m, mont, out, out_inf, 1); }
+int32_t dgpu_msm_g1_segments(const uint64_t *b, const uint8_t *inf, const uint64_t *s, size_t N, const uint64_t *seg_end, size_t nseg, int32_t mont, uint64_t *out, uint8_t *out_inf) { return msm_segments<G1, hostf::Fq>(b, inf, s, N, seg_end, nseg, mont, out, out_inf); }
 int32_t dgpu_msm_g1_sharded(const uint64_t *b, const uint8_t *inf, const uint64_t *s, size_t n, int32_t ngpus, uint64_t out[18]) { return msm_sharded_oneshot<G1, hostf::Fq>(b, inf, s, n, ngpus, false, out); }
 int32_t dgpu_bases_upload_g1_sharded(const uint64_t *b, const uint8_t *inf, size_t n, int32_t ngpus, uint64_t *h) { return bases_upload_sharded<G1>(b, inf, n, ngpus, h, 1); }
 int32_t dgpu_msm_g1_sharded_handle(uint64_t b, const uint64_t *s, size_t n, int32_t mont, uint64_t out[18]) { return msm_sharded_handle<G1, hostf::Fq>(b, s, n, mont, out, 1); }

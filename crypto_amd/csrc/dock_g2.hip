@@ -22,6 +22,7 @@ int32_t dgpu_reserve_g2(size_t n) { CtxScope here(cur_index()); return reserve_s
 int32_t dgpu_bases_upload_g2(const uint64_t *b, const uint8_t *inf, size_t n, uint64_t *h) { return bases_upload<G2>(RawBases::packed<G2>(b, inf), n, h, 2); }
 int32_t dgpu_msm_g2_handle(uint64_t b, size_t off, const uint64_t *s, size_t n, int32_t mont, uint64_t out[36]) { return msm_handle<G2, hostf::Fq2>(b, off, s, n, mont, out, 2); }
 int32_t dgpu_msm_g2_handle_many(uint64_t b, size_t off, const uint64_t *s, size_t row_stride, size_t n, size_t m, int32_t mont, uint64_t *out, uint8_t *out_inf) { return msm_handle_many<G2, hostf::Fq2>(b, off, s, row_stride, n, m, mont, out, out_inf, 2); }
+int32_t dgpu_msm_g2_segments(const uint64_t *b, const uint8_t *inf, const uint64_t *s, size_t N, const uint64_t *seg_end, size_t nseg, int32_t mont, uint64_t *out, uint8_t *out_inf) { return msm_segments<G2, hostf::Fq2>(b, inf, s, N, seg_end, nseg, mont, out, out_inf); }
 int32_t dgpu_msm_g2_sharded(const uint64_t *b, const uint8_t *inf, const uint64_t *s, size_t n, int32_t ngpus, uint64_t out[36]) { return msm_sharded_oneshot<G2, hostf::Fq2>(b, inf, s, n, ngpus, false, out); }
 int32_t dgpu_bases_upload_g2_sharded(const uint64_t *b, const uint8_t *inf, size_t n, int32_t ngpus, uint64_t *h) { return bases_upload_sharded<G2>(b, inf, n, ngpus, h, 2); }
 int32_t dgpu_msm_g2_sharded_handle(uint64_t b, const uint64_t *s, size_t n, int32_t mont, uint64_t out[36]) { return msm_sharded_handle<G2, hostf::Fq2>(b, s, n, mont, out, 2); }

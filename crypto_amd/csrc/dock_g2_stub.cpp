@@ -9,5 +9,6 @@ int32_t dgpu_msm_g2_mont(const uint64_t *, const uint8_t *, const uint64_t *, si
 int32_t dgpu_bases_upload_g2(const uint64_t *, const uint8_t *, size_t, uint64_t *) { return DGPU_E_NODEVICE; }
 int32_t dgpu_msm_g2_handle(uint64_t, size_t, const uint64_t *, size_t, int32_t, uint64_t *) { return DGPU_E_NODEVICE; }
 int32_t dgpu_msm_g2_handle_many(uint64_t, size_t, const uint64_t *, size_t, size_t, size_t, int32_t, uint64_t *, uint8_t *) { return DGPU_E_NODEVICE; }
+int32_t dgpu_msm_g2_segments(const uint64_t *, const uint8_t *, const uint64_t *, size_t, const uint64_t *, size_t, int32_t, uint64_t *, uint8_t *) { return DGPU_E_NODEVICE; }
 int32_t dgpu_msm_g2_resident(uint64_t, size_t, uint64_t, size_t, size_t, uint64_t *) { return DGPU_E_NODEVICE; }
 }

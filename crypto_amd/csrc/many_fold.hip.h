@@ -82,6 +82,20 @@ template <class F, class Q4> FD void many_horner_step(Xyzz<F> &acc, bool &ainf, 
     }
     xyzz_add_rounds(acc, ainf, s, sinf, q4);
 }
+// Horner over `nwin` window sums, the most significant first: acc = sum_v 16^v S_v.  load(s, v) fills s with S_v and returns its identity flag (the
+// coordinates of an identity are never read: leave them zero).  The many-row fold runs it over 16 super-windows, the segmented one (seg_layout.hip.h) over 64.
+template <class F, class Q4, class L> FD void many_horner(Xyzz<F> &acc, bool &ainf, int nwin, const L &load, const Q4 &q4) {
+    ainf = true;
+    fzero(acc.x); fzero(acc.y); fzero(acc.zz); fzero(acc.zzz);
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (int v = nwin - 1; v >= 0; v--) {
+        Xyzz<F> s;
+        const bool sinf = load(s, v);
+        many_horner_step(acc, ainf, s, sinf, v == nwin - 1, q4);
+    }
+}
 // (X / ZZ, Y / ZZZ) with 1 / ZZ = (ZZ / ZZZ)^2: the affine coordinates, i.e. the Jacobian representative with Z = 1 the ABI returns
 // (host_field.hpp to_normalised_jacobian).  acc is not the identity.
 template <class F> FD void many_normalise(F &x, F &y, const Xyzz<F> &acc) {
@@ -90,6 +104,14 @@ template <class F> FD void many_normalise(F &x, F &y, const Xyzz<F> &acc) {
     fnorm(z2, acc.zz); fmul(t, z2, i3); fsqr(i2, t);
     fnorm(xn, acc.x); fnorm(yn, acc.y);
     fmul(x, xn, i2); fmul(y, yn, i3);
+}
+
+// the whole tail: (ox, oy, oz) = the ABI's representative of sum_v 16^v S_v over nwin window sums: (X, Y, 1) normalised; (1, 1, 0) and ainf for the identity
+template <class F, class Q4, class L> FD void many_tail(F &ox, F &oy, F &oz, bool &ainf, int nwin, const L &load, const Q4 &q4) {
+    Xyzz<F> acc;
+    many_horner(acc, ainf, nwin, load, q4);
+    if (ainf) { fset_one(ox); fset_one(oy); fzero(oz); }
+    else { many_normalise(ox, oy, acc); fset_one(oz); }
 }
 
 }  // namespace bls29

@@ -122,30 +122,24 @@ __global__ void __launch_bounds__(256 * A::LPP) k_many_tree(const uint32_t *__re
     write_window(acc, ainf);
 }
 
-// row r: out_xyz[r] = the normalised Jacobian point (X, Y, 1) of sum_v 16^v S_v in ABI words, (1, 1, 0) and out_inf[r] = 1 for the identity — word for
-// word what host_fold writes for one row.  One group of four members per row; no barrier, whole groups leave together.
+// the tail of one row / segment on its four members: Horner over the `nwin` window sums at win[at0 .. at0 + nwin) (the accumulator's own form), one inversion,
+// then out_xyz[row] = the normalised Jacobian point (X, Y, 1) in ABI words, (1, 1, 0) and out_inf[row] = 1 for the identity — word for word what host_fold
+// writes.  No barrier: whole groups run it together.
 template <class A>
-__global__ void __launch_bounds__(256 * A::LPP) k_many_fold(const uint32_t *__restrict__ win, const uint8_t *__restrict__ win_inf, size_t rows,
-                                                             uint32_t *__restrict__ out_xyz, uint8_t *__restrict__ out_inf) {
+__device__ __forceinline__ void many_fold_row(const uint32_t *__restrict__ win, const uint8_t *__restrict__ win_inf, size_t at0, int nwin, size_t row,
+                                              uint32_t *__restrict__ out_xyz, uint8_t *__restrict__ out_inf) {
     typedef typename A::F F;
-    constexpr int LPP = A::LPP, GL = 4 * LPP, WPS = SMALL_W / SMALL_S, OW = 3 * 12 * LPP;
+    constexpr int LPP = A::LPP, GL = 4 * LPP, OW = 3 * 12 * LPP;
     const int t = (int)threadIdx.x, h = t % LPP;
-    const size_t row = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / GL;
-    if (row >= rows) return;
     const QuadLanes<LPP> q4;
-    Xyzz<F> acc, s; bool ainf = true;
-    fzero(acc.x); fzero(acc.y); fzero(acc.zz); fzero(acc.zzz);
-#pragma unroll 1
-    for (int v = WPS - 1; v >= 0; v--) {
-        const size_t at = row * WPS + v;
+    F ox, oy, oz; bool ainf;
+    many_tail(ox, oy, oz, ainf, nwin, [&](Xyzz<F> &s, int v) __attribute__((always_inline)) {
+        const size_t at = at0 + v;
         const bool sinf = win_inf[at] != 0;
         fzero(s.x); fzero(s.y); fzero(s.zz); fzero(s.zzz);
         if (!sinf) load_soa<A>(s, win, 0, at);
-        many_horner_step(acc, ainf, s, sinf, v == WPS - 1, q4);
-    }
-    F ox, oy, oz;
-    if (ainf) { fset_one(ox); fset_one(oy); fzero(oz); }
-    else { many_normalise(ox, oy, acc); fset_one(oz); }
+        return sinf;
+    }, q4);
     if (t % GL == 0) out_inf[row] = ainf;
     const int r = q4.role;                                            // member r < 3 converts coordinate r (G2: each lane its half)
     const Fs *fx = reinterpret_cast<const Fs *>(&ox), *fy = reinterpret_cast<const Fs *>(&oy), *fz = reinterpret_cast<const Fs *>(&oz);
@@ -153,6 +147,16 @@ __global__ void __launch_bounds__(256 * A::LPP) k_many_fold(const uint32_t *__re
 #pragma unroll
     for (int k = 0; k < SN; k++) mine.l[k] = pick4(r, fx->l[k], fy->l[k], fz->l[k], fz->l[k]);
     if (r < 3) fs_to_abi(out_xyz + row * OW + 12 * (LPP * r + h), mine);
+}
+
+// row r: the tail over its 16 super-window sums.  One group of four members per row; whole groups leave together.
+template <class A>
+__global__ void __launch_bounds__(256 * A::LPP) k_many_fold(const uint32_t *__restrict__ win, const uint8_t *__restrict__ win_inf, size_t rows,
+                                                             uint32_t *__restrict__ out_xyz, uint8_t *__restrict__ out_inf) {
+    constexpr int GL = 4 * A::LPP, WPS = SMALL_W / SMALL_S;
+    const size_t row = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / GL;
+    if (row >= rows) return;
+    many_fold_row<A>(win, win_inf, row * WPS, WPS, row, out_xyz, out_inf);
 }
 
 // launchers (instantiated by k_g1_many.hip / k_g2_many.hip; declared in msm_launch.hip.h)

@@ -1095,6 +1095,160 @@ int32_t msm_handle_many(uint64_t bases, size_t offset, const uint64_t *scalars, 
     return DGPU_OK;
 }
 
+// ---- many small MSMs, each over its own bases, in one call (seg_kernels.hip.h) ----------------------------------------------------------------
+// Segments travel in chunks of whole segments: at most SEG_CHUNK_TERMS terms (the table of eight multiples per base is 1.6 KB per G1 base, 3.3 KB per G2
+// base: 109 / 218 MB) and SEG_CHUNK_SEGS segments (64 window sums each: 55 / 109 MB) per chunk; dgpu_set_msm_segments (development surface) overrides the
+// term limit.  From SEG_DEVICE_FOLD_MIN segments in a chunk on, k_seg_fold folds them on the device; below, the host threads' host_fold does (up to 16 threads per
+// chunk through par_run: several calls in flight with few segments each share the host's cores).
+constexpr size_t SEG_CHUNK_TERMS = (size_t)1 << 16, SEG_CHUNK_SEGS = 4096;
+constexpr size_t SEG_DEVICE_FOLD_MIN = 24;              // PROVISIONAL, not measured: the crossover is what tests/perf/msm_segments_timing.py's fold sweep finds on an MI355X
+template <class C> int32_t ws_seg(Slot &sl, const RawBases &rb, size_t terms, size_t nseg, size_t blocks, size_t pslots) {
+    int32_t rc;
+    typedef typename C::ACC A;
+    constexpr size_t W = SMALL_MSM_W, WIN_BYTES = std::max<size_t>(A::XW * 4, 4 * C::ABI_W * 4);      // a window sum in either form
+    if ((rc = sl.flags.ensure(64))) return rc;
+    if ((rc = sl.in_scalars.ensure(terms * 32))) return rc;
+    if ((rc = ws_stage_bases<C>(sl, rb, terms))) return rc;
+    if ((rc = sl.prepped.ensure(terms * C::AFF_STRIDE * 4))) return rc;
+    if ((rc = sl.bucket.ensure(terms * SMALL_MSM_E * A::XW * 4))) return rc;               // the table and its identity flags
+    if ((rc = sl.bucket_inf.ensure(terms * SMALL_MSM_E))) return rc;
+    if ((rc = sl.entries.ensure(blocks * 64 * sizeof(SegDesc)))) return rc;                 // the descriptors
+    if ((rc = sl.l1.ensure(nseg * W * WIN_BYTES))) return rc;                               // the window sums and their flags
+    if ((rc = sl.l1_inf.ensure(nseg * W))) return rc;
+    if (pslots) {
+        if ((rc = sl.head.ensure(pslots * W * A::XW * 4))) return rc;                       // the blocks' partials, their flags, the per-window block counters
+        if ((rc = sl.part_inf.ensure(pslots * W))) return rc;
+        if ((rc = sl.cnt.ensure(pslots * W * 4))) return rc;
+    }
+    if ((rc = sl.win.ensure(nseg * 3 * C::ABI_W * 4))) return rc;                           // the results and their identity flags
+    return sl.win_inf.ensure(nseg);
+}
+inline bool jac_is_identity(const uint64_t *xyz, size_t JW) { uint64_t z = 0; for (size_t k = 2 * JW / 3; k < JW; k++) z |= xyz[k]; return z == 0; }
+// segments [s0, s1) (all within the small path's reach, T > 0 terms in all) on the device: one upload, table, tree, fold (device or host), results down
+template <class C, class HF>
+int32_t msm_seg_chunk(Slot &sl, const RawBases &rb, const uint64_t *scalars, const uint64_t *seg_end, size_t s0, size_t s1, bool mont, const SegLayout &lay, bool device_fold,
+                      std::vector<uint64_t> &hwin, std::vector<uint8_t> &hinf, uint64_t *out, uint8_t *out_inf) {
+    constexpr size_t JW = 3 * sizeof(HF) / 8, W = SMALL_MSM_W, WW = 4 * sizeof(HF) / 8;   // u64 words per result / per window sum
+    const size_t t0 = s0 ? seg_end[s0 - 1] : 0, T = seg_end[s1 - 1] - t0, ns = s1 - s0;
+    hipStream_t s = sl.stream;
+    uint32_t *const d_sc = sl.in_scalars.as<uint32_t>(), *const d_bad = sl.flags.as<uint32_t>();
+    uint32_t *const hbad = (uint32_t *)sl.hpin;
+    int32_t rc;
+    HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
+    HIPCHK(hipMemcpyAsync(sl.entries.p, lay.desc.data(), lay.blocks * 64 * sizeof(SegDesc), hipMemcpyHostToDevice, sl.cstream));      // (ordered before the scalars' event)
+    RawBases part = rb; part.p = rb.p + t0 * rb.stride; if (rb.is_inf) part.is_inf = rb.is_inf + t0;
+    if ((rc = stage_scalars(sl, scalars + t0 * 4, T, mont, d_sc))) return rc;
+    if ((rc = stage_bases<C>(sl, part, T, sl.prepped.as<uint32_t>()))) return rc;
+    {
+        StageTimer st(sl, "msm.small_table");
+        launch_small_table<C>(s, sl.prepped.as<uint32_t>(), T, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>());
+    }
+    if (lay.pslots) HIPCHK(hipMemsetAsync(sl.cnt.p, 0, lay.pslots * W * 4, s));
+    {
+        StageTimer st(sl, "msm.seg_tree");
+        launch_seg_tree<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_sc, sl.entries.p, lay.blocks, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(),
+                           sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), !device_fold, d_bad);
+    }
+    if (device_fold) {
+        {
+            StageTimer st(sl, "msm.seg_fold");
+            launch_seg_fold<C>(s, sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), ns, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out + s0 * JW, sl.win.p, ns * JW * 8, hipMemcpyDeviceToHost, s));
+        if (out_inf) HIPCHK(hipMemcpyAsync(out_inf + s0, sl.win_inf.p, ns, hipMemcpyDeviceToHost, s));
+    } else {
+        HIPCHK(hipGetLastError());
+        hwin.resize(ns * W * WW); hinf.resize(ns * W);
+        HIPCHK(hipMemcpyAsync(hwin.data(), sl.l1.p, ns * W * WW * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hinf.data(), sl.l1_inf.p, ns * W, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipMemcpyAsync(hbad, d_bad, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                      // (the next chunk's operands overwrite this one's)
+    if (gs.prof) prof_flush(sl);
+    if (*hbad) return DGPU_E_BADARG;                      // a scalar >= 2^255 somewhere in the chunk: the whole call is refused
+    if (!device_fold) {
+        const size_t TH = std::min<size_t>(std::min<size_t>(ns, 16), std::max<size_t>(1, std::thread::hardware_concurrency()));
+        auto tail = [&](size_t g) {
+            host_fold<HF>(hwin.data() + g * W * WW, hinf.data() + g * W, (int)W, SMALL_MSM_C, out + (s0 + g) * JW);
+            if (out_inf) out_inf[s0 + g] = jac_is_identity(out + (s0 + g) * JW, JW);
+        };
+        if (TH <= 1) { for (size_t g = 0; g < ns; g++) tail(g); }
+        else if ((rc = par_run(TH, [&](size_t k) -> int32_t { for (size_t g = k; g < ns; g += TH) tail(g); return DGPU_OK; }))) return rc;
+    }
+    return DGPU_OK;
+}
+template <class C, class HF>
+int32_t msm_segments(const uint64_t *bases, const uint8_t *is_inf, const uint64_t *scalars, size_t N, const uint64_t *seg_end, size_t nseg, int mont, uint64_t *out, uint8_t *out_inf) {
+    if (nseg == 0) return DGPU_OK;
+    constexpr size_t JW = 3 * sizeof(HF) / 8;
+    if (!bases || !scalars || !out || !seg_end || N >= (1ull << 31)) return DGPU_E_BADARG;
+    { uint64_t prev = 0; for (size_t g = 0; g < nseg; g++) { if (seg_end[g] < prev) return DGPU_E_BADARG; prev = seg_end[g]; } if (prev != N) return DGPU_E_BADARG; }
+    if (!cur().ready) return DGPU_E_NODEVICE;             // (before the size threshold, like the single call)
+    if (!tl_no_min && N < gs.min_gpu_n) return DGPU_E_TOO_SMALL;      // the batch is the unit: many one-term segments are device work
+    const RawBases rb = RawBases::packed<C>(bases, is_inf);
+    const size_t reach = std::min<size_t>(SMALL_MSM_MAX_N, gs.small_max.load());
+    const int forced_terms = gs.seg_chunk.load(), forced_fold = gs.seg_fold.load();
+    const size_t chunk_terms = forced_terms > 0 ? (size_t)forced_terms : SEG_CHUNK_TERMS;
+    auto len = [&](size_t g) { return (size_t)(seg_end[g] - (g ? seg_end[g - 1] : 0)); };
+    // the chunks: runs of whole segments within the small path's reach; a longer segment ends the run and goes through the single-call driver afterwards
+    struct Chunk { size_t s0, s1; };
+    std::vector<Chunk> chunks; std::vector<size_t> slow;
+    for (size_t g = 0; g < nseg;) {
+        if (len(g) > reach) { slow.push_back(g++); continue; }
+        size_t e = g, terms = 0;
+        while (e < nseg && len(e) <= reach && e - g < SEG_CHUNK_SEGS && (e == g || terms + len(e) <= chunk_terms)) terms += len(e++);
+        chunks.push_back(Chunk{g, e});
+        g = e;
+    }
+    if (!chunks.empty()) {
+        SLOT_ACQUIRE(L, sl);
+        HIPCHK(hipSetDevice(cur().device));
+        // one pass over the layouts for the workspace (grow-only; a shape already seen allocates nothing), one more to run them
+        SegLayout lay;
+        size_t mt = 0, ms = 0, mb = 0, mp = 0;
+        for (const Chunk &c : chunks) {
+            const size_t T = seg_end[c.s1 - 1] - (c.s0 ? seg_end[c.s0 - 1] : 0);
+            if (T == 0) continue;
+            seg_layout(seg_end, c.s0, c.s1, lay);
+            mt = std::max(mt, T); ms = std::max(ms, c.s1 - c.s0); mb = std::max(mb, lay.blocks); mp = std::max(mp, lay.pslots);
+        }
+        int32_t rc;
+        const uint64_t allocs0 = g_dev_allocs.load();
+        if (mt && (rc = ws_seg<C>(sl, rb, mt, ms, mb, mp))) return rc;
+        if (g_dev_allocs.load() != allocs0) {             // a new shape: the caller's other host threads come with it next (msm_device_many does the same)
+            Ctx &cx = cur();
+            for (int k = 0; k < N_SLOTS; k++) {
+                Slot &o = cx.slots[k];
+                if (&o == &sl || !o.mu.try_lock()) continue;
+                (void)ws_seg<C>(o, rb, mt, ms, mb, mp);
+                o.mu.unlock();
+            }
+        }
+        std::vector<uint64_t> hwin; std::vector<uint8_t> hinf;
+        for (const Chunk &c : chunks) {
+            const size_t T = seg_end[c.s1 - 1] - (c.s0 ? seg_end[c.s0 - 1] : 0), ns = c.s1 - c.s0;
+            if (T == 0) {                                 // nothing but empty segments
+                for (size_t g = c.s0; g < c.s1; g++) { write_identity<HF>(out + g * JW); if (out_inf) out_inf[g] = 1; }
+                continue;
+            }
+            seg_layout(seg_end, c.s0, c.s1, lay);
+            const bool device_fold = forced_fold == 2 || (forced_fold != 1 && ns >= SEG_DEVICE_FOLD_MIN);
+            rc = msm_seg_chunk<C, HF>(sl, rb, scalars, seg_end, c.s0, c.s1, mont != 0, lay, device_fold, hwin, hinf, out, out_inf);
+            if (rc) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); return rc; }      // nothing of ours may still read the caller's buffers
+        }
+    }
+    // segments beyond the small path's reach: the single-call driver, one after the other (the slot is released: that driver takes its own)
+    for (size_t g : slow) {
+        const size_t lo = g ? seg_end[g - 1] : 0;
+        RawBases part = rb; part.p = rb.p + lo * rb.stride; if (rb.is_inf) part.is_inf = rb.is_inf + lo;
+        const int32_t rc = msm_oneshot_ctx<C, HF>(part, scalars + lo * 4, len(g), mont != 0, out + g * JW);
+        if (rc) return rc;
+        if (out_inf) out_inf[g] = jac_is_identity(out + g * JW, JW);
+    }
+    return DGPU_OK;
+}
+
 // ---- the resident-bases cache (bases_cache.hpp) --------------------------------------------------------------------------------------------
 // device bytes of an entry of n points as a table of width c (0: the automatic choice; a handle too short for a table stays plain)
 template <class C> inline size_t cache_entry_bytes(size_t n, int c) {

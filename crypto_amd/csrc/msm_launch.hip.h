@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "msm_kernels.hip.h"
 #include "many_fold.hip.h"
+#include "seg_layout.hip.h"
 
 namespace msm {
 
@@ -44,6 +45,13 @@ template <class C> void launch_small_tree(hipStream_t s, const uint32_t *tab, co
 template <class C> void launch_many_tree(hipStream_t s, const uint32_t *tab, const uint8_t *tab_inf, const uint32_t *scalars, size_t n, size_t row_stride, size_t rows, uint32_t *partial,
                                          uint8_t *partial_inf, uint32_t *count, uint32_t *win, uint8_t *win_inf, uint32_t *bad_flag);
 template <class C> void launch_many_fold(hipStream_t s, const uint32_t *win, const uint8_t *win_inf, size_t rows, uint32_t *out_xyz, uint8_t *out_inf);
+
+// many small MSMs, each over its own bases, in one call (seg_kernels.hip.h; k_g1_seg.hip / k_g2_seg.hip): the tree over a chunk of ragged segments laid out
+// by seg_layout.hip.h (desc: 64 descriptors per block; window sums in the accumulator's own form, or in host_fold's when `abi`; *bad_flag |= a scalar >= 2^255),
+// then Horner + normalisation per segment
+template <class C> void launch_seg_tree(hipStream_t s, const uint32_t *tab, const uint8_t *tab_inf, const uint32_t *scalars, const void *desc, size_t blocks, uint32_t *partial,
+                                        uint8_t *partial_inf, uint32_t *count, uint32_t *win, uint8_t *win_inf, bool abi, uint32_t *bad_flag);
+template <class C> void launch_seg_fold(hipStream_t s, const uint32_t *win, const uint8_t *win_inf, size_t nseg, uint32_t *out_xyz, uint8_t *out_inf);
 
 // precomputed-multiples tables (pre_kernels.hip.h; k_g1_pre.hip / k_g2_pre.hip)
 template <class C> void launch_pre_step(hipStream_t s, const uint32_t *prev, size_t n, int c, uint32_t *tmp, uint32_t *out);

@@ -96,6 +96,34 @@ def msm_unchecked(curve, bases, scalars_mont, is_inf=None):
     return out
 
 
+def msm_segments(curve, bases, scalars, seg_end, is_inf=None, montgomery=False, flags=False):
+    """dgpu_msm_*_segments: many MSMs, each over its own bases, in one call.  bases (N, 12 | 24), scalars (N, 4); segment g is the terms
+    [seg_end[g - 1], seg_end[g]) with seg_end[-1] = 0 and seg_end[-1 + nseg] == N -> (nseg, 18 | 36), each row what msm_bigint gives for that
+    segment alone (an empty segment: the identity); flags=True also returns the (nseg,) identity flags."""
+    _ensure()
+    bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, curve.AW)
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    seg_end = np.ascontiguousarray(seg_end, dtype=np.uint64).reshape(-1)
+    if len(bases) != len(scalars):
+        raise ValueError("bases and scalars must have the same length")
+    n = len(bases)
+    inf = None
+    if is_inf is not None:
+        inf = np.ascontiguousarray(is_inf, dtype=np.uint8)
+        if len(inf) < n:
+            raise ValueError("is_inf shorter than the batch")
+    nseg = len(seg_end)
+    if n == 0:                                   # (an empty numpy array has no address the ABI would accept)
+        bases = np.zeros((1, curve.AW), np.uint64)
+        scalars = np.zeros((1, 4), np.uint64)
+    out = np.zeros((nseg, curve.JW), dtype=np.uint64)
+    oinf = np.zeros(nseg, dtype=np.uint8)
+    rc = curve.fn("dgpu_msm_%s_segments")(_p(bases), _p(inf), _p(scalars), n, _p(seg_end) if nseg else None, nseg, int(montgomery), _p(out) if nseg else None, _p(oinf) if nseg else None)
+    if rc:
+        raise DockGpuError(rc, "dgpu_msm_%s_segments" % curve.tag)
+    return (out, oinf) if flags else out
+
+
 def affine_struct_dtype(curve):
     """numpy dtype with the layout of ark-ec 0.4's in-memory `Affine<P> { x, y, infinity }` as rustc lays it out for BLS12-381 today
     (x, y, then the bool, padded to the 8-byte alignment of the limbs): 104 bytes for G1, 200 for G2.  The strided entry points take the

@@ -206,6 +206,29 @@ int32_t dgpu_msm_g1_handle_many(uint64_t bases, size_t offset, const uint64_t *s
                                 uint64_t *out_xyz /* m * 18 */, uint8_t *out_inf /* m or NULL */);
 int32_t dgpu_msm_g2_handle_many(uint64_t bases, size_t offset, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, int32_t montgomery,
                                 uint64_t *out_xyz /* m * 36 */, uint8_t *out_inf /* m or NULL */);
+/* MANY small MSMs, each over its OWN bases, in one call: N terms (bases_xy, is_inf, scalars as for dgpu_msm_g*) cut into nseg segments; segment g is the
+ * terms [seg_end[g - 1], seg_end[g]) with seg_end[-1] = 0, seg_end ascending and seg_end[nseg - 1] == N (the convention of dgpu_multi_miller_loop_segments).
+ * out_xyz[g] (18 / 36 words) is bit for bit what dgpu_msm_g* writes for that segment alone with the size threshold off: the normalised Jacobian point
+ * (X, Y, 1), or (1, 1, 0) with out_inf[g] = 1 for the identity (out_inf may be NULL); an empty segment is the identity.  montgomery != 0 takes &[Fr] limbs as
+ * dgpu_msm_g*_mont does.  Bases may be any points of the curve.  The reference issues such batches back to back: saver/src/encryption.rs:710-740 (chunks + 2
+ * msm_bigint calls, one per ciphertext column), legogroth16/src/link/utils.rs:85-120 (one sum per matrix column), the paired halving MSMs of
+ * legogroth16/src/aggregation/utils.rs:51-81, the per-proof MSMs of bbs_plus/src/proof.rs:580.
+ * Refusals: a scalar with bit 255 set ANYWHERE refuses the whole call (DGPU_E_BADARG; no row of out_xyz is then defined); nseg = 0 is DGPU_OK without touching
+ * a device or the pointers; with nseg > 0, a NULL bases_xy / scalars / out_xyz / seg_end, a descending seg_end, seg_end[nseg - 1] != N or N >= 2^31:
+ * DGPU_E_BADARG, decided before the device is looked at; DGPU_E_NODEVICE comes before any size threshold; DGPU_E_TOO_SMALL only when N (the batch, not the
+ * segment) is below dgpu_get_min_gpu_n(): 300 segments of one term are device work.
+ * Paths: segments of up to 8192 terms (and dgpu_set_small_msm_max) travel in chunks of whole segments — one upload, ONE launch of the table of eight multiples
+ * over all the chunk's bases, ONE launch of the 64 window trees of every segment (short segments share blocks; crypto_amd/csrc/seg_kernels.hip.h), and the
+ * per-segment fold: on the device in one more launch when the chunk has many segments, on the host's threads when it has few (the count at which the device takes over is a
+ * provisional default until it is measured; no times are quoted for this call yet).  A LONGER segment goes through
+ * the single-call driver inside the call: correct, not faster than the caller's own dgpu_msm_g* call.
+ * Memory: the call owns one slot; a chunk holds at most 2^16 terms (the table is 1.6 KB per G1 base, 3.3 KB per G2 base: at most 109 / 218 MB) and 4096
+ * segments (64 window sums each: 55 / 109 MB), so the slot's grow-only workspace stays bounded whatever N, a failed or refused call leaves nothing else
+ * behind, and a second call of a shape already seen allocates nothing.  Thread-safe like every entry point: several calls may be in flight. */
+int32_t dgpu_msm_g1_segments(const uint64_t *bases_xy /* N * 12 */, const uint8_t *is_inf /* N or NULL */, const uint64_t *scalars /* N * 4 */, size_t N,
+                             const uint64_t *seg_end, size_t nseg, int32_t montgomery, uint64_t *out_xyz /* nseg * 18 */, uint8_t *out_inf /* nseg or NULL */);
+int32_t dgpu_msm_g2_segments(const uint64_t *bases_xy /* N * 24 */, const uint8_t *is_inf /* N or NULL */, const uint64_t *scalars /* N * 4 */, size_t N,
+                             const uint64_t *seg_end, size_t nseg, int32_t montgomery, uint64_t *out_xyz /* nseg * 36 */, uint8_t *out_inf /* nseg or NULL */);
 /* Precomputed-multiples mode for a resident query (in place; the handle keeps its id): the device builds table[w][i] = 2^(c w) P_i for the
  * W = 255 / c + 1 windows (W x the memory: 1.7 GB for a 2^20-point G1 query at c = 20 — sized for 288 GB of HBM), after which every MSM on
  * the handle adds digit w of scalar i into ONE bucket set shared by all windows: wider windows (13 instead of 16 additions per term at

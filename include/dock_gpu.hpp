@@ -65,6 +65,7 @@ struct G1 {
     static int32_t upload(const uint64_t *b, const uint8_t *i, size_t n, uint64_t *h) { return dgpu_bases_upload_g1(b, i, n, h); }
     static int32_t msm_handle(uint64_t h, size_t off, const uint64_t *s, size_t n, int32_t mont, uint64_t *o) { return dgpu_msm_g1_handle(h, off, s, n, mont, o); }
     static int32_t msm_handle_many(uint64_t h, size_t off, const uint64_t *s, size_t rs, size_t n, size_t m, int32_t mont, uint64_t *o, uint8_t *oi) { return dgpu_msm_g1_handle_many(h, off, s, rs, n, m, mont, o, oi); }
+    static int32_t msm_segments(const uint64_t *b, const uint8_t *i, const uint64_t *s, size_t n, const uint64_t *se, size_t ns, int32_t mont, uint64_t *o, uint8_t *oi) { return dgpu_msm_g1_segments(b, i, s, n, se, ns, mont, o, oi); }
     static int32_t msm_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, const uint64_t *s, size_t n, int32_t mont, uint64_t *o) { return dgpu_msm_g1_strided(b, st, xo, yo, io, s, n, mont, o); }
     static int32_t upload_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, size_t n, uint64_t *h) { return dgpu_bases_upload_g1_strided(b, st, xo, yo, io, n, h); }
     static int32_t table(const uint64_t *b, uint64_t *h) { return dgpu_window_table_g1(b, h); }
@@ -82,6 +83,7 @@ struct G2 {
     static int32_t upload(const uint64_t *b, const uint8_t *i, size_t n, uint64_t *h) { return dgpu_bases_upload_g2(b, i, n, h); }
     static int32_t msm_handle(uint64_t h, size_t off, const uint64_t *s, size_t n, int32_t mont, uint64_t *o) { return dgpu_msm_g2_handle(h, off, s, n, mont, o); }
     static int32_t msm_handle_many(uint64_t h, size_t off, const uint64_t *s, size_t rs, size_t n, size_t m, int32_t mont, uint64_t *o, uint8_t *oi) { return dgpu_msm_g2_handle_many(h, off, s, rs, n, m, mont, o, oi); }
+    static int32_t msm_segments(const uint64_t *b, const uint8_t *i, const uint64_t *s, size_t n, const uint64_t *se, size_t ns, int32_t mont, uint64_t *o, uint8_t *oi) { return dgpu_msm_g2_segments(b, i, s, n, se, ns, mont, o, oi); }
     static int32_t msm_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, const uint64_t *s, size_t n, int32_t mont, uint64_t *o) { return dgpu_msm_g2_strided(b, st, xo, yo, io, s, n, mont, o); }
     static int32_t upload_strided(const void *b, size_t st, size_t xo, size_t yo, size_t io, size_t n, uint64_t *h) { return dgpu_bases_upload_g2_strided(b, st, xo, yo, io, n, h); }
     static int32_t table(const uint64_t *b, uint64_t *h) { return dgpu_window_table_g2(b, h); }
@@ -135,6 +137,26 @@ template <class G> struct VariableBaseMSM {
         std::array<uint64_t, G::AW * 3 / 2> out{};
         check(G::msm_strided(bases.data(), sizeof(Affine), offsetof(Affine, x), offsetof(Affine, y), offsetof(Affine, infinity), n ? scalars[0].mont.data() : nullptr, n, 1, out.data()), "msm_unchecked");
         return projective_from_abi<G>(out.data());
+    }
+    // one msm_bigint per (bases[g], bigints[g]) pair in one call (dgpu_msm_*_segments): every MSM over its own points, each truncated to its shorter operand —
+    // the chunks + 2 column MSMs of saver/src/encryption.rs:710-740, the column sums of legogroth16/src/link/utils.rs:85-120
+    static std::vector<Projective> msm_bigint_segments(const std::vector<std::vector<Affine>> &bases, const std::vector<std::vector<BigInt256>> &bigints) {
+        const size_t nseg = std::min(bases.size(), bigints.size());
+        std::vector<uint64_t> seg_end(nseg + 1, 0);
+        std::vector<Affine> flat; std::vector<uint64_t> sc;
+        for (size_t g = 0; g < nseg; g++) {
+            const size_t n = std::min(bases[g].size(), bigints[g].size());
+            flat.insert(flat.end(), bases[g].begin(), bases[g].begin() + n);
+            for (size_t i = 0; i < n; i++) sc.insert(sc.end(), bigints[g][i].begin(), bigints[g][i].end());
+            seg_end[g] = flat.size();
+        }
+        const Packed<G> pk(flat, flat.size());
+        std::vector<uint64_t> xy(pk.xy), out(nseg * (G::AW * 3 / 2) + 1);
+        xy.push_back(0); sc.push_back(0);                              // (never NULL)
+        check(G::msm_segments(xy.data(), pk.inf.empty() ? nullptr : pk.inf.data(), sc.data(), flat.size(), seg_end.data(), nseg, 0, out.data(), nullptr), "msm_segments");
+        std::vector<Projective> res(nseg);
+        for (size_t g = 0; g < nseg; g++) res[g] = projective_from_abi<G>(&out[g * (G::AW * 3 / 2)]);
+        return res;
     }
     // msm(bases, scalars): Err(min_len) on a length mismatch — returned as {nullopt, min_len}
     static std::pair<std::optional<Projective>, size_t> msm(const std::vector<Affine> &bases, const std::vector<Fr> &scalars) {

@@ -20,6 +20,10 @@ int32_t dgpu_set_chunk(int32_t terms);
 /* rows per launch of dgpu_msm_g*_handle_many (1..65535; 0 = automatic from the row length: 2^17 terms' worth, at most 4096 rows).  Any value gives the
  * same rows (tests compare chunked against unchunked). */
 int32_t dgpu_set_many_chunk_rows(int32_t rows);
+/* dgpu_msm_g*_segments: fold = 0 the per-segment fold by the chunk's segment count, 1 always the host threads' host_fold, 2 always k_seg_fold on the device;
+ * chunk_terms = terms per chunk (1 .. 2^20; 0 = automatic, 2^16; a segment longer than the limit travels alone).  Any setting gives the same words (tests
+ * cross chunk boundaries with small inputs and compare both folds). */
+int32_t dgpu_set_msm_segments(int32_t fold, int32_t chunk_terms);
 /* log2 of the buckets one lane of the bucket reduction sums serially on the table pipeline (0..6; -1 = automatic: 3 for a 2^19-bucket table when the
  * call runs alone, 4 when three or more calls are in flight on the device context).  Any value gives the same point. */
 int32_t dgpu_set_reduce_shift(int32_t log2_buckets_per_lane);

@@ -20,6 +20,7 @@ use ark_ec::pairing::{MillerLoopOutput, Pairing, PairingOutput};
 use ark_ec::{AffineRepr, VariableBaseMSM};
 use ark_ff::{BigInt, PrimeField};
 use ark_std::vec::Vec;
+use crate::{msm_bigint_segments_g1, msm_bigint_segments_g2};
 
 type Cfg = ark_bls12_381::Config;
 
@@ -70,6 +71,21 @@ pub fn msm_bigint<G: AffineRepr>(bases: &[G], bigints: &[<G::ScalarField as Prim
         return unsafe { cast_val::<G2Projective, G::Group>(crate::msm_bigint_g2(cast_slice::<G, G2Affine>(bases), cast_slice::<<G::ScalarField as PrimeField>::BigInt, BigInt<4>>(bigints))) };
     }
     G::Group::msm_bigint(bases, bigints)
+}
+/// `bases.iter().zip(bigints).map(|(b, s)| G::Group::msm_bigint(b, s))` as ONE call (`dgpu_msm_*_segments`): many small MSMs, each over its own points —
+/// saver/src/encryption.rs:710-740, legogroth16/src/link/utils.rs:85-120, legogroth16/src/aggregation/utils.rs:51-81; arkworks pair by pair for every other curve.
+pub fn msm_bigint_segments<G: AffineRepr>(bases: &[&[G]], bigints: &[&[<G::ScalarField as PrimeField>::BigInt]]) -> Vec<G::Group> {
+    if same::<G, G1Affine>() {
+        let b: Vec<&[G1Affine]> = bases.iter().map(|x| unsafe { cast_slice::<G, G1Affine>(x) }).collect();
+        let s: Vec<&[BigInt<4>]> = bigints.iter().map(|x| unsafe { cast_slice::<<G::ScalarField as PrimeField>::BigInt, BigInt<4>>(x) }).collect();
+        return unsafe { cast_val::<Vec<G1Projective>, Vec<G::Group>>(msm_bigint_segments_g1(&b, &s)) };
+    }
+    if same::<G, G2Affine>() {
+        let b: Vec<&[G2Affine]> = bases.iter().map(|x| unsafe { cast_slice::<G, G2Affine>(x) }).collect();
+        let s: Vec<&[BigInt<4>]> = bigints.iter().map(|x| unsafe { cast_slice::<<G::ScalarField as PrimeField>::BigInt, BigInt<4>>(x) }).collect();
+        return unsafe { cast_val::<Vec<G2Projective>, Vec<G::Group>>(msm_bigint_segments_g2(&b, &s)) };
+    }
+    bases.iter().zip(bigints.iter()).map(|(b, s)| { let n = b.len().min(s.len()); G::Group::msm_bigint(&b[..n], &s[..n]) }).collect()
 }
 /// `rows.iter().map(|r| G::Group::msm_unchecked(bases, r))` as ONE call (`dgpu_msm_*_handle_many`): the batches of small MSMs over one commitment key —
 /// verifiable_encryption/src/tz_21/dkgith.rs:174-192,368; rdkgith.rs:140-147; bbs_plus/src/setup.rs:128-146,176-193; kvac/src/bbdt_2016/setup.rs:109;

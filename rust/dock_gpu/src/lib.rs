@@ -133,6 +133,47 @@ pub fn msm_unchecked_g2(bases: &[G2Affine], scalars: &[Fr]) -> G2Projective {
     g2_from_xyz(&out)
 }
 
+/// `bases.iter().zip(scalars).map(|(b, s)| G1Projective::msm_bigint(b, s))` as ONE call (`dgpu_msm_g1_segments`): many small MSMs, each over its OWN points —
+/// the `chunks + 2` column MSMs of saver/src/encryption.rs:710-740, the column sums of legogroth16/src/link/utils.rs:85-120, the paired halving MSMs of
+/// legogroth16/src/aggregation/utils.rs:51-81.  Each pair is truncated to its shorter side as arkworks does; arkworks pair by pair when the device declines.
+/// Public as `generic::msm_bigint_segments::<G1Affine>`; its cargo-side case is tests/segments_parity.rs.
+pub(crate) fn msm_bigint_segments_g1(bases: &[&[G1Affine]], scalars: &[&[BigInt<4>]]) -> Vec<G1Projective> {
+    let nseg = bases.len().min(scalars.len());
+    let lens: Vec<usize> = (0..nseg).map(|g| bases[g].len().min(scalars[g].len())).collect();
+    let flat_b: Vec<G1Affine> = (0..nseg).flat_map(|g| bases[g][..lens[g]].iter().copied()).collect();
+    let flat_s: Vec<BigInt<4>> = (0..nseg).flat_map(|g| scalars[g][..lens[g]].iter().copied()).collect();
+    let (mut xy, inf) = pack_g1(&flat_b);
+    xy.push(0);                                            // (never a dangling pointer for an all-empty batch)
+    let mut seg_end = Vec::with_capacity(nseg);
+    let mut acc = 0u64;
+    for l in &lens { acc += *l as u64; seg_end.push(acc); }
+    let mut out = ark_std::vec![0u64; nseg * 18 + 1];
+    let sp = if flat_s.is_empty() { xy.as_ptr() } else { flat_s.as_ptr() as *const u64 };
+    let rc = unsafe { dgpu_msm_g1_segments(xy.as_ptr(), inf.as_ptr(), sp, flat_b.len(), seg_end.as_ptr(), nseg, 0, out.as_mut_ptr(), core::ptr::null_mut()) };
+    if rc != DGPU_OK { return (0..nseg).map(|g| G1Projective::msm_bigint(&bases[g][..lens[g]], &scalars[g][..lens[g]])).collect(); }
+    out[..nseg * 18].chunks_exact(18).map(|w| g1_from_xyz(w.try_into().unwrap())).collect()
+}
+/// `bases.iter().zip(scalars).map(|(b, s)| G2Projective::msm_bigint(b, s))` as ONE call (`dgpu_msm_g2_segments`): many small MSMs, each over its OWN points —
+/// the `chunks + 2` column MSMs of saver/src/encryption.rs:710-740, the column sums of legogroth16/src/link/utils.rs:85-120, the paired halving MSMs of
+/// legogroth16/src/aggregation/utils.rs:51-81.  Each pair is truncated to its shorter side as arkworks does; arkworks pair by pair when the device declines.
+/// Public as `generic::msm_bigint_segments::<G2Affine>`; its cargo-side case is tests/segments_parity.rs.
+pub(crate) fn msm_bigint_segments_g2(bases: &[&[G2Affine]], scalars: &[&[BigInt<4>]]) -> Vec<G2Projective> {
+    let nseg = bases.len().min(scalars.len());
+    let lens: Vec<usize> = (0..nseg).map(|g| bases[g].len().min(scalars[g].len())).collect();
+    let flat_b: Vec<G2Affine> = (0..nseg).flat_map(|g| bases[g][..lens[g]].iter().copied()).collect();
+    let flat_s: Vec<BigInt<4>> = (0..nseg).flat_map(|g| scalars[g][..lens[g]].iter().copied()).collect();
+    let (mut xy, inf) = pack_g2(&flat_b);
+    xy.push(0);                                            // (never a dangling pointer for an all-empty batch)
+    let mut seg_end = Vec::with_capacity(nseg);
+    let mut acc = 0u64;
+    for l in &lens { acc += *l as u64; seg_end.push(acc); }
+    let mut out = ark_std::vec![0u64; nseg * 36 + 1];
+    let sp = if flat_s.is_empty() { xy.as_ptr() } else { flat_s.as_ptr() as *const u64 };
+    let rc = unsafe { dgpu_msm_g2_segments(xy.as_ptr(), inf.as_ptr(), sp, flat_b.len(), seg_end.as_ptr(), nseg, 0, out.as_mut_ptr(), core::ptr::null_mut()) };
+    if rc != DGPU_OK { return (0..nseg).map(|g| G2Projective::msm_bigint(&bases[g][..lens[g]], &scalars[g][..lens[g]])).collect(); }
+    out[..nseg * 36].chunks_exact(36).map(|w| g2_from_xyz(w.try_into().unwrap())).collect()
+}
+
 /// a proving-key query resident in HBM (uploaded once per key; `precompute` turns it into the window table the 2^20-term MSMs run on)
 pub struct ResidentG1 { handle: u64, host: Vec<G1Affine> }
 impl ResidentG1 {
