@@ -110,7 +110,7 @@ template <class F2> FD void f12_mul_by_014(Fp12T<F2> &f, const F2 &c0, const F2 
 }
 // ---- the dense Fp12 product as 18 independent Fp2 products ("roles") and 6 output combinations --------------------------------------
 // f12_mul above is one long dependent sequence (18 Fp2 products behind each other on whoever computes the node); the product tree of the
-// Miller loop is latency-bound, so k_product_tree18 (dock_pairing.hip) gives every node 18 lane pairs: lane pair r forms the operands of
+// Miller loop is latency-bound, so k_product_tree18 (pairing_kernels.hip.h) gives every node 18 lane pairs: lane pair r forms the operands of
 // role r, multiplies, parks the product in LDS, and after a barrier the first 6 lane pairs combine the products into one output
 // coefficient each.  Same formulas as f6_mul / f12_mul, only regrouped; the functions below are that regrouping, host + device, so that
 // the FP29_CHECK build proves the bounds of exactly what the kernel runs (f12_mul_roles == f12_mul, tests/test_device_code_on_host.py).
@@ -222,7 +222,7 @@ template <class F2> FD void line_dbl_step(G2ProjT<F2> &R, LineT<F2> &l) {
     fadd(t, j, j); fadd(t, t, j); fnorm(l.c1, t);
     f2_neg_n<32>(l.c2, h);
 }
-// ---- the doubling step as k_miller_lines_hex runs it (dock_pairing.hip: sixteen lanes per pair, one instruction stream for every role, so
+// ---- the doubling step as k_miller_lines_hex runs it (pairing_kernels.hip.h: sixteen lanes per pair, one instruction stream for every role, so
 // every instruction saved is saved on the critical path).  Same VALUES as line_dbl_step — so the raw Miller output does not change — with
 // fewer carry passes and halvings:
 //   * all five operations of the first round are squarings: X Y = ((X + Y)^2 - X^2 - Y^2) / 2;
@@ -280,7 +280,7 @@ template <class F2> FD void line_add_step(G2ProjT<F2> &R, const Aff<F2> &Q, Line
     fmul(t, theta, Q.x); fmul(u, lam, Q.y); f2_sub_n<8>(j, t, u);
     l.c0 = j; f2_neg_n<64>(l.c1, theta); l.c2 = lam;
 }
-// ---- the steps as k_miller_lines_ws runs them (dock_pairing.hip: a wave per role, a lane quad per pair).  Same VALUES as line_dbl_step /
+// ---- the steps as k_miller_lines_ws runs them (pairing_kernels.hip.h: a wave per role, a lane quad per pair).  Same VALUES as line_dbl_step /
 // line_add_step; what differs from line_dbl_step_fast is which products are formed:
 //   * a general Fp2 product is FOUR separately reduced Fp products, one per lane of the quad (392 multiply-adds on the critical path instead of
 //     the 588 of the fused two-product form): c0 = a0 b0 - a1 b1 + 4 p, c1 = a0 b1 + a1 b0, one carry pass (f2_mul_q);

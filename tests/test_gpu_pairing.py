@@ -236,12 +236,13 @@ def test_mixed_affine_and_prepared_operands_in_one_call(n):
 
 
 @pytest.mark.parametrize("sizes", [[1, 1], [0, 3, 0, 1, 7], [5, 64, 65, 2, 256, 257, 1], [1, 2, 4, 8, 16, 32, 64, 128, 256, 512], [3000, 1, 0, 900], [9000, 4, 17],
-                                   [2048, 2048, 1024, 1024, 1024, 1024], [8192, 513, 0, 700, 4097]])
+                                   [2048, 2048, 1024, 1024, 1024, 1024], [8192, 513, 0, 700, 4097], [(i * 7) % 4 for i in range(120)], [5, 64, 65, 2, 257]])
 def test_segmented_miller_loops_equal_the_single_calls(sizes):
     """dgpu_multi_miller_loop_segments: every segment's raw Fp12 output is limb for limb what dgpu_multi_miller_loop returns for that segment
     alone — empty segments (one), single pairs, sizes around the slice and group borders, identity members, skip flags, a segment long enough
     for the per-segment path, segments long enough for the second tree level (the commitments of a 1024-proof aggregation; 8192 + 4097: with and without the
-    pieces), and the argument checks."""
+    pieces), 120 segments of 0 - 3 pairs (more per-step products than the pinned buffer of the pieces takes: one launch of the chain at a small n), the
+    development forms of the pieces on the twin (none, moved cuts, the last piece's slice length, which segments ignore), and the argument checks."""
     import ctypes as C
     from crypto_amd import pairing
     from crypto_amd._native import lib
@@ -254,8 +255,20 @@ def test_segmented_miller_loops_equal_the_single_calls(sizes):
     jobs = [(ps[a:b], qs[a:b]) for a, b in zip(starts, ends)]
     got = pairing.multi_miller_loops(jobs)
     assert len(got) == len(sizes)
-    for (a, b), f in zip(zip(starts, ends), got):
-        assert (f == ca.multi_miller_loop(ps[a:b], qs[a:b])).all(), (a, b)
+    want = [ca.multi_miller_loop(ps[a:b], qs[a:b]) for a, b in zip(starts, ends)]
+    for (a, b), f, w in zip(zip(starts, ends), got, want):
+        assert (f == w).all(), (a, b)
+    if sizes == [5, 64, 65, 2, 257]:
+        with ca.twin():
+            try:
+                for mode in (30, 31 | 45 << 8 | 20 << 16, 31 | 2 << 24):
+                    assert lib().dgpu_set_miller_pipeline(mode) == 0
+                    dev = pairing.multi_miller_loops(jobs)
+                    assert len(dev) == len(sizes)
+                    for k, (f, w) in enumerate(zip(dev, want)):
+                        assert (f == w).all(), (mode, k)
+            finally:
+                lib().dgpu_set_miller_pipeline(31)
     gts = pairing.multi_pairings(jobs)
     for f, g in zip(got, gts):
         assert (g == ca.final_exponentiation(f)).all()
