@@ -19,6 +19,7 @@
 //                  one Fp2 inversion (fp_safegcd.hip.h) on every lane alike
 // Everything is exact arithmetic on residues, so the results equal the host functions' word for word (GT and raw Miller outputs alike).
 #pragma once
+#include <stddef.h>
 #include "pairing29.hip.h"
 #include "fp_safegcd.hip.h"
 
@@ -181,6 +182,201 @@ template <class X, class Load> FD void gt_miller_tail(X &x, Fp2 &out, const Load
         if ((BLS_X_ABS >> b) & 1) { load(idx++, l); gt_mul(x, f, f, l); }
     }
     gt_conj(out, f, x.lane());
+}
+
+// ---- powers, products of powers and membership (k_gt_pow.hip; `PairingOutput::mul_bigint` and `Valid::check` over many elements) ----
+// Between kernels and inside a kernel's table an element lives in the INTERNAL form: coefficient e as 2 NL limbs (class N, value < 2 p: what gt_mul
+// and gt_cyc_sqr leave) at word e GT_TABW of its GT_ELW words.  Lane e stores and loads coefficient e only.
+constexpr int GT_TABW = 2 * NL;                   // words of one coefficient
+constexpr int GT_ELW = GT_LANES * GT_TABW;        // words of one element
+constexpr int GT_ABIW = 144;                      // words of one element in the ABI form (72 u64)
+constexpr int GT_TAB = 8;                         // table entries per base: a^1 .. a^8
+constexpr int GT_MAX_K = 8;                       // bases per group
+constexpr int GT_FOLD = 8;                        // inputs per group of a fold level
+
+FD void gt_put(uint32_t *dst, const Fp2 &v) {
+    CHK(assert(v.c0.vb <= 2.0 && v.c1.vb <= 2.0); for (int i = 0; i < NL - 1; i++) assert(v.c0.ub[i] <= (1ull << LB) + 7 && v.c1.ub[i] <= (1ull << LB) + 7);)
+#pragma unroll
+    for (int i = 0; i < NL; i++) { dst[i] = v.c0.l[i]; dst[NL + i] = v.c1.l[i]; }
+}
+FD void gt_get(Fp2 &v, const uint32_t *src) {
+#pragma unroll
+    for (int i = 0; i < NL; i++) { v.c0.l[i] = src[i]; v.c1.l[i] = src[NL + i]; }
+    CHK(chk_set_N(v.c0, 2.0); chk_set_N(v.c1, 2.0); chk_actual(v.c0); chk_actual(v.c1);)
+}
+// coefficient e of an element in the ABI form (tower order, 12 words per Fp)
+FD void gt_get_abi(Fp2 &v, const uint32_t *el, int e) {
+    const uint32_t *src = el + gt_tower_of(e) * 24;
+    uint32_t w[24];
+#pragma unroll
+    for (int k = 0; k < 24; k++) w[k] = src[k];
+    fp_from_abi(v.c0, w); fp_from_abi(v.c1, w + 12);
+}
+FD void gt_put_abi(uint32_t *el, int e, const Fp2 &v) {
+    uint32_t *dst = el + gt_tower_of(e) * 24;
+    uint32_t w[24]; fp_to_abi(w, v.c0); fp_to_abi(w + 12, v.c1);
+#pragma unroll
+    for (int k = 0; k < 24; k++) dst[k] = w[k];
+}
+// coefficient e of the element one
+FD void gt_one(Fp2 &r, int e) { Fp2 o, z; fset_one(o); fzero(z); fsel(r, e == 0, o, z); }
+// r = c ? a : b where c depends on the DATA (a digit, a bit of an exponent): the check build keeps the wider of the two bounds
+FD void gt_sel_data(Fp2 &r, bool c, const Fp2 &a, const Fp2 &b) {
+    fsel(r, c, a, b);
+    CHK(for (int i = 0; i < NL; i++) { r.c0.ub[i] = a.c0.ub[i] > b.c0.ub[i] ? a.c0.ub[i] : b.c0.ub[i]; r.c1.ub[i] = a.c1.ub[i] > b.c1.ub[i] ? a.c1.ub[i] : b.c1.ub[i]; }
+        r.c0.vb = a.c0.vb > b.c0.vb ? a.c0.vb : b.c0.vb; r.c1.vb = a.c1.vb > b.c1.vb ? a.c1.vb : b.c1.vb;)
+}
+
+// Signed 4-bit digits of a 256-bit exponent (eight 32-bit words), d_w in [-7, 8], w = 0 .. 64, sum d_w 16^w = the exponent: the rule of
+// signed_digits in dock_gt.cpp (v = nibble + carry; v > 8 gives v - 16 and a carry), digit 64 the carry out of bit 255.  A lane keeps the 64
+// carries as one word (bit w = the carry OUT of window w) and forms a digit from the exponent word that holds its nibble.
+FD uint64_t gt_digit_carries(const uint32_t e[8]) {
+    uint64_t m = 0; uint32_t c = 0;
+#pragma unroll 1
+    for (int w = 0; w < 64; w++) { const uint32_t v = ((e[w >> 3] >> (4 * (w & 7))) & 15u) + c; c = v > 8 ? 1u : 0u; m |= (uint64_t)c << w; }
+    return m;
+}
+FD int gt_digit(uint32_t word, uint64_t carries, int w) {       // word = exponent word w / 8 (anything for w = 64)
+    const int nib = w < 64 ? (int)((word >> (4 * (w & 7))) & 15u) : 0;
+    const int cin = w > 0 ? (int)((carries >> (w - 1)) & 1) : 0, cout = w < 64 ? (int)((carries >> w) & 1) : 0;
+    return nib + cin - 16 * cout;
+}
+FD void gt_signed_digits(const uint32_t e[8], int8_t d[65]) {
+    const uint64_t m = gt_digit_carries(e);
+    for (int w = 0; w <= 64; w++) d[w] = (int8_t)gt_digit(e[w < 64 ? w >> 3 : 7], m, w);
+}
+
+// words of a and b in the ABI form compared: 0 iff a == b as residues.  (Values between steps are lazy residues: never compare those.)
+FD uint32_t gt_abi_diff(const Fp2 &a, const Fp2 &b, uint32_t &any_b) {
+    uint32_t wa[12], wb[12], d = 0;
+    fp_to_abi(wa, a.c0); fp_to_abi(wb, b.c0);
+#pragma unroll
+    for (int k = 0; k < 12; k++) { d |= wa[k] ^ wb[k]; any_b |= wb[k]; }
+    fp_to_abi(wa, a.c1); fp_to_abi(wb, b.c1);
+#pragma unroll
+    for (int k = 0; k < 12; k++) { d |= wa[k] ^ wb[k]; any_b |= wb[k]; }
+    return d;
+}
+// f in the cyclotomic subgroup (in_cyclotomic of dock_gt.cpp): f^(p^4) f == f^(p^2), zero is not
+template <class X> FD bool gt_in_cyclotomic(X &x, const Fp2 &f) {
+    const int e = x.lane();
+    Fp2 f2, f4, l; gt_frob2(f2, f, e); gt_frob2(f4, f2, e); gt_mul(x, l, f4, f);
+    uint32_t any = 0;
+    const uint32_t diff = gt_abi_diff(l, f2, any);
+    const bool eq = x.all(diff == 0), zero = x.all(any == 0);          // (f^(p^2) is zero iff f is)
+    return eq && !zero;
+}
+// f in GT (in_gt of dock_gt.cpp): in the cyclotomic subgroup and f^p == f^x.  Every lane runs the whole chain whatever the first test said.
+template <class X> FD bool gt_in_gt(X &x, const Fp2 &f) {
+    const bool cyc = gt_in_cyclotomic(x, f);
+    Fp2 l, r; gt_frob1(l, f, x.lane()); gt_exp_by_x(x, r, f);
+    uint32_t any = 0;
+    const uint32_t diff = gt_abi_diff(l, r, any);
+    return x.all(diff == 0) && cyc;
+}
+
+// tab[d - 1] = a^d, d = 1 .. 8, for a in the cyclotomic subgroup; entry 0 is already there.  `tab` is this lane's column of the base's table
+// (entries GT_ELW words apart).  Seven steps: even d squares entry d / 2, odd d multiplies the entry before by a.
+template <class X> FD void gt_pow_table(X &x, uint32_t *tab) {
+    Fp2 a, cur; gt_get(a, tab); cur = a;
+#pragma unroll 1
+    for (int d = 2; d <= GT_TAB; d++) {
+        if (d & 1) gt_mul(x, cur, cur, a);                               // (d is the same on every lane)
+        else { Fp2 h; gt_get(h, tab + (d / 2 - 1) * GT_ELW); gt_cyc_sqr(x, cur, h); }
+        gt_put(tab + (d - 1) * GT_ELW, cur);
+    }
+}
+// acc = prod_j a_j^(e_j) over the k bases of a group, all of the cyclotomic subgroup, by signed 4-bit windows from the top: four Granger-Scott
+// squarings shared by the group's bases, then per base ONE product by an operand picked by selects — the table entry of |d|, conjugated for d < 0,
+// the element one for d = 0 — so every lane of a wave runs the same stream whatever the digits are (no `started` flag: the accumulator starts
+// at one, and squaring one is harmless).  tab: this lane's column of the group's tables (base j at j GT_TAB GT_ELW); dig(j, w) = digit w of base j.
+template <class X, class Dig> FD void gt_pow_cyc(X &x, Fp2 &acc, const uint32_t *tab, int k, const Dig &dig) {
+    const int e = x.lane();
+    Fp2 one; gt_one(one, e);
+    acc = one;
+#pragma unroll 1
+    for (int w = 64; w >= 0; w--) {
+#pragma unroll 1
+        for (int s = 0; s < 4; s++) gt_cyc_sqr(x, acc, acc);
+#pragma unroll 1
+        for (int j = 0; j < k; j++) {
+            const int d = dig(j, w), m = d < 0 ? -d : d;
+            Fp2 tv, tc, op; gt_get(tv, tab + ((size_t)j * GT_TAB + (m ? m - 1 : 0)) * GT_ELW);
+            gt_conj(tc, tv, e);
+            gt_sel_data(op, d < 0, tc, tv); gt_sel_data(op, d == 0, one, op);
+            gt_mul(x, acc, acc, op);
+        }
+    }
+}
+// the same product for ANY Fp12 bases (untrusted input, raw Miller outputs, zero): binary square-and-multiply from the top bit, the square a
+// plain product, the multiplier a select between the base (entry 0 of its table) and one.  0^0 = one and 0^e = 0 fall out of it.
+template <class X, class Bit> FD void gt_pow_generic(X &x, Fp2 &acc, const uint32_t *tab, int k, const Bit &bit) {
+    Fp2 one; gt_one(one, x.lane());
+    acc = one;
+#pragma unroll 1
+    for (int b = 255; b >= 0; b--) {
+        gt_mul(x, acc, acc, acc);
+#pragma unroll 1
+        for (int j = 0; j < k; j++) {
+            Fp2 a, op; gt_get(a, tab + (size_t)j * GT_TAB * GT_ELW);
+            gt_sel_data(op, bit(j, b), a, one);
+            gt_mul(x, acc, acc, op);
+        }
+    }
+}
+
+// What one group of k_gt_pow does: the product of the powers of bases [first, first + k) of nb (ABI form, `in`; missing ones count as one), exponent
+// of base b at exps + b ew (ew = 8 words, or 0 for one exponent for all), into dst (this group's element, ABI or internal form).
+// tab: the group's k tables; cm: k words of this lane's own (carries of the digits), cs apart.
+// The short path needs every base of every group of the WAVE in the cyclotomic subgroup (x.wave_all: the branch is the same on every lane of the
+// wave, so the lock step of the exchanges holds); otherwise the whole wave runs the generic one.  Both are exact, so the words are the same.
+// force_generic: tests only.
+template <class X> FD void gt_pow_group(X &x, const uint32_t *in, const uint32_t *exps, int ew, size_t nb, size_t first, int k, uint32_t *tab,
+                                        uint64_t *cm, int cs, bool force_generic, uint32_t *dst, bool dst_abi) {
+    const int e = x.lane();
+    uint32_t *mytab = tab + e * GT_TABW;
+    bool cyc = true;
+#pragma unroll 1
+    for (int j = 0; j < k; j++) {
+        const bool valid = first + j < nb;
+        const size_t b = valid ? first + j : nb - 1;
+        Fp2 a, one; gt_get_abi(a, in + b * GT_ABIW, e); gt_one(one, e);
+        gt_sel_data(a, valid, a, one);
+        gt_put(mytab + (size_t)j * GT_TAB * GT_ELW, a);
+        const bool c = gt_in_cyclotomic(x, a);
+        cyc = cyc && c;
+        uint32_t w[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) w[i] = exps[b * ew + i];
+        const uint64_t m = gt_digit_carries(w);
+        cm[j * cs] = valid ? m : 0;
+    }
+    const bool use_cyc = x.wave_all(cyc) && !force_generic;
+    auto word = [&](int j, int wi) -> uint32_t { const bool valid = first + j < nb; return valid ? exps[(first + j) * ew + wi] : 0u; };
+    Fp2 acc;
+    if (use_cyc) {
+#pragma unroll 1
+        for (int j = 0; j < k; j++) gt_pow_table(x, mytab + (size_t)j * GT_TAB * GT_ELW);
+        gt_pow_cyc(x, acc, mytab, k, [&](int j, int w) { return gt_digit(word(j, w < 64 ? w >> 3 : 7), cm[j * cs], w); });
+    } else {
+        gt_pow_generic(x, acc, mytab, k, [&](int j, int b) { return ((word(j, b >> 5) >> (b & 31)) & 1u) != 0; });
+    }
+    if (dst_abi) gt_put_abi(dst, e, acc); else gt_put(dst + e * GT_TABW, acc);
+}
+// What one group of k_gt_fold does: the product of inputs [first, first + GT_FOLD) of n_in (a missing one counts as one; a lone input is copied)
+template <class X> FD void gt_fold_group(X &x, const uint32_t *in, bool in_abi, size_t n_in, size_t first, uint32_t *dst, bool dst_abi) {
+    const int e = x.lane();
+    Fp2 acc, one; gt_one(one, e);
+    auto get = [&](Fp2 &v, size_t idx) { if (in_abi) gt_get_abi(v, in + idx * GT_ABIW, e); else gt_get(v, in + idx * GT_ELW + e * GT_TABW); };
+    get(acc, first);
+#pragma unroll 1
+    for (int s = 1; s < GT_FOLD; s++) {
+        const bool valid = first + s < n_in;
+        Fp2 v; get(v, valid ? first + s : first);
+        gt_sel_data(v, valid, v, one);
+        gt_mul(x, acc, acc, v);
+    }
+    if (dst_abi) gt_put_abi(dst, e, acc); else gt_put(dst + e * GT_TABW, acc);
 }
 
 }  // namespace bls29

@@ -50,15 +50,40 @@ def fp12_pow(a, e):
     return out
 
 
-def fp12_multi_pow(bases, exps):
-    """prod bases[i]^exps[i] (dgpu_fp12_multi_pow: host threads, shared squarings)"""
+def fp12_multi_pow(bases, exps, device=False):
+    """prod bases[i]^exps[i] (dgpu_fp12_multi_pow: host threads, shared squarings; device=True: dgpu_fp12_multi_pow_device, the same words from
+    the GPU — for thousands of bases)"""
     n = len(bases)
     a = np.ascontiguousarray(np.stack([np.asarray(b, dtype=np.uint64).reshape(72) for b in bases]))
     e = np.ascontiguousarray(np.stack([_limbs(int(x) % R_MOD) for x in exps]))
     out = np.zeros(72, dtype=np.uint64)
-    rc = lib().dgpu_fp12_multi_pow(_p(a), _p(e), n, _p(out))
+    if device:
+        _ensure()
+    name = "dgpu_fp12_multi_pow_device" if device else "dgpu_fp12_multi_pow"
+    rc = getattr(lib(), name)(_p(a), _p(e), n, _p(out))
     if rc:
-        raise DockGpuError(rc, "dgpu_fp12_multi_pow")
+        raise DockGpuError(rc, name)
+    return out
+
+
+def fp12_pow_batch(bases, exps):
+    """[bases[i]^exps[i]] on the device (dgpu_fp12_pow_batch): `PairingOutput::mul_bigint` per element, any Fp12 base.  exps: one integer per base,
+    or ONE integer for all; below 2^256 and NOT reduced mod r (what mul_bigint does with a BigInt).  Returns an (n, 72) array."""
+    a = np.ascontiguousarray(np.asarray(bases, dtype=np.uint64).reshape(-1, 72))
+    n = len(a)
+    one_for_all = not isinstance(exps, (list, tuple, np.ndarray))
+    ex = [exps] if one_for_all else list(exps)
+    if not one_for_all and len(ex) != n:
+        raise ValueError("%d bases, %d exponents" % (n, len(ex)))
+    if any(not 0 <= int(x) < 1 << 256 for x in ex):
+        raise ValueError("exponents are 256-bit")
+    e = np.ascontiguousarray(np.stack([_limbs(int(x)) for x in ex])) if ex else np.zeros((0, 4), np.uint64)
+    out = np.zeros((n, 72), dtype=np.uint64)
+    if n:
+        _ensure()
+    rc = lib().dgpu_fp12_pow_batch(_p(a), _p(e), 0 if one_for_all else 4, n, _p(out))
+    if rc:
+        raise DockGpuError(rc, "dgpu_fp12_pow_batch")
     return out
 
 

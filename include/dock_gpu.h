@@ -376,6 +376,16 @@ int32_t dgpu_gt_in_subgroup(const uint64_t *a /* n*72 */, size_t n, uint8_t *ok 
 /* prod_i a_i^{e_i}: the fold of `PairingOutput::mul_bigint` + `add_assign` in the aggregation verifier
  * (legogroth16/src/aggregation/groth16/verifier.rs:272-370); host threads, generic Fp12 arithmetic */
 int32_t dgpu_fp12_multi_pow(const uint64_t *a /* n*72 */, const uint64_t *e /* n*4 */, size_t n, uint64_t out[72]);
+/* The same three on the DEVICE, for many elements (crypto_amd/csrc/gt_kernels.hip.h: one element per group of six lanes, signed 4-bit windows over
+ * a table of eight powers with Granger-Scott squarings when every base of a wave lies in the cyclotomic subgroup, binary square-and-multiply
+ * otherwise).  Any Fp12 base, any 256-bit exponent (not reduced mod r: `PairingOutput::mul_bigint`); the words are those of dgpu_fp12_pow,
+ * dgpu_fp12_multi_pow and dgpu_gt_in_subgroup.  No size threshold: the device runs whatever n, in chunks of bounded device memory; the host entry
+ * points above stay the choice for a few elements (the crossover has not been measured yet: tests/perf/gt_pow_timing.py writes it to
+ * profiles/gt_pow_timing.json).  n = 0: DGPU_OK without a device (the product is then the
+ * element one); NULL pointers with n > 0, an e_stride other than 4 (an exponent per base) or 0 (one for all): DGPU_E_BADARG. */
+int32_t dgpu_fp12_pow_batch(const uint64_t *a /* n*72 */, const uint64_t *e, size_t e_stride /* 4 or 0 */, size_t n, uint64_t *out /* n*72 */);
+int32_t dgpu_fp12_multi_pow_device(const uint64_t *a /* n*72 */, const uint64_t *e /* n*4 */, size_t n, uint64_t out[72]);
+int32_t dgpu_gt_in_subgroup_device(const uint64_t *a /* n*72 */, size_t n, uint8_t *ok /* n */);
 
 /* ---- fixed-base batch multiplication ----
  * replaces ark-ec FixedBase::{get_window_table, msm} as the reference calls them: WindowTable::new / multiply_many and

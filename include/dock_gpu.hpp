@@ -271,6 +271,25 @@ inline std::optional<Fq12> final_exponentiation(const Fq12 &f) {
     check(rc, "final_exponentiation");
     return out;
 }
+// GT over many elements on the device: `PairingOutput::mul_bigint` per element (one exponent each, or one for all), the product of such powers,
+// and `Valid::check` (membership of GT) per element.  Exponents are 4 x u64, not reduced.
+inline std::vector<Fq12> fp12_pow_batch(const std::vector<Fq12> &bases, const std::vector<std::array<uint64_t, 4>> &exps) {
+    if (exps.size() != bases.size() && exps.size() != 1) throw Error(DGPU_E_BADARG, "fp12_pow_batch");
+    std::vector<Fq12> out(bases.size());
+    check(dgpu_fp12_pow_batch(bases.empty() ? nullptr : bases[0].data(), exps[0].data(), exps.size() == 1 ? 0 : 4, bases.size(), out.empty() ? nullptr : out[0].data()), "fp12_pow_batch");
+    return out;
+}
+inline Fq12 fp12_multi_pow_device(const std::vector<Fq12> &bases, const std::vector<std::array<uint64_t, 4>> &exps) {
+    if (exps.size() != bases.size()) throw Error(DGPU_E_BADARG, "fp12_multi_pow_device");
+    Fq12 out{};
+    check(dgpu_fp12_multi_pow_device(bases.empty() ? nullptr : bases[0].data(), exps.empty() ? nullptr : exps[0].data(), bases.size(), out.data()), "fp12_multi_pow_device");
+    return out;
+}
+inline std::vector<uint8_t> gt_in_subgroup_device(const std::vector<Fq12> &a) {
+    std::vector<uint8_t> ok(a.size());
+    check(dgpu_gt_in_subgroup_device(a.empty() ? nullptr : a[0].data(), a.size(), ok.data()), "gt_in_subgroup_device");
+    return ok;
+}
 inline Fq12 multi_pairing(const std::vector<G1::Affine> &a, const std::vector<G2::Affine> &b) { return *final_exponentiation(multi_miller_loop(a, b)); }
 
 

@@ -24,6 +24,11 @@ int32_t dgpu_set_many_chunk_rows(int32_t rows);
  * chunk_terms = terms per chunk (1 .. 2^20; 0 = automatic, 2^16; a segment longer than the limit travels alone).  Any setting gives the same words (tests
  * cross chunk boundaries with small inputs and compare both folds). */
 int32_t dgpu_set_msm_segments(int32_t fold, int32_t chunk_terms);
+/* Geometry of dgpu_fp12_pow_batch, dgpu_fp12_multi_pow_device and dgpu_gt_in_subgroup_device, and of nothing else (the final-exponentiation
+ * launchers keep their own rule): groups of six lanes per wave (1..10), bases per group of the product of powers (1..8; the batch form always takes one), elements per chunk
+ * (1..65536; the power table takes 5.4 KB per element).  0 = automatic: by the launch's group count, n / 2048 clamped to 1..8 (provisional until
+ * tests/perf/gt_pow_timing.py's sweep has run), 16384.  Any setting gives the same bytes. */
+int32_t dgpu_set_gt_pow(int32_t groups_per_wave, int32_t bases_per_group, int32_t chunk_elems);
 /* log2 of the buckets one lane of the bucket reduction sums serially on the table pipeline (0..6; -1 = automatic: 3 for a 2^19-bucket table when the
  * call runs alone, 4 when three or more calls are in flight on the device context).  Any value gives the same point. */
 int32_t dgpu_set_reduce_shift(int32_t log2_buckets_per_lane);

@@ -457,3 +457,33 @@ pub(crate) fn handle_serialize_g2(handle: u64, offset: usize, n: usize, compress
     if unsafe { dgpu_bases_serialize_g2(handle, offset, n, compressed as i32, out.as_mut_ptr()) } != DGPU_OK { return None; }
     Some(out)
 }
+
+// ---- GT over many elements on the device (dgpu_fp12_pow_batch, dgpu_fp12_multi_pow_device, dgpu_gt_in_subgroup_device) ----
+/// `a_i.mul_bigint(e_i)` for every element of a batch (any Fp12 value inside, exponents not reduced).  None when the library declined.
+pub fn gt_pow_batch(bases: &[ark_ec::pairing::PairingOutput<ark_bls12_381::Bls12_381>], exps: &[BigInt<4>]) -> Option<Vec<ark_ec::pairing::PairingOutput<ark_bls12_381::Bls12_381>>> {
+    if bases.len() != exps.len() { return None; }
+    let w: Vec<u64> = bases.iter().flat_map(|f| crate::fq12_to_words(&f.0)).collect();
+    let e: Vec<u64> = exps.iter().flat_map(|x| x.0).collect();
+    let mut out = ark_std::vec![0u64; bases.len() * 72];
+    let rc = unsafe { dgpu_fp12_pow_batch(w.as_ptr(), e.as_ptr(), 4, bases.len(), out.as_mut_ptr()) };
+    if rc != DGPU_OK { return None; }
+    Some((0..bases.len()).map(|i| ark_ec::pairing::PairingOutput(crate::fq12_from_words(out[72 * i..72 * i + 72].try_into().unwrap()))).collect())
+}
+/// sum_i a_i.mul_bigint(e_i) (GT written additively: the Fp12 product of the powers).  None when the library declined.
+pub fn gt_multi_pow_device(bases: &[ark_ec::pairing::PairingOutput<ark_bls12_381::Bls12_381>], exps: &[BigInt<4>]) -> Option<ark_ec::pairing::PairingOutput<ark_bls12_381::Bls12_381>> {
+    if bases.len() != exps.len() { return None; }
+    let w: Vec<u64> = bases.iter().flat_map(|f| crate::fq12_to_words(&f.0)).collect();
+    let e: Vec<u64> = exps.iter().flat_map(|x| x.0).collect();
+    let mut out = [0u64; 72];
+    let rc = unsafe { dgpu_fp12_multi_pow_device(w.as_ptr(), e.as_ptr(), bases.len(), out.as_mut_ptr()) };
+    if rc != DGPU_OK { return None; }
+    Some(ark_ec::pairing::PairingOutput(crate::fq12_from_words(&out)))
+}
+/// `Valid::check` of every element: true where it lies in GT.  None when the library declined.
+pub fn gt_in_subgroup_device(a: &[ark_ec::pairing::PairingOutput<ark_bls12_381::Bls12_381>]) -> Option<Vec<bool>> {
+    let w: Vec<u64> = a.iter().flat_map(|f| crate::fq12_to_words(&f.0)).collect();
+    let mut ok = ark_std::vec![0u8; a.len()];
+    let rc = unsafe { dgpu_gt_in_subgroup_device(w.as_ptr(), a.len(), ok.as_mut_ptr()) };
+    if rc != DGPU_OK { return None; }
+    Some(ok.iter().map(|&v| v != 0).collect())
+}

@@ -587,3 +587,24 @@ fn instance_map_and_key_generation_on_a_resident_circuit() {
     let rhs = Bls12_381::multi_pairing([vk.alpha_g1, d.into_affine(), pc], [(g2 * beta).into_affine(), vk.gamma_g2, vk.delta_g2]);
     assert_eq!(lhs, rhs);
 }
+
+// GT on the device over many elements against arkworks: mul_bigint per element, the sum of such, Valid::check
+#[test]
+fn gt_powers_on_the_device() {
+    use ark_ec::pairing::PairingOutput;
+    use ark_serialize::Valid;
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5EED0C07);
+    let n = 70usize;
+    let mut bases: Vec<PairingOutput<Bls12_381>> = (0..n).map(|_| Bls12_381::pairing(g1s(&mut rng, 1)[0], g2s(&mut rng, 1)[0])).collect();
+    bases[3] = PairingOutput(Bls12_381::multi_miller_loop(g1s(&mut rng, 1), g2s(&mut rng, 1)).0);      // not in GT
+    bases[9] = PairingOutput(<Bls12_381 as Pairing>::TargetField::zero());
+    let mut exps: Vec<BigInt<4>> = (0..n).map(|_| ark_bls12_381::Fr::rand(&mut rng).into_bigint()).collect();
+    exps[1] = BigInt::<4>([u64::MAX; 4]);
+    let want: Vec<PairingOutput<Bls12_381>> = bases.iter().zip(exps.iter()).map(|(b, e)| PairingOutput(b.0.pow(e.0))).collect();
+    assert_eq!(dock_gpu::host::gt_pow_batch(&bases, &exps).unwrap(), want);
+    let prod = want.iter().fold(<Bls12_381 as Pairing>::TargetField::from(1u64), |acc, w| acc * w.0);
+    assert_eq!(dock_gpu::host::gt_multi_pow_device(&bases, &exps).unwrap().0, prod);
+    let ok = dock_gpu::host::gt_in_subgroup_device(&bases).unwrap();
+    for (i, b) in bases.iter().enumerate() { assert_eq!(ok[i], !b.0.is_zero() && b.check().is_ok(), "element {i}"); }
+}
