@@ -16,6 +16,10 @@ int32_t dgpu_set_gt_pow(int32_t groups_per_wave, int32_t bases_per_group, int32_
     if (groups_per_wave < 0 || groups_per_wave > 10 || bases_per_group < 0 || bases_per_group > 8 || chunk_elems < 0 || chunk_elems > 65536) return DGPU_E_BADARG;
     gs.gt_pow_g = groups_per_wave; gs.gt_pow_k = bases_per_group; gs.gt_pow_chunk = chunk_elems; return DGPU_OK;
 }
+int32_t dgpu_set_wm_many(int32_t chunk_rows, int32_t rows_per_block) {
+    if (chunk_rows < 0 || chunk_rows > 4096 || rows_per_block < 0 || rows_per_block > 512) return DGPU_E_BADARG;
+    gs.wm_many_chunk = chunk_rows; gs.wm_many_rpb = rows_per_block; return DGPU_OK;
+}
 int32_t dgpu_set_reduce_lanes(int32_t lanes) { if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4) return DGPU_E_BADARG; gs.reduce_lanes = lanes; return DGPU_OK; }
 int32_t dgpu_set_reduce_shift(int32_t sh) { if (sh < -1 || sh > 6) return DGPU_E_BADARG; gs.reduce_shift = sh; return DGPU_OK; }
 int32_t dgpu_set_miller_pipeline(int32_t mode) {       // bits 0-4: forms; bits 8-13 / 16-21: where the chain is cut (0: default); bits 24-27: slice length of the last piece's products (0: automatic); bits 28-29: log2 of the factor on the block limit of k_line_products3

@@ -5,6 +5,7 @@
 #include "dock_ctx.hpp"
 #include "host_field.hpp"
 #include "qap_launch.hip.h"
+#include <algorithm>
 
 namespace {
 using namespace dock;
@@ -75,8 +76,9 @@ int32_t upload_matrix(Slot &sl, const Csr &m, size_t rows, int mont, DevCsr &out
     return DGPU_OK;
 }
 
-// assignment: host scalars (uploaded here), or d_assignment != nullptr: canonical scalars already resident on this device
-int32_t witness_map_device(Slot &sl, const DevR1cs &r, const uint64_t *assignment, int32_t montgomery, uint64_t *out_h, uint64_t *out_handle, size_t *out_len, const uint32_t *d_assignment = nullptr) {
+// assignment: host scalars (uploaded here), or d_assignment != nullptr: canonical scalars already resident on this device.
+// d_dst != nullptr (out_handle is then NULL): the canonical h scalars are written there, D * 8 words of a vector the caller owns
+int32_t witness_map_device(Slot &sl, const DevR1cs &r, const uint64_t *assignment, int32_t montgomery, uint64_t *out_h, uint64_t *out_handle, size_t *out_len, const uint32_t *d_assignment = nullptr, uint32_t *d_dst = nullptr) {
     int logn = 0; while (((size_t)1 << logn) < r.num_constraints + r.num_inputs) logn++;
     if (logn < 1) logn = 1;
     if (logn > 28) return DGPU_E_BADARG;
@@ -92,8 +94,8 @@ int32_t witness_map_device(Slot &sl, const DevR1cs &r, const uint64_t *assignmen
     // the h scalars are written where they stay: the caller's resident vector (a recycled buffer) if one is asked for, else scratch
     void *kept = nullptr;
     if (out_handle) { if (!(kept = scalar_alloc(scalar_bytes(D)))) return DGPU_E_OOM; }
-    else if ((rc = hw.ensure(D * 32))) return rc;
-    uint32_t *const h_words = kept ? (uint32_t *)kept : hw.as<uint32_t>();
+    else if (!d_dst && (rc = hw.ensure(D * 32))) return rc;
+    uint32_t *const h_words = kept ? (uint32_t *)kept : (d_dst ? d_dst : hw.as<uint32_t>());
     hipStream_t s = sl.stream;
     struct Giveback { void *&p; size_t bytes; hipStream_t st; ~Giveback() { if (p) { (void)hipStreamSynchronize(st); scalar_release(cur_index(), p, bytes); } } } giveback{kept, scalar_bytes(D), s};   // on any early return
     uint32_t *arr[3] = {qa.as<uint32_t>(), qb.as<uint32_t>(), qc.as<uint32_t>()};
@@ -116,7 +118,7 @@ int32_t witness_map_device(Slot &sl, const DevR1cs &r, const uint64_t *assignmen
     if (out_h) {
         const uint32_t *src = h_words;
         if (montgomery & DGPU_WM_H_MONTGOMERY) {          // the host copy as &[Fr] (what QAP::witness_map returns); a resident vector stays canonical
-            if (kept) { if ((rc = hw.ensure(D * 32))) return rc; HIPCHK(hipMemcpyAsync(hw.p, h_words, D * 32, hipMemcpyDeviceToDevice, s)); }
+            if (kept || d_dst) { if ((rc = hw.ensure(D * 32))) return rc; HIPCHK(hipMemcpyAsync(hw.p, h_words, D * 32, hipMemcpyDeviceToDevice, s)); }
             ntt::launch_fr_canonical_to_mont(s, hw.as<uint32_t>(), D);
             src = hw.as<uint32_t>();
         }
@@ -125,6 +127,72 @@ int32_t witness_map_device(Slot &sl, const DevR1cs &r, const uint64_t *assignmen
     if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return DGPU_E_HIP; }
     if (out_handle) { *out_handle = register_handle(kept, D, 3); kept = nullptr; }     // registered last: no handle is left behind by a failing call
     if (gs.prof) prof_flush(sl);
+    return DGPU_OK;
+}
+
+// rows per chunk of the many-row call: at most 4096 rows, 2^17 domain elements and 2^21 assignment scalars, so the slot's workspace stays bounded
+size_t wm_chunk_rows(size_t D, size_t num_vars) {
+    if (int forced = gs.wm_many_chunk.load()) return (size_t)forced;
+    size_t rows = ((size_t)1 << 17) / D, by_z = ((size_t)1 << 21) / (num_vars ? num_vars : 1);
+    if (rows > 4096) rows = 4096;
+    if (rows > by_z) rows = by_z;
+    return rows ? rows : 1;
+}
+// m witness maps of one resident circuit (dgpu_witness_map_r1cs_many): domains of up to 2^WM_BLOCK_MAX_LOG through k_wm_block, chunk by chunk; larger
+// ones row by row through witness_map_device, straight into the call's vector
+int32_t witness_map_many_device(Slot &sl, const DevR1cs &r, const uint64_t *assignments, size_t row_stride, size_t m, int32_t montgomery, uint64_t *out_h, uint64_t *out_handle, size_t *out_len) {
+    int logn = 0; while (((size_t)1 << logn) < r.num_constraints + r.num_inputs) logn++;
+    if (logn < 1) logn = 1;
+    if (logn > 28) return DGPU_E_BADARG;
+    const size_t D = (size_t)1 << logn;
+    if (m > (~(size_t)0 >> 6) / D) return DGPU_E_BADARG;                     // m * D * 32 bytes must be addressable
+    int32_t rc;
+    hipStream_t s = sl.stream;
+    void *kept = nullptr;
+    if (out_handle && !(kept = scalar_alloc(scalar_bytes(m * D)))) return DGPU_E_OOM;
+    struct Giveback { void *&p; size_t bytes; hipStream_t st; ~Giveback() { if (p) { (void)hipStreamSynchronize(st); scalar_release(cur_index(), p, bytes); } } } giveback{kept, scalar_bytes(m * D), s};   // on any early return
+    const bool h_mont = (montgomery & DGPU_WM_H_MONTGOMERY) != 0;
+    if (logn > ntt::WM_BLOCK_MAX_LOG) {
+        for (size_t j = 0; j < m; j++)
+            if ((rc = witness_map_device(sl, r, assignments + 4 * row_stride * j, montgomery, out_h ? out_h + 4 * D * j : nullptr, nullptr, nullptr, nullptr, kept ? (uint32_t *)kept + 8 * D * j : nullptr))) return rc;
+    } else {
+        NttDomain dom;
+        if ((rc = get_domain(sl, logn, dom))) return rc;
+        const size_t chunk = std::min(wm_chunk_rows(D, r.num_vars), m);
+        uint32_t rpb = (uint32_t)gs.wm_many_rpb.load();
+        if (!rpb) rpb = ntt::wm_rows_per_block(logn);
+        rpb = std::min(rpb, ntt::wm_max_rows_per_block(logn));
+        Buf &zw = sl.q[12], &hw = sl.entries;
+        if ((rc = zw.ensure(chunk * r.num_vars * 32))) return rc;
+        const bool via_hw = !kept || (out_h && h_mont);                      // the chunk's host copy leaves from scratch (as Fr limbs if asked for); a resident vector stays canonical
+        if (via_hw && (rc = hw.ensure(chunk * D * 32))) return rc;
+        ntt::WmCircuit c;
+        for (int k = 0; k < 3; k++) { c.rowptr[k] = r.m[k].rowptr; c.cols[k] = r.m[k].cols; c.vals[k] = r.m[k].vals; c.nnz[k] = r.m[k].nnz; }
+        c.rows = r.num_constraints; c.extra = r.num_inputs;
+        const ntt::WmTables tb{(const uint32_t *)dom.tw_f, (const uint32_t *)dom.tw_i, (const uint32_t *)dom.pwr_f, (const uint32_t *)dom.pwr_i, (const uint32_t *)dom.zinv};
+        for (size_t j0 = 0; j0 < m; j0 += chunk) {
+            const size_t rows = std::min(chunk, m - j0);
+            {
+                StageTimer st(sl, "qapm.upload");     // one copy per chunk; the words between two rows of the caller's block are not touched
+                HIPCHK(hipMemcpy2DAsync(zw.p, r.num_vars * 32, assignments + 4 * row_stride * j0, row_stride * 32, r.num_vars * 32, rows, hipMemcpyHostToDevice, s));
+            }
+            uint32_t *const dst = kept ? (uint32_t *)kept + 8 * D * j0 : hw.as<uint32_t>();
+            {
+                StageTimer st(sl, "qapm.map");
+                ntt::launch_wm_block(s, c, tb, ntt::WmJob{zw.as<uint32_t>(), r.num_vars * 8, montgomery & 1, (uint32_t)rows, dst, (!kept && h_mont) ? 1 : 0, logn, rpb});
+                if (kept && out_h && h_mont) {
+                    HIPCHK(hipMemcpyAsync(hw.p, dst, rows * D * 32, hipMemcpyDeviceToDevice, s));
+                    ntt::launch_fr_canonical_to_mont(s, hw.as<uint32_t>(), rows * D);
+                }
+            }
+            HIPCHK(hipGetLastError());
+            if (out_h) HIPCHK(hipMemcpyAsync(out_h + 4 * D * j0, (kept && !h_mont) ? (const void *)dst : (const void *)hw.p, rows * D * 32, hipMemcpyDeviceToHost, s));
+        }
+        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return DGPU_E_HIP; }
+        if (gs.prof) prof_flush(sl);
+    }
+    if (out_len) *out_len = D;
+    if (out_handle) { *out_handle = register_handle(kept, m * D, 3); kept = nullptr; }     // registered last: no handle is left behind by a failing call
     return DGPU_OK;
 }
 
@@ -206,6 +274,19 @@ int32_t dgpu_witness_map_r1cs(uint64_t r1cs, const uint64_t *assignment, size_t 
     SLOT_ACQUIRE(slot_lock, sl);
     HIPCHK(hipSetDevice(cur().device));
     return witness_map_device(sl, *r, assignment, montgomery, out_h, out_handle, out_len);
+}
+int32_t dgpu_witness_map_r1cs_many(uint64_t r1cs, const uint64_t *assignments, size_t row_stride, size_t num_vars, size_t m, int32_t montgomery, uint64_t *out_h, uint64_t *out_handle, size_t *out_len) {
+    if (m == 0) return DGPU_OK;
+    if (!assignments || (!out_h && !out_handle) || row_stride < num_vars) return DGPU_E_BADARG;
+    HandleRef href(r1cs);                                      // (the handle table needs no device: a bad handle is refused before one is looked at)
+    if (!href.ok || href.h.kind != 4) return DGPU_E_BADARG;
+    const DevR1cs *r = (const DevR1cs *)href.h.p;
+    if (num_vars != r->num_vars) return DGPU_E_BADARG;
+    CtxScope on_owner(href.h.ctx);
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    SLOT_ACQUIRE(slot_lock, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    return witness_map_many_device(sl, *r, assignments, row_stride, m, montgomery, out_h, out_handle, out_len);
 }
 // the assignment already resident (dgpu_scalars_upload: canonical after the upload): one upload of z serves the witness map and, at
 // scalar offset 1, the prover's `assignment` = z[1..] (prover.rs:319-321)

@@ -13,20 +13,12 @@
 // the buffer addressing of the main kernel), k_ntt_r4 (everything else).
 #pragma once
 #include <hip/hip_runtime.h>
-#include "fr29.hip.h"
+#include "ntt_lanes.hip.h"
 
 namespace ntt {
 using namespace fr29;
 
-__device__ __forceinline__ void ld(Fr &r, const uint32_t *__restrict__ buf, size_t D, size_t i) {
-#pragma unroll
-    for (int l = 0; l < NL; l++) r.l[l] = buf[(size_t)l * D + i];
-}
-__device__ __forceinline__ void st(uint32_t *__restrict__ buf, size_t D, size_t i, const Fr &a) {
-#pragma unroll
-    for (int l = 0; l < NL; l++) buf[(size_t)l * D + i] = a.l[l];
-}
-__device__ __forceinline__ uint32_t bitrev(uint32_t x, int logn) { return __brev(x) >> (32 - logn); }
+// (ld / st / bitrev, tw_stage_offset, ld_words and the lane bodies: ntt_lanes.hip.h)
 
 // words (8 x u32 per element, canonical or Montgomery) -> internal SoA; elements [n, D) are zeroed
 __global__ void __launch_bounds__(256) k_fr_load(const uint32_t *__restrict__ words, size_t n, int mont, uint32_t *__restrict__ out, size_t D) {
@@ -70,11 +62,7 @@ __global__ void __launch_bounds__(256) k_fr_powers(const uint32_t *__restrict__ 
     for (size_t e = k; e; e >>= 1) { if (e & 1) fr_mul(acc, acc, b); fr_mul(b, b, b); }
     st(out, count, k, acc);
 }
-// Per-stage twiddle tables.  A stage whose twiddle exponents are j << sigma reads T_sigma[j] = w^(j << sigma), H >> sigma entries stored
-// contiguously (limb-major, stride H >> sigma) behind the full table T_0: consecutive butterflies read consecutive words.  Indexing T_0
-// with the stride 2^sigma made every lane of a wave touch its own cache line (0.6 of the 2.4 ms of the seven transforms at D = 2^20).
-// Word offset of T_sigma inside the buffer: NL * (2H - 2 (H >> sigma)); the whole buffer holds < 2H elements.
-__host__ __device__ inline size_t tw_stage_offset(size_t H, int sigma) { return (size_t)NL * (2 * H - 2 * (H >> sigma)); }
+// Per-stage twiddle tables (layout: tw_stage_offset, ntt_lanes.hip.h), built behind the full table T_0
 __global__ void __launch_bounds__(256) k_tw_compact(uint32_t *__restrict__ tw, size_t H, int logh) {
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // t in [0, H - 1): position inside T_1 .. T_logh
     if (t + 1 >= H) return;
@@ -90,27 +78,11 @@ __global__ void __launch_bounds__(256) k_tw_compact(uint32_t *__restrict__ tw, s
 // z is gathered from the caller's scalar words (8 x u32 = 32 contiguous bytes per variable: one cache line per gather) and converted on
 // the fly; gathering from a limb-major copy touched ten cache lines per variable and made this kernel 3x slower than the transforms'
 // share of the witness map warranted.
-__device__ __forceinline__ void ld_words(Fr &r, const uint32_t *__restrict__ words, size_t i, bool mont) {
-    uint32_t w[8];
-    const uint4 *p = reinterpret_cast<const uint4 *>(words + i * 8);
-    uint4 a = p[0], b = p[1];
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-    fr_from_words(r, w, mont);
-}
 __global__ void __launch_bounds__(256) k_csr_eval(const uint64_t *__restrict__ rowptr, const uint32_t *__restrict__ cols, const uint32_t *__restrict__ vals_soa, size_t nnz,
                                                   const uint32_t *__restrict__ z_words, int z_mont, size_t nvars, size_t rows, size_t extra, uint32_t *__restrict__ out, size_t D) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= D) return;
-    Fr acc; fr_zero(acc);
-    if (i < rows) {
-        for (uint64_t k = rowptr[i]; k < rowptr[i + 1]; k++) {
-            Fr c, zz, t; ld(c, vals_soa, nnz, k); ld_words(zz, z_words, cols[k], z_mont != 0);
-            fr_mul(t, zz, c); fr_add(acc, acc, t); fr_norm(acc, acc);
-        }
-        // a long row leaves a sum of (row length) products of < 2 r each: one product with the Montgomery one brings it back under 2 r, so
-        // that what the inverse transform accumulates is bounded by the domain size alone (fr_sub's M = 2^34 case)
-        if (rowptr[i + 1] - rowptr[i] > 8) { Fr one; fr_one(one); fr_mul(acc, acc, one); }
-    } else if (i < rows + extra) ld_words(acc, z_words, i - rows, z_mont != 0);
+    Fr acc; csr_row(acc, rowptr, cols, vals_soa, nnz, z_words, z_mont != 0, rows, extra, i);
     (void)nvars;
     st(out, D, i, acc);
 }
@@ -224,7 +196,6 @@ struct NttBatch { uint32_t *buf[3]; };
 // element offset in a VGPR shared by the ten rows — no per-limb 64-bit address arithmetic on the vector ALU (hipcc otherwise re-associates
 // base + l * stride + i into ten v_lshl_add_u64 and ten address register pairs).  Offsets are 32-bit: arrays of up to 4 GB (logn <= 26).
 constexpr int PIPE_MAX_LOGN = 26;
-constexpr int PIPE_TILE_LOG = 10;      // 1024 elements = 40 KB of LDS, 256 lanes (one radix-4 unit each), four blocks per CU
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_of(const uint32_t *base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(base), 0, 0xffffffff, 0x00020000);
 }
@@ -237,18 +208,6 @@ __device__ __forceinline__ void stg(__amdgpu_buffer_rsrc_t rows, uint32_t stride
     const uint32_t off = i << 2;
 #pragma unroll
     for (int l = 0; l < NL; l++) __builtin_amdgcn_raw_buffer_store_b32(a.l[l], rows, off, l * stride_bytes, 0);
-}
-template <bool DIF> __device__ __forceinline__ void butterfly(Fr &x, Fr &y, const Fr &w) {
-    Fr u, v;
-    if (DIF) {
-        fr_add(u, x, y); fr_norm(u, u);
-        fr_sub<FR_BIG>(v, x, y); fr_norm(v, v); fr_mul(v, v, w);     // y: an unreduced partial sum (up to 2^32 r)
-    } else {
-        Fr yw; fr_mul(yw, y, w);
-        fr_add(u, x, yw); fr_norm(u, u);
-        fr_sub(v, x, yw); fr_norm(v, v);
-    }
-    x = u; y = v;
 }
 // Barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory counter (s_waitcnt vmcnt(0)): here that would make
 // every stage wait for the prefetched operands of the next tile, for the twiddle requested one butterfly ahead and — at the end of a tile —
@@ -333,7 +292,7 @@ k_ntt_r4(NttBatch B, int logn, int s0, int S, const uint32_t *__restrict__ tw, c
             uint32_t mid, c_; elem(e, mid, c_);
             const uint32_t a = gaddr(mid, c_);
             Fr x, y, z, t; ldg(x, rows, Db, a); ldg(y, rb, Db, a); ldg(z, rc, Db, a);
-            fr_mul(t, x, y); fr_sub<FR_BIG>(t, t, z); fr_norm(t, t); fr_mul(t, t, zi);      // z is an un-reduced transform output
+            pointwise_lane(t, x, y, z, zi);
             const uint32_t p = slot(mid, c_);
 #pragma unroll
             for (int l = 0; l < NL; l++) lds[l * TILE + p] = t.l[l];
@@ -363,7 +322,7 @@ k_ntt_r4(NttBatch B, int logn, int s0, int S, const uint32_t *__restrict__ tw, c
     if (S < 2) { q = 0; c_ = 0; } else if (flat) { q = threadIdx.x & ((1u << (S - 2)) - 1); c_ = threadIdx.x >> (S - 2); } else { c_ = threadIdx.x & ((1u << cols_log) - 1); q = threadIdx.x >> cols_log; }
     for (; st + 1 < S; st += 2) {
         const bool from_global = (st == 0) && !staged_in, to_global = (st + 2 == S) && !staged_out;
-        Fr x00, x01, x10, x11, t;
+        Fr x00, x01, x10, x11;
         if (DIF) {
             const int pos = S - 2 - st;                    // bit position of hb
             const uint32_t hb = 1u << pos, ha = hb << 1;
@@ -372,12 +331,7 @@ k_ntt_r4(NttBatch B, int logn, int s0, int S, const uint32_t *__restrict__ tw, c
             twiddle(wa0, st, c_, jm); twiddle(wa1, st, c_, jm + hb); twiddle(wb, st + 1, c_, jm);
             load(x00, from_global, m00, c_); load(x10, from_global, m00 + ha, c_);
             load(x01, from_global, m00 + hb, c_); load(x11, from_global, m00 + ha + hb, c_);
-            // A
-            fr_sub<FR_BIG>(t, x00, x10); fr_add(x00, x00, x10); fr_norm(t, t); fr_mul(x10, t, wa0);
-            fr_sub<FR_BIG>(t, x01, x11); fr_add(x01, x01, x11); fr_norm(t, t); fr_mul(x11, t, wa1);
-            // B (x00, x01 carry limbs < 2^30 + 16: dominated by the subtraction constant, and their sum fits a word)
-            fr_sub<FR_BIG>(t, x00, x01); fr_add(x00, x00, x01); fr_norm(x00, x00); fr_norm(t, t); fr_mul(x01, t, wb);
-            fr_sub<FR_BIG>(t, x10, x11); fr_add(x10, x10, x11); fr_norm(x10, x10); fr_norm(t, t); fr_mul(x11, t, wb);
+            r4_dif(x00, x01, x10, x11, wa0, wa1, wb);
             store(to_global, m00, c_, x00); store(to_global, m00 + hb, c_, x01);
             store(to_global, m00 + ha, c_, x10); store(to_global, m00 + ha + hb, c_, x11);
         } else {
@@ -387,12 +341,7 @@ k_ntt_r4(NttBatch B, int logn, int s0, int S, const uint32_t *__restrict__ tw, c
             twiddle(wa, st, c_, jm); twiddle(wb0, st + 1, c_, jm); twiddle(wb1, st + 1, c_, jm + ha);
             load(x00, from_global, m00, c_); load(x01, from_global, m00 + ha, c_);
             load(x10, from_global, m00 + hb, c_); load(x11, from_global, m00 + ha + hb, c_);
-            // A: no carry pass; sums < 2^30 + 16, differences < 2^31 per limb
-            fr_mul(t, x01, wa); fr_sub<512, 30>(x01, x00, t); fr_add(x00, x00, t);
-            fr_mul(t, x11, wa); fr_sub<512, 30>(x11, x10, t); fr_add(x10, x10, t);
-            // B
-            fr_mul(t, x10, wb0); fr_sub<512, 30>(x10, x00, t); fr_add(x00, x00, t); fr_norm(x00, x00); fr_norm(x10, x10);
-            fr_mul(t, x11, wb1); fr_sub<512, 30>(x11, x01, t); fr_add(x01, x01, t); fr_norm(x01, x01); fr_norm(x11, x11);
+            r4_dit(x00, x01, x10, x11, wa, wb0, wb1);
             store(to_global, m00, c_, x00); store(to_global, m00 + ha, c_, x01);
             store(to_global, m00 + hb, c_, x10); store(to_global, m00 + ha + hb, c_, x11);
         }
@@ -444,7 +393,7 @@ __global__ void __launch_bounds__(256) k_pointwise(uint32_t *__restrict__ a, con
     if (i >= D) return;
     uint32_t zw[8]; for (int k = 0; k < 8; k++) zw[k] = zinv_words[k];
     Fr x, y, z, zi, t; ld(x, a, D, i); ld(y, b, D, i); ld(z, c, D, i); fr_from_words(zi, zw, false);
-    fr_mul(t, x, y); fr_sub<FR_BIG>(t, t, z); fr_norm(t, t); fr_mul(t, t, zi);   // z is an un-reduced transform output
+    pointwise_lane(t, x, y, z, zi);
     st(a, D, i, t);
 }
 

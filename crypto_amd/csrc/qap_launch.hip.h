@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "wm_block_args.hip.h"
 namespace ntt {
 constexpr int FR_WORDS = 10;   // u32 per internal Fr element
 void launch_fr_mont_to_canonical(hipStream_t s, uint32_t *words, size_t n);
@@ -19,4 +20,7 @@ void launch_ntt_final(hipStream_t s, uint32_t *a, uint32_t *b, uint32_t *c, int 
 void launch_coset_scale(hipStream_t s, uint32_t *buf, int logn, const uint32_t *pw, uint32_t *out_words, int pw_in_data_order = 0);
 void launch_bitrev_table(hipStream_t s, const uint32_t *src, uint32_t *dst, int logn);
 void launch_pointwise(hipStream_t s, uint32_t *a, const uint32_t *b, const uint32_t *c, size_t D, const uint32_t *zinv_words);
+// the whole witness map of j.nrows statements of one small circuit (j.logn <= WM_BLOCK_MAX_LOG, j.rows_per_block << j.logn <= 2^WM_BLOCK_MAX_LOG): ONE launch
+// of k_wm_block (k_wm_many.hip), ceil(nrows / rows_per_block) blocks
+void launch_wm_block(hipStream_t s, const WmCircuit &c, const WmTables &tb, const WmJob &j);
 }  // namespace ntt

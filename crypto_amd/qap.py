@@ -57,6 +57,36 @@ def witness_map(A, B, Cm, assignment, num_inputs, num_constraints, montgomery=Fa
     return out, ds
 
 
+def witness_map_many(circuit, assignments, montgomery=False, h_montgomery=False, to_host=True, resident=False):
+    """The witness maps of ONE resident circuit over MANY assignments in one call (dgpu_witness_map_r1cs_many).  circuit: a DeviceR1cs; assignments:
+    (m, num_vars, 4) scalars, or a view with a larger row stride (assignments[:, :num_vars] of a wider block: the words in between are never read).
+    Returns (h (m, D, 4) or None, DeviceScalars of m * D canonical scalars or None: row j at scalar offset j * D)."""
+    _ensure()
+    z = np.asarray(assignments, dtype=np.uint64)
+    if z.ndim != 3 or z.shape[1] != circuit.num_vars or z.shape[2] != 4:
+        raise ValueError("assignments must be (m, num_vars, 4)")
+    m = z.shape[0]
+    if not (m <= 1 or (z.strides[2] == 8 and z.strides[1] == 32 and z.strides[0] >= 32 * circuit.num_vars and z.strides[0] % 32 == 0)):
+        z = np.ascontiguousarray(z)
+    stride = z.strides[0] // 32 if m > 1 else circuit.num_vars
+    if m <= 1:
+        z = np.ascontiguousarray(z)
+    D = 2
+    while D < circuit.num_constraints + circuit.num_inputs:
+        D *= 2
+    out = np.zeros((m, D, 4), dtype=np.uint64) if to_host else None
+    handle = C.c_uint64(0); olen = C.c_size_t(D)
+    rc = lib().dgpu_witness_map_r1cs_many(circuit.handle, z.ctypes.data_as(C.c_void_p) if m else None, stride, circuit.num_vars, m, int(bool(montgomery)) | (2 if h_montgomery else 0),
+                                          None if out is None or not m else out.ctypes.data_as(C.c_void_p), C.byref(handle) if resident else None, C.byref(olen))
+    if rc:
+        raise DockGpuError(rc, "dgpu_witness_map_r1cs_many")
+    ds = None
+    if resident and m:
+        ds = DeviceScalars.__new__(DeviceScalars)
+        ds.n, ds.handle = m * olen.value, handle.value
+    return out, ds
+
+
 class DeviceR1cs:
     """The circuit's three constraint matrices resident in HBM (dgpu_r1cs_upload): fixed per circuit, reused by every proof."""
 

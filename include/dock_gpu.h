@@ -463,6 +463,25 @@ int32_t dgpu_witness_map_r1cs(uint64_t r1cs, const uint64_t *assignment, size_t 
 /* the same with the assignment z already resident (a dgpu_scalars_upload handle of num_vars scalars on the circuit's device): ONE upload of z
  * per proof then serves the witness map and — at scalar offset 1 — the prover's `assignment` = z[1..] of the a / b_g1 / b_g2 / l MSMs */
 int32_t dgpu_witness_map_r1cs_resident(uint64_t r1cs, uint64_t assignment, uint64_t *out_h, uint64_t *out_handle, size_t *out_len);
+/* MANY witness maps of ONE resident circuit in one call: row j is the num_vars scalars at assignments + 4 * row_stride * j (row_stride >= num_vars scalars
+ * between rows, the convention of dgpu_msm_g1_handle_many; what lies between two rows is never read) and out_h + 4 * D * j receives, word for word, what
+ * dgpu_witness_map_r1cs(r1cs, row j, num_vars, montgomery, out_h_j, NULL, ..) writes, with montgomery & 1 and with montgomery & DGPU_WM_H_MONTGOMERY alike.
+ * *out_len = D, the length PER ROW.  out_handle receives ONE resident scalar vector of m * D canonical scalars, row j at scalar offset j * D (what
+ * dgpu_msm_g1_handle / dgpu_scalars_copy_range address by offset); it is registered last, so a failing call leaves no handle and no allocation behind.  The
+ * reference proves its small circuits statement by statement (proof_system/src/sub_protocols/bound_check_legogroth16.rs, r1cs_legogorth16.rs: bound checks,
+ * MiMC, the circom vectors); a service proving the same circuit over thousands of assignments has its witness maps here.
+ * Refusals, decided before the device is looked at: m = 0 is DGPU_OK without touching a device or the pointers; NULL assignments, both outputs NULL,
+ * row_stride < num_vars, num_vars disagreeing with the circuit's shape, m * D beyond the address space, a bad handle: DGPU_E_BADARG.  There is no
+ * DGPU_E_TOO_SMALL: the caller has uploaded a circuit and wants it used.
+ * Paths: a circuit whose domain is at most 2^10 takes the block kernel (crypto_amd/csrc/wm_block_kernels.hip.h: a statement's a, b, c stay in one
+ * block's LDS from the sparse rows to the h scalars; domains of up to 128 elements share blocks): per chunk of rows ONE upload of the chunk's assignments, ONE
+ * launch (two more, a copy and a conversion, when Fr-limb host output and a resident vector are asked for together) and ONE download, whatever the number of rows.
+ * Larger domains run row by row through the single call's driver inside the call: correct, not faster than the caller's own loop.
+ * Memory: the call owns one slot; rows go in chunks of at most 4096 rows, 2^17 domain elements (rows * D) and 2^21 assignment scalars (rows * num_vars), so
+ * the slot's grow-only workspace stays bounded whatever m, and a second call of a shape already seen allocates nothing (the resident vector, when asked
+ * for, is the caller's).  Thread-safe like every entry point: several calls may be in flight. */
+int32_t dgpu_witness_map_r1cs_many(uint64_t r1cs, const uint64_t *assignments, size_t row_stride, size_t num_vars, size_t m, int32_t montgomery,
+                                   uint64_t *out_h /* m * D * 4, or NULL */, uint64_t *out_handle /* or NULL */, size_t *out_len);
 
 /* ---- LegoGroth16 key generation from a resident circuit ----
  * dgpu_qap_instance_map replaces LibsnarkReduction::instance_map_with_evaluation (legogroth16/src/r1cs_to_qap.rs:105-147) on a dgpu_r1cs_upload circuit:

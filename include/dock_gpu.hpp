@@ -493,6 +493,21 @@ struct R1CSFile {
 
 // ---- legogroth16::create_proof_with_reduction (legogroth16/src/prover.rs:153-180 -> :267-383) over dgpu_legogroth16_prove ----
 namespace legogroth16 {
+// QAP::witness_map of ONE resident circuit (a circom::R1csFile::upload / dgpu_r1cs_upload handle) over MANY assignments in one call
+// (dgpu_witness_map_r1cs_many): rows = m assignments of num_vars canonical scalars each, one after another; returns the m * D canonical coefficients
+// of h, row j at [j * D, (j + 1) * D), and D through `domain` if asked for
+inline std::vector<BigInt256> witness_map_many(uint64_t r1cs, const std::vector<BigInt256> &rows, size_t num_vars, size_t *domain = nullptr) {
+    if (num_vars == 0 || rows.size() % num_vars) throw Error(DGPU_E_BADARG, "witness_map_many: rows is not a whole number of assignments");
+    const size_t m = rows.size() / num_vars;
+    size_t nv = 0, ni = 0, nc = 0, D = 2;
+    check(dgpu_r1cs_shape(r1cs, &nv, &ni, &nc), "r1cs_shape");
+    while (D < nc + ni) D <<= 1;
+    std::vector<BigInt256> h(m * D);
+    size_t len = D;
+    check(dgpu_witness_map_r1cs_many(r1cs, m ? rows[0].data() : nullptr, num_vars, num_vars, m, 0, m ? h[0].data() : nullptr, nullptr, &len), "witness_map_r1cs_many");
+    if (domain) *domain = D;
+    return h;
+}
 // ProvingKey (legogroth16/src/data_structures.rs:55-70,151-168): the five queries live on the device, the O(1) elements on the host
 struct ProvingKey {
     DeviceBases<G1> a_query, b_g1_query, h_query, l_query; DeviceBases<G2> b_g2_query;

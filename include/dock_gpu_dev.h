@@ -29,6 +29,10 @@ int32_t dgpu_set_msm_segments(int32_t fold, int32_t chunk_terms);
  * (1..65536; the power table takes 5.4 KB per element).  0 = automatic: by the launch's group count, n / 2048 clamped to 1..8 (provisional until
  * tests/perf/gt_pow_timing.py's sweep has run), 16384.  Any setting gives the same bytes. */
 int32_t dgpu_set_gt_pow(int32_t groups_per_wave, int32_t bases_per_group, int32_t chunk_elems);
+/* dgpu_witness_map_r1cs_many: rows per chunk (1..4096; 0 = automatic: at most 4096 rows, 2^17 domain elements, 2^21 assignment scalars) and statements per
+ * block of the block kernel (1..512, clamped to 2^10 / D, the most a block's LDS holds; 0 = automatic: 256 / D for D <= 128, else 1; both provisional until
+ * tests/perf/witness_map_many_timing.py has run).  Any setting gives the same bytes (tests cross chunk and block boundaries at small m). */
+int32_t dgpu_set_wm_many(int32_t chunk_rows, int32_t rows_per_block);
 /* log2 of the buckets one lane of the bucket reduction sums serially on the table pipeline (0..6; -1 = automatic: 3 for a 2^19-bucket table when the
  * call runs alone, 4 when three or more calls are in flight on the device context).  Any value gives the same point. */
 int32_t dgpu_set_reduce_shift(int32_t log2_buckets_per_lane);

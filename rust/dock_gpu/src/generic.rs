@@ -244,6 +244,14 @@ pub fn witness_map_from_matrices<F: PrimeField>(a: &[Vec<(F, usize)>], b: &[Vec<
                                                                     cast_slice::<Vec<(F, usize)>, Vec<(Fr, usize)>>(c), num_inputs, num_constraints, cast_slice::<F, Fr>(full_assignment)) }?;
     Some(unsafe { cast_val::<Vec<Fr>, Vec<F>>(h) })
 }
+/// the same over MANY assignments of one circuit (m rows of `num_vars` scalars back to back -> m * D coefficients, row by row), or None (another field, the
+/// library declined) — the caller then maps its statements one by one
+pub fn witness_map_many<F: PrimeField>(a: &[Vec<(F, usize)>], b: &[Vec<(F, usize)>], c: &[Vec<(F, usize)>], num_vars: usize, num_inputs: usize, num_constraints: usize, assignments: &[F]) -> Option<Vec<F>> {
+    if !same::<F, Fr>() { return None; }
+    let h: Vec<Fr> = unsafe { crate::host::witness_map_many(cast_slice::<Vec<(F, usize)>, Vec<(Fr, usize)>>(a), cast_slice::<Vec<(F, usize)>, Vec<(Fr, usize)>>(b),
+                                                            cast_slice::<Vec<(F, usize)>, Vec<(Fr, usize)>>(c), num_vars, num_inputs, num_constraints, cast_slice::<F, Fr>(assignments)) }?;
+    Some(unsafe { cast_val::<Vec<Fr>, Vec<F>>(h) })
+}
 
 // ---- fixed-base batch multiplication: utils/src/msm.rs:8-62 ---------------------------------------------------------------------------------------
 /// `FixedBase::msm(.., &table, elements)` as `WindowTable::multiply_many` and `multiply_field_elems_with_same_group_elem` use it: `base` times every

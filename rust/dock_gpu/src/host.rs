@@ -260,6 +260,20 @@ impl R1cs {
         if rc != DGPU_OK || len != d { return None; }
         Some(h)
     }
+    /// the same for MANY assignments in one call (dgpu_witness_map_r1cs_many): `assignments` holds m rows of num_vars scalars back to back; returns the
+    /// m * D coefficients, row j at [j * D, (j + 1) * D).  Circuits of up to 2^10 domain elements run a whole statement per block on the device.
+    pub fn witness_map_many(&self, assignments: &[Fr]) -> Option<Vec<Fr>> {
+        if self.num_vars == 0 || assignments.len() % self.num_vars != 0 { return None; }
+        let m = assignments.len() / self.num_vars;
+        let d = (self.num_constraints + self.num_inputs).next_power_of_two().max(2);
+        let mut h = ark_std::vec![Fr::from(0u64); m * d];
+        if m == 0 { return Some(h); }
+        let mut len = 0usize;
+        let rc = unsafe { dgpu_witness_map_r1cs_many(self.handle, assignments.as_ptr() as *const u64, self.num_vars, self.num_vars, m, 1 | DGPU_WM_H_MONTGOMERY,
+                                                     h.as_mut_ptr() as *mut u64, core::ptr::null_mut(), &mut len) };
+        if rc != DGPU_OK || len != d { return None; }
+        Some(h)
+    }
     /// `instance_map_with_evaluation(cs, t)` (r1cs_to_qap.rs:105-147) on the resident circuit: (a, b, c, Z(t), domain size), the three vectors of
     /// num_vars entries each as `Vec<Fr>`; None for a t inside the domain
     pub fn instance_map(&self, t: Fr) -> Option<(Vec<Fr>, Vec<Fr>, Vec<Fr>, Fr, usize)> {
@@ -301,6 +315,12 @@ pub fn resident_circuit(a: &[Vec<(Fr, usize)>], b: &[Vec<(Fr, usize)>], c: &[Vec
 pub fn witness_map_from_matrices(a: &[Vec<(Fr, usize)>], b: &[Vec<(Fr, usize)>], c: &[Vec<(Fr, usize)>], num_inputs: usize, num_constraints: usize, full_assignment: &[Fr]) -> Option<Vec<Fr>> {
     if num_constraints < (1 << 12) { return None; }              // small circuits: the CPU map is microseconds-to-milliseconds, a device round trip is not
     resident_circuit(a, b, c, full_assignment.len(), num_inputs, num_constraints)?.witness_map(full_assignment)
+}
+/// `witness_map_from_matrices` over many assignments of one circuit (a service proving the same statement shape again and again:
+/// proof_system/src/sub_protocols/bound_check_legogroth16.rs, r1cs_legogorth16.rs): the circuit is resident by content hash, the rows run in one call.
+/// No size threshold: the caller has a batch.  `assignments`: m rows of `num_vars` scalars back to back.
+pub fn witness_map_many(a: &[Vec<(Fr, usize)>], b: &[Vec<(Fr, usize)>], c: &[Vec<(Fr, usize)>], num_vars: usize, num_inputs: usize, num_constraints: usize, assignments: &[Fr]) -> Option<Vec<Fr>> {
+    resident_circuit(a, b, c, num_vars, num_inputs, num_constraints)?.witness_map_many(assignments)
 }
 
 // ---- the LegoGroth16 prover for a key held the way the reference holds it ---------------------------------------------------------------------------------

@@ -390,6 +390,23 @@ fn cpu_proof(k: &SyntheticKey, h: &[Fr], inst: &[Fr], wit: &[Fr], r: Fr, s: Fr, 
 }
 
 #[test]
+fn witness_map_many_rows_of_a_small_circuit() {
+    setup();
+    // D = 512: a whole statement per block on the device; five assignments of the same circuit, each row against the CPU map
+    let m = (1usize << 9) - 2;
+    let (a, b, c, z, num_inputs) = square_chain(m);
+    let want_h = cpu_witness_map(&a, &b, &c, num_inputs, m, &z);
+    let rows: Vec<Fr> = (0..5).flat_map(|_| z.iter().copied()).collect();
+    let circuit = R1cs::upload(&a, &b, &c, z.len(), num_inputs, m).expect("resident circuit");
+    let got = circuit.witness_map_many(&rows).expect("witness_map_many");
+    assert_eq!(got.len(), 5 * want_h.len());
+    for row in got.chunks(want_h.len()) { assert_eq!(row, &want_h[..]); }
+    assert_eq!(host::witness_map_many(&a, &b, &c, z.len(), num_inputs, m, &rows).unwrap(), got);
+    assert_eq!(dock_gpu::generic::witness_map_many::<Fr>(&a, &b, &c, z.len(), num_inputs, m, &rows).unwrap(), got);
+    assert_eq!(circuit.witness_map_many(&[]).unwrap().len(), 0);
+}
+
+#[test]
 fn witness_map_and_the_prover_for_a_host_held_key() {
     setup();
     cache::clear(); assert!(cache::set_min_n(1 << 10));
