@@ -114,7 +114,7 @@ struct Shared {
     std::atomic<int> window_bits{0};
     std::atomic<size_t> small_max{8192};      // dgpu_set_small_msm_max: MSMs of up to this many terms on plain bases take the two-launch tree path (small_kernels.hip.h); 0 = never
     std::atomic<int> chunk{0};
-    std::atomic<int> many_chunk{0};           // dgpu_set_many_chunk_rows: rows per launch of the many-row small MSM (0 = automatic from n, msm_driver.hip.h many_chunk_rows)
+    std::atomic<int> many_chunk{0};           // dgpu_set_many_chunk_rows: rows per launch of the many-row small MSM (0 = automatic from n, msm_many.hip.h many_chunk_rows)
     std::atomic<int> seg_chunk{0}, seg_fold{0};   // dgpu_set_msm_segments: terms per chunk of the segmented small MSM (0 = automatic) and its fold (0 = by segment count, 1 = host threads, 2 = device)
     std::atomic<int> gt_pow_g{0}, gt_pow_k{0}, gt_pow_chunk{0};   // dgpu_set_gt_pow: groups per wave, bases per group and elements per chunk of the GT power kernels (dock_gt_dev.hip; 0 = automatic)
     std::atomic<int> wm_many_chunk{0}, wm_many_rpb{0};   // dgpu_set_wm_many: rows per chunk and statements per block of dgpu_witness_map_r1cs_many (dock_qap.hip; 0 = automatic)

@@ -1,5 +1,8 @@
 // crypto_amd/csrc/dock_g2.hip — BLS12-381 G2 entry points of include/dock_gpu.h.
 #include "msm_driver.hip.h"
+#include "msm_many.hip.h"
+#include "msm_cache.hip.h"
+#include "msm_sharded.hip.h"
 using namespace dock;
 
 namespace dock {

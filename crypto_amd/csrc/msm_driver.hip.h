@@ -1,11 +1,11 @@
-// crypto_amd/csrc/msm_driver.hip.h — host driver of the MSM pipeline (templated on the curve), included by
-// dock_g1.hip and dock_g2.hip so the two curves compile in parallel.
+// crypto_amd/csrc/msm_driver.hip.h — host driver of the MSM pipelines (templated on the curve): geometry, workspaces, the small, plain and table
+// pipelines, staging, uploads and the single-call entry points.  dock_g1.hip and dock_g2.hip include it (the two curves compile in parallel) together
+// with msm_many.hip.h, msm_cache.hip.h and msm_sharded.hip.h; the host-side folds are msm_host_fold.hpp.
 #pragma once
 #include <chrono>
-#include <thread>
 #include "dock_ctx.hpp"
 #include "bases_cache.hpp"
-#include "host_field.hpp"
+#include "msm_host_fold.hpp"
 #include "msm_launch.hip.h"
 #include "sort_launch.hip.h"
 #include "qap_launch.hip.h"
@@ -13,91 +13,42 @@
 namespace dock {
 using namespace msm;
 
-// host tail: Horner over window sums (ABI XYZZ form), normalised Jacobian out
-template <class HF>
-void host_fold(const uint64_t *win_abi, const uint8_t *win_inf, int W, int c, uint64_t *out_xyz) {
-    typedef hostf::HXyzz<HF> PT;
-    PT acc = PT::identity();
-    const size_t FWORDS = sizeof(HF) / 8;
-    for (int w = W - 1; w >= 0; w--) {
-        if (!acc.inf) for (int k = 0; k < c; k++) acc.dbl_in_place();
-        if (!win_inf[w]) {
-            PT t; t.inf = false;
-            const uint64_t *src = win_abi + (size_t)w * 4 * FWORDS;
-            memcpy(&t.x, src, sizeof(HF)); memcpy(&t.y, src + FWORDS, sizeof(HF)); memcpy(&t.zz, src + 2 * FWORDS, sizeof(HF)); memcpy(&t.zzz, src + 3 * FWORDS, sizeof(HF));
-            acc.add_in_place(t);
-        }
-    }
-    HF X, Y, Z; acc.to_normalised_jacobian(X, Y, Z);
-    memcpy(out_xyz, &X, sizeof(HF)); memcpy(out_xyz + FWORDS, &Y, sizeof(HF)); memcpy(out_xyz + 2 * FWORDS, &Z, sizeof(HF));
+// ---- chunk geometry + workspace of the accumulate stage (both pipelines) -----------------------------------------------------------------
+// chunk length / heavy-bucket threshold of the accumulation are fixed on the device once the pair count is known (dyn_chunk.hip.h): CH and T only size
+// the launch and the partial slots (the rule WITHOUT the run-length term gives the most chunks any E <= Emax can have)
+struct AccGeom { size_t Emax; int CH; size_t T; uint32_t min_chunk, max_chunks, lanes_per_chunk, HEAVY_CAP; };
+template <class C> AccGeom acc_geometry(size_t Emax) {
+    AccGeom a;
+    a.Emax = Emax;
+    a.min_chunk = C::NFP == 2 ? 32u : 16u; a.max_chunks = C::NFP == 2 ? 150000u : 300000u; a.lanes_per_chunk = C::NFP == 2 ? 2u : 1u;
+    a.CH = choose_chunk(Emax, (int)a.min_chunk, a.max_chunks, (int)a.lanes_per_chunk);
+    a.T = (Emax + a.CH - 1) / a.CH;
+    // a heavy bucket has >= 16 chunk lengths of terms and a chunk is never shorter than 16 terms (k_dyn_chunk, forced_chunk), whatever min_chunk says
+    a.HEAVY_CAP = (uint32_t)(Emax / (16u * 16u)) + 1;
+    return a;
 }
-
-// sum of k Jacobian triples (host): partial results gathered from the other ranks
-template <class HF>
-int32_t host_fold_jacobian(const uint64_t *xyz, size_t k, uint64_t *out_xyz) {
-    if (!out_xyz || (k && !xyz)) return DGPU_E_BADARG;
-    typedef hostf::HXyzz<HF> PT;
-    const size_t FWORDS = sizeof(HF) / 8;
-    PT acc = PT::identity();
-    for (size_t i = 0; i < k; i++) {
-        HF X, Y, Z;
-        memcpy(&X, xyz + i * 3 * FWORDS, sizeof(HF)); memcpy(&Y, xyz + i * 3 * FWORDS + FWORDS, sizeof(HF)); memcpy(&Z, xyz + i * 3 * FWORDS + 2 * FWORDS, sizeof(HF));
-        if (Z.is_zero()) continue;
-        PT t; t.inf = false; t.x = X; t.y = Y; t.zz = Z * Z; t.zzz = t.zz * Z;   // Jacobian (X, Y, Z) == XYZZ (X, Y, Z^2, Z^3)
-        acc.add_in_place(t);
-    }
-    HF X, Y, Z; acc.to_normalised_jacobian(X, Y, Z);
-    memcpy(out_xyz, &X, sizeof(HF)); memcpy(out_xyz + FWORDS, &Y, sizeof(HF)); memcpy(out_xyz + 2 * FWORDS, &Z, sizeof(HF));
-    return DGPU_OK;
-}
-
-// sum_i s_i P_i over k <= DGPU_MAX_LINCOMB affine points on the HOST (4-bit windows, one table of 15 multiples per point, joint doublings).
-// This is not the MSM path: it is the O(1) group arithmetic around it that the reference does with `mul_bigint` / FixedBase on the CPU — the
-// r delta, s g_a + r g1_b, -rs delta - v eta/delta of a proof (prover.rs:309-313, 350-355, 585-594) — next to
-// dgpu_fold_* and dgpu_final_exponentiation.  A 2..4-term product costs 0.15 - 0.35 ms of one host core and no device launch; the same
-// through the bucket pipeline is ~0.75 ms of launch latency per call and queues behind the accumulation kernels of the large MSMs.
-template <class HF>
-int32_t host_lincomb(const uint64_t *points_xy, const uint8_t *is_inf, const uint64_t *scalars, size_t k, uint64_t *out_xyz) {
-    if (!out_xyz || k > DGPU_MAX_LINCOMB || (k && (!points_xy || !scalars))) return DGPU_E_BADARG;
-    typedef hostf::HXyzz<HF> PT;
-    const size_t FWORDS = sizeof(HF) / 8;
-    std::vector<PT> tab(k * 15);
-    std::vector<uint8_t> live(k, 0);
-    for (size_t i = 0; i < k; i++) {
-        HF X, Y;
-        memcpy(&X, points_xy + i * 2 * FWORDS, sizeof(HF)); memcpy(&Y, points_xy + i * 2 * FWORDS + FWORDS, sizeof(HF));
-        const uint64_t *sc = scalars + 4 * i;
-        uint64_t any = 0; for (size_t w = 0; w < 2 * FWORDS; w++) any |= points_xy[i * 2 * FWORDS + w];      // all-zero coordinates: the ABI's other spelling of the identity
-        if ((is_inf && is_inf[i]) || !any || !(sc[0] | sc[1] | sc[2] | sc[3])) continue;
-        live[i] = 1;
-        PT p; p.inf = false; p.x = X; p.y = Y; p.zz = HF::one(); p.zzz = HF::one();
-        tab[i * 15] = p;
-        for (int m = 1; m < 15; m++) { PT t = tab[i * 15 + m - 1]; if (m == 1) t.dbl_in_place(); else t.add_in_place(p); tab[i * 15 + m] = t; }
-    }
-    PT acc = PT::identity();
-    for (int w = 63; w >= 0; w--) {
-        for (int d = 0; d < 4; d++) acc.dbl_in_place();
-        for (size_t i = 0; i < k; i++) {
-            if (!live[i]) continue;
-            const unsigned nib = (unsigned)(scalars[4 * i + (w >> 4)] >> ((w & 15) * 4)) & 15u;
-            if (nib) acc.add_in_place(tab[i * 15 + nib - 1]);
-        }
-    }
-    HF X, Y, Z; acc.to_normalised_jacobian(X, Y, Z);
-    memcpy(out_xyz, &X, sizeof(HF)); memcpy(out_xyz + FWORDS, &Y, sizeof(HF)); memcpy(out_xyz + 2 * FWORDS, &Z, sizeof(HF));
-    return DGPU_OK;
-}
-
-template <class HF> void write_identity(uint64_t *out_xyz) {
-    typedef hostf::HXyzz<HF> PT; PT id = PT::identity(); HF X, Y, Z; id.to_normalised_jacobian(X, Y, Z);
-    const size_t FWORDS = sizeof(HF) / 8; memcpy(out_xyz, &X, sizeof(HF)); memcpy(out_xyz + FWORDS, &Y, sizeof(HF)); memcpy(out_xyz + 2 * FWORDS, &Z, sizeof(HF));
+// one set of NB buckets, the chunks' partials, the chunking and the heavy-bucket list (grow-only, like every workspace below)
+template <class C> int32_t ws_acc(Slot &sl, size_t NB, const AccGeom &a) {
+    int32_t rc;
+    const size_t T = a.T, hslots = 2 * (T / msm::HEAVY_RANGE + 2);
+    if ((rc = sl.bucket.ensure(soa_points(NB) * C::XW * 4))) return rc;
+    if ((rc = sl.bucket_inf.ensure(NB))) return rc;
+    if ((rc = sl.head.ensure(soa_points(T) * C::XW * 4))) return rc;
+    if ((rc = sl.tail.ensure(soa_points(T) * C::XW * 4))) return rc;
+    if ((rc = sl.head_b.ensure(T * 4))) return rc;
+    if ((rc = sl.tail_b.ensure(T * 4))) return rc;
+    if ((rc = sl.part_inf.ensure(T * 2))) return rc;
+    if ((rc = sl.heavy.ensure(((size_t)a.HEAVY_CAP + 1) * 4))) return rc;
+    if ((rc = sl.dyn.ensure(msm::dyn_words(T) * 4))) return rc;
+    if ((rc = sl.hpart.ensure(hslots * C::XW * 4))) return rc;
+    return sl.hpart_inf.ensure(hslots);
 }
 
 constexpr size_t PLAIN_PSORT_MIN_N = (size_t)1 << 17;
 // ---- geometry + workspace of the plain pipeline ---------------------------------------------------------------------------------------
 struct PlainGeom {
-    int c, W; uint32_t B, NB; int mshift, G; size_t NG, Emax; int CH; size_t T, nblk; bool wide; size_t n_pad; int RANGES, rb_log; unsigned sort_grid; size_t lds_bytes;
-    uint32_t min_chunk, max_chunks, lanes_per_chunk, HEAVY_CAP;
+    int c, W; uint32_t B, NB; int mshift, G; size_t NG, nblk; bool wide; size_t n_pad; int RANGES, rb_log; unsigned sort_grid; size_t lds_bytes;
+    AccGeom acc;
     bool psort;            // the two-level partition sort (psort_kernels.hip.h) instead of the per-window sweeps: large n
 };
 template <class C> int32_t plain_geometry(size_t n, PlainGeom &g) {
@@ -110,9 +61,7 @@ template <class C> int32_t plain_geometry(size_t n, PlainGeom &g) {
     g.mshift = std::max(0, g.c - 1 - 12);
     g.G = (int)(g.B >> (6 + g.mshift));          // groups per window (<= 64), B >= 64 because c >= 7
     g.NG = (size_t)g.W * g.G;
-    g.Emax = (size_t)n * g.W;
-    g.CH = C::NFP == 2 ? choose_chunk(g.Emax, 32, 150000, 2) : choose_chunk(g.Emax, 16, 300000, 1);
-    g.T = (g.Emax + g.CH - 1) / g.CH;
+    g.acc = acc_geometry<C>((size_t)n * g.W);
     g.nblk = scan_blocks(g.NB);
     // counting sort of the n*W (key, term) pairs: digit codes -> LDS histograms per (window, bucket range) -> scan -> LDS cursors
     g.wide = g.c > 16;
@@ -121,11 +70,6 @@ template <class C> int32_t plain_geometry(size_t n, PlainGeom &g) {
     g.rb_log = 0; while ((1u << g.rb_log) < g.B / g.RANGES) g.rb_log++;
     g.sort_grid = (unsigned)(8 * ((g.W + 7) / 8) * g.RANGES);
     g.lds_bytes = ((size_t)1 << g.rb_log) * 4;
-    // chunk length / heavy-bucket threshold of the accumulation are fixed on the device once the pair count is known (dyn_chunk.hip.h): CH and T
-    // only size the launch and the partial slots
-    g.min_chunk = C::NFP == 2 ? 32u : 16u; g.max_chunks = C::NFP == 2 ? 150000u : 300000u; g.lanes_per_chunk = C::NFP == 2 ? 2u : 1u;
-    // a heavy bucket has >= 16 chunk lengths of terms and a chunk is never shorter than 16 terms (k_dyn_chunk, forced_chunk), whatever min_chunk says
-    g.HEAVY_CAP = (uint32_t)(g.Emax / (16u * 16u)) + 1;
     // From 2^17 terms on the sweeps (every digit column re-read once per bucket range: 0.38 ms at n = 2^20) give way to the partition sort the table
     // pipeline uses (0.2 ms), with one bucket set per window in the key: key = w B + |digit| - 1
     g.psort = g.W <= PS_MAX_W && n >= PLAIN_PSORT_MIN_N;
@@ -134,37 +78,28 @@ template <class C> int32_t plain_geometry(size_t n, PlainGeom &g) {
 // grow-only workspace of one slot for the plain pipeline of that geometry (no-ops once the slot has seen the size: dgpu_reserve_*, uploads)
 template <class C> int32_t ws_plain(Slot &sl, const PlainGeom &g) {
     int32_t rc;
-    const size_t NB = g.NB, T = g.T;
+    const size_t NB = g.NB, Emax = g.acc.Emax;
+    if ((rc = ws_acc<C>(sl, NB, g.acc))) return rc;
     if ((rc = sl.flags.ensure(64))) return rc;
     if ((rc = sl.cnt.ensure((NB + 1) * 4))) return rc;
     if ((rc = sl.off.ensure((NB + 1) * 4))) return rc;
     if ((rc = sl.cursor.ensure((NB + 1) * 4))) return rc;
     if ((rc = sl.bsums.ensure((g.nblk + 2) * 4))) return rc;
-    if ((rc = sl.entries.ensure(g.Emax * 4))) return rc;
-    if ((rc = sl.bucket.ensure(soa_points(NB) * C::XW * 4))) return rc;
-    if ((rc = sl.bucket_inf.ensure(NB))) return rc;
-    if ((rc = sl.head.ensure(soa_points(T) * C::XW * 4))) return rc;
-    if ((rc = sl.tail.ensure(soa_points(T) * C::XW * 4))) return rc;
-    if ((rc = sl.head_b.ensure(T * 4))) return rc;
-    if ((rc = sl.tail_b.ensure(T * 4))) return rc;
-    if ((rc = sl.part_inf.ensure(T * 2))) return rc;
+    if ((rc = sl.entries.ensure(Emax * 4))) return rc;
     if ((rc = sl.l1.ensure(g.NG * 2 * C::XW * 4))) return rc;
     if ((rc = sl.l1_inf.ensure(g.NG * 2))) return rc;
     if ((rc = sl.win.ensure((size_t)g.W * 4 * C::ABI_W * 4))) return rc;
     if ((rc = sl.win_inf.ensure(g.W))) return rc;
     if ((rc = sl.digits.ensure((size_t)g.W * g.n_pad * (g.wide ? 4 : 2)))) return rc;
     if (g.psort) {                                 // cnt1 / off1 per (partition, tile), the (key, value) pairs
-        const size_t n_terms = g.Emax / g.W;
+        const size_t n_terms = Emax / g.W;
         const uint32_t P = (g.NB + (1u << ps_part_log(g.NB)) - 1) >> ps_part_log(g.NB);
         const size_t n1 = (size_t)P * ((n_terms + PS_TILE - 1) / PS_TILE);
         if ((rc = sl.cnt.ensure((n1 + 1) * 4))) return rc;
         if ((rc = sl.cursor.ensure((n1 + 1) * 4))) return rc;
         if ((rc = sl.bsums.ensure((scan_blocks(n1) + 2) * 4))) return rc;
-        if ((rc = sl.digits.ensure(g.Emax * 8))) return rc;
+        if ((rc = sl.digits.ensure(Emax * 8))) return rc;
     }
-    if ((rc = sl.heavy.ensure(((size_t)g.HEAVY_CAP + 1) * 4))) return rc;
-    if ((rc = sl.dyn.ensure(msm::dyn_words(T) * 4))) return rc;
-    { const size_t hslots = 2 * (T / msm::HEAVY_RANGE + 2); if ((rc = sl.hpart.ensure(hslots * C::XW * 4))) return rc; if ((rc = sl.hpart_inf.ensure(hslots))) return rc; }
     return DGPU_OK;
 }
 
@@ -239,6 +174,69 @@ int32_t msm_device_small(Slot &sl, const uint32_t *d_bases, const uint32_t *d_sc
     return DGPU_OK;
 }
 
+// ---- the two stages both pipelines share ------------------------------------------------------------------------------------------------
+// Accumulate stage: the key-sorted list (`off`, `entries`) over the records `recs` into bucket set `set`, then the fix-up of the buckets that chunk
+// borders cut, the heavy buckets, and the merge into set 0 when set > 0.  skip_identity: the kernel that passes over identity records (and maps rows
+// by `map`); heavy_thr: k_fixup's threshold where dyn[] does not replace it; gather_mask: a knob of the development twin (plain kernel only).
+// The caller has set the set's bucket_inf and has dyn[] and the heavy list queued.
+template <class C>
+void acc_stage(Slot &sl, const AccGeom &a, uint32_t NB, const uint32_t *recs, const uint32_t *off, const uint32_t *entries, size_t set, bool skip_identity, const msm::RowMap &map,
+               uint32_t heavy_thr, uint32_t gather_mask = 0xffffffffu) {
+    hipStream_t s = sl.stream;
+    const size_t T = a.T; const uint32_t CH = (uint32_t)a.CH;
+    uint32_t *const dyn = sl.dyn.as<uint32_t>();
+    uint32_t *const bucket = sl.bucket.as<uint32_t>() + set * soa_points(NB) * C::XW;
+    uint8_t *const bucket_inf = sl.bucket_inf.as<uint8_t>() + set * (size_t)NB;
+    {
+        StageTimer st(sl, "msm.accumulate");
+        if (skip_identity) launch_accumulate_skip_identity<C>(s, recs, entries, off, NB, bucket, bucket_inf,
+                           sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(), sl.head_b.as<uint32_t>(), sl.tail_b.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, CH, dyn, map);
+        else launch_accumulate<C>(s, recs, entries, off, NB, bucket, bucket_inf,
+                           sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(), sl.head_b.as<uint32_t>(), sl.tail_b.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, CH, gather_mask, dyn);
+    }
+    {
+        StageTimer st(sl, "msm.fixup");
+        launch_fixup<C>(s, NB, bucket, bucket_inf, sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(),
+                           sl.head_b.as<uint32_t>(), sl.tail_b.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, off, heavy_thr, dyn);
+        launch_fixup_heavy<C>(s, sl.heavy.as<uint32_t>(), a.HEAVY_CAP, off, CH, NB, bucket, bucket_inf,
+                           sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, dyn, sl.hpart.as<uint32_t>(), sl.hpart_inf.as<uint8_t>());
+        if (set > 0) launch_merge_buckets<C>(s, NB, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), bucket, bucket_inf);
+    }
+}
+// Read-back: the npts window points of sl.win, their identity flags and (check_flag) the slot's bad-scalar word come to the host, then fold(points, flags)
+// runs on them where they landed (the caller holds the slot until we return; the offsets are multiples of 8 bytes).
+// They land in the slot's PINNED scratch: a copy to pageable memory is synchronous inside hipMemcpyAsync (the runtime waits for the
+// stream, then stages the bytes under a lock of its own) — with several calls in flight their host threads queued up there, and the default bench line
+// fell to half its rate on loaded hosts (round 5: 420 -> 190 - 240 MSM/s with kernels of unchanged length).  Pinned: three asynchronous copies, one wait.
+template <class C, class Fold>
+int32_t read_back_fold(Slot &sl, size_t npts, bool check_flag, Fold fold) {
+    hipStream_t s = sl.stream;
+    const size_t wb = npts * 4 * C::ABI_W * 4, ib = (npts + 7) & ~(size_t)7;
+    static_assert((size_t)64 * 4 * 24 * 4 + 64 + 16 <= Slot::HPIN_BYTES, "pinned scratch");
+    // (the plain pipeline has W <= 37 windows today, c >= 7, and the table pipeline a few dozen points: the pinned scratch fits.  A future window rule that breaks
+    //  this, or a forced geometry with hundreds of pseudo-windows — a knob of the twin — falls back to pageable memory instead of overflowing it)
+    std::vector<uint8_t> big;
+    if (wb + ib + 4 > Slot::HPIN_BYTES) big.resize(wb + ib + 4);
+    uint8_t *const hp = big.empty() ? (uint8_t *)sl.hpin : big.data();
+    memset(hp + wb + ib, 0, 4);
+    HIPCHK(hipMemcpyAsync(hp, sl.win.p, wb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hp + wb, sl.win_inf.p, npts, hipMemcpyDeviceToHost, s));
+    if (check_flag) HIPCHK(hipMemcpyAsync(hp + wb + ib, sl.flags.p, 4, hipMemcpyDeviceToHost, s));      // (a shared sort was checked by dgpu_scalars_sort)
+    auto tsync0 = std::chrono::steady_clock::now();
+    HIPCHK(hipStreamSynchronize(s));
+    auto tsync1 = std::chrono::steady_clock::now();
+    if (gs.prof) prof_flush(sl);
+    uint32_t hbad; memcpy(&hbad, hp + wb + ib, 4);
+    if (hbad) return DGPU_E_BADARG;                  // a scalar >= 2^255 (sort_kernels.hip.h k_digit_codes)
+    fold((const uint64_t *)hp, hp + wb);
+    if (gs.prof) {
+        auto t2 = std::chrono::steady_clock::now();
+        prof_add_host("msm.host_wait", std::chrono::duration<double, std::milli>(tsync1 - tsync0).count());
+        prof_add_host("msm.host_fold", std::chrono::duration<double, std::milli>(t2 - tsync1).count());
+    }
+    return DGPU_OK;
+}
+
 // d_bases: prepared records; d_scalars: canonical 8 x u32 per scalar.  Caller holds the slot.
 // bases_pending: the base records are written by work that `ready_bases(k, lo, hi)` queues on this stream between the sort and the accumulation
 // of range k (one-shot calls: the bases cross PCIe while the scalars are sorted): the sort does not look at them and the accumulation passes over
@@ -251,19 +249,16 @@ int32_t msm_device_ranges(Slot &sl, const uint32_t *d_bases, const uint32_t *d_s
     if ((rc = plain_geometry<C>(n, g))) return rc;
     if ((rc = ws_plain<C>(sl, g))) return rc;
     if (K > 1 && (rc = ws_bucket_sets<C>(sl, g.NB, K))) return rc;
-    const int c = g.c, W = g.W; const uint32_t NB = g.NB; const size_t T = g.T; const int CH = g.CH;
+    const int c = g.c, W = g.W; const uint32_t NB = g.NB; const AccGeom &a = g.acc; const size_t T = a.T;
     hipStream_t s = sl.stream;
-    const uint32_t heavy_thr = 0xffffffffu /* the sweeps flag nothing: k_flag_heavy does, after the scan */, HEAVY_CAP = g.HEAVY_CAP;
+    const uint32_t heavy_thr = 0xffffffffu /* the sweeps flag nothing: k_flag_heavy does, after the scan */, HEAVY_CAP = a.HEAVY_CAP;
     uint32_t *const dyn = sl.dyn.as<uint32_t>();
-    const size_t set_words = soa_points(NB) * C::XW;
     HIPCHK(hipMemsetAsync(sl.bucket_inf.p, 1, K * (size_t)NB, s));
     HIPCHK(hipMemsetAsync(sl.flags.p, 0, 4, s));
     for (size_t k = 0; k < K; k++) {
         size_t lo, hi; range_bounds(n, K, k, lo, hi);
         const size_t nk = hi - lo, nk_pad = (nk + 7) & ~(size_t)7;
         if (nk == 0) continue;
-        uint32_t *const bucket = sl.bucket.as<uint32_t>() + k * set_words;
-        uint8_t *const bucket_inf = sl.bucket_inf.as<uint8_t>() + k * (size_t)NB;
         const uint32_t *const bases_k = d_bases + lo * C::AFF_STRIDE, *const scalars_k = d_scalars + lo * 8;
         if ((rc = ready_scalars(k, lo, hi))) return rc;
         if (g.psort) {
@@ -273,10 +268,10 @@ int32_t msm_device_ranges(Slot &sl, const uint32_t *d_bases, const uint32_t *d_s
             q.c = c; q.W = W; q.key_wstride = g.B; q.val_base = 0; q.val_wstride = 0;
             q.part_log = ps_part_log(NB); q.P = (NB + (1u << q.part_log) - 1) >> q.part_log; q.ntiles = (uint32_t)((nk + PS_TILE - 1) / PS_TILE);
             q.bad = sl.flags.as<uint32_t>();
-            const uint32_t dyn_args[6] = {(uint32_t)forced_chunk(), g.min_chunk, g.max_chunks, g.lanes_per_chunk, (uint32_t)T, 0u};
+            const uint32_t dyn_args[6] = {(uint32_t)forced_chunk(), a.min_chunk, a.max_chunks, a.lanes_per_chunk, (uint32_t)T, 0u};
             HIPCHK(hipMemsetAsync(sl.heavy.p, 0, 4, s));
             launch_psort(s, q, NB, sl.cnt.as<uint32_t>(), sl.cursor.as<uint32_t>(), sl.bsums.as<uint32_t>(), sl.digits.p, sl.off.as<uint32_t>(), sl.entries.as<uint32_t>(),
-                         16u * (uint32_t)CH /* replaced on the device, dyn_chunk.hip.h */, sl.heavy.as<uint32_t>(), HEAVY_CAP, dyn_args, dyn);
+                         16u * (uint32_t)a.CH /* replaced on the device, dyn_chunk.hip.h */, sl.heavy.as<uint32_t>(), HEAVY_CAP, dyn_args, dyn);
         } else {
         {
             StageTimer st(sl, "msm.count");
@@ -287,7 +282,7 @@ int32_t msm_device_ranges(Slot &sl, const uint32_t *d_bases, const uint32_t *d_s
         {
             StageTimer st(sl, "msm.scan");
             launch_scan(s, sl.cnt.as<uint32_t>(), sl.off.as<uint32_t>(), sl.cursor.as<uint32_t>(), sl.bsums.as<uint32_t>(), (size_t)NB);
-            launch_dyn_chunk(s, sl.off.as<uint32_t>() + NB, (uint32_t)forced_chunk(), g.min_chunk, g.max_chunks, g.lanes_per_chunk, (uint32_t)T, dyn);
+            launch_dyn_chunk(s, sl.off.as<uint32_t>() + NB, (uint32_t)forced_chunk(), a.min_chunk, a.max_chunks, a.lanes_per_chunk, (uint32_t)T, dyn);
             launch_flag_heavy(s, sl.off.as<uint32_t>(), NB, dyn, sl.heavy.as<uint32_t>(), HEAVY_CAP);
         }
         {
@@ -296,26 +291,12 @@ int32_t msm_device_ranges(Slot &sl, const uint32_t *d_bases, const uint32_t *d_s
         }
         }
         if ((rc = ready_bases(k, lo, hi))) return rc;
-        {
-            StageTimer st(sl, "msm.accumulate");
 #ifdef DGPU_DEV
-            static const uint32_t dbg_mask = getenv("DGPU_DBG_NOGATHER") ? 1023u : 0xffffffffu;   // development experiment (wrong results by design): L2-resident points
+        static const uint32_t dbg_mask = getenv("DGPU_DBG_NOGATHER") ? 1023u : 0xffffffffu;   // development experiment (wrong results by design): L2-resident points
 #else
-            constexpr uint32_t dbg_mask = 0xffffffffu;
+        constexpr uint32_t dbg_mask = 0xffffffffu;
 #endif
-            if (bases_pending || g.psort) launch_accumulate_skip_identity<C>(s, bases_k, sl.entries.as<uint32_t>(), sl.off.as<uint32_t>(), NB, bucket, bucket_inf,
-                               sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(), sl.head_b.as<uint32_t>(), sl.tail_b.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, (uint32_t)CH, dyn, msm::RowMap{});
-            else launch_accumulate<C>(s, bases_k, sl.entries.as<uint32_t>(), sl.off.as<uint32_t>(), NB, bucket, bucket_inf,
-                               sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(), sl.head_b.as<uint32_t>(), sl.tail_b.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, (uint32_t)CH, dbg_mask, dyn);
-        }
-        {
-            StageTimer st(sl, "msm.fixup");
-            launch_fixup<C>(s, NB, bucket, bucket_inf, sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(),
-                               sl.head_b.as<uint32_t>(), sl.tail_b.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, sl.off.as<uint32_t>(), heavy_thr, dyn);
-            launch_fixup_heavy<C>(s, sl.heavy.as<uint32_t>(), HEAVY_CAP, sl.off.as<uint32_t>(), (uint32_t)CH, NB, bucket, bucket_inf,
-                               sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, dyn, sl.hpart.as<uint32_t>(), sl.hpart_inf.as<uint8_t>());
-            if (k > 0) launch_merge_buckets<C>(s, NB, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), bucket, bucket_inf);
-        }
+        acc_stage<C>(sl, g.acc, NB, bases_k, sl.off.as<uint32_t>(), sl.entries.as<uint32_t>(), k, bases_pending || g.psort, msm::RowMap{}, heavy_thr, dbg_mask);
     }
     {
         StageTimer st(sl, "msm.reduce");
@@ -323,33 +304,7 @@ int32_t msm_device_ranges(Slot &sl, const uint32_t *d_bases, const uint32_t *d_s
         launch_reduce_top<C>(s, (unsigned)W, sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), g.G, 6 + g.mshift, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>(), gs.reduce_lanes.load() == 1 ? 1 : 4);
     }
     HIPCHK(hipGetLastError());
-    std::vector<uint64_t> hwin((size_t)W * 2 * C::ABI_W);
-    std::vector<uint8_t> hinf(W);
-    // The results come back into the slot's PINNED scratch: a copy to pageable memory is synchronous inside hipMemcpyAsync (the runtime waits for the
-    // stream, then stages the bytes under a lock of its own) — with several calls in flight their host threads queued up there, and the default bench line
-    // fell to half its rate on loaded hosts (round 5: 420 -> 190 - 240 MSM/s with kernels of unchanged length).  Pinned: three asynchronous copies, one wait.
-    const size_t wb = (size_t)W * 4 * C::ABI_W * 4, ib = ((size_t)W + 7) & ~(size_t)7;
-    static_assert((size_t)64 * 4 * 24 * 4 + 64 + 16 <= Slot::HPIN_BYTES, "pinned scratch");
-    std::vector<uint8_t> big;                        // (W <= 37 today, c >= 7: the pinned scratch always fits — a future window rule that breaks this falls back to pageable memory instead of overflowing it)
-    if (wb + ib + 4 > Slot::HPIN_BYTES) big.resize(wb + ib + 4);
-    uint8_t *const hp = big.empty() ? (uint8_t *)sl.hpin : big.data();
-    HIPCHK(hipMemcpyAsync(hp, sl.win.p, wb, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hp + wb, sl.win_inf.p, W, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hp + wb + ib, sl.flags.p, 4, hipMemcpyDeviceToHost, s));
-    auto tsync0 = std::chrono::steady_clock::now();
-    HIPCHK(hipStreamSynchronize(s));
-    auto tsync1 = std::chrono::steady_clock::now();
-    if (gs.prof) prof_flush(sl);
-    uint32_t hbad; memcpy(&hbad, hp + wb + ib, 4);
-    if (hbad) return DGPU_E_BADARG;                  // a scalar >= 2^255 (sort_kernels.hip.h k_digit_codes)
-    memcpy(hwin.data(), hp, wb); memcpy(hinf.data(), hp + wb, W);
-    host_fold<HF>(hwin.data(), hinf.data(), W, c, out_xyz);
-    if (gs.prof) {
-        auto t2 = std::chrono::steady_clock::now();
-        prof_add_host("msm.host_wait", std::chrono::duration<double, std::milli>(tsync1 - tsync0).count());
-        prof_add_host("msm.host_fold", std::chrono::duration<double, std::milli>(t2 - tsync1).count());
-    }
-    return DGPU_OK;
+    return read_back_fold<C>(sl, (size_t)W, true, [&](const uint64_t *hwin, const uint8_t *hinf) { host_fold<HF>(hwin, hinf, W, c, out_xyz); });
 }
 template <class C, class HF>
 int32_t msm_device(Slot &sl, const uint32_t *d_bases, const uint32_t *d_scalars, size_t n, uint64_t *out_xyz, const SmallSub *sub = nullptr) {
@@ -410,42 +365,12 @@ inline int choose_c_pre(size_t n) {
     if (n < (1u << 15)) return 0;
     return n >= 320000 ? 20 : 16;      // (re-measured in round 4, profiles/r04zz_table_widths.txt: at 2^18 terms width 16 is 1.32 ms against 1.44 for width 20 and equal with four in flight; at 2^19 width 20 wins both ways)
 }
-
-// sum_j A_j + 2^lb * sum_j j S_j over the PW pseudo-windows (bucket b = j 2^lb + k of the one bucket set weighs b + 1 = (k + 1) + j 2^lb)
-template <class HF>
-void host_fold_shared(const uint64_t *a_abi, const uint8_t *a_inf, const uint64_t *s_abi, const uint8_t *s_inf, int PW, int lb, uint64_t *out_xyz) {
-    typedef hostf::HXyzz<HF> PT;
-    const size_t FWORDS = sizeof(HF) / 8;
-    auto load = [&](const uint64_t *src, bool inf) { PT t = PT::identity(); if (!inf) { t.inf = false; memcpy(&t.x, src, sizeof(HF)); memcpy(&t.y, src + FWORDS, sizeof(HF)); memcpy(&t.zz, src + 2 * FWORDS, sizeof(HF)); memcpy(&t.zzz, src + 3 * FWORDS, sizeof(HF)); } return t; };
-    PT suffix = PT::identity(), weighted = PT::identity(), total = PT::identity();
-    for (int j = PW - 1; j >= 1; j--) { suffix.add_in_place(load(s_abi + (size_t)j * 4 * FWORDS, s_inf[j] != 0)); weighted.add_in_place(suffix); }   // sum_{j>=1} j S_j
-    for (int k = 0; k < lb; k++) weighted.dbl_in_place();
-    for (int j = 0; j < PW; j++) total.add_in_place(load(a_abi + (size_t)j * 4 * FWORDS, a_inf[j] != 0));
-    total.add_in_place(weighted);
-    HF X, Y, Z; total.to_normalised_jacobian(X, Y, Z);
-    memcpy(out_xyz, &X, sizeof(HF)); memcpy(out_xyz + FWORDS, &Y, sizeof(HF)); memcpy(out_xyz + 2 * FWORDS, &Z, sizeof(HF));
-}
-
-// P + 2^shift * sum_t 2^t M_t (reduce_kernels.hip.h): pts[0] = P, pts[1 + t] = M_t, nm marginals
-template <class HF>
-void host_fold_marginals(const uint64_t *pts, const uint8_t *inf, int nm, int shift, uint64_t *out_xyz) {
-    typedef hostf::HXyzz<HF> PT;
-    const size_t FWORDS = sizeof(HF) / 8;
-    auto load = [&](int i) { PT t = PT::identity(); if (!inf[i]) { const uint64_t *src = pts + (size_t)i * 4 * FWORDS; t.inf = false; memcpy(&t.x, src, sizeof(HF)); memcpy(&t.y, src + FWORDS, sizeof(HF)); memcpy(&t.zz, src + 2 * FWORDS, sizeof(HF)); memcpy(&t.zzz, src + 3 * FWORDS, sizeof(HF)); } return t; };
-    PT acc = PT::identity();
-    for (int t = nm - 1; t >= 0; t--) { if (!acc.inf) acc.dbl_in_place(); acc.add_in_place(load(1 + t)); }
-    if (!acc.inf) for (int k = 0; k < shift; k++) acc.dbl_in_place();
-    acc.add_in_place(load(0));
-    HF X, Y, Z; acc.to_normalised_jacobian(X, Y, Z);
-    memcpy(out_xyz, &X, sizeof(HF)); memcpy(out_xyz + FWORDS, &Y, sizeof(HF)); memcpy(out_xyz + 2 * FWORDS, &Z, sizeof(HF));
-}
-
 // ---- the shared-bucket-set pipeline over a precomputed-multiples table, in two stages -------------------------------------------------
 // Stage 1 (pre_sort): scalars -> the key-sorted row list `entries` and the bucket offsets `off` (off[NB] = number of pairs).  The result
 // depends on the scalars and on the table's SHAPE (c, W, rows, first row) only, not on the curve or on the points: the MSMs of a proof
 // that multiply one assignment vector by several tables (A, B in G1, B in G2 of create_proof) can share it (dgpu_scalars_sort_*).
 // Stage 2 (pre_tail): accumulate / fix-up / reduce / host fold on any table of that shape.
-struct PreGeom { uint32_t NB; int mshift, lb, PW, G; size_t NG, Emax, T; int CH; uint32_t min_chunk, max_chunks, lanes_per_chunk, HEAVY_CAP; };
+struct PreGeom { uint32_t NB; int mshift, lb, PW, G; size_t NG; AccGeom acc; };
 template <class C> int32_t pre_geometry(const PreTable &pt, size_t n, PreGeom &g) {
     const int c = pt.c, W = pt.W;
     g.NB = 1u << (c - 1);
@@ -461,35 +386,24 @@ template <class C> int32_t pre_geometry(const PreTable &pt, size_t n, PreGeom &g
     g.PW = (int)(g.NB >> g.lb);
     g.G = 1 << (g.lb - 6 - g.mshift);             // groups per pseudo-window (<= 64)
     g.NG = (size_t)g.PW * g.G;
-    g.Emax = (size_t)n * W;
-    if (g.Emax >= (1ull << 32) || (uint64_t)W * pt.n >= (1ull << 31) || W > PS_MAX_W) return DGPU_E_BADARG;
-    g.CH = C::NFP == 2 ? choose_chunk(g.Emax, 32, 150000, 2) : choose_chunk(g.Emax, 16, 300000, 1);     // (sizes the partial slots: the rule WITHOUT the run-length term gives the most chunks any E <= Emax can have)
-    g.T = (g.Emax + g.CH - 1) / g.CH;
-    g.min_chunk = C::NFP == 2 ? 32u : 16u; g.max_chunks = C::NFP == 2 ? 150000u : 300000u; g.lanes_per_chunk = C::NFP == 2 ? 2u : 1u;
-    g.HEAVY_CAP = (uint32_t)(g.Emax / (16u * 16u)) + 1;         // (see plain_geometry)
+    if ((uint64_t)n * W >= (1ull << 32) || (uint64_t)W * pt.n >= (1ull << 31) || W > PS_MAX_W) return DGPU_E_BADARG;
+    g.acc = acc_geometry<C>((size_t)n * W);
     return DGPU_OK;
 }
 // grow-only workspace of one slot for the table pipeline (sort + tail) of n terms on a table of pt's shape
 template <class C> int32_t ws_pre(Slot &sl, const PreTable &pt, const PreGeom &g, size_t n) {
-    const uint32_t NB = g.NB; const size_t T = g.T; const int PW = g.PW;
+    const uint32_t NB = g.NB; const int PW = g.PW;
     const uint32_t P = (NB + (1u << ps_part_log(NB)) - 1) >> ps_part_log(NB);
     const size_t n1 = (size_t)P * ((n + PS_TILE - 1) / PS_TILE);
     int32_t rc;
+    if ((rc = ws_acc<C>(sl, NB, g.acc))) return rc;
     if ((rc = sl.flags.ensure(64))) return rc;
     if ((rc = sl.cnt.ensure((n1 + 1) * 4))) return rc;
     if ((rc = sl.cursor.ensure((n1 + 1) * 4))) return rc;                 // off1
     if ((rc = sl.bsums.ensure((scan_blocks(n1) + 2) * 4))) return rc;
-    if ((rc = sl.digits.ensure(g.Emax * 8))) return rc;                   // (key, val) pairs
-    if ((rc = sl.heavy.ensure(((size_t)g.HEAVY_CAP + 1) * 4))) return rc;
+    if ((rc = sl.digits.ensure(g.acc.Emax * 8))) return rc;               // (key, val) pairs
     if ((rc = sl.off.ensure(((size_t)NB + 1) * 4))) return rc;
-    if ((rc = sl.entries.ensure(g.Emax * 4))) return rc;
-    if ((rc = sl.bucket.ensure(soa_points(NB) * C::XW * 4))) return rc;
-    if ((rc = sl.bucket_inf.ensure(NB))) return rc;
-    if ((rc = sl.head.ensure(soa_points(T) * C::XW * 4))) return rc;
-    if ((rc = sl.tail.ensure(soa_points(T) * C::XW * 4))) return rc;
-    if ((rc = sl.head_b.ensure(T * 4))) return rc;
-    if ((rc = sl.tail_b.ensure(T * 4))) return rc;
-    if ((rc = sl.part_inf.ensure(T * 2))) return rc;
+    if ((rc = sl.entries.ensure(g.acc.Emax * 4))) return rc;
     // (sized for the reduction's shape of a call that runs alone as well: pre_geometry picks fewer, longer groups when the context is busy, and a
     //  slot reserved under load must not allocate when it is later used by a lone call)
     const size_t NGw = std::max(g.NG, (size_t)(NB >> 9)), PWw = std::max((size_t)PW, (size_t)(NB >> 15));
@@ -497,11 +411,8 @@ template <class C> int32_t ws_pre(Slot &sl, const PreTable &pt, const PreGeom &g
     if ((rc = sl.l1.ensure(std::max(NGw * 2, mpts) * C::XW * 4))) return rc;
     if ((rc = sl.l1_inf.ensure(std::max(NGw * 2, mpts)))) return rc;
     if ((rc = sl.win.ensure(std::max((size_t)2 * PWw, (size_t)32) * 4 * C::ABI_W * 4))) return rc;        // A_j then S_j; or P and the marginals
-    if ((rc = sl.win_inf.ensure(std::max((size_t)2 * PWw, (size_t)32)))) return rc;
-    if ((rc = sl.dyn.ensure(msm::dyn_words(T) * 4))) return rc;
-    { const size_t hslots = 2 * (T / msm::HEAVY_RANGE + 2); if ((rc = sl.hpart.ensure(hslots * C::XW * 4))) return rc; if ((rc = sl.hpart_inf.ensure(hslots))) return rc; }
     (void)pt;
-    return DGPU_OK;
+    return sl.win_inf.ensure(std::max((size_t)2 * PWw, (size_t)32));
 }
 // sizes of `off` / `entries` for a sort kept outside a slot
 // a table's allocation: W rows of n prepared records, then one identity-flag byte per base (what the sort reads instead of the records' flag words)
@@ -521,46 +432,28 @@ int32_t pre_sort(Slot &sl, const PreTable &pt, const PreGeom &g, size_t boff, co
     int32_t rc;
     if ((rc = ws_pre<C>(sl, pt, g, n))) return rc;
     q.bad = sl.flags.as<uint32_t>();
-    const uint32_t heavy_thr = dyn ? 16u * (uint32_t)g.CH /* replaced on the device, dyn_chunk.hip.h */ : 0xffffffffu /* nothing flagged */;
-    const uint32_t dyn_args[6] = {(uint32_t)forced_chunk(), g.min_chunk, g.max_chunks, g.lanes_per_chunk, (uint32_t)g.T, g.NB};
+    const uint32_t heavy_thr = dyn ? 16u * (uint32_t)g.acc.CH /* replaced on the device, dyn_chunk.hip.h */ : 0xffffffffu /* nothing flagged */;
+    const uint32_t dyn_args[6] = {(uint32_t)forced_chunk(), g.acc.min_chunk, g.acc.max_chunks, g.acc.lanes_per_chunk, (uint32_t)g.acc.T, g.NB};
     StageTimer st(sl, "msm.psort");
     HIPCHK(hipMemsetAsync(sl.heavy.p, 0, 4, sl.stream));
     if (reset_flag) HIPCHK(hipMemsetAsync(sl.flags.p, 0, 4, sl.stream));
     launch_psort(sl.stream, q, g.NB, sl.cnt.as<uint32_t>(), sl.cursor.as<uint32_t>(), sl.bsums.as<uint32_t>(), sl.digits.p, off, entries,
-                 heavy_thr, sl.heavy.as<uint32_t>(), g.HEAVY_CAP, dyn_args, dyn);
+                 heavy_thr, sl.heavy.as<uint32_t>(), g.acc.HEAVY_CAP, dyn_args, dyn);
     return DGPU_OK;
 }
-// Stage 2a (pre_acc): accumulate + fix-up of one sorted list into bucket set `set` (merged into set 0 when set > 0).
+// Stage 2a (pre_acc): accumulate stage of one sorted list into bucket set `set` (acc_stage).
 // derive_dyn: `off` / `entries` come from a shared sort — chunking and heavy-bucket list are derived here from off[] (as the plain pipeline does)
 template <class C>
 int32_t pre_acc(Slot &sl, const PreTable &pt, const PreGeom &g, const uint32_t *off, const uint32_t *entries, bool derive_dyn, const msm::RowMap &map, size_t set) {
-    const uint32_t NB = g.NB; const size_t T = g.T;
-    uint32_t *const dyn = sl.dyn.as<uint32_t>();
-    const uint32_t heavy_thr = 16u * (uint32_t)g.CH;      // (replaced on the device by dyn[])
+    const uint32_t NB = g.NB; const AccGeom &a = g.acc;
     hipStream_t s = sl.stream;
-    uint32_t *const bucket = sl.bucket.as<uint32_t>() + set * soa_points(NB) * C::XW;
-    uint8_t *const bucket_inf = sl.bucket_inf.as<uint8_t>() + set * (size_t)NB;
-    HIPCHK(hipMemsetAsync(bucket_inf, 1, NB, s));
+    HIPCHK(hipMemsetAsync(sl.bucket_inf.as<uint8_t>() + set * (size_t)NB, 1, NB, s));
     if (derive_dyn) {
         HIPCHK(hipMemsetAsync(sl.heavy.p, 0, 4, s));
-        launch_dyn_chunk(s, off + NB, (uint32_t)forced_chunk(), g.min_chunk, g.max_chunks, g.lanes_per_chunk, (uint32_t)T, dyn, NB);
-        launch_flag_heavy(s, off, NB, dyn, sl.heavy.as<uint32_t>(), g.HEAVY_CAP);
+        launch_dyn_chunk(s, off + NB, (uint32_t)forced_chunk(), a.min_chunk, a.max_chunks, a.lanes_per_chunk, (uint32_t)a.T, sl.dyn.as<uint32_t>(), NB);
+        launch_flag_heavy(s, off, NB, sl.dyn.as<uint32_t>(), sl.heavy.as<uint32_t>(), a.HEAVY_CAP);
     }
-    {
-        StageTimer st(sl, "msm.accumulate");
-        if (derive_dyn) launch_accumulate_skip_identity<C>(s, (const uint32_t *)pt.tab, entries, off, NB, bucket, bucket_inf,
-                           sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(), sl.head_b.as<uint32_t>(), sl.tail_b.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, (uint32_t)g.CH, dyn, map);
-        else launch_accumulate<C>(s, (const uint32_t *)pt.tab, entries, off, NB, bucket, bucket_inf,
-                           sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(), sl.head_b.as<uint32_t>(), sl.tail_b.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, (uint32_t)g.CH, 0xffffffffu, dyn);
-    }
-    {
-        StageTimer st(sl, "msm.fixup");
-        launch_fixup<C>(s, NB, bucket, bucket_inf, sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(),
-                           sl.head_b.as<uint32_t>(), sl.tail_b.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, off, heavy_thr, dyn);
-        launch_fixup_heavy<C>(s, sl.heavy.as<uint32_t>(), g.HEAVY_CAP, off, (uint32_t)g.CH, NB, bucket, bucket_inf,
-                           sl.head.as<uint32_t>(), sl.tail.as<uint32_t>(), sl.part_inf.as<uint8_t>(), T, dyn, sl.hpart.as<uint32_t>(), sl.hpart_inf.as<uint8_t>());
-        if (set > 0) launch_merge_buckets<C>(s, NB, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), bucket, bucket_inf);
-    }
+    acc_stage<C>(sl, a, NB, (const uint32_t *)pt.tab, off, entries, set, derive_dyn, map, 16u * (uint32_t)a.CH /* replaced on the device by dyn[] */);
     return DGPU_OK;
 }
 // Stage 2b (pre_finish): reduction of bucket set 0, read-back, host fold.  check_flag: the slot's flag word (a scalar >= 2^255 seen by this call's sort)
@@ -583,38 +476,15 @@ int32_t pre_finish(Slot &sl, const PreGeom &g, bool check_flag, uint64_t *out_xy
         }
     }
     HIPCHK(hipGetLastError());
-    const size_t npts = marginals ? (size_t)nm + 1 : (size_t)2 * PW;
-    std::vector<uint64_t> hwin(npts * 2 * C::ABI_W);
-    std::vector<uint8_t> hinf(npts);
-    // (into the slot's pinned scratch: see the plain pipeline's read-back above)
-    const size_t wb = npts * 4 * C::ABI_W * 4, ib = (npts + 7) & ~(size_t)7;
-    std::vector<uint8_t> big;                        // (a forced geometry with hundreds of pseudo-windows — a knob of the twin — does not fit the pinned scratch: pageable then)
-    if (wb + ib + 4 > Slot::HPIN_BYTES) big.resize(wb + ib + 4);
-    uint8_t *const hp = big.empty() ? (uint8_t *)sl.hpin : big.data();
-    memset(hp + wb + ib, 0, 4);
-    HIPCHK(hipMemcpyAsync(hp, sl.win.p, wb, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hp + wb, sl.win_inf.p, npts, hipMemcpyDeviceToHost, s));
-    if (check_flag) HIPCHK(hipMemcpyAsync(hp + wb + ib, sl.flags.p, 4, hipMemcpyDeviceToHost, s));      // (a shared sort was checked by dgpu_scalars_sort)
-    auto tsync0 = std::chrono::steady_clock::now();
-    HIPCHK(hipStreamSynchronize(s));
-    auto tsync1 = std::chrono::steady_clock::now();
-    if (gs.prof) prof_flush(sl);
-    uint32_t hbad; memcpy(&hbad, hp + wb + ib, 4);
-    if (hbad) return DGPU_E_BADARG;                  // a scalar >= 2^255 (sort_kernels.hip.h k_digit_codes)
-    memcpy(hwin.data(), hp, wb); memcpy(hinf.data(), hp + wb, npts);
-    if (marginals) host_fold_marginals<HF>(hwin.data(), hinf.data(), nm, g.mshift + (C::NFP == 2 ? 1 : 0), out_xyz);
-    else host_fold_shared<HF>(hwin.data(), hinf.data(), hwin.data() + (size_t)PW * 2 * C::ABI_W, hinf.data() + PW, PW, g.lb, out_xyz);
-    if (gs.prof) {
-        auto t2 = std::chrono::steady_clock::now();
-        prof_add_host("msm.host_wait", std::chrono::duration<double, std::milli>(tsync1 - tsync0).count());
-        prof_add_host("msm.host_fold", std::chrono::duration<double, std::milli>(t2 - tsync1).count());
-    }
-    return DGPU_OK;
+    return read_back_fold<C>(sl, marginals ? (size_t)nm + 1 : (size_t)2 * PW, check_flag, [&](const uint64_t *hwin, const uint8_t *hinf) {
+        if (marginals) host_fold_marginals<HF>(hwin, hinf, nm, g.mshift + (C::NFP == 2 ? 1 : 0), out_xyz);
+        else host_fold_shared<HF>(hwin, hinf, hwin + (size_t)PW * 2 * C::ABI_W, hinf + PW, PW, g.lb, out_xyz);
+    });
 }
 template <class C, class HF>
 int32_t pre_tail(Slot &sl, const PreTable &pt, const PreGeom &g, const uint32_t *off, const uint32_t *entries, bool derive_dyn, uint64_t *out_xyz, const msm::RowMap &map = msm::RowMap{}) {
     int32_t rc;
-    if ((rc = ws_pre<C>(sl, pt, g, g.Emax / pt.W))) return rc;
+    if ((rc = ws_pre<C>(sl, pt, g, g.acc.Emax / pt.W))) return rc;
     if ((rc = pre_acc<C>(sl, pt, g, off, entries, derive_dyn, map, 0))) return rc;
     return pre_finish<C, HF>(sl, g, !derive_dyn, out_xyz);
 }
@@ -762,6 +632,7 @@ struct RawBases {
     template <class C> static RawBases packed(const uint64_t *xy, const uint8_t *is_inf) {
         return RawBases{(const uint8_t *)xy, (size_t)2 * C::ABI_W * 4, 0, (size_t)C::ABI_W * 4, msm::NO_INF_OFF, is_inf};
     }
+    RawBases from(size_t lo) const { RawBases r = *this; r.p = p + lo * stride; if (is_inf) r.is_inf = is_inf + lo; return r; }      // the view of points lo ..
     template <class C> bool ok() const {
         const size_t fb = (size_t)C::ABI_W * 4;
         return stride >= 2 * fb && stride % 8 == 0 && x_off % 8 == 0 && y_off % 8 == 0 && x_off + fb <= stride && y_off + fb <= stride &&
@@ -816,6 +687,9 @@ inline int32_t stage_scalars(Slot &sl, const uint64_t *h, size_t lo, size_t hi, 
 }
 inline int32_t stage_scalars(Slot &sl, const uint64_t *h, size_t n, bool mont, uint32_t *d_out) { return stage_scalars(sl, h, 0, n, mont, d_out); }
 
+// error paths of calls that read the caller's memory: nothing of ours may still read the caller's buffers when the call returns
+inline void drain(Slot &sl) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); }
+
 // ---- workspaces sized ahead of the calls (no hipMalloc on an MSM path in steady state) ---------------------------------------------------
 // what: 1 = one-shot call of n terms (raw bases of `stride` bytes + scalars + prepared records + plain pipeline), 2 = fresh host scalars on a
 // plain handle of n terms, 3 = the same on a table (pt)
@@ -851,12 +725,13 @@ template <class C> int32_t reserve_slots(int what, size_t n, size_t stride, cons
 }
 // the same for the slots that are idle right now (called by a one-shot call that had to grow its own slot: the other host threads of the
 // caller — rayon workers — will come with the same size next, and would each stall the device in hipMalloc / hipFree)
-template <class C> void reserve_idle_slots(const Slot *mine, int what, size_t n, size_t stride) {
+// (`ws(slot)`: the workspace function of the shape)
+template <class WS> void reserve_idle_slots(const Slot *mine, WS ws) {
     Ctx &cx = cur();
     for (int k = 0; k < N_SLOTS; k++) {
         Slot &o = cx.slots[k];
         if (&o == mine || !o.mu.try_lock()) continue;
-        (void)ws_for<C>(o, what, n, stride, nullptr);
+        (void)ws(o);
         o.mu.unlock();
     }
 }
@@ -878,11 +753,11 @@ int32_t msm_oneshot_here(const RawBases &rb, const uint64_t *scalars, size_t n, 
     rc = msm_device_ranges<C, HF>(sl, sl.prepped.as<uint32_t>(), sl.in_scalars.as<uint32_t>(), n, K, out, true,
                                   [&](size_t, size_t lo, size_t hi) { return stage_scalars(sl, scalars, lo, hi, mont, sl.in_scalars.as<uint32_t>()); },
                                   [&](size_t, size_t lo, size_t hi) { return stage_bases<C>(sl, rb, lo, hi, sl.prepped.as<uint32_t>()); });
-    if (rc) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); }      // nothing of ours may still read the caller's buffers
-    if (grew) reserve_idle_slots<C>(&sl, 1, n, rb.stride);
+    if (rc) drain(sl);
+    if (grew) reserve_idle_slots(&sl, [&](Slot &o) { return ws_for<C>(o, 1, n, rb.stride, nullptr); });
     return rc;
 }
-template <class C, class HF> bool msm_oneshot_cached(const RawBases &rb, const uint64_t *scalars, size_t n, bool mont, uint64_t *out, int kind, int32_t &rc);      // (defined below)
+template <class C, class HF> bool msm_oneshot_cached(const RawBases &rb, const uint64_t *scalars, size_t n, bool mont, uint64_t *out, int kind, int32_t &rc);      // (msm_cache.hip.h: whoever instantiates msm_oneshot / msm_oneshot_ctx includes it)
 // one-shot MSM on the calling thread's context: from the resident-bases cache if the caller's points are (or now become) resident, else from host memory
 template <class C, class HF>
 int32_t msm_oneshot_ctx(const RawBases &rb, const uint64_t *scalars, size_t n, bool mont, uint64_t *out) {
@@ -908,8 +783,7 @@ int32_t msm_oneshot(const RawBases &rb, const uint64_t *scalars, size_t n, bool 
             std::vector<uint64_t> parts(cx.size() * JW);
             const int32_t rc = run_shards(cx.size(), [&](size_t k) {
                 CtxScope here(cx[k]);
-                RawBases part = rb; part.p = rb.p + lo[k] * rb.stride; if (rb.is_inf) part.is_inf = rb.is_inf + lo[k];
-                return msm_oneshot_ctx<C, HF>(part, scalars + lo[k] * 4, lo[k + 1] - lo[k], mont, parts.data() + k * JW);
+                return msm_oneshot_ctx<C, HF>(rb.from(lo[k]), scalars + lo[k] * 4, lo[k + 1] - lo[k], mont, parts.data() + k * JW);
             });
             if (rc) return rc;
             return host_fold_jacobian<HF>(parts.data(), cx.size(), out);
@@ -978,433 +852,8 @@ int32_t msm_handle(uint64_t bases, size_t offset, const uint64_t *scalars, size_
         SmallSub sub; const bool have = K == 1 && n && small_sub_for<C>(sl, bases, hb.h, offset, n, sub);
         rc = msm_device_ranges<C, HF>(sl, (const uint32_t *)hb.h.p + offset * C::AFF_STRIDE, sl.in_scalars.as<uint32_t>(), n, K, out, false, ready, nothing, have ? &sub : nullptr);
     }
-    if (rc) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); }      // nothing of ours may still read the caller's scalars
+    if (rc) drain(sl);
     return rc;
-}
-
-// ---- many rows of scalars over one plain handle in one call (many_kernels.hip.h) -----------------------------------------------------------
-// rows per launch: 2^17 terms' worth, at most 4096 rows — the scalars, 16 window sums per row and (rows of more than 128 terms) up to 64 partials per
-// window stay below ~70 MB of the slot's grow-only buffers whatever m; dgpu_set_many_chunk_rows (development surface) overrides it
-inline size_t many_chunk_rows(size_t n) {
-    const int forced = gs.many_chunk.load();
-    if (forced > 0) return (size_t)forced;
-    const size_t r = ((size_t)1 << 17) / std::max<size_t>(n, 1);
-    return std::min<size_t>(4096, std::max<size_t>(r, 1));
-}
-template <class C> int32_t ws_many(Slot &sl, size_t n, size_t rows, const ManyGeom &g) {
-    int32_t rc;
-    typedef typename C::ACC A;
-    constexpr size_t WPS = SMALL_MSM_W / SMALL_MSM_S;
-    if ((rc = sl.flags.ensure(64))) return rc;
-    if ((rc = sl.in_scalars.ensure(rows * n * 32))) return rc;
-    if ((rc = sl.bucket.ensure(rows * WPS * A::XW * 4))) return rc;                      // the window sums and their flags
-    if ((rc = sl.bucket_inf.ensure(rows * WPS))) return rc;
-    if (g.nblk > 1) {
-        if ((rc = sl.head.ensure(rows * WPS * g.nblk * A::XW * 4))) return rc;          // the blocks' partials, their flags, the per-window block counters
-        if ((rc = sl.part_inf.ensure(rows * WPS * g.nblk))) return rc;
-        if ((rc = sl.cnt.ensure(rows * WPS * 4))) return rc;
-    }
-    if ((rc = sl.win.ensure(rows * 3 * C::ABI_W * 4))) return rc;                        // the rows' results and their identity flags
-    return sl.win_inf.ensure(rows);
-}
-// the rows on the device, chunk by chunk: scalars up (rows packed: what lies between them in the caller's memory never crosses), tree, fold, results down
-template <class C>
-int32_t msm_device_many(Slot &sl, const SmallSub &sub, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, bool mont, uint64_t *out, uint8_t *out_inf) {
-    int32_t rc;
-    constexpr size_t JW = 3 * C::ABI_W / 2;                                               // u64 words per result
-    const ManyGeom g = many_geometry(n);
-    const size_t chunk = std::min(m, many_chunk_rows(n));
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws_many<C>(sl, n, chunk, g))) return rc;
-    if (g_dev_allocs.load() != allocs0) {                 // a new shape: the caller's other host threads come with it next (reserve_idle_slots: the one-shot calls do the same)
-        Ctx &cx = cur();
-        for (int k = 0; k < N_SLOTS; k++) {
-            Slot &o = cx.slots[k];
-            if (&o == &sl || !o.mu.try_lock()) continue;
-            (void)ws_many<C>(o, n, chunk, g);
-            o.mu.unlock();
-        }
-    }
-    hipStream_t s = sl.stream;
-    uint32_t *const d_sc = sl.in_scalars.as<uint32_t>(), *const d_bad = sl.flags.as<uint32_t>();
-    HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
-    uint32_t *const hbad = (uint32_t *)sl.hpin;
-    for (size_t r0 = 0; r0 < m; r0 += chunk) {
-        const size_t rows = std::min(chunk, m - r0);
-        const uint64_t *src = scalars + r0 * row_stride * 4;
-        hipEvent_t ev = sl.copy_ev[sl.ev_next++ % (Slot::N_COPY_EV + 1)];
-        if (row_stride == n) HIPCHK(hipMemcpyAsync(d_sc, src, rows * n * 32, hipMemcpyHostToDevice, sl.cstream));
-        else HIPCHK(hipMemcpy2DAsync(d_sc, n * 32, src, row_stride * 32, n * 32, rows, hipMemcpyHostToDevice, sl.cstream));
-        HIPCHK(hipEventRecord(ev, sl.cstream));
-        HIPCHK(hipStreamWaitEvent(s, ev, 0));
-        if (mont) ntt::launch_fr_mont_to_canonical(s, d_sc, rows * n);
-        if (g.nblk > 1) HIPCHK(hipMemsetAsync(sl.cnt.p, 0, rows * (SMALL_MSM_W / SMALL_MSM_S) * 4, s));
-        {
-            StageTimer st(sl, "msm.many_tree");
-            launch_many_tree<C>(s, sub.tab, sub.tab_inf, d_sc, n, n, rows, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(), sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_bad);
-        }
-        {
-            StageTimer st(sl, "msm.many_fold");
-            launch_many_fold<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), rows, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out + r0 * JW, sl.win.p, rows * JW * 8, hipMemcpyDeviceToHost, s));
-        if (out_inf) HIPCHK(hipMemcpyAsync(out_inf + r0, sl.win_inf.p, rows, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(hbad, d_bad, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));                  // (the next chunk's scalars overwrite this one's)
-        if (gs.prof) prof_flush(sl);
-        if (*hbad) return DGPU_E_BADARG;                  // a scalar >= 2^255 somewhere in the block: the whole call is refused
-    }
-    return DGPU_OK;
-}
-template <class C, class HF>
-int32_t msm_handle_many(uint64_t bases, size_t offset, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, int mont, uint64_t *out, uint8_t *out_inf, int kind) {
-    if (m == 0) return DGPU_OK;
-    constexpr size_t JW = 3 * sizeof(HF) / 8;
-    if (!out || (n && (!scalars || row_stride < n)) || m >= (1ull << 31) || n >= (1ull << 31) || row_stride >= (1ull << 31)) return DGPU_E_BADARG;
-    if (!cur().ready) return DGPU_E_NODEVICE;             // (before the size threshold, like the single call)
-    if (!tl_no_min && m * n < std::min<size_t>(gs.min_gpu_n, DGPU_MIN_GPU_N_HANDLE)) return DGPU_E_TOO_SMALL;      // the batch is the unit: many one-term rows are device work
-    bool served = false;
-    int32_t rc = DGPU_OK;
-    {
-        HandleRef hb(bases);
-        if (!hb.ok || (hb.h.kind != kind && hb.h.kind != kind + 9) || offset > hb.h.n || n > hb.h.n - offset) return DGPU_E_BADARG;
-        if (n == 0) {                                     // every row is the empty sum
-            for (size_t j = 0; j < m; j++) { write_identity<HF>(out + j * JW); if (out_inf) out_inf[j] = 1; }
-            return DGPU_OK;
-        }
-        // the new kernels serve plain handles within the small path's reach; anything else (a precomputed table, more than 8192 bases, the small path switched
-        // off, no memory for the table) runs its rows through the single-row driver below
-        if (hb.h.kind == kind && hb.h.n <= SMALL_MSM_MAX_N && n <= gs.small_max.load()) {
-            CtxScope on_owner(hb.h.ctx);
-            SLOT_ACQUIRE(L, sl);
-            HIPCHK(hipSetDevice(cur().device));
-            SmallSub sub;
-            if (small_sub_for<C>(sl, bases, hb.h, offset, n, sub, true)) {
-                served = true;
-                rc = msm_device_many<C>(sl, sub, scalars, row_stride, n, m, mont != 0, out, out_inf);
-                if (rc) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); }      // nothing of ours may still read the caller's scalars
-            }
-        }
-    }
-    if (served) return rc;
-    for (size_t j = 0; j < m; j++) {
-        if ((rc = msm_handle<C, HF>(bases, offset, scalars + 4 * row_stride * j, n, mont, out + j * JW, kind, false))) return rc;
-        if (out_inf) { uint64_t z = 0; for (size_t k = 2 * JW / 3; k < JW; k++) z |= out[j * JW + k]; out_inf[j] = z == 0; }
-    }
-    return DGPU_OK;
-}
-
-// ---- many small MSMs, each over its own bases, in one call (seg_kernels.hip.h) ----------------------------------------------------------------
-// Segments travel in chunks of whole segments: at most SEG_CHUNK_TERMS terms (the table of eight multiples per base is 1.6 KB per G1 base, 3.3 KB per G2
-// base: 109 / 218 MB) and SEG_CHUNK_SEGS segments (64 window sums each: 55 / 109 MB) per chunk; dgpu_set_msm_segments (development surface) overrides the
-// term limit.  From SEG_DEVICE_FOLD_MIN segments in a chunk on, k_seg_fold folds them on the device; below, the host threads' host_fold does (up to 16 threads per
-// chunk through par_run: several calls in flight with few segments each share the host's cores).
-constexpr size_t SEG_CHUNK_TERMS = (size_t)1 << 16, SEG_CHUNK_SEGS = 4096;
-constexpr size_t SEG_DEVICE_FOLD_MIN = 24;              // PROVISIONAL, not measured: the crossover is what tests/perf/msm_segments_timing.py's fold sweep finds on an MI355X
-template <class C> int32_t ws_seg(Slot &sl, const RawBases &rb, size_t terms, size_t nseg, size_t blocks, size_t pslots) {
-    int32_t rc;
-    typedef typename C::ACC A;
-    constexpr size_t W = SMALL_MSM_W, WIN_BYTES = std::max<size_t>(A::XW * 4, 4 * C::ABI_W * 4);      // a window sum in either form
-    if ((rc = sl.flags.ensure(64))) return rc;
-    if ((rc = sl.in_scalars.ensure(terms * 32))) return rc;
-    if ((rc = ws_stage_bases<C>(sl, rb, terms))) return rc;
-    if ((rc = sl.prepped.ensure(terms * C::AFF_STRIDE * 4))) return rc;
-    if ((rc = sl.bucket.ensure(terms * SMALL_MSM_E * A::XW * 4))) return rc;               // the table and its identity flags
-    if ((rc = sl.bucket_inf.ensure(terms * SMALL_MSM_E))) return rc;
-    if ((rc = sl.entries.ensure(blocks * 64 * sizeof(SegDesc)))) return rc;                 // the descriptors
-    if ((rc = sl.l1.ensure(nseg * W * WIN_BYTES))) return rc;                               // the window sums and their flags
-    if ((rc = sl.l1_inf.ensure(nseg * W))) return rc;
-    if (pslots) {
-        if ((rc = sl.head.ensure(pslots * W * A::XW * 4))) return rc;                       // the blocks' partials, their flags, the per-window block counters
-        if ((rc = sl.part_inf.ensure(pslots * W))) return rc;
-        if ((rc = sl.cnt.ensure(pslots * W * 4))) return rc;
-    }
-    if ((rc = sl.win.ensure(nseg * 3 * C::ABI_W * 4))) return rc;                           // the results and their identity flags
-    return sl.win_inf.ensure(nseg);
-}
-inline bool jac_is_identity(const uint64_t *xyz, size_t JW) { uint64_t z = 0; for (size_t k = 2 * JW / 3; k < JW; k++) z |= xyz[k]; return z == 0; }
-// segments [s0, s1) (all within the small path's reach, T > 0 terms in all) on the device: one upload, table, tree, fold (device or host), results down
-template <class C, class HF>
-int32_t msm_seg_chunk(Slot &sl, const RawBases &rb, const uint64_t *scalars, const uint64_t *seg_end, size_t s0, size_t s1, bool mont, const SegLayout &lay, bool device_fold,
-                      std::vector<uint64_t> &hwin, std::vector<uint8_t> &hinf, uint64_t *out, uint8_t *out_inf) {
-    constexpr size_t JW = 3 * sizeof(HF) / 8, W = SMALL_MSM_W, WW = 4 * sizeof(HF) / 8;   // u64 words per result / per window sum
-    const size_t t0 = s0 ? seg_end[s0 - 1] : 0, T = seg_end[s1 - 1] - t0, ns = s1 - s0;
-    hipStream_t s = sl.stream;
-    uint32_t *const d_sc = sl.in_scalars.as<uint32_t>(), *const d_bad = sl.flags.as<uint32_t>();
-    uint32_t *const hbad = (uint32_t *)sl.hpin;
-    int32_t rc;
-    HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
-    HIPCHK(hipMemcpyAsync(sl.entries.p, lay.desc.data(), lay.blocks * 64 * sizeof(SegDesc), hipMemcpyHostToDevice, sl.cstream));      // (ordered before the scalars' event)
-    RawBases part = rb; part.p = rb.p + t0 * rb.stride; if (rb.is_inf) part.is_inf = rb.is_inf + t0;
-    if ((rc = stage_scalars(sl, scalars + t0 * 4, T, mont, d_sc))) return rc;
-    if ((rc = stage_bases<C>(sl, part, T, sl.prepped.as<uint32_t>()))) return rc;
-    {
-        StageTimer st(sl, "msm.small_table");
-        launch_small_table<C>(s, sl.prepped.as<uint32_t>(), T, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>());
-    }
-    if (lay.pslots) HIPCHK(hipMemsetAsync(sl.cnt.p, 0, lay.pslots * W * 4, s));
-    {
-        StageTimer st(sl, "msm.seg_tree");
-        launch_seg_tree<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_sc, sl.entries.p, lay.blocks, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(),
-                           sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), !device_fold, d_bad);
-    }
-    if (device_fold) {
-        {
-            StageTimer st(sl, "msm.seg_fold");
-            launch_seg_fold<C>(s, sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), ns, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out + s0 * JW, sl.win.p, ns * JW * 8, hipMemcpyDeviceToHost, s));
-        if (out_inf) HIPCHK(hipMemcpyAsync(out_inf + s0, sl.win_inf.p, ns, hipMemcpyDeviceToHost, s));
-    } else {
-        HIPCHK(hipGetLastError());
-        hwin.resize(ns * W * WW); hinf.resize(ns * W);
-        HIPCHK(hipMemcpyAsync(hwin.data(), sl.l1.p, ns * W * WW * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(hinf.data(), sl.l1_inf.p, ns * W, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipMemcpyAsync(hbad, d_bad, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                      // (the next chunk's operands overwrite this one's)
-    if (gs.prof) prof_flush(sl);
-    if (*hbad) return DGPU_E_BADARG;                      // a scalar >= 2^255 somewhere in the chunk: the whole call is refused
-    if (!device_fold) {
-        const size_t TH = std::min<size_t>(std::min<size_t>(ns, 16), std::max<size_t>(1, std::thread::hardware_concurrency()));
-        auto tail = [&](size_t g) {
-            host_fold<HF>(hwin.data() + g * W * WW, hinf.data() + g * W, (int)W, SMALL_MSM_C, out + (s0 + g) * JW);
-            if (out_inf) out_inf[s0 + g] = jac_is_identity(out + (s0 + g) * JW, JW);
-        };
-        if (TH <= 1) { for (size_t g = 0; g < ns; g++) tail(g); }
-        else if ((rc = par_run(TH, [&](size_t k) -> int32_t { for (size_t g = k; g < ns; g += TH) tail(g); return DGPU_OK; }))) return rc;
-    }
-    return DGPU_OK;
-}
-template <class C, class HF>
-int32_t msm_segments(const uint64_t *bases, const uint8_t *is_inf, const uint64_t *scalars, size_t N, const uint64_t *seg_end, size_t nseg, int mont, uint64_t *out, uint8_t *out_inf) {
-    if (nseg == 0) return DGPU_OK;
-    constexpr size_t JW = 3 * sizeof(HF) / 8;
-    if (!bases || !scalars || !out || !seg_end || N >= (1ull << 31)) return DGPU_E_BADARG;
-    { uint64_t prev = 0; for (size_t g = 0; g < nseg; g++) { if (seg_end[g] < prev) return DGPU_E_BADARG; prev = seg_end[g]; } if (prev != N) return DGPU_E_BADARG; }
-    if (!cur().ready) return DGPU_E_NODEVICE;             // (before the size threshold, like the single call)
-    if (!tl_no_min && N < gs.min_gpu_n) return DGPU_E_TOO_SMALL;      // the batch is the unit: many one-term segments are device work
-    const RawBases rb = RawBases::packed<C>(bases, is_inf);
-    const size_t reach = std::min<size_t>(SMALL_MSM_MAX_N, gs.small_max.load());
-    const int forced_terms = gs.seg_chunk.load(), forced_fold = gs.seg_fold.load();
-    const size_t chunk_terms = forced_terms > 0 ? (size_t)forced_terms : SEG_CHUNK_TERMS;
-    auto len = [&](size_t g) { return (size_t)(seg_end[g] - (g ? seg_end[g - 1] : 0)); };
-    // the chunks: runs of whole segments within the small path's reach; a longer segment ends the run and goes through the single-call driver afterwards
-    struct Chunk { size_t s0, s1; };
-    std::vector<Chunk> chunks; std::vector<size_t> slow;
-    for (size_t g = 0; g < nseg;) {
-        if (len(g) > reach) { slow.push_back(g++); continue; }
-        size_t e = g, terms = 0;
-        while (e < nseg && len(e) <= reach && e - g < SEG_CHUNK_SEGS && (e == g || terms + len(e) <= chunk_terms)) terms += len(e++);
-        chunks.push_back(Chunk{g, e});
-        g = e;
-    }
-    if (!chunks.empty()) {
-        SLOT_ACQUIRE(L, sl);
-        HIPCHK(hipSetDevice(cur().device));
-        // one pass over the layouts for the workspace (grow-only; a shape already seen allocates nothing), one more to run them
-        SegLayout lay;
-        size_t mt = 0, ms = 0, mb = 0, mp = 0;
-        for (const Chunk &c : chunks) {
-            const size_t T = seg_end[c.s1 - 1] - (c.s0 ? seg_end[c.s0 - 1] : 0);
-            if (T == 0) continue;
-            seg_layout(seg_end, c.s0, c.s1, lay);
-            mt = std::max(mt, T); ms = std::max(ms, c.s1 - c.s0); mb = std::max(mb, lay.blocks); mp = std::max(mp, lay.pslots);
-        }
-        int32_t rc;
-        const uint64_t allocs0 = g_dev_allocs.load();
-        if (mt && (rc = ws_seg<C>(sl, rb, mt, ms, mb, mp))) return rc;
-        if (g_dev_allocs.load() != allocs0) {             // a new shape: the caller's other host threads come with it next (msm_device_many does the same)
-            Ctx &cx = cur();
-            for (int k = 0; k < N_SLOTS; k++) {
-                Slot &o = cx.slots[k];
-                if (&o == &sl || !o.mu.try_lock()) continue;
-                (void)ws_seg<C>(o, rb, mt, ms, mb, mp);
-                o.mu.unlock();
-            }
-        }
-        std::vector<uint64_t> hwin; std::vector<uint8_t> hinf;
-        for (const Chunk &c : chunks) {
-            const size_t T = seg_end[c.s1 - 1] - (c.s0 ? seg_end[c.s0 - 1] : 0), ns = c.s1 - c.s0;
-            if (T == 0) {                                 // nothing but empty segments
-                for (size_t g = c.s0; g < c.s1; g++) { write_identity<HF>(out + g * JW); if (out_inf) out_inf[g] = 1; }
-                continue;
-            }
-            seg_layout(seg_end, c.s0, c.s1, lay);
-            const bool device_fold = forced_fold == 2 || (forced_fold != 1 && ns >= SEG_DEVICE_FOLD_MIN);
-            rc = msm_seg_chunk<C, HF>(sl, rb, scalars, seg_end, c.s0, c.s1, mont != 0, lay, device_fold, hwin, hinf, out, out_inf);
-            if (rc) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); return rc; }      // nothing of ours may still read the caller's buffers
-        }
-    }
-    // segments beyond the small path's reach: the single-call driver, one after the other (the slot is released: that driver takes its own)
-    for (size_t g : slow) {
-        const size_t lo = g ? seg_end[g - 1] : 0;
-        RawBases part = rb; part.p = rb.p + lo * rb.stride; if (rb.is_inf) part.is_inf = rb.is_inf + lo;
-        const int32_t rc = msm_oneshot_ctx<C, HF>(part, scalars + lo * 4, len(g), mont != 0, out + g * JW);
-        if (rc) return rc;
-        if (out_inf) out_inf[g] = jac_is_identity(out + g * JW, JW);
-    }
-    return DGPU_OK;
-}
-
-// ---- the resident-bases cache (bases_cache.hpp) --------------------------------------------------------------------------------------------
-// device bytes of an entry of n points as a table of width c (0: the automatic choice; a handle too short for a table stays plain)
-template <class C> inline size_t cache_entry_bytes(size_t n, int c) {
-    if (c == 0) c = choose_c_pre(n);
-    if (c == 0) return n * (size_t)C::AFF_STRIDE * 4 + (n <= SMALL_MSM_MAX_N ? small_sub_bytes<C>(n) : 0);
-    return pre_tab_bytes<C>(n, 255 / c + 1);
-}
-// The cache's state machine for one sighting of `rb` (n points): true = `e` is a resident entry that still matches the caller's memory (records
-// [off, off + n) of its handle; the shared_ptr pins it), false = not resident (first sighting, another thread is filling the entry, a stale or oversized
-// key, a failed fill): the caller takes the points from host memory.  table_c: window width of the table a fill builds (0 = automatic).
-// verify_now = false: the caller checks the entry against the host memory itself (msm_oneshot_cached in the exact mode: beside the MSM, not in front of it)
-template <class C>
-bool cache_acquire(const RawBases &rb, size_t n, int kind, int table_c, std::shared_ptr<CacheEntry> &e, size_t &off, bool verify_now = true, bool *was_resident = nullptr) {
-    const CacheKey key{rb.p, n, rb.stride, rb.x_off, rb.y_off, rb.inf_off, rb.is_inf, kind, cur_index()};
-    constexpr int words = C::ABI_W / 2;
-    std::vector<std::shared_ptr<CacheEntry>> dropped;        // (destroyed after the locks are released: an entry's destructor frees its handle)
-    e.reset(); off = 0;
-    bool fill = false;
-    {
-        std::lock_guard<std::mutex> lk(gcache.mu);
-        for (auto &c : gcache.entries) if (c->state == CacheEntry::READY && key.inside(c->k, &off)) { e = c; e->last_use = ++gcache.tick; break; }
-    }
-    if (was_resident) *was_resident = (bool)e;
-    if (e && verify_now && !cache_verify(*e, key, off, words)) {            // the host memory behind the entry changed: forget it; this sighting is the new contents' first
-        std::lock_guard<std::mutex> lk(gcache.mu);
-        cache_remove_locked(e.get(), dropped);
-        gcache.stale++; e.reset();
-    }
-    if (e) return true;
-    off = 0;
-    const uint64_t fp = range_fingerprint(key, words);
-    size_t budget_auto = 0;
-    if (gcache.budget.load() == CACHE_BUDGET_AUTO) {          // a quarter of what the device has free now (resolved once; dgpu_set_bases_cache_bytes overrides)
-        size_t fr = 0, tot = 0;
-        if (hipSetDevice(cur().device) == hipSuccess && hipMemGetInfo(&fr, &tot) == hipSuccess) budget_auto = fr / 4; else (void)hipGetLastError();
-    }
-    {
-        std::lock_guard<std::mutex> lk(gcache.mu);
-        if (gcache.budget.load() == CACHE_BUDGET_AUTO) gcache.budget = budget_auto;
-        std::shared_ptr<CacheEntry> seen;
-        for (auto &c : gcache.entries) if (c->state != CacheEntry::READY && c->k.same(key)) { seen = c; break; }
-        if (!seen) {                                          // first sighting: remember the fingerprint
-            size_t n_seen = 0, oldest = gcache.entries.size();
-            for (size_t i = 0; i < gcache.entries.size(); i++) if (gcache.entries[i]->state == CacheEntry::SEEN) { n_seen++; if (oldest == gcache.entries.size() || gcache.entries[i]->last_use < gcache.entries[oldest]->last_use) oldest = i; }
-            if (n_seen >= CACHE_MAX_SEEN) { dropped.push_back(std::move(gcache.entries[oldest])); gcache.entries.erase(gcache.entries.begin() + oldest); }
-            auto c = std::make_shared<CacheEntry>(); c->k = key; c->fp = fp; c->last_use = ++gcache.tick;
-            gcache.entries.push_back(std::move(c));
-        } else if (seen->state == CacheEntry::SEEN) {
-            seen->last_use = ++gcache.tick;
-            if (seen->fp != fp) seen->fp = fp;                // other contents at the same address: a first sighting again
-            else if (cache_make_room_locked(cache_entry_bytes<C>(n, table_c), seen.get(), dropped)) { seen->state = CacheEntry::FILLING; e = seen; fill = true; }
-        }                                                     // (FILLING: another thread is uploading this key right now)
-    }
-    if (!fill) { gcache.misses++; return false; }
-    // second sighting: upload once (+ the per-record fingerprints), make it a table
-    e->rec_hash.resize(n);
-    uint64_t h = 0;
-    int32_t frc = bases_upload<C>(rb, n, &h, kind, &e->rec_hash);
-    if (!frc) {
-        frc = bases_precompute<C>(h, table_c, kind);
-        if (frc) { (void)dgpu_bases_free(h); h = 0; }
-    }
-    std::lock_guard<std::mutex> lk(gcache.mu);
-    if (frc) { cache_remove_locked(e.get(), dropped); e.reset(); gcache.misses++; return false; }
-    e->handle = h; e->bytes = cache_entry_bytes<C>(n, table_c); gcache.fills++;
-    bool listed = false;
-    for (auto &c : gcache.entries) if (c.get() == e.get()) listed = true;
-    // (not listed any more: dgpu_bases_cache_clear ran meanwhile — this call still uses the table, which goes when the call lets go of it)
-    if (listed) {
-        e->state = CacheEntry::READY; e->last_use = ++gcache.tick; gcache.used += e->bytes;
-        for (size_t i = 0; i < gcache.entries.size();) {      // an older entry that lies wholly inside the new one is redundant
-            size_t o; CacheEntry &c = *gcache.entries[i];
-            if (&c != e.get() && c.state == CacheEntry::READY && c.k.inside(e->k, &o)) { gcache.used -= c.bytes; dropped.push_back(std::move(gcache.entries[i])); gcache.entries.erase(gcache.entries.begin() + i); }
-            else i++;
-        }
-    }
-    return true;
-}
-// true: the call was served from a resident entry and rc is its answer; false: run it one-shot
-template <class C, class HF>
-bool msm_oneshot_cached(const RawBases &rb, const uint64_t *scalars, size_t n, bool mont, uint64_t *out, int kind, int32_t &rc) {
-    std::shared_ptr<CacheEntry> e; size_t off = 0;
-    // DGPU_CACHE_VERIFY_FULL: re-fingerprinting every record of a 2^20-point slice is 1.5 ms of host work — it runs BESIDE the MSM on the resident copy (whose
-    // result is thrown away if the check fails) instead of in front of it: 4.8 -> 3.3 ms per call, the sampled check's latency with the exact answer
-    const bool full = gcache.verify_samples.load(std::memory_order_relaxed) < 0;
-    bool was_resident = false;
-    if (!cache_acquire<C>(rb, n, kind, 0, e, off, !full, &was_resident)) return false;
-    if (full && was_resident) {
-        const CacheKey key{rb.p, n, rb.stride, rb.x_off, rb.y_off, rb.inf_off, rb.is_inf, kind, cur_index()};
-        bool same = true; int32_t mrc = DGPU_OK;
-        const int32_t prc = par_run(2, [&](size_t part) -> int32_t {
-            if (part == 0) mrc = msm_handle<C, HF>(e->handle, off, scalars, n, mont, out, kind, false);
-            else same = cache_verify(*e, key, off, C::ABI_W / 2);
-            return DGPU_OK;
-        });
-        if (prc) same = false;                                // (the two parts could not be run: nothing was checked and nothing may be taken from `out`)
-        if (!same) {                                          // the key changed under the entry: forget it, the one-shot path answers (and notes the new contents at its next call)
-            std::vector<std::shared_ptr<CacheEntry>> dropped;
-            std::lock_guard<std::mutex> lk(gcache.mu);
-            cache_remove_locked(e.get(), dropped);
-            gcache.stale++; return false;
-        }
-        rc = mrc;
-    } else
-    rc = msm_handle<C, HF>(e->handle, off, scalars, n, mont, out, kind, false);
-    if (rc != DGPU_OK && rc != DGPU_E_BADARG) {               // a device-side failure on the resident path: forget the entry, let the one-shot path answer
-        std::vector<std::shared_ptr<CacheEntry>> dropped;
-        std::lock_guard<std::mutex> lk(gcache.mu);
-        cache_remove_locked(e.get(), dropped);
-        gcache.misses++; return false;
-    }
-    gcache.hits++;
-    return true;
-}
-// A view of host bases as a handle for the duration of a larger call (dgpu_legogroth16_prove_host): the cache's entry when the WHOLE view is one
-// (pinned by *pin), else a temporary upload that view_release frees.  Never fails for want of a cache: the temporary upload is the one-shot path.
-// `check`: the entry was taken WITHOUT the stale-key check (the exact mode: view_verify runs it beside the proof, dock_prover.cpp)
-struct ViewPin { std::shared_ptr<CacheEntry> e; uint64_t temp = 0; bool check = false; CacheKey key{}; int words = 0; };
-template <class C>
-int32_t view_acquire(const RawBases &rb, size_t n, int kind, int table_c, uint64_t *handle, void **pin) {
-    if (!handle || !pin || (n && !rb.p) || n >= (1ull << 31) || !rb.ok<C>()) return DGPU_E_BADARG;
-    if (!cur().ready) return DGPU_E_NODEVICE;
-    ViewPin *vp = new ViewPin();
-    size_t off = 0;
-    const bool full = gcache.verify_samples.load(std::memory_order_relaxed) < 0;
-    bool was_resident = false;
-    if (n && gcache.enabled.load() && n >= gcache.min_n.load() && cache_acquire<C>(rb, n, kind, table_c, vp->e, off, !full, &was_resident)) {
-        if (off == 0 && vp->e->k.n == n) {
-            gcache.hits++; *handle = vp->e->handle; *pin = vp;
-            if (full && was_resident) { vp->check = true; vp->key = CacheKey{rb.p, n, rb.stride, rb.x_off, rb.y_off, rb.inf_off, rb.is_inf, kind, cur_index()}; vp->words = C::ABI_W / 2; }
-            return DGPU_OK;
-        }
-        vp->e.reset();                        // (a sub-range of a larger entry: the prover addresses its queries from row 0 — take the points from the host)
-    }
-    const int32_t rc = bases_upload<C>(rb, n, &vp->temp, kind);
-    if (rc) { delete vp; return rc; }
-    *handle = vp->temp; *pin = vp;
-    return DGPU_OK;
-}
-// the deferred stale-key check of a view (exact mode).  False: the host memory behind the entry changed — the entry is forgotten and whatever was computed
-// from it must be thrown away
-inline bool view_verify(void *pin) {
-    ViewPin *vp = (ViewPin *)pin;
-    if (!vp || !vp->check || !vp->e) return true;
-    if (cache_verify(*vp->e, vp->key, 0, vp->words)) return true;
-    std::vector<std::shared_ptr<CacheEntry>> dropped;
-    std::lock_guard<std::mutex> lk(gcache.mu);
-    cache_remove_locked(vp->e.get(), dropped);
-    gcache.stale++;
-    return false;
-}
-inline void view_release(void *pin) {
-    ViewPin *vp = (ViewPin *)pin;
-    if (!vp) return;
-    if (vp->temp) (void)dgpu_bases_free(vp->temp);
-    delete vp;
 }
 
 template <class C, class HF>
@@ -1422,79 +871,5 @@ int32_t msm_resident(uint64_t bases, size_t boff, uint64_t scalars, size_t soff,
     SmallSub sub; const bool have = n && small_sub_for<C>(sl, bases, hb.h, boff, n, sub);
     return msm_device<C, HF>(sl, (const uint32_t *)hb.h.p + boff * C::AFF_STRIDE, (const uint32_t *)hs.h.p + soff * 8, n, out, have ? &sub : nullptr);
 }
-
-// ---- several GPUs behind the ABI (SURVEY.md 8b `dgpu_msm_g1_sharded`, 8e point-chunk sharding) ----------------------------------------
-// One process, one context per device, one host thread per device inside the call: device k runs the whole pipeline on the terms
-// [lo_k, lo_{k+1}) and hands back one normalised Jacobian point (144 / 288 B); the partials are folded on the host.  No collective is
-// needed inside a process; the multi-process form (one rank per GPU, RCCL all_gather of the same partials) stays above the ABI.
-template <class C, class HF>
-int32_t msm_sharded_oneshot(const uint64_t *bases, const uint8_t *is_inf, const uint64_t *scalars, size_t n, int32_t ngpus, bool mont, uint64_t *out) {
-    if (!out || (n && (!bases || !scalars)) || n >= (1ull << 31) || ngpus < 0) return DGPU_E_BADARG;
-    const std::vector<int> cx = ready_contexts(ngpus);
-    if (cx.empty()) return DGPU_E_NODEVICE;
-    if (ngpus > 0 && (int)cx.size() < ngpus) return DGPU_E_BADARG;
-    if (!tl_no_min && n < gs.min_gpu_n) return DGPU_E_TOO_SMALL;
-    std::vector<size_t> lo; shard_bounds(n, cx.size(), lo);
-    const size_t JW = 3 * sizeof(HF) / 8, BW = 2 * sizeof(HF) / 8;
-    std::vector<uint64_t> parts(cx.size() * JW);
-    int32_t rc = run_shards(cx.size(), [&](size_t k) {
-        CtxScope here(cx[k]);
-        const size_t cnt = lo[k + 1] - lo[k];
-        return msm_oneshot_here<C, HF>(RawBases::packed<C>(bases + lo[k] * BW, is_inf ? is_inf + lo[k] : nullptr), scalars + lo[k] * 4, cnt, mont, parts.data() + k * JW);
-    });
-    if (rc) return rc;
-    return host_fold_jacobian<HF>(parts.data(), cx.size(), out);
-}
-template <class C>
-int32_t bases_upload_sharded(const uint64_t *bases, const uint8_t *is_inf, size_t n, int32_t ngpus, uint64_t *handle, int kind /* 1 | 2 */) {
-    if (!handle || (n && !bases) || n >= (1ull << 31) || ngpus < 0) return DGPU_E_BADARG;
-    const std::vector<int> cx = ready_contexts(ngpus);
-    if (cx.empty()) return DGPU_E_NODEVICE;
-    if (ngpus > 0 && (int)cx.size() < ngpus) return DGPU_E_BADARG;
-    ShardSet *ss = new ShardSet();
-    ss->n = n; ss->sub.assign(cx.size(), 0); shard_bounds(n, cx.size(), ss->lo);
-    const size_t BW = 2 * C::ABI_W / 2;           // u64 words per affine point
-    int32_t rc = run_shards(cx.size(), [&](size_t k) {
-        CtxScope here(cx[k]);
-        return bases_upload<C>(RawBases::packed<C>(bases + ss->lo[k] * BW, is_inf ? is_inf + ss->lo[k] : nullptr), ss->lo[k + 1] - ss->lo[k], &ss->sub[k], kind);
-    });
-    if (rc) { for (uint64_t h : ss->sub) if (h) (void)dgpu_bases_free(h); delete ss; return rc; }
-    *handle = register_handle(ss, n, kind + 6);       // 7 = G1 sharded, 8 = G2 sharded
-    return DGPU_OK;
-}
-// fresh host scalars against a sharded bases handle: shard k uploads and uses scalars [lo_k, min(lo_{k+1}, n))
-template <class C, class HF>
-int32_t msm_sharded_handle(uint64_t bases, const uint64_t *scalars, size_t n, int mont, uint64_t *out, int kind) {
-    if (!out || (n && !scalars)) return DGPU_E_BADARG;
-    HandleRef hb(bases);
-    if (!hb.ok || hb.h.kind != kind + 6 || n > hb.h.n) return DGPU_E_BADARG;
-    if (!tl_no_min && n < gs.min_gpu_n) return DGPU_E_TOO_SMALL;
-    const ShardSet &ss = *(const ShardSet *)hb.h.p;
-    const size_t G = ss.sub.size(), JW = 3 * sizeof(HF) / 8;
-    std::vector<uint64_t> parts(G * JW);
-    int32_t rc = run_shards(G, [&](size_t k) {
-        const size_t lo = std::min(ss.lo[k], n), hi = std::min(ss.lo[k + 1], n);
-        return msm_handle<C, HF>(ss.sub[k], 0, scalars + lo * 4, hi - lo, mont, parts.data() + k * JW, kind, false);
-    });
-    if (rc) return rc;
-    return host_fold_jacobian<HF>(parts.data(), G, out);
-}
-// both operands resident on their devices (inputs pre-sharded: BASELINE config 5's timed region)
-template <class C, class HF>
-int32_t msm_sharded_resident(uint64_t bases, uint64_t scalars, uint64_t *out, int kind) {
-    if (!out) return DGPU_E_BADARG;
-    HandleRef hb(bases), hs(scalars);
-    if (!hb.ok || !hs.ok || hb.h.kind != kind + 6 || hs.h.kind != 9) return DGPU_E_BADARG;
-    const ShardSet &sb = *(const ShardSet *)hb.h.p, &sv = *(const ShardSet *)hs.h.p;
-    if (sb.sub.size() != sv.sub.size() || sv.n > sb.n) return DGPU_E_BADARG;
-    for (size_t k = 0; k < sb.sub.size(); k++) if (sv.lo[k] != std::min(sb.lo[k], sv.n) || sv.lo[k + 1] != std::min(sb.lo[k + 1], sv.n)) return DGPU_E_BADARG;
-    if (sv.n < gs.min_gpu_n) return DGPU_E_TOO_SMALL;
-    const size_t G = sb.sub.size(), JW = 3 * sizeof(HF) / 8;
-    std::vector<uint64_t> parts(G * JW);
-    int32_t rc = run_shards(G, [&](size_t k) { return msm_resident<C, HF>(sb.sub[k], 0, sv.sub[k], 0, sv.lo[k + 1] - sv.lo[k], parts.data() + k * JW, kind, false); });
-    if (rc) return rc;
-    return host_fold_jacobian<HF>(parts.data(), G, out);
-}
-
 
 }  // namespace dock

@@ -6,7 +6,7 @@ The shapes are the reference's: 34 x 64 (saver/src/encryption.rs:710-740), 256 x
 tests/test_gpu_msm_segments.py.  `faster` is (a).median < (b).median.
 The second part runs on the development twin and times the per-segment fold both ways (host threads' host_fold / k_seg_fold on the device, forced by
 dgpu_set_msm_segments) over a sweep of segment counts: the crossover is the first count from which the device fold's median stays below the host's —
-msm_driver.hip.h SEG_DEVICE_FOLD_MIN is set from it.  Writes profiles/msm_segments_timing.json (OUT=...) and prints a table.
+msm_many.hip.h SEG_DEVICE_FOLD_MIN is set from it.  Writes profiles/msm_segments_timing.json (OUT=...) and prints a table.
 ONE=g1:1024:16 runs a few segmented calls of that shape and exits (for a kernel trace)."""
 import ctypes as C
 import json

@@ -199,6 +199,34 @@ def test_one_sort_shared_by_tables_of_one_shape(n, c):
         t.free()
 
 
+def test_g2_table_in_two_term_ranges_closed_form():
+    """Fresh host scalars on a G2 table at n = 2^19, the smallest n at which the scalars cross in two term ranges (a bucket set each, merged before
+    the reduction): closed form over known discrete logs."""
+    G, curve = O.G2, ca.G2
+    n = 1 << 19
+    bases, k0, d = U.seq_bases(G, n, 6161, threads=64)
+    sc = O.rand_scalars(6162, n)
+    tab = ca.DeviceBases(curve, bases).precompute(20)
+    assert U.jac_to_model(G, tab.msm_bigint(sc)) == U.closed_form(G, sc, k0, d)
+    tab.free()
+
+
+def test_g2_sorted_list_with_a_row_shift():
+    """A G2 table one row shorter than the shape its list was sorted for (rows 1 .. n - 1): row 0 is passed over; against the table's own sort
+    and the oracle."""
+    G, curve = O.G2, ca.G2
+    n = 700
+    bases, _, _ = U.seq_bases(G, n, 6261, threads=16)
+    sc = O.rand_scalars(6262, n)
+    full = ca.DeviceBases(curve, bases).precompute(16); short = ca.DeviceBases(curve, bases[1:]).precompute(16)
+    ds = ca.DeviceScalars(sc); srt = ca.SortedScalars(full, ds, n)
+    got = short.msm_sorted(srt, row_shift=1)
+    assert (got == short.msm_resident(ds, n=n - 1, scalar_offset=1)).all()
+    assert U.jac_to_model(G, got) == U.jac_to_model(G, G.msm(bases[1:], sc[1:], threads=16))
+    for h in (srt, ds, full, short):
+        h.free()
+
+
 @pytest.mark.parametrize("gname,n,c", [("G1", 1 << 19, 0), ("G2", 1 << 17, 20), ("G1", (1 << 15) + 77, 16)])
 def test_few_distinct_bases_collide_everywhere(gname, n, c):
     """The headline shape (n >= 320 000: 20-bit windows, 13 of them, ONE bucket set, bit-marginal reduction) on inputs made of collisions: the bases are
