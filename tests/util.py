@@ -276,3 +276,94 @@ def mul_add_oracle(G, P, p_inf, sc, A, a_inf):
 def first_bad(got, got_inf, want, want_inf):
     """the first rows (at most eight) whose words or identity flag differ"""
     return np.nonzero((got != want).any(axis=1) | (np.asarray(got_inf) != np.asarray(want_inf)))[0][:8]
+
+
+# ---- the signed radix-2^c recoding of the bucket MSMs (crypto_amd/csrc/digit_codes.hip.h, ps_digits.hip.h) as a big-integer model, and the scalars that
+# ---- reach its edges (tests/test_digit_codes_device_code_on_host.py, tests/test_gpu_window_edges.py) -----------------------------------------------------
+def window_shape(c):
+    """(W, B, M, t): windows, largest digit 2^(c-1), the window mask 2^c - 1, and the scalar bits the top window holds (0: it receives a carry only)"""
+    W = 255 // c + 1
+    return W, 1 << (c - 1), (1 << c) - 1, 255 - (W - 1) * c
+
+
+def signed_digits(s, c):
+    """the W = 255 // c + 1 digits d_w in [-(B - 1), B], B = 2^(c-1), with sum d_w 2^(c w) = s mod 2^255: a window value above B becomes negative and
+    carries one into the next window; the top window holds fewer than c bits and never carries out"""
+    W, B, M, _ = window_shape(c)
+    s &= (1 << 255) - 1
+    out, carry = [], 0
+    for w in range(W):
+        v = ((s >> (c * w)) & M) + carry
+        carry = 1 if v > B else 0
+        out.append(v - (carry << c))
+    assert carry == 0 and all(-(B - 1) <= d <= B for d in out) and sum(d << (c * w) for w, d in enumerate(out)) == s
+    return out
+
+
+def digit_code(d, bits):
+    """the stored spelling of a digit: (|d| - 1) | sign << top bit, all-ones for zero"""
+    return (1 << bits) - 1 if d == 0 else (abs(d) - 1) | ((1 << (bits - 1)) if d < 0 else 0)
+
+
+def ps_part_log(NB):
+    """log2 of the buckets per partition of the two-level sort for a set of NB buckets (sort_launch.hip.h ps_part_log)"""
+    lg = (NB - 1).bit_length()
+    return min(max(lg - 10, 5), 11)
+
+
+def edge_named(c):
+    """the scalars built to put an extreme digit into every window"""
+    W, B, M, t = window_shape(c)
+    return {
+        "maxpos": sum(B << (c * w) for w in range(W - 1)),                                        # every digit +B, the top digit 0
+        "minneg": (B + 1) + sum(B << (c * w) for w in range(1, W - 1)),                           # every digit -(B - 1), the top digit +1 out of the carry alone
+        "topmax": (((1 << t) - 1) << (c * (W - 1))) + ((B + 1) << (c * (W - 2))),                 # the top digit 2^t: its largest (B at c = 8 and 16, the bare carry at 15 and 17)
+        "zero_carry": (B + 1) + (M << c),                                                         # -(B - 1), then 2^c - 1 plus the carry: a zero digit that carries, then +1
+        "all_ones": (1 << 255) - 1,                                                               # -1, zeros that each pass the carry on, 2^t
+    }
+
+
+def edge_scalars(c, n_random=0, seed=0, part_logs=None):
+    """the edge family of window width c as a list of distinct integers below 2^255: edge_named(c) first, then 0, 1, r - 1, r, r + 1, 2^254, 2^255 - 2,
+    the single-digit probes d 2^(c w), the partition borders of the sort (part_logs: the partition widths to border, default that of the shared bucket set
+    of a table) and n_random seeded 255-bit values"""
+    import random
+    W, B, M, t = window_shape(c)
+    out = list(edge_named(c).values()) + [0, 1, R - 1, R, R + 1, 1 << 254, (1 << 255) - 2]
+    for w in (0, 1, W - 2):
+        out += [d << (c * w) for d in (1, 2, B - 1, B, B + 1, M)]
+    if t > 0:
+        out += [d << (c * (W - 1)) for d in (1, (1 << t) - 1)]
+    for k in range(c - 1):                                                                        # one bit of the bucket index at a time (2^k + 1), and all below it (2^k)
+        out += [(1 << k) << c, ((1 << k) + 1) << c]
+    for pl in ([ps_part_log(B)] if part_logs is None else part_logs):
+        for w in (0, W - 2):
+            out += [(m1 + 1) << (c * w) for m1 in ((1 << pl) - 1, 1 << pl, B - (1 << pl) - 1, B - (1 << pl))]
+    rng = random.Random(1000 * c + seed)
+    out += [rng.getrandbits(255) for _ in range(n_random)]
+    assert all(0 <= v < 1 << 255 for v in out)
+    return list(dict.fromkeys(out))
+
+
+def edge_coverage_missing(scalars, c, part_log=None, per_window=False):
+    """what a vector of integer scalars leaves out of the edge conditions of width c (an empty list: all are met):
+    digit +B and digit -(B - 1) in every window below the top, the top window's largest digit 2^t, a zero digit that carries, and the first and last bucket of
+    the first and last partition of the sort (buckets 0, 2^pl - 1, B - 2^pl, B - 1; pl = part_log, default that of a table's shared set: in any window;
+    per_window: in window 0 and in window W - 2, where every window has a bucket set of its own)"""
+    W, B, M, t = window_shape(c)
+    pl = ps_part_log(B) if part_log is None else part_log
+    seen = [set() for _ in range(W)]
+    zero_carry = False
+    for s in scalars:
+        for w, d in enumerate(signed_digits(s, c)):
+            seen[w].add(d)
+            zero_carry |= d == 0 and ((s & ((1 << 255) - 1)) >> (c * w)) & M == M
+    miss = []
+    for w in range(W - 1):
+        miss += [("+B", w)] * (B not in seen[w]) + [("-(B-1)", w)] * (-(B - 1) not in seen[w])
+    miss += [("top", 1 << t)] * ((1 << t) not in seen[W - 1]) + [("zero digit that carries",)] * (not zero_carry)
+    borders = (0, (1 << pl) - 1, B - (1 << pl), B - 1)
+    for ws in ([[0], [W - 2]] if per_window else [list(range(W))]):
+        have = set(abs(d) - 1 for w in ws for d in seen[w] if d)
+        miss += [("bucket", ws[0], b) for b in borders if b not in have]
+    return miss
