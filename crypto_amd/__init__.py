@@ -14,3 +14,4 @@ from .pairing import multi_miller_loop, final_exponentiation, multi_pairing  # n
 from .pairing_check import RandomizedPairingChecker  # noqa: F401,E402
 from . import qap  # noqa: F401,E402
 from . import serde  # noqa: F401,E402
+from . import accumulator  # noqa: F401,E402

@@ -1,0 +1,58 @@
+"""Mirror of the accumulator manager's batch witness update (vb_accumulator/src/witness.rs:165-285) on the C ABI.
+
+    Witness::compute_update_using_secret_key_after_batch_updates(additions, removals, elements, old_witnesses, old_accumulator, sk)
+        -> update_witnesses(additions, removals, alpha, elements, witnesses, accumulator)     returns (d_factors, new_witnesses)
+    ..._after_batch_additions / ..._after_batch_removals       -> the same call with `removals` / `additions` empty
+    the factors alone (d_A / d_D and v_AD / d_D per element)   -> update_factors(additions, removals, alpha, elements)
+
+Field elements are (n, 4) uint64 limb arrays or Python ints, canonical unless `montgomery=True` (then ark-ff Montgomery limbs in and out).  Witnesses
+and the accumulator are G1 affine Montgomery limbs, (m, 12) and (12,) uint64; an identity is all-zero words.  New witnesses come back normalised
+(G::Group::normalize_batch, witness.rs:284) as an (m, 12) array plus a uint8 identity mask: a holder whose element was removed gets d_factor = 0 and
+the identity.
+"""
+import ctypes as C
+import numpy as np
+from ._native import lib, DockGpuError
+from .msm import _ensure
+from .fixed_base import _scalars_to_limbs, _p
+
+
+def _limbs(values):
+    s = _scalars_to_limbs(values) if len(values) else np.zeros((0, 4), np.uint64)
+    return s, (_p(s) if len(s) else None)
+
+
+def update_factors(additions, removals, alpha, elements, montgomery=False):
+    """(f, g): f_i = d_A(y_i) / d_D(y_i) (the reference's d_factor), g_i = v_AD(y_i) / d_D(y_i), each an (m, 4) uint64 array"""
+    _ensure()
+    a, pa = _limbs(additions)
+    r, pr = _limbs(removals)
+    y, py = _limbs(elements)
+    al = _scalars_to_limbs([alpha] if isinstance(alpha, int) else alpha).reshape(4)
+    m = len(y)
+    f, g = np.zeros((m, 4), np.uint64), np.zeros((m, 4), np.uint64)
+    rc = lib().dgpu_accumulator_update_factors(pa, len(a), pr, len(r), _p(al), py, m, 1 if montgomery else 0, _p(f), _p(g))
+    if rc:
+        raise DockGpuError(rc, "dgpu_accumulator_update_factors")
+    return f, g
+
+
+def update_witnesses(additions, removals, alpha, elements, witnesses, accumulator, montgomery=False):
+    """(d_factors, (new_witnesses, identity_mask)): C_i' = f_i C_i + g_i V for every holder"""
+    _ensure()
+    a, pa = _limbs(additions)
+    r, pr = _limbs(removals)
+    y, py = _limbs(elements)
+    al = _scalars_to_limbs([alpha] if isinstance(alpha, int) else alpha).reshape(4)
+    m = len(y)
+    w = np.ascontiguousarray(witnesses, dtype=np.uint64).reshape(-1, 12)
+    if len(w) != m:
+        raise ValueError("NeedSameNoOfElementsAndWitnesses: %d elements, %d witnesses" % (m, len(w)))      # witness.rs:246-248
+    v = np.ascontiguousarray(accumulator, dtype=np.uint64).reshape(12)
+    d = np.zeros((m, 4), np.uint64)
+    out = np.zeros((m, 12), np.uint64)
+    inf = np.zeros(m, np.uint8)
+    rc = lib().dgpu_accumulator_update_witnesses_g1(pa, len(a), pr, len(r), _p(al), py, _p(w) if m else None, m, _p(v), 1 if montgomery else 0, _p(d), _p(out), _p(inf))
+    if rc:
+        raise DockGpuError(rc, "dgpu_accumulator_update_witnesses_g1")
+    return d, (out, inf)

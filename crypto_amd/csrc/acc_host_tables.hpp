@@ -1,0 +1,64 @@
+// crypto_amd/csrc/acc_host_tables.hpp — the host's share of the accumulator witness update (dock_accumulator.hip): the tables that depend on the secret key.
+// Host-only and free of HIP, so that tests/native/acc_dev_host_shim.cpp compiles it as it is (tests/test_acc_device_code_on_host.py compares the tables
+// with big integers).
+#pragma once
+#include <cstdint>
+#include <cstring>
+#include <vector>
+#include "host_field.hpp"
+#include "../../include/dock_gpu.h"
+
+namespace acch {
+using hostf::FrH;
+using hostf::u128;
+
+// 4 words -> field element in Montgomery form: canonical (any value below 2^256, reduced) or ark-ff Montgomery limbs
+inline FrH fr_in(const uint64_t w[4], bool mont) {
+    FrH a, r2, one{{1, 0, 0, 0}}; memcpy(a.l, w, 32); memcpy(r2.l, FrH::R2, 32);
+    FrH x = a * r2;
+    return mont ? x * one : x;
+}
+inline bool fr_is_zero(const FrH &x) { return (x.l[0] | x.l[1] | x.l[2] | x.l[3]) == 0; }
+inline FrH fr_plus(const FrH &a, const FrH &b) {                 // both < r
+    FrH s; uint64_t c = 0;
+    for (int i = 0; i < 4; i++) { u128 t = (u128)a.l[i] + b.l[i] + c; s.l[i] = (uint64_t)t; c = (uint64_t)(t >> 64); }
+    bool ge = c != 0;
+    if (!ge) { ge = true; for (int i = 3; i >= 0; i--) { if (s.l[i] > FrH::MOD[i]) break; if (s.l[i] < FrH::MOD[i]) { ge = false; break; } } }
+    if (ge) { uint64_t br = 0; for (int i = 0; i < 4; i++) { u128 d = (u128)s.l[i] - FrH::MOD[i] - br; s.l[i] = (uint64_t)d; br = (uint64_t)(d >> 64) & 1; } }
+    return s;
+}
+inline void wipe(void *p, size_t bytes) { volatile uint8_t *q = (volatile uint8_t *)p; for (size_t i = 0; i < bytes; i++) q[i] = 0; }
+// the host's tables as ark-ff Montgomery words, [a | F | r | G | Phi]; wiped when the call ends
+struct Tables {
+    std::vector<uint64_t> w;
+    ~Tables() { if (!w.empty()) wipe(w.data(), w.size() * 8); }
+};
+// DGPU_E_BADARG for an addition or a removal equal to -alpha: F would hold a zero from there on, G would need its inverse (the reference computes garbage there)
+inline int32_t build_tables(const uint64_t *additions, size_t na, const uint64_t *removals, size_t nr, const uint64_t alpha[4], bool mont, Tables &t) {
+    t.w.assign((2 * na + 2 * nr + 1) * 4, 0);
+    FrH *a = (FrH *)t.w.data(), *F = a + na, *r = F + na, *G = r + nr, *phi = G + nr;
+    FrH al = fr_in(alpha, mont), acc = FrH::from_u64(1);
+    int32_t rc = DGPU_OK;
+    for (size_t s = 0; s < na && !rc; s++) {
+        a[s] = fr_in(additions + 4 * s, mont);
+        const FrH u = fr_plus(a[s], al);
+        if (fr_is_zero(u)) rc = DGPU_E_BADARG;
+        F[s] = acc; acc = acc * u;
+    }
+    *phi = acc;
+    // G_s = 1 / prod_{i <= s} (r_i + alpha): the prefix products, ONE inversion, then back down (1 / Q_{s-1} = (r_s + alpha) / Q_s); r_s + alpha is parked in G_s meanwhile
+    acc = FrH::from_u64(1);
+    for (size_t s = 0; s < nr && !rc; s++) {
+        r[s] = fr_in(removals + 4 * s, mont);
+        G[s] = fr_plus(r[s], al);
+        if (fr_is_zero(G[s])) rc = DGPU_E_BADARG;
+        acc = acc * G[s];
+    }
+    if (!rc && nr) {
+        FrH inv = acc.inv();
+        for (size_t s = nr; s-- > 0;) { const FrH u = G[s]; G[s] = inv; inv = inv * u; }
+    }
+    wipe(&al, sizeof al); wipe(&acc, sizeof acc);
+    return rc;
+}
+}  // namespace acch

@@ -515,6 +515,34 @@ int32_t dgpu_legogroth16_setup(uint64_t r1cs, size_t commit_witness_count, const
                                int32_t montgomery, uint64_t out_handles[5], uint64_t *out_g1, uint64_t *out_g2, uint64_t *gamma_abc_g1, size_t gamma_abc_cap,
                                uint64_t **query_xy, uint8_t **query_inf, size_t *out_domain_size);
 
+/* ---- accumulator manager: the witnesses of many holders after a batch of additions and removals ----
+ * Witness::compute_update_using_secret_key_after_batch_updates (vb_accumulator/src/witness.rs:238-285) and its additions-only and removals-only
+ * forms (:165-233: the same formula with an empty list), with the evaluations of vb_accumulator/src/batch_utils.rs:81-470 (Poly_d, Poly_v_A, Poly_v_D,
+ * Poly_v_AD ::eval_direct / eval_direct_on_batch).  For every element y_i of a holder:
+ *     f_i = d_A(y_i) / d_D(y_i)     (the reference's returned d_factor)           d_U(y) = prod_{u in U} (u - y), 1 for an empty U
+ *     g_i = v_AD(y_i) / d_D(y_i)
+ *     C_i' = f_i C_i + g_i V          (V: the accumulator the reference's variant expects, witness.rs:162-164,196-198,235-237)
+ * O(m (n_add + n_rem)) field products and 2 m scalar multiplications on the device; alpha is used on the host only, for O(n_add + n_rem) table entries
+ * whose device copy is zeroed before the call returns.  Nothing is cached between calls.
+ *   additions / removals   n_add / n_rem x 4 words, in the order the manager applied them (either list may be empty: NULL is fine then)
+ *   alpha                  the secret key
+ *   elements               m x 4 words
+ *   montgomery != 0        every Fr input and output is ark-ff Montgomery limbs (Fr as it lies in memory); else canonical, any 256-bit input taken mod r
+ *   witnesses_xy, out_xy   affine Montgomery limbs, x then y; accumulator_xy likewise.  An identity witness or accumulator is all-zero words (the convention of
+ *                          dgpu_g1_mul_add_batch's inputs); an identity result is zero words and out_inf[i] = 1
+ * A holder whose element is among the removals has d_D = 0: it gets d_factor = 0 and the identity (zero words, out_inf = 1), the point the reference's
+ * arithmetic yields there (its batch inversion leaves the zero).  A holder whose element was just added gets d_factor = 0 and g_i V.
+ * m = 0: DGPU_OK, nothing is read.  DGPU_E_BADARG: a NULL pointer with a non-zero count, m >= 2^31, n_add + n_rem >= 2^31, an addition or a removal equal
+ * to -alpha (a table entry would be zero or need its inverse; the reference computes garbage there) — all decided before the device is looked at.  No size
+ * threshold.  Thread-safe like every other entry point.  Stage timers acc.prep, acc.factors, acc.table_mul, acc.scale. */
+int32_t dgpu_accumulator_update_factors(const uint64_t *additions, size_t n_add, const uint64_t *removals, size_t n_rem,
+                                        const uint64_t alpha[4], const uint64_t *elements /* m*4 */, size_t m, int32_t montgomery,
+                                        uint64_t *f /* m*4 */, uint64_t *g /* m*4 */);
+int32_t dgpu_accumulator_update_witnesses_g1(const uint64_t *additions, size_t n_add, const uint64_t *removals, size_t n_rem,
+                                             const uint64_t alpha[4], const uint64_t *elements /* m*4 */, const uint64_t *witnesses_xy /* m*12 */, size_t m,
+                                             const uint64_t accumulator_xy[12], int32_t montgomery,
+                                             uint64_t *d_factors /* m*4 */, uint64_t *out_xy /* m*12 */, uint8_t *out_inf /* m */);
+
 /* ---- the LegoGroth16 prover as one call ----
  * replaces create_proof_and_committed_witnesses_with_assignment (legogroth16/src/prover.rs:267-383, with calculate_coeff :585-594) and — when
  * the circuit is resident (r1cs != 0) — the QAP::witness_map call in front of it (create_proof_with_reduction, :153-180): the whole schedule

@@ -33,6 +33,11 @@ int32_t dgpu_set_gt_pow(int32_t groups_per_wave, int32_t bases_per_group, int32_
  * block of the block kernel (1..512, clamped to 2^10 / D, the most a block's LDS holds; 0 = automatic: 256 / D for D <= 128, else 1; both provisional until
  * tests/perf/witness_map_many_timing.py has run).  Any setting gives the same bytes (tests cross chunk and block boundaries at small m). */
 int32_t dgpu_set_wm_many(int32_t chunk_rows, int32_t rows_per_block);
+/* dgpu_accumulator_update_*: chunks per element of the two passes (1..4096; 0 = automatic: 1 when the elements alone fill the device, else enough chunks of
+ * at least 32 list entries to reach 65536 lanes — both constants unmeasured until tests/perf/acc_update_timing.py has run).  Any value gives the same words
+ * (tests force 1, 2 and 5 at small shapes).  dgpu_dev_get_acc_split returns the chunk count the process's last call ran with (0: none yet). */
+int32_t dgpu_dev_set_acc_split(int32_t chunks);
+int32_t dgpu_dev_get_acc_split(void);
 /* log2 of the buckets one lane of the bucket reduction sums serially on the table pipeline (0..6; -1 = automatic: 3 for a 2^19-bucket table when the
  * call runs alone, 4 when three or more calls are in flight on the device context).  Any value gives the same point. */
 int32_t dgpu_set_reduce_shift(int32_t log2_buckets_per_lane);

@@ -210,6 +210,32 @@ pub fn fixed_base_g2(base: &G2Affine, elements: &[Fr]) -> Option<Vec<G2Affine>> 
     Some((0..n).map(|i| g2_affine(xy[24 * i..24 * i + 24].try_into().unwrap(), inf[i])).collect())
 }
 
+// ---- accumulator manager: witnesses after a batch of additions and removals (vb_accumulator/src/witness.rs:165-285) --------------------------------
+/// the factors of `compute_update_using_secret_key_after_batch_updates` alone: `(d_A(y) / d_D(y), v_AD(y) / d_D(y))` per element
+/// (vb_accumulator/src/batch_utils.rs:81-470: `Poly_d`, `Poly_v_AD` `::eval_direct`); an element among the removals gets `(0, 0)`
+pub fn accumulator_update_factors(additions: &[Fr], removals: &[Fr], alpha: &Fr, elements: &[Fr]) -> Option<(Vec<Fr>, Vec<Fr>)> {
+    let m = elements.len();
+    let (mut f, mut g) = (ark_std::vec![Fr::from(0u64); m], ark_std::vec![Fr::from(0u64); m]);
+    let rc = unsafe { dgpu_accumulator_update_factors(additions.as_ptr() as *const u64, additions.len(), removals.as_ptr() as *const u64, removals.len(), alpha as *const Fr as *const u64,
+                                                      elements.as_ptr() as *const u64, m, 1, f.as_mut_ptr() as *mut u64, g.as_mut_ptr() as *mut u64) };
+    if rc != DGPU_OK { return None; }
+    Some((f, g))
+}
+/// `Witness::compute_update_using_secret_key_after_batch_updates(additions, removals, elements, old_witnesses, old_accumulator, sk)`: the returned
+/// `d_factor`s and the new witnesses, normalised.  The additions-only and removals-only forms are this call with an empty slice.
+pub fn accumulator_update_witnesses(additions: &[Fr], removals: &[Fr], alpha: &Fr, elements: &[Fr], old_witnesses: &[G1Affine], old_accumulator: &G1Affine) -> Option<(Vec<Fr>, Vec<G1Affine>)> {
+    let m = elements.len();
+    if old_witnesses.len() != m { return None; }                      // NeedSameNoOfElementsAndWitnesses (witness.rs:246-248)
+    let (w, _) = pack_g1(old_witnesses);                              // identity: zero words
+    let (v, _) = pack_g1(core::slice::from_ref(old_accumulator));
+    let mut d = ark_std::vec![Fr::from(0u64); m];
+    let (mut xy, mut inf) = (ark_std::vec![0u64; m * 12], ark_std::vec![0u8; m]);
+    let rc = unsafe { dgpu_accumulator_update_witnesses_g1(additions.as_ptr() as *const u64, additions.len(), removals.as_ptr() as *const u64, removals.len(), alpha as *const Fr as *const u64,
+                                                           elements.as_ptr() as *const u64, w.as_ptr(), m, v.as_ptr(), 1, d.as_mut_ptr() as *mut u64, xy.as_mut_ptr(), inf.as_mut_ptr()) };
+    if rc != DGPU_OK { return None; }
+    Some((d, (0..m).map(|i| g1_affine(xy[12 * i..12 * i + 12].try_into().unwrap(), inf[i])).collect()))
+}
+
 // ---- R1CS -> QAP witness map (legogroth16/src/r1cs_to_qap.rs:150-210) ---------------------------------------------------------------------------------
 /// one constraint matrix of ark-relations' `ConstraintMatrices` (`Matrix<F> = Vec<Vec<(F, usize)>>`) as the CSR arrays the ABI takes, with a 64-bit hash of
 /// its whole contents computed on the way (the copy reads every coefficient anyway)

@@ -278,6 +278,55 @@ fn sharded_msm_window_tables_and_serde() {
     }
 }
 
+// Witness::compute_update_using_secret_key_after_batch_updates' arithmetic (vb_accumulator/src/witness.rs:238-285, batch_utils.rs:102-106,171-199,328-359,448-454) with arkworks
+fn cpu_accumulator_factors(additions: &[Fr], removals: &[Fr], alpha: &Fr, y: &Fr) -> (Fr, Fr) {
+    use ark_ff::{Field, One};
+    let d = |u: &[Fr]| u.iter().fold(Fr::one(), |a, e| (*e - *y) * a);
+    let (d_a, d_d_inv) = (d(additions), d(removals).inverse().unwrap_or(Fr::zero()));      // batch_inversion leaves a zero
+    let mut v_a = Fr::zero();
+    for s in 0..additions.len() {
+        let factor = additions[..s].iter().fold(Fr::one(), |a, e| a * (*e + *alpha));
+        v_a += additions[s + 1..].iter().fold(factor, |a, e| a * (*e - *y));
+    }
+    let mut v_d = Fr::zero();
+    for s in 0..removals.len() {
+        let factor = removals[..s + 1].iter().fold(Fr::one(), |a, e| a * (*e + *alpha)).inverse().unwrap();
+        v_d += removals[..s].iter().fold(factor, |a, e| a * (*e - *y));
+    }
+    let phi = additions.iter().fold(Fr::one(), |a, e| a * (*e + *alpha));
+    (d_a * d_d_inv, (v_a - v_d * phi) * d_d_inv)
+}
+
+#[test]
+fn accumulator_witness_update_with_the_secret_key() {
+    use ark_ff::Field;
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5EED00AC);
+    let (alpha, v) = (Fr::rand(&mut rng), Fr::rand(&mut rng));
+    let (additions, removals, mut elements) = (frs(&mut rng, 40), frs(&mut rng, 25), frs(&mut rng, 300));
+    elements[3] = removals[1];                                        // a removed holder: d_factor = 0 and the identity
+    elements[5] = additions[2];                                       // a holder whose element was just added: d_factor = 0
+    let g = G1Affine::generator();
+    let acc = (g * v).into_affine();
+    let mut wits = G1Projective::normalize_batch(&elements.iter().map(|y| g * (v * (*y + alpha).inverse().unwrap())).collect::<Vec<_>>());
+    wits[7] = G1Affine::identity();
+    for (a, r) in [(&additions[..], &removals[..]), (&additions[..], &removals[..0]), (&additions[..0], &removals[..]), (&additions[..1], &removals[..1])] {
+        let want: Vec<(Fr, Fr)> = elements.iter().map(|y| cpu_accumulator_factors(a, r, &alpha, y)).collect();
+        let (f, gg) = host::accumulator_update_factors(a, r, &alpha, &elements).expect("factors");
+        assert_eq!(f, want.iter().map(|x| x.0).collect::<Vec<_>>());
+        assert_eq!(gg, want.iter().map(|x| x.1).collect::<Vec<_>>());
+        let (d, new_wits) = host::accumulator_update_witnesses(a, r, &alpha, &elements, &wits, &acc).expect("witnesses");
+        assert_eq!(d, f);
+        for i in 0..elements.len() { assert_eq!(new_wits[i], (wits[i] * want[i].0 + acc * want[i].1).into_affine(), "holder {}", i); }
+        if !r.is_empty() { assert!(d[3].is_zero() && new_wits[3].is_zero()); }
+        // an ordinary holder's new witness verifies against the new accumulator: C' (y + alpha) = V'
+        let v_new = a.iter().fold(v, |x, e| x * (*e + alpha)) * r.iter().fold(Fr::from(1u64), |x, e| x * (*e + alpha)).inverse().unwrap();
+        assert_eq!((new_wits[0] * (elements[0] + alpha)).into_affine(), (g * v_new).into_affine());
+    }
+    assert!(host::accumulator_update_witnesses(&additions, &removals, &alpha, &elements[..2], &wits[..3], &acc).is_none());
+    assert!(host::accumulator_update_factors(&[-alpha], &removals, &alpha, &elements).is_none());      // an addition equal to -alpha: refused
+}
+
 #[test]
 fn many_small_msms_over_one_key() {
     // m rows against m arkworks calls: the shapes of dkgith.rs:174-192 (many short rows), one row of the key's full length, an identity row, &[Fr] and BigInt rows
