@@ -3,6 +3,7 @@
 // exports none of these symbols (tests/test_abi_host.py asserts both) and runs every knob at its default.
 #include "msm_driver.hip.h"
 #include "acc_launch.hip.h"
+#include "qap_launch.hip.h"
 #include "../../include/dock_gpu_dev.h"
 
 using namespace dock;
@@ -23,6 +24,12 @@ int32_t dgpu_set_wm_many(int32_t chunk_rows, int32_t rows_per_block) {
 }
 int32_t dgpu_dev_set_acc_split(int32_t chunks) { if (chunks < 0 || chunks > (int32_t)acck::ACC_MAX_SPLIT) return DGPU_E_BADARG; gs.acc_split = chunks; return DGPU_OK; }
 int32_t dgpu_dev_get_acc_split(void) { return gs.acc_last_split.load(); }
+int32_t dgpu_dev_set_ntt(int32_t path, const int32_t *split, int32_t n_split) { return ntt::dev_set_ntt(path, split, n_split) ? DGPU_OK : DGPU_E_BADARG; }
+int32_t dgpu_dev_get_ntt_last(int32_t *path, int32_t *groups, int32_t cap) {
+    if (!path || cap < 0 || (cap > 0 && !groups)) return DGPU_E_BADARG;
+    int route = 0; const int n = ntt::dev_get_ntt_last(&route, groups, cap);
+    *path = route; return n;
+}
 int32_t dgpu_set_reduce_lanes(int32_t lanes) { if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4) return DGPU_E_BADARG; gs.reduce_lanes = lanes; return DGPU_OK; }
 int32_t dgpu_set_reduce_shift(int32_t sh) { if (sh < -1 || sh > 6) return DGPU_E_BADARG; gs.reduce_shift = sh; return DGPU_OK; }
 int32_t dgpu_set_miller_pipeline(int32_t mode) {       // bits 0-4: forms; bits 8-13 / 16-21: where the chain is cut (0: default); bits 24-27: slice length of the last piece's products (0: automatic); bits 28-29: log2 of the factor on the block limit of k_line_products3

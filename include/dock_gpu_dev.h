@@ -38,6 +38,20 @@ int32_t dgpu_set_wm_many(int32_t chunk_rows, int32_t rows_per_block);
  * (tests force 1, 2 and 5 at small shapes).  dgpu_dev_get_acc_split returns the chunk count the process's last call ran with (0: none yet). */
 int32_t dgpu_dev_set_acc_split(int32_t chunks);
 int32_t dgpu_dev_get_acc_split(void);
+/* Route of the witness map's transforms (crypto_amd/csrc/k_ntt.hip run_passes).  path = 0: automatic — one k_ntt_stage launch per stage below 2^10, the piped
+ * k_ntt_r4 passes with the (ab - c) / Z step and the coset epilogue fused into the first / last pass for 2^10 .. 2^26, k_ntt_fused (2^11-element tiles, groups
+ * of up to 7 stages) with the separate k_pointwise / k_coset_scale above (arrays beyond 4 GB).  path = 1: one launch per stage with the separate k_coset_scale /
+ * k_pointwise at every size.  path = 2: k_ntt_fused with the separate epilogue — what domains above 2^26 run — for every domain of at least 2^11 elements (one
+ * tile); smaller domains keep the automatic route.  split / n_split: stage counts of the piped passes in decimation-in-frequency order (the strided passes, then
+ * the flat one; the forward transform runs them reversed), 1 .. 10 stages each, at most 12 entries; a split applies only to domains whose log2 equals its sum
+ * and only on the piped route; n_split = 0 clears it.  Flat passes of fewer than 6 stages and strided passes whose columns are less than a tile's width apart
+ * never occur automatically; k_ntt_r4 handles them (tests force 5,5,5,1 and its like to imitate the three strided passes of 2^23 .. 2^26 at small sizes).
+ * DGPU_E_BADARG, with the previous setting left in place, for anything else.  Any setting gives the same bytes (tests/test_gpu_ntt_paths.py compares every
+ * route with the CPU oracle).
+ * dgpu_dev_get_ntt_last: *path = the route of the last transform the process launched (0 piped, 1 per stage, 2 staged), groups[0 .. min(cap, n)) = its stage
+ * groups in launch order (per stage: n = log2 D ones); returns n (0: no transform yet). */
+int32_t dgpu_dev_set_ntt(int32_t path, const int32_t *split, int32_t n_split);
+int32_t dgpu_dev_get_ntt_last(int32_t *path, int32_t *groups, int32_t cap);
 /* log2 of the buckets one lane of the bucket reduction sums serially on the table pipeline (0..6; -1 = automatic: 3 for a 2^19-bucket table when the
  * call runs alone, 4 when three or more calls are in flight on the device context).  Any value gives the same point. */
 int32_t dgpu_set_reduce_shift(int32_t log2_buckets_per_lane);
