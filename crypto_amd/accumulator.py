@@ -5,6 +5,11 @@
     ..._after_batch_additions / ..._after_batch_removals       -> the same call with `removals` / `additions` empty
     the factors alone (d_A / d_D and v_AD / d_D per element)   -> update_factors(additions, removals, alpha, elements)
 
+    Omega::new(additions, removals, old_accumulator, sk)       -> omega(additions, removals, alpha, accumulator)               returns (points, identity_mask)
+    Omega::new_for_kb_positive_accumulator(removals, V, sk)    -> omega([], members, alpha, -V)
+    Witness::compute_update_using_public_info_after_batch_updates(additions, removals, omega, element, old_witness), for m holders at once (witness.rs:292-314)
+        -> update_witnesses_public(additions, removals, omega, elements, witnesses)       returns (d_factors, new_witnesses, ok)
+
 Field elements are (n, 4) uint64 limb arrays or Python ints, canonical unless `montgomery=True` (then ark-ff Montgomery limbs in and out).  Witnesses
 and the accumulator are G1 affine Montgomery limbs, (m, 12) and (12,) uint64; an identity is all-zero words.  New witnesses come back normalised
 (G::Group::normalize_batch, witness.rs:284) as an (m, 12) array plus a uint8 identity mask: a holder whose element was removed gets d_factor = 0 and
@@ -56,3 +61,49 @@ def update_witnesses(additions, removals, alpha, elements, witnesses, accumulato
     if rc:
         raise DockGpuError(rc, "dgpu_accumulator_update_witnesses_g1")
     return d, (out, inf)
+
+
+def omega(additions, removals, alpha, accumulator, montgomery=False):
+    """(points, identity_mask): omega_j = c_j V for the coefficients c_j of v_AD, trimmed like ark-poly trims the polynomial (trailing zero coefficients
+    dropped: two empty lists, or the zero polynomial, give no entries); a zero coefficient below the last one is an identity entry"""
+    _ensure()
+    a, pa = _limbs(additions)
+    r, pr = _limbs(removals)
+    al = _scalars_to_limbs([alpha] if isinstance(alpha, int) else alpha).reshape(4)
+    v = np.ascontiguousarray(accumulator, dtype=np.uint64).reshape(12)
+    n = max(len(a), len(r))
+    out = np.zeros((n, 12), np.uint64)
+    inf = np.zeros(n, np.uint8)
+    length = C.c_size_t(0)
+    rc = lib().dgpu_accumulator_omega_g1(pa, len(a), pr, len(r), _p(al), _p(v), 1 if montgomery else 0, _p(out) if n else None, _p(inf) if n else None, C.byref(length))
+    if rc:
+        raise DockGpuError(rc, "dgpu_accumulator_omega_g1")
+    return out[:length.value], inf[:length.value]
+
+
+def update_witnesses_public(additions, removals, omega, elements, witnesses, montgomery=False):
+    """(d_factors, (new_witnesses, identity_mask), ok) without the secret key: C_i' = f_i C_i + <s_i y_i^j, omega_j>.  `omega` is (points, identity_mask) as
+    omega() returns it, or the points alone (an entry of zero words is an identity).  ok[i] = 0 marks a holder whose element was removed (the reference's
+    CannotBeZero): d_factor 0 and the identity for that holder, everyone else unaffected"""
+    _ensure()
+    a, pa = _limbs(additions)
+    r, pr = _limbs(removals)
+    y, py = _limbs(elements)
+    opts, oinf = omega if isinstance(omega, tuple) else (omega, None)
+    o = np.ascontiguousarray(opts, dtype=np.uint64).reshape(-1, 12)
+    oi = None if oinf is None else np.ascontiguousarray(oinf, dtype=np.uint8)
+    if oi is not None and len(oi) != len(o):
+        raise ValueError("omega: %d points, %d identity flags" % (len(o), len(oi)))
+    m = len(y)
+    w = np.ascontiguousarray(witnesses, dtype=np.uint64).reshape(-1, 12)
+    if len(w) != m:
+        raise ValueError("NeedSameNoOfElementsAndWitnesses: %d elements, %d witnesses" % (m, len(w)))
+    d = np.zeros((m, 4), np.uint64)
+    out = np.zeros((m, 12), np.uint64)
+    inf = np.zeros(m, np.uint8)
+    ok = np.zeros(m, np.uint8)
+    rc = lib().dgpu_accumulator_update_witnesses_public_g1(pa, len(a), pr, len(r), _p(o) if len(o) else None, _p(oi) if oi is not None and len(oi) else None, len(o),
+                                                           py, _p(w) if m else None, m, 1 if montgomery else 0, _p(d), _p(out), _p(inf), _p(ok))
+    if rc:
+        raise DockGpuError(rc, "dgpu_accumulator_update_witnesses_public_g1")
+    return d, (out, inf), ok

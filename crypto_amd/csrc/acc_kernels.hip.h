@@ -94,6 +94,71 @@ template <class E, class LD, class ST, class OUT> FRD void finish_share(size_t n
     }
 }
 
+// ---- Omega (batch_utils.rs:498-509): the coefficients of v_AD from its values at the N-th roots of unity ---------------------------------------------
+// v_AD has max(|A|, |D|) coefficients, so its values at the N >= max(|A|, |D|) roots of unity and one inverse transform of size N give them exactly.
+// The finishing of one evaluation point when v_AD alone is wanted: no d_D, no inversion.  SA, SD as finish_share takes them; the result is a product
+// (what the transform takes).
+FRD void omega_value(Fr &v, const Fr &SA, const Fr &SD, const Fr &phi) {
+    Fr t, one; fr_one(one);
+    fr_mul(t, SD, phi);                                        // 2^32 r * 2 r
+    fr_sub(v, SA, t); fr_norm(v, v);                           // limbs < 2^29 + 8, value < 516 r
+    fr_mul(v, v, one);                                         // 516 r * r
+}
+// the transform of size two with its scaling: c_0 = (e_0 + e_1) / 2, c_1 = (e_0 - e_1) / 2.  e_0, e_1, half: products.
+FRD void omega_pair(Fr &c0, Fr &c1, const Fr &e0, const Fr &e1, const Fr &half) {
+    Fr s, d;
+    fr_add(s, e0, e1);                                         // two products: limbs < 2^30, value < 4 r
+    fr_sub<512, 30>(d, e0, e1);                                // limbs < 2^31, value < 514 r
+    fr_mul(c0, s, half); fr_mul(c1, d, half);                  // 4 r * 2 r, 514 r * 2 r
+}
+
+// ---- the holders' update from public information (witness.rs:292-314) --------------------------------------------------------------------------------
+// Per holder f = d_A(y) / d_D(y) and s = 1 / d_D(y); the row [s, s y, .., s y^(n-1)] then meets Omega in an MSM.  No secret, no F / G / Phi.
+// the chunk [alo, ahi) of d_A(y) = prod (a_s - y) and [rlo, rhi) of d_D(y), both started from one: two independent chains, interleaved while both have
+// entries left.  la(s, a) / lr(s, r) load entry s of the lists (products); y: a product.  Chunks combine by a plain product.
+template <class LA, class LR> FRD void pub_chunk(const Fr &y, size_t alo, size_t ahi, size_t rlo, size_t rhi, LA la, LR lr, Fr &PA, Fr &PD) {
+    fr_one(PA); PD = PA;
+    const size_t na = ahi - alo, nr = rhi - rlo, both = na < nr ? na : nr;
+    Fr u, w, d, e;
+    for (size_t s = 0; s < both; s++) {
+        la(alo + s, u); lr(rlo + s, w);
+        fr_sub<512, 30>(d, u, y); fr_sub<512, 30>(e, w, y);   // limbs < 2^31, value < 514 r: first operands, no carry pass
+        fr_mul(PA, d, PA); fr_mul(PD, e, PD);                  // 514 r * 2 r
+    }
+    for (size_t s = both; s < na; s++) { la(alo + s, u); fr_sub<512, 30>(d, u, y); fr_mul(PA, d, PA); }
+    for (size_t s = both; s < nr; s++) { lr(rlo + s, w); fr_sub<512, 30>(e, w, y); fr_mul(PD, e, PD); }
+}
+// f = d_A / d_D and s = 1 / d_D for the n holders of one lane's share, with ONE fr_inv (fr_batch_inv, as finish_share uses it).
+//   elem(k, PA, PD)    the finished products of holder k (products)
+//   ld / st            four scratch slots per holder as in finish_share: 0 the numerator of f, 1 the mark (one, or zero for a zero d_D), 2 the denominator, 3 the
+//                      prefix product, then the inverse
+//   out(k, f, s, ok)   products; a zero d_D (the element is among the removals: the reference's Err(CannotBeZero)) gives f = s = 0 and ok = false, and one
+//                      takes its place in the trick
+template <class E, class LD, class ST, class OUT> FRD void pub_finish_share(size_t n, E elem, LD ld, ST st, OUT out) {
+    for (size_t k = 0; k < n; k++) {
+        Fr PA, PD, mk;
+        elem(k, PA, PD);
+        fr_one(mk);
+        if (is_zero(PD)) { fr_zero(PA); fr_zero(mk); fr_one(PD); }
+        st(k, 0, PA); st(k, 1, mk); st(k, 2, PD);
+    }
+    fr_batch_inv(n, [&](size_t k, Fr &v) { ld(k, 2, v); }, [&](size_t k, Fr &v) { ld(k, 3, v); }, [&](size_t k, const Fr &v) { st(k, 3, v); });
+    for (size_t k = 0; k < n; k++) {
+        Fr nf, mk, inv, f, s;
+        ld(k, 0, nf); ld(k, 1, mk); ld(k, 3, inv);
+        fr_mul(f, nf, inv);                                    // 2 r * 2 r
+        fr_mul(s, inv, mk);                                    // 2 r * r
+        out(k, f, s, !is_zero(mk));
+    }
+}
+// cnt consecutive entries j0, j0 + 1, .. of the row s y^j: the start power by square and multiply (at most 2 log2(j0) products), then one product per
+// entry, so that the lanes of a row share it in runs.  y, s and everything derived from them are products: every fr_mul below is 2 r * 2 r.
+template <class OUT> FRD void pub_row_run(const Fr &y, const Fr &s, size_t j0, size_t cnt, OUT out) {
+    Fr cur = s, b = y;
+    for (size_t e = j0; e; e >>= 1) { if (e & 1) fr_mul(cur, cur, b); if (e > 1) fr_mul(b, b, b); }
+    for (size_t j = 0; j < cnt; j++) { out(j0 + j, cur); if (j + 1 < cnt) fr_mul(cur, cur, y); }
+}
+
 #if defined(__HIPCC__)
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------------------
 // Tables: entry e of the internal-form table at tab[e * NL ..]: [a_0 .. | F_0 .. | r_0 .. | G_0 .. | Phi], 2 na + 2 nr + 1 entries.  Every lane of a block
@@ -115,11 +180,11 @@ __device__ __forceinline__ void st_words(uint32_t *__restrict__ words, size_t i,
     uint4 *q = reinterpret_cast<uint4 *>(words + i * 8);
     q[0] = make_uint4(w[0], w[1], w[2], w[3]); q[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
-// the host's tables (ark-ff Montgomery words) -> internal form, once per call
-__global__ void __launch_bounds__(256) k_acc_prep(const uint32_t *__restrict__ words, size_t n, uint32_t *__restrict__ tab) {
+// the host's tables (ark-ff Montgomery words), or the caller's public lists (mont = 0: canonical words) -> internal form, once per call
+__global__ void __launch_bounds__(256) k_acc_prep(const uint32_t *__restrict__ words, size_t n, uint32_t *__restrict__ tab, int mont) {
     const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    Fr x; ld_words(x, words, e, true);
+    Fr x; ld_words(x, words, e, mont != 0);
 #pragma unroll
     for (int l = 0; l < NL; l++) tab[e * NL + l] = x.l[l];
 }
@@ -183,6 +248,150 @@ __global__ void __launch_bounds__(256) k_acc_combine(const uint32_t *__restrict_
                  },
                  [&](size_t k, int q, Fr &v) { io.ld(k, q, v); }, [&](size_t k, int q, const Fr &v) { io.st(k, q, v); },
                  [&](size_t k, const Fr &f, const Fr &gg) { io.out(k, f, gg); });
+}
+// ---- Omega -----------------------------------------------------------------------------------------------------------------------------------------------
+// pts, ev: N elements in the transform's form (limb-major: word l of element i at [l * N + i]); pts = the N-th roots of unity, ev = v_AD there.
+__device__ __forceinline__ void ld_soa(Fr &r, const uint32_t *__restrict__ a, size_t n, size_t i) {
+#pragma unroll
+    for (int l = 0; l < NL; l++) r.l[l] = a[(size_t)l * n + i];
+}
+__device__ __forceinline__ void st_soa(uint32_t *__restrict__ a, size_t n, size_t i, const Fr &x) {
+#pragma unroll
+    for (int l = 0; l < NL; l++) a[(size_t)l * n + i] = x.l[l];
+}
+// grid (N / 256, K): lane (i, c) runs chunk c of both passes at point i.  K = 1: the passes run whole and ev[i] = v_A - Phi v_D is written; K > 1: the chunk's
+// results go to part (the layout of k_acc_eval, m = N) for k_acc_omega_combine.
+__global__ void __launch_bounds__(256) k_acc_omega_eval(const uint32_t *__restrict__ tab, size_t na, size_t nr, const uint32_t *__restrict__ pts, size_t N, uint32_t K,
+                                                        uint32_t *__restrict__ part, uint32_t *__restrict__ ev) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= N) return;
+    const uint32_t *ta_ = tab, *tf_ = tab + na * NL, *tr_ = tab + 2 * na * NL, *tg_ = tab + (2 * na + nr) * NL;
+    auto ta = [&](size_t s, Fr &a, Fr &F) { ld_tab(a, ta_, s); ld_tab(F, tf_, s); };
+    auto tr = [&](size_t s, Fr &r, Fr &Gs) { ld_tab(r, tr_, s); ld_tab(Gs, tg_, s); };
+    const size_t c = blockIdx.y;
+    Fr y, r[4]; ld_soa(y, pts, N, g);
+    eval_chunk(y, na * c / K, na * (c + 1) / K, nr * c / K, nr * (c + 1) / K, ta, tr, r[0], r[1], r[2], r[3]);
+    if (K == 1) {
+        Fr phi, v; ld_tab(phi, tab, 2 * na + 2 * nr);
+        omega_value(v, r[1], r[3], phi);
+        st_soa(ev, N, g, v);
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int l = 0; l < NL; l++) part[((size_t)(q * NL + l) * K + c) * N + g] = r[q].l[l];
+}
+__global__ void __launch_bounds__(256) k_acc_omega_combine(const uint32_t *__restrict__ tab, size_t na, size_t nr, const uint32_t *__restrict__ part, size_t N, uint32_t K,
+                                                           uint32_t *__restrict__ ev) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= N) return;
+    Fr PA, SA, PD, SD, phi, v;
+    fr_one(PA); PD = PA; fr_zero(SA); fr_zero(SD);
+    for (uint32_t c = 0; c < K; c++) {
+        Fr r[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+            for (int l = 0; l < NL; l++) r[q].l[l] = part[((size_t)(q * NL + l) * K + c) * N + g];
+        combine_step(PA, SA, PD, SD, r[0], r[1], r[2], r[3]);
+    }
+    ld_tab(phi, tab, 2 * na + 2 * nr);
+    omega_value(v, SA, SD, phi);
+    st_soa(ev, N, g, v);
+}
+// After the inverse transform (decimation in frequency: bit-reversed, times N) of N = 2^logn >= 4 values, or instead of it for N = 1 (nothing to do) and
+// N = 2 (omega_pair): coefficient k = ev[rev k] / N as canonical words at coeff[8 k ..] and nz[k] = (it is not zero), for the k < len the polynomial can have.
+struct Words8 { uint32_t w[8]; };
+__global__ void __launch_bounds__(256) k_acc_omega_coeffs(const uint32_t *__restrict__ ev, int logn, Words8 ninv_words, size_t len, uint32_t *__restrict__ coeff, uint8_t *__restrict__ nz) {
+    const size_t N = (size_t)1 << logn, p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N) return;
+    Fr ninv, c; fr_from_words(ninv, ninv_words.w, false);
+    size_t k = p;
+    if (logn == 1) {
+        Fr e0, e1, c0, c1; ld_soa(e0, ev, N, 0); ld_soa(e1, ev, N, 1);
+        omega_pair(c0, c1, e0, e1, ninv);
+        c = p ? c1 : c0;
+    } else {
+        Fr x; ld_soa(x, ev, N, p);
+        fr_mul(c, x, ninv);                                    // the transform's output is a first operand (as k_coset_scale takes it); ninv: a product
+        if (logn > 1) k = (size_t)(__brev((uint32_t)p) >> (32 - logn));
+    }
+    if (k >= len) return;
+    st_words(coeff, k, c);
+    nz[k] = is_zero(c) ? 0 : 1;
+}
+
+// ---- the public update ------------------------------------------------------------------------------------------------------------------------------------
+// lists: the internal-form entries [a_0 .. | r_0 ..] (k_acc_prep).  part (K > 1): word l of result q (PA, PD) of chunk c of holder i at
+// part[((q * NL + l) * K + c) * m + i].  scratch: as above.  fs: canonical words, f_i at fs[8 i ..], s_i at fs[8 (m + i) ..].  ok[i] = (d_D(y_i) != 0).
+struct PubIo {
+    uint32_t *__restrict__ scratch; uint32_t *__restrict__ fs; uint8_t *__restrict__ ok; size_t m, g, G;
+    __device__ __forceinline__ void ld(size_t k, int q, Fr &v) const {
+#pragma unroll
+        for (int l = 0; l < NL; l++) v.l[l] = scratch[(size_t)(q * NL + l) * m + g + k * G];
+    }
+    __device__ __forceinline__ void st(size_t k, int q, const Fr &v) const {
+#pragma unroll
+        for (int l = 0; l < NL; l++) scratch[(size_t)(q * NL + l) * m + g + k * G] = v.l[l];
+    }
+    __device__ __forceinline__ void out(size_t k, const Fr &f, const Fr &s, bool good) const { st_words(fs, g + k * G, f); st_words(fs, m + g + k * G, s); ok[g + k * G] = good ? 1 : 0; }
+};
+// grid (lanes / 256, K), as k_acc_eval: K = 1: lane g of G owns the holders g + k G, runs both products whole and finishes them; K > 1: lane (i, c) runs chunk c
+// of holder i (G = m) and leaves the results to k_acc_pub_combine.
+__global__ void __launch_bounds__(256) k_acc_pub_factors(const uint32_t *__restrict__ lists, size_t na, size_t nr, const uint32_t *__restrict__ elems, int mont, size_t m, uint32_t K, size_t G,
+                                                         uint32_t *__restrict__ part, uint32_t *__restrict__ scratch, uint32_t *__restrict__ fs, uint8_t *__restrict__ ok) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const uint32_t *lr_ = lists + na * NL;
+    auto la = [&](size_t s, Fr &a) { ld_tab(a, lists, s); };
+    auto lr = [&](size_t s, Fr &r) { ld_tab(r, lr_, s); };
+    if (K == 1) {
+        const PubIo io{scratch, fs, ok, m, g, G};
+        pub_finish_share((m - g + G - 1) / G,
+                         [&](size_t k, Fr &PA, Fr &PD) { Fr y; ld_words(y, elems, g + k * G, mont != 0); pub_chunk(y, 0, na, 0, nr, la, lr, PA, PD); },
+                         [&](size_t k, int q, Fr &v) { io.ld(k, q, v); }, [&](size_t k, int q, const Fr &v) { io.st(k, q, v); },
+                         [&](size_t k, const Fr &f, const Fr &s, bool good) { io.out(k, f, s, good); });
+        return;
+    }
+    const size_t c = blockIdx.y;
+    Fr y, r[2]; ld_words(y, elems, g, mont != 0);
+    pub_chunk(y, na * c / K, na * (c + 1) / K, nr * c / K, nr * (c + 1) / K, la, lr, r[0], r[1]);
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+#pragma unroll
+        for (int l = 0; l < NL; l++) part[((size_t)(q * NL + l) * K + c) * m + g] = r[q].l[l];
+}
+__global__ void __launch_bounds__(256) k_acc_pub_combine(const uint32_t *__restrict__ part, size_t m, uint32_t K, size_t G, uint32_t *__restrict__ scratch, uint32_t *__restrict__ fs,
+                                                         uint8_t *__restrict__ ok) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const PubIo io{scratch, fs, ok, m, g, G};
+    pub_finish_share((m - g + G - 1) / G,
+                     [&](size_t k, Fr &PA, Fr &PD) {
+                         const size_t i = g + k * G;
+                         fr_one(PA); PD = PA;
+                         for (uint32_t c = 0; c < K; c++) {
+                             Fr r[2];
+#pragma unroll
+                             for (int q = 0; q < 2; q++)
+#pragma unroll
+                                 for (int l = 0; l < NL; l++) r[q].l[l] = part[((size_t)(q * NL + l) * K + c) * m + i];
+                             fr_mul(PA, PA, r[0]); fr_mul(PD, PD, r[1]);      // 2 r * 2 r
+                         }
+                     },
+                     [&](size_t k, int q, Fr &v) { io.ld(k, q, v); }, [&](size_t k, int q, const Fr &v) { io.st(k, q, v); },
+                     [&](size_t k, const Fr &f, const Fr &s, bool good) { io.out(k, f, s, good); });
+}
+// rows[(i * n + j) * 8 ..] = the canonical words of s_i y_i^j for the holders i < rows and j < n: the scalars of the many-row MSM, rows packed.  A row is shared by
+// ceil(n / run) lanes, each walking `run` consecutive powers from a start power of its own (pub_row_run).
+__global__ void __launch_bounds__(256) k_acc_pub_rows(const uint32_t *__restrict__ elems, int mont, const uint32_t *__restrict__ s_words, size_t rows, size_t n, size_t run,
+                                                      uint32_t *__restrict__ out_rows) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, per_row = (n + run - 1) / run, i = t / per_row;
+    if (i >= rows) return;
+    const size_t j0 = (t % per_row) * run, cnt = n - j0 < run ? n - j0 : run;
+    Fr y, s; ld_words(y, elems, i, mont != 0); ld_words(s, s_words, i, false);
+    pub_row_run(y, s, j0, cnt, [&](size_t j, const Fr &v) { st_words(out_rows, i * n + j, v); });
 }
 #endif
 

@@ -1,5 +1,6 @@
-// crypto_amd/csrc/dock_accumulator.hip — the accumulator manager's batch witness update (include/dock_gpu.h: dgpu_accumulator_update_factors,
-// dgpu_accumulator_update_witnesses_g1).  Replaces Witness::compute_update_using_secret_key_after_batch_updates and its additions-only / removals-only
+// crypto_amd/csrc/dock_accumulator.hip — the accumulator's batch witness updates (include/dock_gpu.h: dgpu_accumulator_update_factors,
+// dgpu_accumulator_update_witnesses_g1 with the secret key; dgpu_accumulator_omega_g1 and dgpu_accumulator_update_witnesses_public_g1, the two halves of
+// the update from public information, further down).  Replaces Witness::compute_update_using_secret_key_after_batch_updates and its additions-only / removals-only
 // forms (vb_accumulator/src/witness.rs:165-285) with the polynomial evaluations of vb_accumulator/src/batch_utils.rs:81-470 in front:
 //   host    F_s, G_s, Phi from the secret key (O(|A| + |D|), one inversion); alpha never leaves the host
 //   device  f_i = d_A(y_i) / d_D(y_i), g_i = v_AD(y_i) / d_D(y_i)                 k_acc_prep, k_acc_eval [, k_acc_combine]   (acc_kernels.hip.h)
@@ -7,7 +8,8 @@
 //   device  T_i = g_i V from a window table of V (k_fb_mul), C_i' = T_i + f_i C_i (k_g1_scale_quad with T as the addend)
 // The device copy of the tables is zeroed before the slot is released; nothing of a call is kept.
 #include <chrono>
-#include "msm_driver.hip.h"
+#include "msm_many.hip.h"
+#include "qap_launch.hip.h"
 #include "fixed_launch.hip.h"
 #include "acc_launch.hip.h"
 #include "acc_host_tables.hpp"
@@ -16,11 +18,24 @@ using namespace acch;
 
 namespace {
 
-// zeroes the device copy of the tables on every return path, before the slot goes back
+// zeroes the device buffers that held what depends on the secret key (the tables; Omega's chunk results, evaluations and coefficients) on every return
+// path, before the slot goes back
 struct DeviceWipe {
-    Slot &sl; void *p = nullptr; size_t bytes = 0;
+    Slot &sl; struct Region { void *p; size_t bytes; }; std::vector<Region> r;
     explicit DeviceWipe(Slot &s) : sl(s) {}
-    ~DeviceWipe() { if (p) { (void)hipMemsetAsync(p, 0, bytes, sl.stream); (void)hipStreamSynchronize(sl.stream); } }
+    void add(void *p, size_t bytes) { if (p && bytes) r.push_back(Region{p, bytes}); }
+    ~DeviceWipe() {
+        if (r.empty()) return;
+        for (const Region &k : r) (void)hipMemsetAsync(k.p, 0, k.bytes, sl.stream);
+        (void)hipStreamSynchronize(sl.stream);
+    }
+};
+// a return before the call's last synchronisation (an error path) waits for the slot's streams first: asynchronous copies may still be queued into or out of
+// host vectors declared BEFORE this guard, which leave scope after it
+struct DrainUnlessDone {
+    Slot &sl; bool done = false;
+    explicit DrainUnlessDone(Slot &s) : sl(s) {}
+    ~DrainUnlessDone() { if (!done) drain(sl); }
 };
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
@@ -39,7 +54,7 @@ int32_t factors_on_slot(Slot &sl, const Tables &t, size_t na, size_t nr, const u
     if ((rc = sl.q[3].ensure(2 * m * 32))) return rc;
     if ((rc = sl.q[4].ensure(m * 32))) return rc;
     hipStream_t s = sl.stream;
-    DeviceWipe dw(sl); dw.p = sl.q[0].p; dw.bytes = words_b + tab_b;
+    DeviceWipe dw(sl); dw.add(sl.q[0].p, words_b + tab_b);
     uint32_t *d_words = sl.q[0].as<uint32_t>(), *d_tab = (uint32_t *)(sl.q[0].as<uint8_t>() + words_b);
     HIPCHK(hipMemcpyAsync(d_words, t.w.data(), ne * 32, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(sl.q[4].p, elements, m * 32, hipMemcpyHostToDevice, s));
@@ -133,6 +148,240 @@ int32_t update_witnesses(const uint64_t *additions, size_t na, const uint64_t *r
     return DGPU_OK;
 }
 
+// ---- the update from public information (section 4.1 of the paper) ------------------------------------------------------------------------------------
+// The manager's half, Omega::new (vb_accumulator/src/batch_utils.rs:498-509) without polynomial arithmetic: v_AD has L = max(|A|, |D|) coefficients, so
+//   device  the N-th roots of unity, N = 2^logn >= L                                                       k_fr_powers
+//   device  v_AD = v_A - Phi v_D at each of them: the passes of the witness update, another finishing         k_acc_prep, k_acc_omega_eval [, k_acc_omega_combine]
+//   device  ONE inverse transform of size N over the context's cached domain (N <= 2: in the next kernel)     launch_ntt
+//   device  / N, un-reversal, canonical words, a non-zero flag per coefficient                                 k_acc_omega_coeffs
+//   device  c_j V from a window table of V, the coefficients still on the device                               k_fb_mul
+// The window table is built into the slot's own workspace (window_table_g1_on_slot, queued on the call's stream), not through dgpu_window_table_g1: a steady-state
+// call allocates nothing and waits for the device once.
+constexpr size_t OMEGA_MAX = DGPU_ACC_OMEGA_MAX;
+
+int32_t omega_g1(const uint64_t *additions, size_t na, const uint64_t *removals, size_t nr, const uint64_t *alpha, const uint64_t *accumulator, bool mont,
+                 uint64_t *out, uint8_t *out_inf, size_t *out_len) {
+    if ((na && !additions) || (nr && !removals) || !alpha || !accumulator || !out_len || na >= (1ull << 31) || nr >= (1ull << 31)) return DGPU_E_BADARG;
+    const size_t L = std::max(na, nr);
+    if (L > OMEGA_MAX || (L && (!out || !out_inf))) return DGPU_E_BADARG;
+    if (L == 0) { *out_len = 0; return DGPU_OK; }
+    Tables t;
+    auto t0 = std::chrono::steady_clock::now();
+    int32_t rc = build_tables(additions, na, removals, nr, alpha, mont, t);
+    if (rc) return rc;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    if (gs.prof) prof_add_host("acc.host_tables", ms_since(t0));
+    int logn = 0; while (((size_t)1 << logn) < L) logn++;
+    const size_t N = (size_t)1 << logn;
+    uint64_t consts[3][4];                                    // the generator of the N-th roots of unity, one, 1 / N: canonical
+    FrH::root_of_unity(logn).to_canonical(consts[0]); FrH::from_u64(1).to_canonical(consts[1]); FrH::from_u64(N).inv().to_canonical(consts[2]);
+    SLOT_ACQUIRE(LK, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    NttDomain dom;
+    if (logn >= 2 && (rc = get_domain(sl, logn, dom))) return rc;
+    const size_t ne = acck::acc_table_entries(na, nr), words_b = (ne * 32 + 255) & ~(size_t)255, tab_b = (ne * 40 + 255) & ~(size_t)255, esz = ntt::FR_WORDS * 4, pt = 96;
+    const acck::AccShape sh = acck::acc_shape(N, na, nr, gs.acc_split.load());
+    gs.acc_last_split = (int)sh.K;
+    // q[0]: the tables (words | internal form), q[1]: chunk results, q[3]: the coefficients, q[5]: the constants, q[6]: the roots, q[7]: the evaluations,
+    // q[8]: the non-zero flags, q[9]: the window table of V, q[10]: [c_j V | identity flags]
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = o.q[0].ensure(words_b + tab_b))) return e;
+        if ((e = o.q[1].ensure(acck::acc_part_bytes(N, sh) + 256))) return e;
+        if ((e = o.q[3].ensure(L * 32))) return e;
+        if ((e = o.q[5].ensure(256))) return e;
+        if ((e = o.q[6].ensure(N * esz))) return e;
+        if ((e = o.q[7].ensure(N * esz))) return e;
+        if ((e = o.q[8].ensure(L))) return e;
+        if ((e = o.q[9].ensure(window_table_g1_bytes()))) return e;
+        if ((e = o.q[10].ensure(L * pt + L))) return e;
+        if ((e = o.prepped.ensure(32 * G1::AFF_STRIDE * 4))) return e;                  // (the window table's scratch)
+        return o.in_bases.ensure(32 * 2 * G1::ABI_W * 4 + 16);
+    };
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws(sl))) return rc;
+    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    hipStream_t s = sl.stream;
+    std::vector<uint64_t> window_bases;                       // (host words of the table's upload: they live until the call's synchronisation)
+    std::vector<uint8_t> nz(L);
+    DrainUnlessDone guard(sl);
+    if ((rc = window_table_g1_on_slot(sl, accumulator, sl.q[9].p, window_bases))) return rc;
+    DeviceWipe dw(sl);
+    dw.add(sl.q[0].p, words_b + tab_b); dw.add(sl.q[1].p, acck::acc_part_bytes(N, sh)); dw.add(sl.q[7].p, N * esz); dw.add(sl.q[3].p, L * 32); dw.add(sl.q[8].p, L);
+    uint32_t *d_words = sl.q[0].as<uint32_t>(), *d_tab = (uint32_t *)(sl.q[0].as<uint8_t>() + words_b), *d_c = sl.q[5].as<uint32_t>(), *d_ev = sl.q[7].as<uint32_t>();
+    uint8_t *d_out = sl.q[10].as<uint8_t>(), *d_inf = d_out + L * pt;
+    HIPCHK(hipMemcpyAsync(d_words, t.w.data(), ne * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_c, consts, sizeof consts, hipMemcpyHostToDevice, s));
+    { StageTimer st(sl, "acc.prep"); acck::launch_acc_prep(s, d_words, ne, d_tab); ntt::launch_fr_powers(s, d_c, d_c + 8, N, sl.q[6].as<uint32_t>()); }
+    { StageTimer st(sl, "acc.omega_eval"); acck::launch_acc_omega_eval(s, d_tab, na, nr, sl.q[6].as<uint32_t>(), N, sh, sl.q[1].as<uint32_t>(), d_ev); }
+    { StageTimer st(sl, "acc.omega_intt");
+      if (logn >= 2) ntt::launch_ntt(s, d_ev, logn, (const uint32_t *)dom.tw_i, 1);
+      acck::launch_acc_omega_coeffs(s, d_ev, logn, (const uint32_t *)consts[2], L, sl.q[3].as<uint32_t>(), sl.q[8].as<uint8_t>()); }
+    { StageTimer st(sl, "acc.omega_mul"); msm::launch_fb_mul<msm::G1>(s, sl.q[9].as<uint32_t>(), sl.q[3].as<uint32_t>(), L, (uint32_t *)d_out, d_inf); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, L * pt, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_inf, d_inf, L, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(nz.data(), sl.q[8].p, L, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    guard.done = true;
+    if (gs.prof) prof_flush(sl);
+    // ark-poly drops trailing zero coefficients; a zero coefficient below the last non-zero one, and every entry of an identity accumulator, is an identity
+    size_t len = L; while (len && !nz[len - 1]) len--;
+    for (size_t j = 0; j < L; j++) if (j >= len || !nz[j] || out_inf[j]) { memset(out + 12 * j, 0, pt); out_inf[j] = 1; }
+    *out_len = len;
+    return DGPU_OK;
+}
+
+// The holders' half, m times Witness::compute_update_using_public_info_after_batch_updates (witness.rs:292-314) with Omega::evaluate (batch_utils.rs:664-691):
+//   device  f_i = d_A(y_i) / d_D(y_i), s_i = 1 / d_D(y_i)                                  k_acc_prep, k_acc_pub_factors [, k_acc_pub_combine]
+//   device  row i = [s_i, s_i y_i, ..] straight into the many-row MSM's scalar buffer      k_acc_pub_rows
+//   device  T_i = <row_i, omega> over the small-path table of omega                        k_many_tree, k_many_fold (msm_many.hip.h many_rows_resident)
+//   host    the GLV split of every f_i, under the MSM
+//   device  C_i' = T_i + f_i C_i                                                           k_g1_scale_quad
+// omega's prepared records and their table live in the slot's workspace for the call (no handle, so nothing to free and no allocation in steady state).  Beyond
+// the many-row kernels' reach a row runs through the single-row driver with its scalars where k_acc_pub_rows left them.
+int32_t public_on_slot(Slot &sl, const uint64_t *additions, size_t na, const uint64_t *removals, size_t nr, const uint64_t *omega, const uint8_t *oinf, size_t n,
+                       const uint64_t *elements, const uint64_t *witnesses, size_t m, bool mont, uint64_t *d_factors, uint64_t *out, uint8_t *out_inf, uint8_t *ok) {
+    const size_t pt = 96, nl = na + nr, words_b = (std::max<size_t>(nl, 1) * 32 + 255) & ~(size_t)255, lists_b = (std::max<size_t>(nl, 1) * 40 + 255) & ~(size_t)255;
+    const size_t reach = std::min<size_t>(SMALL_MSM_MAX_N, gs.small_max.load());
+    const bool many = n && n <= reach;
+    const acck::AccShape sh = acck::acc_shape(m, na, nr, gs.acc_split.load());
+    gs.acc_last_split = (int)sh.K;
+    int32_t rc;
+    // q[0]: the lists (words | internal form), q[1]: chunk results, q[2]: scratch slots, q[3]: f | s, q[4]: the elements, q[5]: the split f, q[6]: [witnesses | T],
+    // q[7]: [out | out_inf], q[8]: [T's identity flags | ok], q[9]: omega's prepared records, q[10]: their small-path table
+    const RawBases rb = RawBases::packed<G1>(omega, oinf);
+    const ManyGeom geom = many_geometry(std::max<size_t>(n, 1));
+    const size_t chunk = !n ? m : many ? std::min(m, many_chunk_rows(n)) : std::min(m, std::max<size_t>(1, ((size_t)1 << 21) / n));      // rows per launch / per 64 MB of scalars
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = o.q[0].ensure(words_b + lists_b))) return e;
+        if ((e = o.q[1].ensure(acck::acc_part_bytes(m, sh) + 256))) return e;
+        if ((e = o.q[2].ensure(acck::acc_scratch_bytes(m)))) return e;
+        if ((e = o.q[3].ensure(2 * m * 32))) return e;
+        if ((e = o.q[4].ensure(m * 32))) return e;
+        if ((e = o.q[5].ensure(m * 32))) return e;
+        if ((e = o.q[6].ensure(2 * m * pt))) return e;
+        if ((e = o.q[7].ensure(m * pt + m))) return e;
+        if ((e = o.q[8].ensure(2 * m))) return e;
+        if ((e = o.q[9].ensure(std::max<size_t>(n, 1) * G1::AFF_STRIDE * 4))) return e;
+        if (!n) return DGPU_OK;
+        if ((e = ws_stage_bases<G1>(o, rb, n))) return e;
+        if (many) { if ((e = o.q[10].ensure(small_sub_bytes<G1>(n)))) return e; return ws_many<G1>(o, n, chunk, geom); }
+        if ((e = ws_for<G1>(o, 2, n, 0, nullptr))) return e;
+        if ((e = o.in_scalars.ensure(chunk * n * 32))) return e;
+        return o.flags.ensure(64);
+    };
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws(sl))) return rc;
+    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    hipStream_t s = sl.stream;
+    std::vector<uint64_t> f_host(m * 4), split(m * 4), jac; std::vector<uint8_t> tinf;      // targets and sources of asynchronous copies ...
+    DrainUnlessDone guard(sl);                                                                // ... so an early return waits for them
+    uint32_t *d_words = sl.q[0].as<uint32_t>(), *d_lists = (uint32_t *)(sl.q[0].as<uint8_t>() + words_b), *d_fs = sl.q[3].as<uint32_t>(), *d_el = sl.q[4].as<uint32_t>();
+    uint8_t *dC = sl.q[6].as<uint8_t>(), *dT = dC + m * pt, *dTinf = sl.q[8].as<uint8_t>(), *d_ok = dTinf + m, *dout_inf = sl.q[7].as<uint8_t>() + m * pt;
+    if (na) HIPCHK(hipMemcpyAsync(d_words, additions, na * 32, hipMemcpyHostToDevice, s));
+    if (nr) HIPCHK(hipMemcpyAsync(d_words + na * 8, removals, nr * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_el, elements, m * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dC, witnesses, m * pt, hipMemcpyHostToDevice, s));
+    if (nl) { StageTimer st(sl, "acc.prep"); acck::launch_acc_prep(s, d_words, nl, d_lists, mont ? 1 : 0); }
+    { StageTimer st(sl, "acc.pub_factors");
+      acck::launch_acc_pub_factors(s, d_lists, na, nr, d_el, mont ? 1 : 0, m, sh, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), d_fs, d_ok); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(f_host.data(), d_fs, m * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ok, d_ok, m, hipMemcpyDeviceToHost, s));
+    hipEvent_t have_f = ev_get(sl);
+    if (!have_f) return DGPU_E_HIP;
+    struct EvBack { Slot &sl; hipEvent_t e; ~EvBack() { sl.ev_pool.push_back(e); } } ev_back{sl, have_f};
+    HIPCHK(hipEventRecord(have_f, s));
+    // T_i = <row_i, omega>
+    if (n == 0) HIPCHK(hipMemsetAsync(dTinf, 1, m, s));
+    else {
+        uint32_t *d_rec = sl.q[9].as<uint32_t>(), *d_rows = sl.in_scalars.as<uint32_t>(), *d_bad = sl.flags.as<uint32_t>();
+        if ((rc = stage_bases<G1>(sl, rb, n, d_rec))) return rc;
+        HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));                  // (rows are canonical: the flag stays clear)
+        SmallSub sub{nullptr, nullptr};
+        if (many) {
+            sub = SmallSub{sl.q[10].as<uint32_t>(), sl.q[10].as<uint8_t>() + small_sub_tab_bytes<G1>(n)};
+            StageTimer st(sl, "msm.small_subtable");
+            launch_small_subtable<G1>(s, d_rec, n, sl.q[10].as<uint32_t>(), sl.q[10].as<uint8_t>() + small_sub_tab_bytes<G1>(n));
+        }
+        for (size_t r0 = 0; r0 < m; r0 += chunk) {
+            const size_t rows = std::min(chunk, m - r0);
+            { StageTimer st(sl, "acc.pub_rows"); acck::launch_acc_pub_rows(s, d_el + r0 * 8, mont ? 1 : 0, d_fs + (m + r0) * 8, rows, n, d_rows); }
+            if (many) {
+                if ((rc = many_rows_resident<G1>(sl, sub, d_rows, n, rows, geom, d_bad))) return rc;
+                // the normalised Jacobian rows (X, Y, 1) -> the affine addends: X and Y of every row, and its identity flag
+                HIPCHK(hipMemcpy2DAsync(dT + r0 * pt, pt, sl.win.p, 3 * pt / 2, pt, rows, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(dTinf + r0, sl.win_inf.p, rows, hipMemcpyDeviceToDevice, s));
+                continue;
+            }
+            // the single-row driver, row by row; its Jacobian results are normalised on the host
+            HIPCHK(hipGetLastError());
+            jac.resize(rows * 18); tinf.resize(rows);
+            for (size_t i = 0; i < rows; i++)
+                if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_rows + i * n * 8, n, jac.data() + 18 * i))) return rc;
+            for (size_t i = 0; i < rows; i++) {
+                uint64_t *p = jac.data() + 18 * i;
+                tinf[i] = jac_is_identity(p, 18);
+                if (tinf[i]) { memset(p, 0, pt); continue; }
+                hostf::Fq x, y, z; memcpy(&x, p, 48); memcpy(&y, p + 6, 48); memcpy(&z, p + 12, 48);
+                const hostf::Fq zi = z.inv(), zi2 = zi * zi;
+                x = x * zi2; y = y * zi2 * zi;
+                memcpy(jac.data() + 12 * i, &x, 48); memcpy(jac.data() + 12 * i + 6, &y, 48);      // (packed in place: 12 i + 12 <= 18 i)
+            }
+            HIPCHK(hipMemcpyAsync(dT + r0 * pt, jac.data(), rows * pt, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(dTinf + r0, tinf.data(), rows, hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));                     // (the next chunk reuses the host vectors)
+        }
+    }
+    HIPCHK(hipEventSynchronize(have_f));
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t parts = std::min<size_t>(16, (m + 4095) / 4096);
+    rc = par_run(parts, [&](size_t k) {
+        const size_t lo = m * k / parts, hi = m * (k + 1) / parts;
+        for (size_t i = lo; i < hi; i++) hostf::glv_decompose(f_host.data() + 4 * i, &split[4 * i], &split[4 * i + 2]);
+        return (int32_t)DGPU_OK;
+    });
+    if (gs.prof) prof_add_host("acc.glv_split", ms_since(t0));
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(sl.q[5].p, split.data(), m * 32, hipMemcpyHostToDevice, s));
+    { StageTimer st(sl, "acc.scale");
+      msm::launch_g1_scale_quad(s, (const uint32_t *)dC, nullptr, sl.q[5].as<uint32_t>(), 8, nullptr, m, sl.q[7].as<uint32_t>(), dout_inf, (const uint32_t *)dT, dTinf); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, sl.q[7].p, m * pt, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_inf, dout_inf, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    guard.done = true;
+    // a zero d_D is the reference's Err(CannotBeZero) for that holder alone: ok = 0, a zero factor, the identity
+    for (size_t i = 0; i < m; i++) {
+        if (!ok[i]) { memset(f_host.data() + 4 * i, 0, 32); out_inf[i] = 1; }
+        if (out_inf[i]) memset(out + 12 * i, 0, pt);
+    }
+    factors_out(f_host.data(), m, mont, d_factors);
+    return DGPU_OK;
+}
+
+int32_t update_witnesses_public(const uint64_t *additions, size_t na, const uint64_t *removals, size_t nr, const uint64_t *omega, const uint8_t *omega_inf, size_t n,
+                                const uint64_t *elements, const uint64_t *witnesses, size_t m, bool mont, uint64_t *d_factors, uint64_t *out, uint8_t *out_inf, uint8_t *ok) {
+    if (m == 0) return DGPU_OK;
+    if ((na && !additions) || (nr && !removals) || (n && !omega) || !elements || !witnesses || !d_factors || !out || !out_inf || !ok || bad_sizes(na, nr, m) || n >= (1ull << 31))
+        return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    // an identity entry of omega: its flag, or zero words (the convention of the points this library writes)
+    std::vector<uint8_t> oinf(n);
+    for (size_t j = 0; j < n; j++) {
+        uint64_t any = 0; for (int k = 0; k < 12; k++) any |= omega[12 * j + k];
+        oinf[j] = ((omega_inf && omega_inf[j]) || !any) ? 1 : 0;
+    }
+    SLOT_ACQUIRE(L, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    const int32_t rc = public_on_slot(sl, additions, na, removals, nr, omega, oinf.data(), n, elements, witnesses, m, mont, d_factors, out, out_inf, ok);
+    if (rc) drain(sl);                                           // nothing of ours still reads the caller's memory
+    if (gs.prof) prof_flush(sl);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -143,5 +392,16 @@ int32_t dgpu_accumulator_update_factors(const uint64_t *additions, size_t n_add,
 int32_t dgpu_accumulator_update_witnesses_g1(const uint64_t *additions, size_t n_add, const uint64_t *removals, size_t n_rem, const uint64_t alpha[4], const uint64_t *elements,
                                              const uint64_t *witnesses_xy, size_t m, const uint64_t accumulator_xy[12], int32_t montgomery, uint64_t *d_factors, uint64_t *out_xy, uint8_t *out_inf) {
     return abi_guard([&] { return update_witnesses(additions, n_add, removals, n_rem, alpha, elements, witnesses_xy, m, accumulator_xy, montgomery != 0, d_factors, out_xy, out_inf); });
+}
+int32_t dgpu_accumulator_omega_g1(const uint64_t *additions, size_t n_add, const uint64_t *removals, size_t n_rem, const uint64_t alpha[4], const uint64_t accumulator_xy[12],
+                                  int32_t montgomery, uint64_t *omega_xy, uint8_t *omega_inf, size_t *omega_len) {
+    return abi_guard([&] { return omega_g1(additions, n_add, removals, n_rem, alpha, accumulator_xy, montgomery != 0, omega_xy, omega_inf, omega_len); });
+}
+int32_t dgpu_accumulator_update_witnesses_public_g1(const uint64_t *additions, size_t n_add, const uint64_t *removals, size_t n_rem, const uint64_t *omega_xy, const uint8_t *omega_inf,
+                                                    size_t n_omega, const uint64_t *elements, const uint64_t *witnesses_xy, size_t m, int32_t montgomery, uint64_t *d_factors, uint64_t *out_xy,
+                                                    uint8_t *out_inf, uint8_t *ok) {
+    return abi_guard([&] {
+        return update_witnesses_public(additions, n_add, removals, n_rem, omega_xy, omega_inf, n_omega, elements, witnesses_xy, m, montgomery != 0, d_factors, out_xy, out_inf, ok);
+    });
 }
 }  // extern "C"

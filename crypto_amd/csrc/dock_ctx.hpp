@@ -258,6 +258,13 @@ template <class Pred> inline bool take_handle(uint64_t id, Pred kind_ok, Handle 
     }
 }
 void free_r1cs_object(void *p);      // dock_qap.hip
+// the context's cached NTT tables of the domain of size 2^logn (logn >= 1), built on the slot's stream the first time a size is asked for (dock_qap.hip)
+int32_t get_domain(Slot &sl, int logn, NttDomain &out);
+// the window table of a G1 point (what dgpu_window_table_g1 builds) into `tab`, FIXED_TABLE_ENTRIES prepared records the caller owns, queued on the caller's
+// slot (sl.in_bases and sl.prepped are its scratch) and not waited for: window_bases receives the host words of the upload and must live until the caller
+// has synchronised the slot's stream (dock_fixed.hip)
+int32_t window_table_g1_on_slot(Slot &sl, const uint64_t base_xy[12], void *tab, std::vector<uint64_t> &window_bases);
+size_t window_table_g1_bytes();
 // the device arrays of a resident circuit (kind 4) for the key generator (dock_setup.hip): CSR per matrix, values limb-major with stride vstride
 struct R1csView { const uint64_t *rowptr[3]; const uint32_t *cols[3]; const uint32_t *vals[3]; size_t vstride[3]; size_t num_vars, num_inputs, num_constraints; };
 R1csView r1cs_view(const void *p);    // dock_qap.hip

@@ -26,13 +26,33 @@ template <class HF> void window_bases_host(const uint64_t *base_abi, uint64_t *o
     }
 }
 
+// the 32 window bases -> the table, queued on the slot's stream and not waited for: the host words wb are the source of an asynchronous copy, so the caller
+// keeps them alive until it has synchronised that stream (table_build does at once; window_table_g1_on_slot hands them to its caller)
+template <class C> int32_t table_into(Slot &sl, const std::vector<uint64_t> &wb, void *tab) {
+    int32_t rc;
+    if ((rc = sl.prepped.ensure(32 * C::AFF_STRIDE * 4))) return rc;
+    // (the fixed-base kernels run over Fp: their window bases are 14 x 29-bit records, not the MSM pipeline's form)
+    rc = sl.in_bases.ensure(32 * 2 * C::ABI_W * 4 + 16);
+    if (rc == DGPU_OK && hipMemcpyAsync(sl.in_bases.p, wb.data(), 32 * 2 * C::ABI_W * 4, hipMemcpyHostToDevice, sl.stream) != hipSuccess) rc = DGPU_E_HIP;
+    if (rc == DGPU_OK) msm::launch_prep_bases_fp<C>(sl.stream, sl.in_bases.as<uint32_t>(), nullptr, 32, sl.prepped.as<uint32_t>());
+    if (rc == DGPU_OK) {
+        StageTimer st(sl, "fixed.table");
+        msm::launch_fb_table<C>(sl.stream, sl.prepped.as<uint32_t>(), (uint32_t *)tab);
+    }
+    return rc;
+}
+template <class C, class HF> void window_bases_of(const uint64_t *base, std::vector<uint64_t> &wb) {
+    constexpr size_t W64 = C::ABI_W;                     // u64 words per affine point (2 coordinates x ABI_W u32)
+    uint64_t any = 0; for (size_t k = 0; k < W64; k++) any |= base[k];
+    wb.assign(32 * W64, 0);
+    if (any) window_bases_host<HF>(base, wb.data());     // identity base: all-zero records -> flagged as identity by k_prep_bases
+}
+
 template <class C, class HF> int32_t table_build(const uint64_t *base, uint64_t *handle, int kind) {
     if (!base || !handle) return DGPU_E_BADARG;
     if (!cur().ready) return DGPU_E_NODEVICE;
-    constexpr size_t W64 = C::ABI_W;                     // u64 words per affine point (2 coordinates x ABI_W u32)
-    uint64_t any = 0; for (size_t k = 0; k < W64; k++) any |= base[k];
-    std::vector<uint64_t> wb(32 * W64, 0);
-    if (any) window_bases_host<HF>(base, wb.data());     // identity base: all-zero records -> flagged as identity by k_prep_bases
+    std::vector<uint64_t> wb;
+    window_bases_of<C, HF>(base, wb);
     void *tab = nullptr;
     {
         SLOT_ACQUIRE(L, sl);
@@ -40,14 +60,7 @@ template <class C, class HF> int32_t table_build(const uint64_t *base, uint64_t 
         int32_t rc;
         if ((rc = sl.prepped.ensure(32 * C::AFF_STRIDE * 4))) return rc;
         if (dev_malloc(&tab, (size_t)msm::FIXED_TABLE_ENTRIES * C::AFF_STRIDE * 4) != hipSuccess) { (void)hipGetLastError(); return DGPU_E_OOM; }
-        // (the fixed-base kernels run over Fp: their window bases are 14 x 29-bit records, not the MSM pipeline's form)
-        rc = sl.in_bases.ensure(32 * 2 * C::ABI_W * 4 + 16);
-        if (rc == DGPU_OK && hipMemcpyAsync(sl.in_bases.p, wb.data(), 32 * 2 * C::ABI_W * 4, hipMemcpyHostToDevice, sl.stream) != hipSuccess) rc = DGPU_E_HIP;
-        if (rc == DGPU_OK) msm::launch_prep_bases_fp<C>(sl.stream, sl.in_bases.as<uint32_t>(), nullptr, 32, sl.prepped.as<uint32_t>());
-        if (rc == DGPU_OK) {
-            StageTimer st(sl, "fixed.table");
-            msm::launch_fb_table<C>(sl.stream, sl.prepped.as<uint32_t>(), (uint32_t *)tab);
-        }
+        rc = table_into<C>(sl, wb, tab);
         if (rc == DGPU_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(sl.stream) != hipSuccess)) rc = DGPU_E_HIP;
         if (gs.prof) prof_flush(sl);
         if (rc) { (void)hipFree(tab); return rc; }
@@ -262,6 +275,11 @@ int32_t fold_apply(bool g2, uint64_t handle, const uint64_t *scalar, const uint6
 }  // namespace
 
 namespace dock {
+int32_t window_table_g1_on_slot(Slot &sl, const uint64_t base_xy[12], void *tab, std::vector<uint64_t> &window_bases) {
+    window_bases_of<G1, hostf::Fq>(base_xy, window_bases);
+    return table_into<G1>(sl, window_bases, tab);
+}
+size_t window_table_g1_bytes() { return (size_t)msm::FIXED_TABLE_ENTRIES * G1::AFF_STRIDE * 4; }
 // table_mul with the scalars already on the slot's device (canonical words: the key generator's, dock_setup.hip): the products go to a new bases
 // allocation (*keep: the records dgpu_window_table_mul_to_bases_* registers; the caller registers it) and / or to the host (affine ABI words and
 // identity flags).  On failure nothing is left allocated.

@@ -12,8 +12,10 @@ using namespace dock;
 using hostf::FrH;
 
 struct Csr { const uint64_t *rowptr; const uint32_t *cols; const uint64_t *vals; size_t nnz; };
+}  // namespace
 
-int32_t get_domain(Slot &sl, int logn, NttDomain &out) {
+// (declared in dock_ctx.hpp: dock_accumulator.hip transforms over the same cached tables)
+int32_t dock::get_domain(Slot &sl, int logn, NttDomain &out) {
     {
         std::lock_guard<std::mutex> lk(gs.mu);
         auto it = cur().ntt_domains.find(logn);
@@ -52,6 +54,7 @@ int32_t get_domain(Slot &sl, int logn, NttDomain &out) {
     return DGPU_OK;
 }
 
+namespace {
 // device-resident R1CS (three CSR matrices, coefficients already in the internal Fr form): uploaded once per circuit
 struct DevCsr { uint64_t *rowptr = nullptr; uint32_t *cols = nullptr; uint32_t *vals = nullptr; size_t nnz = 0; };
 struct DevR1cs { DevCsr m[3]; size_t num_vars = 0, num_inputs = 0, num_constraints = 0; };

@@ -30,6 +30,24 @@ template <class C> int32_t ws_many(Slot &sl, size_t n, size_t rows, const ManyGe
     if ((rc = sl.win.ensure(rows * 3 * C::ABI_W * 4))) return rc;                        // the rows' results and their identity flags
     return sl.win_inf.ensure(rows);
 }
+// one chunk whose canonical scalars are on the device already (rows packed; the workspace is ws_many's): tree, fold.  The rows' normalised Jacobian results
+// are left in sl.win, their identity flags in sl.win_inf, *d_bad |= a scalar >= 2^255.  Shared by msm_device_many and the accumulator's public update
+// (dock_accumulator.hip), whose rows are made on the device.
+template <class C>
+int32_t many_rows_resident(Slot &sl, const SmallSub &sub, const uint32_t *d_sc, size_t n, size_t rows, const ManyGeom &g, uint32_t *d_bad) {
+    hipStream_t s = sl.stream;
+    if (g.nblk > 1) HIPCHK(hipMemsetAsync(sl.cnt.p, 0, rows * (SMALL_MSM_W / SMALL_MSM_S) * 4, s));
+    {
+        StageTimer st(sl, "msm.many_tree");
+        launch_many_tree<C>(s, sub.tab, sub.tab_inf, d_sc, n, n, rows, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(), sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_bad);
+    }
+    {
+        StageTimer st(sl, "msm.many_fold");
+        launch_many_fold<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), rows, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
+    }
+    HIPCHK(hipGetLastError());
+    return DGPU_OK;
+}
 // the rows on the device, chunk by chunk: scalars up (rows packed: what lies between them in the caller's memory never crosses), tree, fold, results down
 template <class C>
 int32_t msm_device_many(Slot &sl, const SmallSub &sub, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, bool mont, uint64_t *out, uint8_t *out_inf) {
@@ -53,16 +71,7 @@ int32_t msm_device_many(Slot &sl, const SmallSub &sub, const uint64_t *scalars, 
         HIPCHK(hipEventRecord(ev, sl.cstream));
         HIPCHK(hipStreamWaitEvent(s, ev, 0));
         if (mont) ntt::launch_fr_mont_to_canonical(s, d_sc, rows * n);
-        if (g.nblk > 1) HIPCHK(hipMemsetAsync(sl.cnt.p, 0, rows * (SMALL_MSM_W / SMALL_MSM_S) * 4, s));
-        {
-            StageTimer st(sl, "msm.many_tree");
-            launch_many_tree<C>(s, sub.tab, sub.tab_inf, d_sc, n, n, rows, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(), sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_bad);
-        }
-        {
-            StageTimer st(sl, "msm.many_fold");
-            launch_many_fold<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), rows, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
-        }
-        HIPCHK(hipGetLastError());
+        if ((rc = many_rows_resident<C>(sl, sub, d_sc, n, rows, g, d_bad))) return rc;
         HIPCHK(hipMemcpyAsync(out + r0 * JW, sl.win.p, rows * JW * 8, hipMemcpyDeviceToHost, s));
         if (out_inf) HIPCHK(hipMemcpyAsync(out_inf + r0, sl.win_inf.p, rows, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(hbad, d_bad, 4, hipMemcpyDeviceToHost, s));

@@ -543,6 +543,42 @@ int32_t dgpu_accumulator_update_witnesses_g1(const uint64_t *additions, size_t n
                                              const uint64_t accumulator_xy[12], int32_t montgomery,
                                              uint64_t *d_factors /* m*4 */, uint64_t *out_xy /* m*12 */, uint8_t *out_inf /* m */);
 
+/* ---- accumulator: the update from public information (section 4.1 of the paper), both halves ----
+ * dgpu_accumulator_omega_g1 is the manager's half, Omega::new (vb_accumulator/src/batch_utils.rs:498-509): the coefficients c_j of v_AD
+ * (Poly_v_AD::generate, :115-140,271-300,433-440), each scaling the accumulator V from before the update: omega_j = c_j V.  v_AD has max(n_add, n_rem)
+ * coefficients, so its values at the N-th roots of unity (N the next power of two; the passes of the witness update, O(N (n_add + n_rem)) products) and ONE
+ * inverse transform of size N give them without polynomial arithmetic.  alpha is used on the host only; the device copies of the tables, the
+ * evaluations and the coefficients are zeroed before the call returns, and nothing is cached.
+ *   omega_xy, omega_inf    max(n_add, n_rem) entries: affine Montgomery limbs and identity flags.  A zero coefficient, and every entry of an identity
+ *                          accumulator, is an identity entry: zero words, flag 1
+ *   omega_len              ark-poly drops trailing zero coefficients: the index of the last non-zero coefficient plus one (0 for two empty lists or the zero
+ *                          polynomial, e.g. one addition and one removal of the same element); entries from omega_len on are identities
+ * Omega::new_for_kb_positive_accumulator (:514-527) is this call with empty additions, the members prf(r) as removals, and the negated accumulator.
+ * DGPU_E_BADARG (before the device is looked at): a NULL pointer with a non-zero count, a count >= 2^31, max(n_add, n_rem) > DGPU_ACC_OMEGA_MAX = 2^18 (the
+ * work is quadratic: longer batches want a product tree), an addition or a removal equal to -alpha.  Both lists empty: DGPU_OK, omega_len = 0, no device
+ * needed.  Stage timers acc.prep, acc.omega_eval, acc.omega_intt, acc.omega_mul.
+ *
+ * dgpu_accumulator_update_witnesses_public_g1 is the holders' half, m times Witness::compute_update_using_public_info_after_batch_updates
+ * (vb_accumulator/src/witness.rs:292-314) with Omega::evaluate (batch_utils.rs:664-691), without the secret key:
+ *     f_i = d_A(y_i) / d_D(y_i),  s_i = 1 / d_D(y_i),  C_i' = f_i C_i + sum_j (s_i y_i^j) omega_j
+ * The m x n_omega scaled powers are made on the device, straight into the scalar rows of the many-row MSM; they never exist on the host.
+ *   omega_xy, omega_inf    n_omega entries as dgpu_accumulator_omega_g1 writes them (omega_inf may be NULL: an entry of zero words is an identity either way).
+ *                          n_omega is not tied to the list lengths; n_omega = 0 gives C_i' = f_i C_i
+ *   d_factors, out_xy, out_inf   as dgpu_accumulator_update_witnesses_g1
+ *   ok                     ok[i] = 0 for a holder whose element is among the removals (d_D = 0, the reference's Err(CannotBeZero)): that holder gets
+ *                          d_factor = 0 and the identity (zero words, out_inf = 1), the call still returns DGPU_OK and every other holder gets ok[i] = 1
+ * Up to 8192 entries of omega (and dgpu_set_small_msm_max) the rows run through the many-row MSM kernels, in chunks of rows; beyond, row by row through
+ * the single-MSM driver.  m = 0: DGPU_OK.  DGPU_E_BADARG as above (n_omega >= 2^31 too).  No size threshold.  Thread-safe; one slot per call.
+ * Stage timers acc.prep, acc.pub_factors, acc.pub_rows, msm.many_tree, msm.many_fold, acc.scale. */
+#define DGPU_ACC_OMEGA_MAX ((size_t)1 << 18)
+int32_t dgpu_accumulator_omega_g1(const uint64_t *additions, size_t n_add, const uint64_t *removals, size_t n_rem,
+                                  const uint64_t alpha[4], const uint64_t accumulator_xy[12], int32_t montgomery,
+                                  uint64_t *omega_xy /* max(n_add, n_rem) * 12 */, uint8_t *omega_inf /* max(n_add, n_rem) */, size_t *omega_len);
+int32_t dgpu_accumulator_update_witnesses_public_g1(const uint64_t *additions, size_t n_add, const uint64_t *removals, size_t n_rem,
+                                                    const uint64_t *omega_xy /* n_omega * 12 */, const uint8_t *omega_inf /* n_omega or NULL */, size_t n_omega,
+                                                    const uint64_t *elements /* m*4 */, const uint64_t *witnesses_xy /* m*12 */, size_t m, int32_t montgomery,
+                                                    uint64_t *d_factors /* m*4 */, uint64_t *out_xy /* m*12 */, uint8_t *out_inf /* m */, uint8_t *ok /* m */);
+
 /* ---- the LegoGroth16 prover as one call ----
  * replaces create_proof_and_committed_witnesses_with_assignment (legogroth16/src/prover.rs:267-383, with calculate_coeff :585-594) and — when
  * the circuit is resident (r1cs != 0) — the QAP::witness_map call in front of it (create_proof_with_reduction, :153-180): the whole schedule

@@ -35,7 +35,9 @@ int32_t dgpu_set_gt_pow(int32_t groups_per_wave, int32_t bases_per_group, int32_
 int32_t dgpu_set_wm_many(int32_t chunk_rows, int32_t rows_per_block);
 /* dgpu_accumulator_update_*: chunks per element of the two passes (1..4096; 0 = automatic: 1 when the elements alone fill the device, else enough chunks of
  * at least 32 list entries to reach 65536 lanes — both constants unmeasured until tests/perf/acc_update_timing.py has run).  Any value gives the same words
- * (tests force 1, 2 and 5 at small shapes).  dgpu_dev_get_acc_split returns the chunk count the process's last call ran with (0: none yet). */
+ * (tests force 1, 2 and 5 at small shapes).  dgpu_dev_get_acc_split returns the chunk count the process's last call ran with (0: none yet).
+ * The public-information pair cuts its passes by the same knob: dgpu_accumulator_omega_g1 per evaluation point, dgpu_accumulator_update_witnesses_public_g1
+ * per holder. */
 int32_t dgpu_dev_set_acc_split(int32_t chunks);
 int32_t dgpu_dev_get_acc_split(void);
 /* Route of the witness map's transforms (crypto_amd/csrc/k_ntt.hip run_passes).  path = 0: automatic — one k_ntt_stage launch per stage below 2^10, the piped

@@ -235,6 +235,34 @@ pub fn accumulator_update_witnesses(additions: &[Fr], removals: &[Fr], alpha: &F
     if rc != DGPU_OK { return None; }
     Some((d, (0..m).map(|i| g1_affine(xy[12 * i..12 * i + 12].try_into().unwrap(), inf[i])).collect()))
 }
+/// `Omega::new(additions, removals, old_accumulator, sk)` (vb_accumulator/src/batch_utils.rs:498-509): the coefficients of `v_AD`, each scaling the accumulator
+/// from before the update, trimmed like ark-poly trims the polynomial.  `Omega::new_for_kb_positive_accumulator` is this call with empty additions, the
+/// members `prf(r)` as removals and the negated accumulator.
+pub fn accumulator_omega(additions: &[Fr], removals: &[Fr], alpha: &Fr, old_accumulator: &G1Affine) -> Option<Vec<G1Affine>> {
+    let n = additions.len().max(removals.len());
+    let (v, _) = pack_g1(core::slice::from_ref(old_accumulator));
+    let (mut xy, mut inf) = (ark_std::vec![0u64; n * 12], ark_std::vec![0u8; n]);
+    let mut len = 0usize;
+    let rc = unsafe { dgpu_accumulator_omega_g1(additions.as_ptr() as *const u64, additions.len(), removals.as_ptr() as *const u64, removals.len(), alpha as *const Fr as *const u64,
+                                                v.as_ptr(), 1, xy.as_mut_ptr(), inf.as_mut_ptr(), &mut len) };
+    if rc != DGPU_OK { return None; }
+    Some((0..len).map(|j| g1_affine(xy[12 * j..12 * j + 12].try_into().unwrap(), inf[j])).collect())
+}
+/// `Witness::compute_update_using_public_info_after_batch_updates(additions, removals, omega, element, old_witness)` (witness.rs:292-314) for every holder in
+/// one call: `Ok((d_factor, new_witness))` per holder, `Err(())` for a holder whose element is among the removals (the reference's `CannotBeZero`).
+pub fn accumulator_update_witnesses_public(additions: &[Fr], removals: &[Fr], omega: &[G1Affine], elements: &[Fr], old_witnesses: &[G1Affine]) -> Option<Vec<Result<(Fr, G1Affine), ()>>> {
+    let m = elements.len();
+    if old_witnesses.len() != m { return None; }
+    let (w, _) = pack_g1(old_witnesses);                              // identity: zero words
+    let (o, oinf) = pack_g1(omega);
+    let mut d = ark_std::vec![Fr::from(0u64); m];
+    let (mut xy, mut inf, mut ok) = (ark_std::vec![0u64; m * 12], ark_std::vec![0u8; m], ark_std::vec![0u8; m]);
+    let rc = unsafe { dgpu_accumulator_update_witnesses_public_g1(additions.as_ptr() as *const u64, additions.len(), removals.as_ptr() as *const u64, removals.len(),
+                                                                  o.as_ptr(), oinf.as_ptr(), omega.len(), elements.as_ptr() as *const u64, w.as_ptr(), m, 1,
+                                                                  d.as_mut_ptr() as *mut u64, xy.as_mut_ptr(), inf.as_mut_ptr(), ok.as_mut_ptr()) };
+    if rc != DGPU_OK { return None; }
+    Some((0..m).map(|i| if ok[i] != 0 { Ok((d[i], g1_affine(xy[12 * i..12 * i + 12].try_into().unwrap(), inf[i]))) } else { Err(()) }).collect())
+}
 
 // ---- R1CS -> QAP witness map (legogroth16/src/r1cs_to_qap.rs:150-210) ---------------------------------------------------------------------------------
 /// one constraint matrix of ark-relations' `ConstraintMatrices` (`Matrix<F> = Vec<Vec<(F, usize)>>`) as the CSR arrays the ABI takes, with a 64-bit hash of

@@ -327,6 +327,51 @@ fn accumulator_witness_update_with_the_secret_key() {
     assert!(host::accumulator_update_factors(&[-alpha], &removals, &alpha, &elements).is_none());      // an addition equal to -alpha: refused
 }
 
+// Poly_v_AD::generate's coefficients with arkworks' own arithmetic, lowest degree first (vb_accumulator/src/batch_utils.rs:115-140,271-300,433-440)
+fn cpu_v_ad_coefficients(additions: &[Fr], removals: &[Fr], alpha: &Fr) -> Vec<Fr> {
+    use ark_ff::{Field, One};
+    let mul_lin = |p: &[Fr], u: &Fr| { let mut q = ark_std::vec![Fr::zero(); p.len() + 1]; for (k, c) in p.iter().enumerate() { q[k] += *c * *u; q[k + 1] -= *c; } q };      // p (u - x)
+    let (mut s, mut f) = (Vec::<Fr>::new(), Fr::one());
+    for a in additions { s = if s.is_empty() { ark_std::vec![] } else { mul_lin(&s, a) }; if s.is_empty() { s.push(f); } else { s[0] += f; } f *= *a + *alpha; }
+    let (mut d, mut p, mut g) = (ark_std::vec![Fr::zero(); removals.len()], ark_std::vec![Fr::one()], Fr::one());
+    for r in removals { g *= (*r + *alpha).inverse().unwrap(); for (k, c) in p.iter().enumerate() { d[k] += *c * g; } p = mul_lin(&p, r); }
+    let mut c = ark_std::vec![Fr::zero(); additions.len().max(removals.len())];
+    for (k, x) in s.iter().enumerate() { c[k] += *x; }
+    for (k, x) in d.iter().enumerate() { c[k] -= *x * f; }
+    while c.last().map_or(false, |x| x.is_zero()) { c.pop(); }
+    c
+}
+
+#[test]
+fn accumulator_update_from_public_information() {
+    use ark_ff::Field;
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5EED00AD);
+    let (alpha, v) = (Fr::rand(&mut rng), Fr::rand(&mut rng));
+    let (additions, removals, mut elements) = (frs(&mut rng, 40), frs(&mut rng, 25), frs(&mut rng, 300));
+    elements[3] = removals[1];                                        // a removed holder: CannotBeZero for that holder alone
+    let g = G1Affine::generator();
+    let acc = (g * v).into_affine();
+    let wits = G1Projective::normalize_batch(&elements.iter().map(|y| g * (v * (*y + alpha).inverse().unwrap())).collect::<Vec<_>>());
+    for (a, r) in [(&additions[..], &removals[..]), (&additions[..], &removals[..0]), (&additions[..0], &removals[..]), (&additions[..1], &removals[..1])] {
+        let omega = host::accumulator_omega(a, r, &alpha, &acc).expect("omega");
+        let want = cpu_v_ad_coefficients(a, r, &alpha);
+        assert_eq!(omega, G1Projective::normalize_batch(&want.iter().map(|c| acc * *c).collect::<Vec<_>>()));
+        let got = host::accumulator_update_witnesses_public(a, r, &omega, &elements, &wits).expect("public update");
+        let (d_sk, w_sk) = host::accumulator_update_witnesses(a, r, &alpha, &elements, &wits, &acc).expect("witnesses");
+        let v_new = a.iter().fold(v, |x, e| x * (*e + alpha)) * r.iter().fold(Fr::from(1u64), |x, e| x * (*e + alpha)).inverse().unwrap();
+        for i in 0..elements.len() {
+            if r.contains(&elements[i]) { assert!(i == 3 && got[i].is_err()); continue; }      // removed in THIS pair's list only: elsewhere holder 3 is an ordinary holder
+            let (d, w) = got[i].unwrap();
+            assert_eq!((d, w), (d_sk[i], w_sk[i]), "holder {}", i);
+            assert_eq!((w * (elements[i] + alpha)).into_affine(), (g * v_new).into_affine());
+        }
+    }
+    let same = [additions[0]];
+    assert!(host::accumulator_omega(&same, &same, &alpha, &acc).expect("omega").is_empty());      // 1 - (a + alpha) / (a + alpha): the zero polynomial
+    assert!(host::accumulator_omega(&[-alpha], &removals, &alpha, &acc).is_none());
+}
+
 #[test]
 fn many_small_msms_over_one_key() {
     // m rows against m arkworks calls: the shapes of dkgith.rs:174-192 (many short rows), one row of the key's full length, an identity row, &[Fr] and BigInt rows
