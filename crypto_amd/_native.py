@@ -86,7 +86,7 @@ _init_args = None    # ("init", device, min_gpu_n) / ("list", [devices], min_gpu
 # every symbol include/dock_gpu_dev.h adds (the twin only)
 DEV_SYMBOLS = ["dgpu_set_window_bits", "dgpu_set_chunk", "dgpu_set_many_chunk_rows", "dgpu_set_msm_segments", "dgpu_set_reduce_shift", "dgpu_set_reduce_lanes", "dgpu_set_miller_pipeline", "dgpu_set_gt_pow", "dgpu_set_wm_many",
                "dgpu_prof_enable", "dgpu_prof_reset", "dgpu_prof_read", "dgpu_selftest_fp_mul", "dgpu_selftest_g1_sum", "dgpu_selftest_glv_decompose", "dgpu_selftest_gls4_decompose",
-               "dgpu_dev_fail_alloc_after", "dgpu_dev_set_acc_split", "dgpu_dev_get_acc_split", "dgpu_dev_set_ntt", "dgpu_dev_get_ntt_last"]
+               "dgpu_dev_fail_alloc_after", "dgpu_dev_set_acc_split", "dgpu_dev_get_acc_split", "dgpu_dev_set_acc_d_pass", "dgpu_dev_set_acc_d_unroll", "dgpu_dev_get_acc_d_unroll", "dgpu_dev_set_ntt", "dgpu_dev_get_ntt_last"]
 
 # every symbol include/dock_gpu.h declares
 SYMBOLS = [
@@ -99,6 +99,7 @@ SYMBOLS = [
     "dgpu_msm_g1_sharded", "dgpu_msm_g2_sharded", "dgpu_bases_upload_g1_sharded", "dgpu_bases_upload_g2_sharded", "dgpu_msm_g1_sharded_handle", "dgpu_msm_g2_sharded_handle", "dgpu_scalars_upload_sharded", "dgpu_scalars_copy_range", "dgpu_msm_g1_sharded_resident", "dgpu_msm_g2_sharded_resident",
     "dgpu_fold_g1", "dgpu_fold_g2", "dgpu_lincomb_g1", "dgpu_lincomb_g2", "dgpu_multi_miller_loop", "dgpu_multi_miller_loop_sharded", "dgpu_bases_table_shape", "dgpu_scalars_sort", "dgpu_msm_g1_sorted", "dgpu_msm_g2_sorted", "dgpu_multi_miller_loop_segments", "dgpu_multi_pairing_segments", "dgpu_g2_prepare", "dgpu_multi_miller_loop_prepared", "dgpu_multi_miller_loop_mixed", "dgpu_multi_miller_loop_scaled", "dgpu_final_exponentiation", "dgpu_final_exponentiation_batch", "dgpu_g1_scale_batch", "dgpu_fp12_mul", "dgpu_fp12_pow", "dgpu_fp12_multi_pow", "dgpu_fp12_pow_batch", "dgpu_fp12_multi_pow_device", "dgpu_gt_in_subgroup_device", "dgpu_gt_in_subgroup", "dgpu_g1_serialize", "dgpu_g1_deserialize", "dgpu_g2_serialize", "dgpu_g2_deserialize", "dgpu_g1_deserialize_device", "dgpu_g2_deserialize_device", "dgpu_bases_upload_g1_serialized", "dgpu_bases_upload_g2_serialized", "dgpu_g1_validate_batch", "dgpu_g2_validate_batch", "dgpu_g1_serialize_device", "dgpu_g2_serialize_device", "dgpu_bases_read_g1", "dgpu_bases_read_g2", "dgpu_bases_serialize_g1", "dgpu_bases_serialize_g2", "dgpu_witness_map", "dgpu_r1cs_upload", "dgpu_r1cs_free", "dgpu_r1cs_shape", "dgpu_witness_map_r1cs", "dgpu_witness_map_r1cs_resident", "dgpu_witness_map_r1cs_many", "dgpu_qap_instance_map", "dgpu_legogroth16_setup",
     "dgpu_accumulator_update_factors", "dgpu_accumulator_update_witnesses_g1", "dgpu_accumulator_omega_g1", "dgpu_accumulator_update_witnesses_public_g1",
+    "dgpu_accumulator_d_for_batch", "dgpu_accumulator_d_for_batch_resident", "dgpu_accumulator_non_membership_witnesses_g1", "dgpu_accumulator_membership_witnesses_g1",
     "dgpu_window_table_g1", "dgpu_window_table_g2", "dgpu_window_table_free", "dgpu_window_table_mul_g1", "dgpu_window_table_mul_g2", "dgpu_window_table_mul_to_bases_g1", "dgpu_window_table_mul_to_bases_g2", "dgpu_fixed_base_g1", "dgpu_fixed_base_g2", "dgpu_g1_mul_add_batch", "dgpu_g2_mul_add_batch",
     "dgpu_legogroth16_prove", "dgpu_legogroth16_prove_host", "dgpu_legogroth16_verify", "dgpu_legogroth16_verify_batch", "dgpu_legogroth16_verify_each", "dgpu_handle_len", "dgpu_handle_context", "dgpu_shard_count", "dgpu_shard_part",
     "dgpu_snarkpack_proof_words", "dgpu_snarkpack_aggregate", "dgpu_snarkpack_verify",
@@ -277,6 +278,10 @@ def _load(path):
         L.dgpu_accumulator_update_witnesses_g1.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, vp, C.c_int32, vp, vp, vp]
         L.dgpu_accumulator_omega_g1.argtypes = [vp, sz, vp, sz, vp, vp, C.c_int32, vp, vp, C.POINTER(sz)]
         L.dgpu_accumulator_update_witnesses_public_g1.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, C.c_int32, vp, vp, vp, vp]
+        L.dgpu_accumulator_d_for_batch.argtypes = [vp, sz, vp, sz, C.c_int32, vp, vp, vp]
+        L.dgpu_accumulator_d_for_batch_resident.argtypes = [C.c_uint64, sz, sz, vp, sz, C.c_int32, vp, vp, vp]
+        L.dgpu_accumulator_non_membership_witnesses_g1.argtypes = [vp, vp, sz, vp, vp, vp, C.c_int32, vp, vp, vp]
+        L.dgpu_accumulator_membership_witnesses_g1.argtypes = [vp, sz, vp, vp, C.c_int32, vp, vp]
         L.dgpu_witness_map.argtypes = [vp, vp, vp, sz] * 3 + [vp, sz, sz, sz, C.c_int32, vp, C.POINTER(u64), C.POINTER(sz)]
         for name in ("dgpu_window_table_g1", "dgpu_window_table_g2"):
             getattr(L, name).argtypes = [vp, C.POINTER(u64)]
@@ -323,6 +328,9 @@ def _load(path):
             L.dgpu_dev_fail_alloc_after.argtypes = [C.c_int64, C.c_int64]
             L.dgpu_dev_set_acc_split.argtypes = [C.c_int32]
             L.dgpu_dev_get_acc_split.argtypes = []
+            L.dgpu_dev_set_acc_d_pass.argtypes = [C.c_int32]
+            L.dgpu_dev_set_acc_d_unroll.argtypes = [C.c_int32]
+            L.dgpu_dev_get_acc_d_unroll.argtypes = []
             L.dgpu_dev_set_ntt.argtypes = [C.c_int32, vp, C.c_int32]
             L.dgpu_dev_get_ntt_last.argtypes = [C.POINTER(C.c_int32), vp, C.c_int32]
         _loaded[path] = L

@@ -10,6 +10,15 @@
     Witness::compute_update_using_public_info_after_batch_updates(additions, removals, omega, element, old_witness), for m holders at once (witness.rs:292-314)
         -> update_witnesses_public(additions, removals, omega, elements, witnesses)       returns (d_factors, new_witnesses, ok)
 
+    UniversalAccumulator::compute_d_for_batch_given_members(non_members, members) (universal.rs:479-495)
+        -> d_for_batch(members, non_members, d_in=None)                                    returns (d, nonzero); members may be resident (DeviceScalars)
+    ...::compute_non_membership_witnesses_for_batch_given_d(d, non_members, sk, params_gen) (universal.rs:499-535)
+        -> non_membership_witnesses(d, non_members, f_V, alpha, params_gen)               returns ((points, identity_mask), ok)
+    ...::get_non_membership_witnesses_for_batch(non_members, sk, state, params_gen) (universal.rs:540-583)
+        -> get_non_membership_witnesses_for_batch(members, non_members, f_V, alpha, params_gen)      returns (d, (points, identity_mask))
+    PositiveAccumulator::compute_membership_witnesses_for_batch(members, sk) (positive.rs:369-381)
+        -> membership_witnesses(members, alpha, accumulator)                                returns (points, identity_mask)
+
 Field elements are (n, 4) uint64 limb arrays or Python ints, canonical unless `montgomery=True` (then ark-ff Montgomery limbs in and out).  Witnesses
 and the accumulator are G1 affine Montgomery limbs, (m, 12) and (12,) uint64; an identity is all-zero words.  New witnesses come back normalised
 (G::Group::normalize_batch, witness.rs:284) as an (m, 12) array plus a uint8 identity mask: a holder whose element was removed gets d_factor = 0 and
@@ -107,3 +116,86 @@ def update_witnesses_public(additions, removals, omega, elements, witnesses, mon
     if rc:
         raise DockGpuError(rc, "dgpu_accumulator_update_witnesses_public_g1")
     return d, (out, inf), ok
+
+
+def _alpha(alpha):
+    return _scalars_to_limbs([alpha] if isinstance(alpha, int) else alpha).reshape(4)
+
+
+def d_for_batch(members, non_members, d_in=None, montgomery=False, offset=0, n=None):
+    """(d, nonzero): d_i = d_in_i prod_j (member_j - y_i) over all members, d_in = None meaning one; nonzero[i] = 0 marks a y_i that is a member.  `members`
+    is an array / list, or a resident scalar vector (crypto_amd.DeviceScalars, or its handle with `n` given) of which the entries [offset, offset + n) are
+    read where they lie; `montgomery` then speaks for non_members, d_in and d only.  Feeding the d of one partition of the members as the d_in of the next
+    is the reference's partitioning (universal.rs:476-478)"""
+    _ensure()
+    y, py = _limbs(non_members)
+    m = len(y)
+    di = None
+    if d_in is not None:
+        di = _scalars_to_limbs(d_in)
+        if len(di) != m:
+            raise ValueError("d_in: %d entries for %d non-members" % (len(di), m))
+    d = np.zeros((m, 4), np.uint64)
+    nz = np.zeros(m, np.uint8)
+    mont = 1 if montgomery else 0
+    if hasattr(members, "handle") or isinstance(members, int):
+        handle = members if isinstance(members, int) else members.handle
+        if n is None:
+            if isinstance(members, int):
+                raise ValueError("a bare handle needs n")
+            n = members.n - offset
+        rc = lib().dgpu_accumulator_d_for_batch_resident(handle, offset, n, py, m, mont, _p(di), _p(d), _p(nz))
+        name = "dgpu_accumulator_d_for_batch_resident"
+    else:
+        a, pa = _limbs(members)
+        a = a[offset:offset + n] if n is not None else a[offset:]
+        rc = lib().dgpu_accumulator_d_for_batch(_p(np.ascontiguousarray(a)) if len(a) else None, len(a), py, m, mont, _p(di), _p(d), _p(nz))
+        name = "dgpu_accumulator_d_for_batch"
+    if rc:
+        raise DockGpuError(rc, name)
+    return d, nz
+
+
+def non_membership_witnesses(d, non_members, f_V, alpha, params_gen, montgomery=False):
+    """((points, identity_mask), ok): C_i = ((f_V - d_i) / (y_i + alpha)) params_gen.  ok[i] = 0 marks a zero d_i (the reference's CannotBeZero): the identity for
+    that entry, everyone else unaffected"""
+    _ensure()
+    y, py = _limbs(non_members)
+    dd, pd = _limbs(d)
+    m = len(y)
+    if len(dd) != m:
+        raise ValueError("%d non-members, %d values of d" % (m, len(dd)))
+    fv = _alpha(f_V)
+    al = _alpha(alpha)
+    g = np.ascontiguousarray(params_gen, dtype=np.uint64).reshape(12)
+    out, inf, ok = np.zeros((m, 12), np.uint64), np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+    rc = lib().dgpu_accumulator_non_membership_witnesses_g1(pd, py, m, _p(fv), _p(al), _p(g), 1 if montgomery else 0, _p(out), _p(inf), _p(ok))
+    if rc:
+        raise DockGpuError(rc, "dgpu_accumulator_non_membership_witnesses_g1")
+    return (out, inf), ok
+
+
+def membership_witnesses(members, alpha, accumulator, montgomery=False):
+    """(points, identity_mask): C_i = (1 / (y_i + alpha)) V"""
+    _ensure()
+    y, py = _limbs(members)
+    m = len(y)
+    al = _alpha(alpha)
+    v = np.ascontiguousarray(accumulator, dtype=np.uint64).reshape(12)
+    out, inf = np.zeros((m, 12), np.uint64), np.zeros(m, np.uint8)
+    rc = lib().dgpu_accumulator_membership_witnesses_g1(py, m, _p(al), _p(v), 1 if montgomery else 0, _p(out), _p(inf))
+    if rc:
+        raise DockGpuError(rc, "dgpu_accumulator_membership_witnesses_g1")
+    return out, inf
+
+
+def get_non_membership_witnesses_for_batch(members, non_members, f_V, alpha, params_gen, montgomery=False):
+    """(d, (points, identity_mask)): the two calls in a row, as the reference does (universal.rs:540-583).  Raises ValueError("CannotBeZero") when a
+    non-member is a member (the reference answers ElementPresent from its state, or CannotBeZero from the product)"""
+    d, nz = d_for_batch(members, non_members, montgomery=montgomery)
+    if not nz.all():
+        raise ValueError("CannotBeZero")
+    wits, ok = non_membership_witnesses(d, non_members, f_V, alpha, params_gen, montgomery=montgomery)
+    if not ok.all():
+        raise ValueError("CannotBeZero")
+    return d, wits

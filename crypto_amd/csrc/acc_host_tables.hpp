@@ -61,4 +61,28 @@ inline int32_t build_tables(const uint64_t *additions, size_t na, const uint64_t
     wipe(&al, sizeof al); wipe(&acc, sizeof acc);
     return rc;
 }
+// the host's share of issuing witnesses (universal.rs:511-513, positive.rs:375-376): t_i = 1 / (y_i + alpha) for the entries [lo, hi), as ark-ff Montgomery
+// words at t + 4 i, with ONE inversion (Montgomery's trick: t holds the prefix products in between).  DGPU_E_BADARG for a y_i equal to -alpha, which has no
+// inverse (the reference's batch_inversion would leave a zero there and issue the identity)
+inline int32_t issue_inverses(const uint64_t *ys, size_t lo, size_t hi, const uint64_t alpha[4], bool mont, uint64_t *t) {
+    FrH al = fr_in(alpha, mont), acc = FrH::from_u64(1);
+    int32_t rc = DGPU_OK;
+    for (size_t i = lo; i < hi && !rc; i++) {
+        const FrH u = fr_plus(fr_in(ys + 4 * i, mont), al);
+        if (fr_is_zero(u)) rc = DGPU_E_BADARG;
+        memcpy(t + 4 * i, acc.l, 32); acc = acc * u;
+    }
+    if (!rc && hi > lo) {
+        FrH inv = acc.inv();
+        for (size_t i = hi; i-- > lo;) {
+            FrH u = fr_plus(fr_in(ys + 4 * i, mont), al), pre; memcpy(pre.l, t + 4 * i, 32);
+            const FrH o = inv * pre; inv = inv * u;
+            memcpy(t + 4 * i, o.l, 32);
+            wipe(&u, sizeof u); wipe(&pre, sizeof pre);
+        }
+        wipe(&inv, sizeof inv);
+    }
+    wipe(&al, sizeof al); wipe(&acc, sizeof acc);
+    return rc;
+}
 }  // namespace acch

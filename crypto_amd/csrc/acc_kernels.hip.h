@@ -159,6 +159,39 @@ template <class OUT> FRD void pub_row_run(const Fr &y, const Fr &s, size_t j0, s
     for (size_t j = 0; j < cnt; j++) { out(j0 + j, cur); if (j + 1 < cnt) fr_mul(cur, cur, y); }
 }
 
+// ---- issuing witnesses (universal.rs:461-535, positive.rs:369-381) ------------------------------------------------------------------------------------
+// d_i = f_V(-y_i) = prod_j (member_j - y_i) over ALL members of the accumulator: few points, an enormous list.  One lane owns U non-members y[0 .. owned)
+// and walks the members [lo, hi) ONCE: one load per member (lm(s, member): a table entry, a product) feeds U independent chains, each started from one.
+// Chains the lane does not own (j >= owned: the tail lane of a call whose m is no multiple of U) are skipped; their P stays one.  y: products.  Chunks
+// combine by a plain product (d_times).
+template <int U, class LM> FRD void d_chunk(const Fr (&y)[U], int owned, size_t lo, size_t hi, LM lm, Fr (&P)[U]) {
+#pragma unroll
+    for (int j = 0; j < U; j++) fr_one(P[j]);
+    Fr t, d;
+    for (size_t s = lo; s < hi; s++) {
+        lm(s, t);
+#pragma unroll
+        for (int j = 0; j < U; j++)
+            if (j < owned) {
+                fr_sub<512, 30>(d, t, y[j]);      // member - y + 512 r: limbs < 2^31, value < 514 r — the first operand, no carry pass
+                fr_mul(P[j], d, P[j]);            // 514 r * 2 r
+            }
+    }
+}
+// the running product D (a product; d_in as it was loaded, limbs <= 2^29 + 1 and value < 3 r at most) takes a chunk's or a pass's product P (a product) on its right
+FRD void d_times(Fr &D, const Fr &P) { fr_mul(D, P, D); }        // 2 r * 3 r
+// the scalar of one witness: (f_V - d) t for a non-membership witness (with_d), t itself for a membership witness; t = 1 / (y + alpha) from the host.
+// fv, d, t: products.  Returns true for d = 0 (the reference's Err(CannotBeZero)): the scalar is zero then.
+FRD bool issue_scalar(Fr &sc, bool with_d, const Fr &fv, const Fr &d, const Fr &t) {
+    if (!with_d) { sc = t; return false; }
+    Fr e;
+    fr_sub<512, 30>(e, fv, d);                    // f_V - d + 512 r: limbs < 2^31, value < 514 r — a first operand, no carry pass
+    fr_mul(sc, e, t);                             // 514 r * 2 r
+    if (!is_zero(d)) return false;
+    fr_zero(sc);
+    return true;
+}
+
 #if defined(__HIPCC__)
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------------------
 // Tables: entry e of the internal-form table at tab[e * NL ..]: [a_0 .. | F_0 .. | r_0 .. | G_0 .. | Phi], 2 na + 2 nr + 1 entries.  Every lane of a block
@@ -392,6 +425,85 @@ __global__ void __launch_bounds__(256) k_acc_pub_rows(const uint32_t *__restrict
     const size_t j0 = (t % per_row) * run, cnt = n - j0 < run ? n - j0 : run;
     Fr y, s; ld_words(y, elems, i, mont != 0); ld_words(s, s_words, i, false);
     pub_row_run(y, s, j0, cnt, [&](size_t j, const Fr &v) { st_words(out_rows, i * n + j, v); });
+}
+
+// ---- issuing witnesses ----------------------------------------------------------------------------------------------------------------------------------
+// tab: the members of one pass in internal form (k_acc_prep), n of them.  run: the running product of every non-member between the passes, limb-major
+// (ld_soa / st_soa over m).  part (K > 1): word l of chunk c of non-member i at part[(l * K + c) * m + i].  d_words: m x 8 words in the caller's form (mont).
+struct DOut {
+    const uint32_t *__restrict__ d_in; uint32_t *__restrict__ run; uint32_t *__restrict__ d_words; uint8_t *__restrict__ nz; size_t m; int mont, first, last;
+    // the product before this pass: d_in (one for NULL) on the first pass, else what the pass before left
+    __device__ __forceinline__ void start(Fr &D, size_t i) const {
+        if (!first) ld_soa(D, run, m, i);
+        else if (d_in) ld_words(D, d_in, i, mont != 0);
+        else fr_one(D);
+    }
+    // after this pass: words and the non-zero flag on the last pass, else the internal form for the next
+    __device__ __forceinline__ void finish(const Fr &D, size_t i) const {
+        if (!last) { st_soa(run, m, i, D); return; }
+        uint32_t w[8]; fr_to_words(w, D, mont != 0);
+        uint4 *q = reinterpret_cast<uint4 *>(d_words + i * 8);
+        q[0] = make_uint4(w[0], w[1], w[2], w[3]); q[1] = make_uint4(w[4], w[5], w[6], w[7]);
+        nz[i] = is_zero(D) ? 0 : 1;
+    }
+};
+// grid (lanes / 256, K): lane g of G = ceil(m / U) owns the non-members g + j G (j < U: the loads of y coalesce) and runs chunk c = blockIdx.y of the pass for
+// all of them at once; every lane of a block reads the same member in the same step.  K = 1 finishes in place (DOut); K > 1 leaves the chunk's products to
+// k_acc_d_combine.
+template <int U> __global__ void __launch_bounds__(256) k_acc_d(const uint32_t *__restrict__ tab, size_t n, const uint32_t *__restrict__ elems, size_t m, uint32_t K, size_t G,
+                                                                 uint32_t *__restrict__ part, DOut o) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const int owned = (int)((m - g + G - 1) / G < (size_t)U ? (m - g + G - 1) / G : (size_t)U);
+    Fr y[U], P[U];
+#pragma unroll
+    for (int j = 0; j < U; j++) { if (j < owned) ld_words(y[j], elems, g + j * G, o.mont != 0); else fr_zero(y[j]); }
+    const size_t c = blockIdx.y;
+    d_chunk<U>(y, owned, n * c / K, n * (c + 1) / K, [&](size_t s, Fr &a) { ld_tab(a, tab, s); }, P);
+    if (K == 1) {
+        // one copy of the finishing code for all chains: P[j] by selects, so that P stays in registers (an index known only at run time would put it in scratch)
+#pragma unroll 1
+        for (int j = 0; j < owned; j++) {
+            Fr Pj = P[0], D;
+#pragma unroll
+            for (int q = 1; q < U; q++) if (j == q) Pj = P[q];
+            const size_t i = g + j * G;
+            o.start(D, i); d_times(D, Pj); o.finish(D, i);
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < U; j++)
+        if (j < owned) {
+#pragma unroll
+            for (int l = 0; l < NL; l++) part[((size_t)l * K + c) * m + g + j * G] = P[j].l[l];
+        }
+}
+// K > 1: one lane per non-member: the running product times its K chunk products
+__global__ void __launch_bounds__(256) k_acc_d_combine(const uint32_t *__restrict__ part, size_t m, uint32_t K, DOut o) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    Fr D, P; o.start(D, i);
+    for (uint32_t c = 0; c < K; c++) {
+#pragma unroll
+        for (int l = 0; l < NL; l++) P.l[l] = part[((size_t)l * K + c) * m + i];
+        d_times(D, P);
+    }
+    o.finish(D, i);
+}
+// sc[8 i ..] = the canonical words of (f_V - d_i) t_i (with_d) or of t_i, the scalars of k_fb_mul; zero[i] = (d_i is zero): that scalar is zero.
+// d_words: the caller's form (mont); t_words: ark-ff Montgomery words from the host; fv: the caller's form.
+__global__ void __launch_bounds__(256) k_acc_issue_scalars(const uint32_t *__restrict__ d_words, const uint32_t *__restrict__ t_words, Words8 fv_words, int mont, int with_d, size_t m,
+                                                           uint32_t *__restrict__ sc, uint8_t *__restrict__ zero) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    Fr fv, d, t, s;
+    fr_zero(fv); fr_zero(d);
+    ld_words(t, t_words, i, true);
+    if (with_d) { fr_from_words(fv, fv_words.w, mont != 0); ld_words(d, d_words, i, mont != 0); }
+    const bool z = issue_scalar(s, with_d != 0, fv, d, t);
+    st_words(sc, i, s);
+    zero[i] = z ? 1 : 0;
 }
 #endif
 

@@ -1,6 +1,6 @@
 // crypto_amd/csrc/dock_accumulator.hip — the accumulator's batch witness updates (include/dock_gpu.h: dgpu_accumulator_update_factors,
 // dgpu_accumulator_update_witnesses_g1 with the secret key; dgpu_accumulator_omega_g1 and dgpu_accumulator_update_witnesses_public_g1, the two halves of
-// the update from public information, further down).  Replaces Witness::compute_update_using_secret_key_after_batch_updates and its additions-only / removals-only
+// the update from public information, further down; dgpu_accumulator_d_for_batch[_resident] and the two calls that issue witnesses at the end).  Replaces Witness::compute_update_using_secret_key_after_batch_updates and its additions-only / removals-only
 // forms (vb_accumulator/src/witness.rs:165-285) with the polynomial evaluations of vb_accumulator/src/batch_utils.rs:81-470 in front:
 //   host    F_s, G_s, Phi from the secret key (O(|A| + |D|), one inversion); alpha never leaves the host
 //   device  f_i = d_A(y_i) / d_D(y_i), g_i = v_AD(y_i) / d_D(y_i)                 k_acc_prep, k_acc_eval [, k_acc_combine]   (acc_kernels.hip.h)
@@ -382,6 +382,143 @@ int32_t update_witnesses_public(const uint64_t *additions, size_t na, const uint
     return rc;
 }
 
+// ---- issuing witnesses (universal.rs:461-583, positive.rs:369-381) ---------------------------------------------------------------------------------------
+// d_i = d_in_i prod_j (member_j - y_i) over ALL members of the accumulator: m n products for a batch of m against an accumulator of n, n the large number.
+//   device  the members of one pass (at most ACC_D_PASS; from the host, or straight out of a resident scalars handle) -> internal form     k_acc_prep
+//   device  every lane walks the pass once for the one or four non-members it owns, in K chunks when the lanes alone do not fill the device   k_acc_d [, k_acc_d_combine]
+// The running products stay on the device in internal form between the passes; the last pass writes words.  Nothing here is secret: nothing is wiped.
+int32_t d_on_slot(Slot &sl, const uint64_t *members, const uint32_t *resident, size_t n, const uint64_t *non_members, size_t m, bool mont, const uint64_t *d_in,
+                  uint64_t *d_out, uint8_t *nonzero) {
+    const size_t forced_pass = (size_t)gs.acc_d_pass.load(), pass = forced_pass ? forced_pass : acck::ACC_D_PASS, longest = std::min(n, pass);
+    const int forced = gs.acc_split.load(), U = acck::acc_d_unroll(m, longest, gs.acc_d_unroll.load(), forced);
+    const size_t G = acck::acc_d_lanes(m, U);
+    const uint32_t K0 = acck::acc_shape(G, longest, 0, forced).K;                 // (a shorter last pass never has more chunks)
+    gs.acc_last_split = (int)K0; gs.acc_d_last_unroll = U;
+    const size_t words_b = resident ? 0 : (std::max<size_t>(longest, 1) * 32 + 255) & ~(size_t)255, tab_b = (std::max<size_t>(longest, 1) * 40 + 255) & ~(size_t)255;
+    // q[0]: the members of a pass (words | internal form), q[1]: chunk products, q[2]: the running products, q[3]: d, q[4]: the non-members, q[5]: d_in, q[8]: non-zero flags
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = o.q[0].ensure(words_b + tab_b))) return e;
+        if ((e = o.q[1].ensure(acck::acc_d_part_bytes(m, K0) + 256))) return e;
+        if ((e = o.q[2].ensure(acck::acc_d_run_bytes(m)))) return e;
+        if ((e = o.q[3].ensure(m * 32))) return e;
+        if ((e = o.q[4].ensure(m * 32))) return e;
+        if ((e = o.q[5].ensure(m * 32))) return e;
+        return o.q[8].ensure(m);
+    };
+    int32_t rc;
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws(sl))) return rc;
+    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    hipStream_t s = sl.stream;
+    DrainUnlessDone guard(sl);
+    uint32_t *d_words = sl.q[0].as<uint32_t>(), *d_tab = (uint32_t *)(sl.q[0].as<uint8_t>() + words_b), *d_el = sl.q[4].as<uint32_t>();
+    const uint32_t *d_din = d_in ? sl.q[5].as<uint32_t>() : nullptr;
+    HIPCHK(hipMemcpyAsync(d_el, non_members, m * 32, hipMemcpyHostToDevice, s));
+    if (d_in) HIPCHK(hipMemcpyAsync(sl.q[5].p, d_in, m * 32, hipMemcpyHostToDevice, s));
+    for (size_t lo = 0;; lo += pass) {
+        const size_t len = std::min(pass, n - lo);
+        const bool first = lo == 0, last = lo + len >= n;
+        if (len) {
+            if (!resident) HIPCHK(hipMemcpyAsync(d_words, members + 4 * lo, len * 32, hipMemcpyHostToDevice, s));      // (queued behind the pass before: its prep has read the words)
+            StageTimer st(sl, "acc.d_prep");
+            acck::launch_acc_prep(s, resident ? resident + lo * 8 : d_words, len, d_tab, resident ? 0 : (mont ? 1 : 0));
+        }
+        { StageTimer st(sl, "acc.d_eval");
+          acck::launch_acc_d(s, d_tab, len, d_el, mont ? 1 : 0, m, U, acck::acc_shape(G, len, 0, forced).K, d_din, first, last, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(),
+                             sl.q[3].as<uint32_t>(), sl.q[8].as<uint8_t>()); }
+        if (last) break;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(d_out, sl.q[3].p, m * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(nonzero, sl.q[8].p, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    guard.done = true;
+    return DGPU_OK;
+}
+// members: the host's words, or (resident) the handle of a resident scalar vector whose entries [offset, offset + n) are read where they lie
+int32_t d_for_batch(const uint64_t *members, bool resident, uint64_t handle, size_t offset, size_t n, const uint64_t *non_members, size_t m, bool mont, const uint64_t *d_in,
+                    uint64_t *d_out, uint8_t *nonzero) {
+    if (m == 0) return DGPU_OK;
+    if ((!resident && n && !members) || !non_members || !d_out || !nonzero || m >= (1ull << 31) || n >= (1ull << 31)) return DGPU_E_BADARG;
+    HandleRef hs;
+    if (resident && (!hs.acquire(handle) || hs.h.kind != 3 || hs.h.ctx != cur_index() || offset > hs.h.n || n > hs.h.n - offset)) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    SLOT_ACQUIRE(L, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    const int32_t rc = d_on_slot(sl, members, resident ? (const uint32_t *)hs.h.p + offset * 8 : nullptr, n, non_members, m, mont, d_in, d_out, nonzero);
+    if (gs.prof) prof_flush(sl);
+    return rc;
+}
+
+// C_i = s_i B with s_i = (f_V - d_i) / (y_i + alpha), B = params_gen for non-membership witnesses (compute_non_membership_witnesses_for_batch_given_d,
+// universal.rs:499-535) and s_i = 1 / (y_i + alpha), B = V for membership witnesses (compute_membership_witnesses_for_batch, positive.rs:369-381):
+//   host    t_i = 1 / (y_i + alpha): one batch inversion per share of the host threads; alpha never leaves the host
+//   device  s_i as canonical words straight into the multiplication's scalar buffer, and the zero-d flags        k_acc_issue_scalars
+//   device  s_i B from a window table of B built in the slot's workspace, normalised affine points              k_fb_table, k_fb_mul
+// The device copies of t, the scalars and the table are zeroed on every return path, the host copy of t too.
+struct SecretWords {
+    std::vector<uint64_t> w;
+    ~SecretWords() { if (!w.empty()) wipe(w.data(), w.size() * 8); }
+};
+int32_t issue_witnesses(bool with_d, const uint64_t *d, const uint64_t *ys, size_t m, const uint64_t *f_V, const uint64_t *alpha, const uint64_t *base, bool mont,
+                        uint64_t *out, uint8_t *out_inf, uint8_t *ok) {
+    if (m == 0) return DGPU_OK;
+    if (!ys || !alpha || !base || !out || !out_inf || (with_d && (!d || !f_V || !ok)) || m >= (1ull << 31)) return DGPU_E_BADARG;
+    SecretWords t;
+    t.w.assign(m * 4, 0);
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t parts = std::min<size_t>(16, (m + 1023) / 1024);
+    int32_t rc = par_run(parts, [&](size_t k) { return issue_inverses(ys, m * k / parts, m * (k + 1) / parts, alpha, mont, t.w.data()); });
+    if (rc) return rc;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    if (gs.prof) prof_add_host("acc.host_inverses", ms_since(t0));
+    SLOT_ACQUIRE(LK, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    const size_t pt = 96;
+    // q[0]: t, q[3]: the scalars, q[4]: d, q[8]: the zero-d flags, q[9]: the window table of B, q[10]: [s_i B | identity flags]
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = o.q[0].ensure(m * 32))) return e;
+        if ((e = o.q[3].ensure(m * 32))) return e;
+        if ((e = o.q[4].ensure(m * 32))) return e;
+        if ((e = o.q[8].ensure(m))) return e;
+        if ((e = o.q[9].ensure(window_table_g1_bytes()))) return e;
+        if ((e = o.q[10].ensure(m * pt + m))) return e;
+        if ((e = o.prepped.ensure(32 * G1::AFF_STRIDE * 4))) return e;                  // (the window table's scratch)
+        return o.in_bases.ensure(32 * 2 * G1::ABI_W * 4 + 16);
+    };
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws(sl))) return rc;
+    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    hipStream_t s = sl.stream;
+    std::vector<uint64_t> window_bases;                       // (host words of the table's upload: they live until the call's synchronisation)
+    std::vector<uint8_t> zero(m);
+    DrainUnlessDone guard(sl);
+    DeviceWipe dw(sl);
+    dw.add(sl.q[0].p, m * 32); dw.add(sl.q[3].p, m * 32); dw.add(sl.q[9].p, window_table_g1_bytes());
+    if ((rc = window_table_g1_on_slot(sl, base, sl.q[9].p, window_bases))) return rc;
+    uint8_t *d_out = sl.q[10].as<uint8_t>(), *d_inf = d_out + m * pt;
+    HIPCHK(hipMemcpyAsync(sl.q[0].p, t.w.data(), m * 32, hipMemcpyHostToDevice, s));
+    if (with_d) HIPCHK(hipMemcpyAsync(sl.q[4].p, d, m * 32, hipMemcpyHostToDevice, s));
+    { StageTimer st(sl, "acc.issue_scalars");
+      acck::launch_acc_issue_scalars(s, with_d ? sl.q[4].as<uint32_t>() : nullptr, sl.q[0].as<uint32_t>(), (const uint32_t *)f_V, mont ? 1 : 0, m, sl.q[3].as<uint32_t>(), sl.q[8].as<uint8_t>()); }
+    { StageTimer st(sl, "acc.table_mul"); msm::launch_fb_mul<msm::G1>(s, sl.q[9].as<uint32_t>(), sl.q[3].as<uint32_t>(), m, (uint32_t *)d_out, d_inf); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, m * pt, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_inf, d_inf, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(zero.data(), sl.q[8].p, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    guard.done = true;
+    if (gs.prof) prof_flush(sl);
+    // a zero d is the reference's Err(CannotBeZero) for that entry alone: ok = 0 and the identity; an identity (a zero scalar, an identity base) is zero words
+    for (size_t i = 0; i < m; i++) {
+        if (with_d) ok[i] = zero[i] ? 0 : 1;
+        if (zero[i] || out_inf[i]) { memset(out + 12 * i, 0, pt); out_inf[i] = 1; }
+    }
+    return DGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -403,5 +540,20 @@ int32_t dgpu_accumulator_update_witnesses_public_g1(const uint64_t *additions, s
     return abi_guard([&] {
         return update_witnesses_public(additions, n_add, removals, n_rem, omega_xy, omega_inf, n_omega, elements, witnesses_xy, m, montgomery != 0, d_factors, out_xy, out_inf, ok);
     });
+}
+int32_t dgpu_accumulator_d_for_batch(const uint64_t *members, size_t n, const uint64_t *non_members, size_t m, int32_t montgomery, const uint64_t *d_in, uint64_t *d_out, uint8_t *nonzero) {
+    return abi_guard([&] { return d_for_batch(members, false, 0, 0, n, non_members, m, montgomery != 0, d_in, d_out, nonzero); });
+}
+int32_t dgpu_accumulator_d_for_batch_resident(uint64_t members, size_t offset, size_t n, const uint64_t *non_members, size_t m, int32_t montgomery, const uint64_t *d_in, uint64_t *d_out,
+                                              uint8_t *nonzero) {
+    return abi_guard([&] { return d_for_batch(nullptr, true, members, offset, n, non_members, m, montgomery != 0, d_in, d_out, nonzero); });
+}
+int32_t dgpu_accumulator_non_membership_witnesses_g1(const uint64_t *d, const uint64_t *non_members, size_t m, const uint64_t f_V[4], const uint64_t alpha[4], const uint64_t params_gen_xy[12],
+                                                     int32_t montgomery, uint64_t *out_xy, uint8_t *out_inf, uint8_t *ok) {
+    return abi_guard([&] { return issue_witnesses(true, d, non_members, m, f_V, alpha, params_gen_xy, montgomery != 0, out_xy, out_inf, ok); });
+}
+int32_t dgpu_accumulator_membership_witnesses_g1(const uint64_t *members, size_t m, const uint64_t alpha[4], const uint64_t accumulator_xy[12], int32_t montgomery, uint64_t *out_xy,
+                                                 uint8_t *out_inf) {
+    return abi_guard([&] { return issue_witnesses(false, nullptr, members, m, nullptr, alpha, accumulator_xy, montgomery != 0, out_xy, out_inf, nullptr); });
 }
 }  // extern "C"

@@ -119,6 +119,7 @@ struct Shared {
     std::atomic<int> gt_pow_g{0}, gt_pow_k{0}, gt_pow_chunk{0};   // dgpu_set_gt_pow: groups per wave, bases per group and elements per chunk of the GT power kernels (dock_gt_dev.hip; 0 = automatic)
     std::atomic<int> wm_many_chunk{0}, wm_many_rpb{0};   // dgpu_set_wm_many: rows per chunk and statements per block of dgpu_witness_map_r1cs_many (dock_qap.hip; 0 = automatic)
     std::atomic<int> acc_split{0}, acc_last_split{0};   // dgpu_dev_set_acc_split: chunks per element of the accumulator witness update (dock_accumulator.hip; 0 = automatic), and the count the last call ran with
+    std::atomic<int> acc_d_pass{0}, acc_d_unroll{0}, acc_d_last_unroll{0};    // dgpu_dev_set_acc_d_pass / dgpu_dev_set_acc_d_unroll: members per pass and non-members per lane of dgpu_accumulator_d_for_batch (dock_accumulator.hip; 0 = automatic), and the non-members per lane the last call ran with
     std::atomic<int> reduce_lanes{0};        // dgpu_set_reduce_lanes: 0 = the shared bucket set by bit marginals (reduce_kernels.hip.h; the plain pipeline then takes 4); 1 / 4: the scan form with k_reduce_top / k_reduce_top_quad (members per point in the last kernel)
     std::atomic<int> reduce_shift{-1};        // dgpu_set_reduce_shift: log2 buckets per lane of k_reduce_l0 on the table pipeline (-1 = automatic)
     std::atomic<int> ml_mode{31};             // dgpu_set_miller_pipeline: bit 0 the two-launch line kernel of small Miller loops, bit 1 the 18-role product tree, bit 2 sixteen lanes per pair in the line kernel, bit 3 (with bit 2) a wave per role, bit 4 three waves per sparse product while the chip is nearly empty (pairing_launch.hip.h: the launchers take this word)

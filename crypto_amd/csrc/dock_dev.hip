@@ -24,6 +24,9 @@ int32_t dgpu_set_wm_many(int32_t chunk_rows, int32_t rows_per_block) {
 }
 int32_t dgpu_dev_set_acc_split(int32_t chunks) { if (chunks < 0 || chunks > (int32_t)acck::ACC_MAX_SPLIT) return DGPU_E_BADARG; gs.acc_split = chunks; return DGPU_OK; }
 int32_t dgpu_dev_get_acc_split(void) { return gs.acc_last_split.load(); }
+int32_t dgpu_dev_set_acc_d_pass(int32_t entries) { if (entries < 0) return DGPU_E_BADARG; gs.acc_d_pass = entries; return DGPU_OK; }
+int32_t dgpu_dev_set_acc_d_unroll(int32_t non_members_per_lane) { if (non_members_per_lane != 0 && non_members_per_lane != 1 && non_members_per_lane != 4) return DGPU_E_BADARG; gs.acc_d_unroll = non_members_per_lane; return DGPU_OK; }
+int32_t dgpu_dev_get_acc_d_unroll(void) { return gs.acc_d_last_unroll.load(); }
 int32_t dgpu_dev_set_ntt(int32_t path, const int32_t *split, int32_t n_split) { return ntt::dev_set_ntt(path, split, n_split) ? DGPU_OK : DGPU_E_BADARG; }
 int32_t dgpu_dev_get_ntt_last(int32_t *path, int32_t *groups, int32_t cap) {
     if (!path || cap < 0 || (cap > 0 && !groups)) return DGPU_E_BADARG;

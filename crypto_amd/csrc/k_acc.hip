@@ -48,4 +48,18 @@ void launch_acc_pub_rows(hipStream_t s, const uint32_t *elems, int mont, const u
     const size_t lanes = rows * ((n + ACC_ROW_RUN - 1) / ACC_ROW_RUN);
     hipLaunchKernelGGL(k_acc_pub_rows, dim3(blocks_for(lanes)), dim3(256), 0, s, elems, mont, s_words, rows, n, ACC_ROW_RUN, out_rows);
 }
+size_t acc_d_part_bytes(size_t m, uint32_t K) { return K > 1 ? align256((size_t)NL * 4 * K * m) : 0; }
+size_t acc_d_run_bytes(size_t m) { return align256((size_t)NL * 4 * m); }
+void launch_acc_d(hipStream_t s, const uint32_t *tab, size_t n, const uint32_t *elems, int mont, size_t m, int U, uint32_t K, const uint32_t *d_in, bool first, bool last,
+                  uint32_t *part, uint32_t *run, uint32_t *d_words, uint8_t *nz) {
+    const DOut o{d_in, run, d_words, nz, m, mont, first ? 1 : 0, last ? 1 : 0};
+    const size_t G = acc_d_lanes(m, U);
+    if (U == 4) hipLaunchKernelGGL(k_acc_d<4>, dim3(blocks_for(G), K), dim3(256), 0, s, tab, n, elems, m, K, G, part, o);
+    else hipLaunchKernelGGL(k_acc_d<1>, dim3(blocks_for(G), K), dim3(256), 0, s, tab, n, elems, m, K, G, part, o);
+    if (K > 1) hipLaunchKernelGGL(k_acc_d_combine, dim3(blocks_for(m)), dim3(256), 0, s, part, m, K, o);
+}
+void launch_acc_issue_scalars(hipStream_t s, const uint32_t *d_words, const uint32_t *t_words, const uint32_t fv_words[8], int mont, size_t m, uint32_t *sc, uint8_t *zero) {
+    Words8 w; for (int k = 0; k < 8; k++) w.w[k] = d_words ? fv_words[k] : 0;
+    hipLaunchKernelGGL(k_acc_issue_scalars, dim3(blocks_for(m)), dim3(256), 0, s, d_words, t_words, w, mont, d_words ? 1 : 0, m, sc, zero);
+}
 }  // namespace acck

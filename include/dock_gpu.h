@@ -579,6 +579,49 @@ int32_t dgpu_accumulator_update_witnesses_public_g1(const uint64_t *additions, s
                                                     const uint64_t *elements /* m*4 */, const uint64_t *witnesses_xy /* m*12 */, size_t m, int32_t montgomery,
                                                     uint64_t *d_factors /* m*4 */, uint64_t *out_xy /* m*12 */, uint8_t *out_inf /* m */, uint8_t *ok /* m */);
 
+/* ---- accumulator manager: issuing membership and non-membership witnesses ----
+ * dgpu_accumulator_d_for_batch is UniversalAccumulator::compute_d_for_batch_given_members (vb_accumulator/src/universal.rs:479-495; the same double loop
+ * opens get_non_membership_witnesses_for_batch, :564-575): for every non-member y_i the product over ALL members of the accumulator ("This is expensive
+ * as a product involving all accumulated elements is needed", :461-463),
+ *     d_out_i = d_in_i prod_{j < n} (member_j - y_i)          d_in = NULL: one
+ * m n field products on the device, n being the size of the accumulator and not of a batch.  d_in is the reference's "partition the members, multiply the
+ * outputs" (:476-478) done inside the call: feed the d_out of one partition as the d_in of the next.
+ *   members / non_members  n / m x 4 words; montgomery as above (it speaks for members, non_members, d_in and d_out)
+ *   nonzero                nonzero[i] = (d_out_i != 0): 0 marks a y_i that IS a member (or a zero d_in)
+ * n = 0 copies d_in (or writes ones).  Members from the host travel in passes of at most 2^20 entries; the running products stay on the device between them.
+ * Nothing here is secret, so nothing is wiped.
+ * dgpu_accumulator_d_for_batch_resident reads the members from a resident scalar vector instead (a dgpu_scalars_upload handle, which holds canonical words
+ * after the upload whatever form they came in): entries [offset, offset + n) straight out of it, nothing but the non-members is uploaded, and one handle
+ * serves every batch and every partition.  montgomery then speaks for non_members, d_in and d_out only.  DGPU_E_BADARG for a handle that is not a scalar
+ * vector, one of another device context than the calling thread's, or a range past its end.
+ *
+ * dgpu_accumulator_non_membership_witnesses_g1 is compute_non_membership_witnesses_for_batch_given_d (universal.rs:499-535):
+ *     C_i = ((f_V - d_i) / (y_i + alpha)) params_gen
+ * and dgpu_accumulator_membership_witnesses_g1 is compute_membership_witnesses_for_batch (vb_accumulator/src/positive.rs:369-381):
+ *     C_i = (1 / (y_i + alpha)) V
+ * The inverses are made on the host (one batch inversion per share of the host threads; alpha is used on the host only), the scalars on the device, straight
+ * into the scalar buffer of a window-table multiplication whose table is built in the call's workspace; the points come back normalised.
+ *   d, non_members / members   m x 4 words; f_V, alpha: 4 words; montgomery as above
+ *   params_gen_xy, accumulator_xy, out_xy, out_inf   as the witnesses of dgpu_accumulator_update_witnesses_g1: an identity base (zero words) gives identities
+ *   ok                     a zero d_i is the reference's Err(CannotBeZero): that entry gets ok[i] = 0, zero words and out_inf[i] = 1, every other entry ok[i] = 1,
+ *                          and the call returns DGPU_OK (the convention of dgpu_accumulator_update_witnesses_public_g1)
+ * A y_i equal to -alpha has no inverse: DGPU_E_BADARG, decided on the host before the device is looked at (as for an addition equal to -alpha above).  The
+ * device copies of the inverses, the scalars and the table are zeroed on every return path, the host copies too; nothing is cached.
+ *
+ * All four: m = 0 is DGPU_OK and reads nothing.  DGPU_E_BADARG for a NULL pointer with a non-zero count, m >= 2^31 or n >= 2^31 — every argument check comes
+ * before the device is looked at.  No size threshold.  Thread-safe; one slot per call; a second call of a shape allocates nothing.  Stage timers acc.d_prep,
+ * acc.d_eval, acc.issue_scalars, acc.table_mul. */
+int32_t dgpu_accumulator_d_for_batch(const uint64_t *members /* n*4 */, size_t n, const uint64_t *non_members /* m*4 */, size_t m, int32_t montgomery,
+                                     const uint64_t *d_in /* m*4 or NULL */, uint64_t *d_out /* m*4 */, uint8_t *nonzero /* m */);
+int32_t dgpu_accumulator_d_for_batch_resident(uint64_t members /* dgpu_scalars_upload handle */, size_t offset, size_t n,
+                                              const uint64_t *non_members /* m*4 */, size_t m, int32_t montgomery,
+                                              const uint64_t *d_in /* m*4 or NULL */, uint64_t *d_out /* m*4 */, uint8_t *nonzero /* m */);
+int32_t dgpu_accumulator_non_membership_witnesses_g1(const uint64_t *d /* m*4 */, const uint64_t *non_members /* m*4 */, size_t m, const uint64_t f_V[4],
+                                                     const uint64_t alpha[4], const uint64_t params_gen_xy[12], int32_t montgomery,
+                                                     uint64_t *out_xy /* m*12 */, uint8_t *out_inf /* m */, uint8_t *ok /* m */);
+int32_t dgpu_accumulator_membership_witnesses_g1(const uint64_t *members /* m*4 */, size_t m, const uint64_t alpha[4], const uint64_t accumulator_xy[12],
+                                                 int32_t montgomery, uint64_t *out_xy /* m*12 */, uint8_t *out_inf /* m */);
+
 /* ---- the LegoGroth16 prover as one call ----
  * replaces create_proof_and_committed_witnesses_with_assignment (legogroth16/src/prover.rs:267-383, with calculate_coeff :585-594) and — when
  * the circuit is resident (r1cs != 0) — the QAP::witness_map call in front of it (create_proof_with_reduction, :153-180): the whole schedule

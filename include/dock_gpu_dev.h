@@ -40,6 +40,14 @@ int32_t dgpu_set_wm_many(int32_t chunk_rows, int32_t rows_per_block);
  * per holder. */
 int32_t dgpu_dev_set_acc_split(int32_t chunks);
 int32_t dgpu_dev_get_acc_split(void);
+/* dgpu_accumulator_d_for_batch[_resident]: members per pass (1 .. 2^31 - 1; 0 = automatic: 2^20, unmeasured) — tests make 33 members take five passes — and
+ * non-members per lane of k_acc_d (1 or 4; 0 = automatic: 4 from 256 non-members on when the chunks then hold at least 512 members; tests/perf/acc_issue_timing.py
+ * compares the two).  The chunks
+ * per pass follow dgpu_dev_set_acc_split.  Any setting gives the same words.  dgpu_dev_get_acc_d_unroll returns the non-members per lane the process's last
+ * call ran with (0: none yet). */
+int32_t dgpu_dev_set_acc_d_pass(int32_t entries);
+int32_t dgpu_dev_set_acc_d_unroll(int32_t non_members_per_lane);
+int32_t dgpu_dev_get_acc_d_unroll(void);
 /* Route of the witness map's transforms (crypto_amd/csrc/k_ntt.hip run_passes).  path = 0: automatic — one k_ntt_stage launch per stage below 2^10, the piped
  * k_ntt_r4 passes with the (ab - c) / Z step and the coset epilogue fused into the first / last pass for 2^10 .. 2^26, k_ntt_fused (2^11-element tiles, groups
  * of up to 7 stages) with the separate k_pointwise / k_coset_scale above (arrays beyond 4 GB).  path = 1: one launch per stage with the separate k_coset_scale /

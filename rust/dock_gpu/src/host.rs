@@ -264,6 +264,30 @@ pub fn accumulator_update_witnesses_public(additions: &[Fr], removals: &[Fr], om
     Some((0..m).map(|i| if ok[i] != 0 { Ok((d[i], g1_affine(xy[12 * i..12 * i + 12].try_into().unwrap(), inf[i]))) } else { Err(()) }).collect())
 }
 
+// ---- issuing witnesses: the raw callers behind src/accumulator_issue.rs (the typed API and its documentation live there) -----------------------------------
+/// `d_out_i = d_in_i prod_j (members_j - non_members_i)`; all slices are ark-ff Montgomery limbs, `d_in` may be empty (one)
+pub(crate) fn raw_accumulator_d_for_batch(members: &[Fr], non_members: &[Fr], d_in: &[Fr], d_out: &mut [Fr], nonzero: &mut [u8]) -> i32 {
+    let din = if d_in.is_empty() { core::ptr::null() } else { d_in.as_ptr() as *const u64 };
+    unsafe { dgpu_accumulator_d_for_batch(members.as_ptr() as *const u64, members.len(), non_members.as_ptr() as *const u64, non_members.len(), 1, din,
+                                          d_out.as_mut_ptr() as *mut u64, nonzero.as_mut_ptr()) }
+}
+/// the same with the members read out of a resident scalar vector: entries `[offset, offset + n)` of `handle`
+pub(crate) fn raw_accumulator_d_for_batch_resident(handle: u64, offset: usize, n: usize, non_members: &[Fr], d_in: &[Fr], d_out: &mut [Fr], nonzero: &mut [u8]) -> i32 {
+    let din = if d_in.is_empty() { core::ptr::null() } else { d_in.as_ptr() as *const u64 };
+    unsafe { dgpu_accumulator_d_for_batch_resident(handle, offset, n, non_members.as_ptr() as *const u64, non_members.len(), 1, din, d_out.as_mut_ptr() as *mut u64, nonzero.as_mut_ptr()) }
+}
+/// `C_i = ((f_V - d_i) / (y_i + alpha)) params_gen`; `xy`: m x 12 words, `inf`, `ok`: m bytes
+pub(crate) fn raw_accumulator_non_membership_witnesses(d: &[Fr], non_members: &[Fr], f_v: &Fr, alpha: &Fr, params_gen: &G1Affine, xy: &mut [u64], inf: &mut [u8], ok: &mut [u8]) -> i32 {
+    let (g, _) = pack_g1(core::slice::from_ref(params_gen));            // identity: zero words
+    unsafe { dgpu_accumulator_non_membership_witnesses_g1(d.as_ptr() as *const u64, non_members.as_ptr() as *const u64, non_members.len(), f_v as *const Fr as *const u64,
+                                                          alpha as *const Fr as *const u64, g.as_ptr(), 1, xy.as_mut_ptr(), inf.as_mut_ptr(), ok.as_mut_ptr()) }
+}
+/// `C_i = (1 / (y_i + alpha)) V`
+pub(crate) fn raw_accumulator_membership_witnesses(members: &[Fr], alpha: &Fr, accumulator: &G1Affine, xy: &mut [u64], inf: &mut [u8]) -> i32 {
+    let (v, _) = pack_g1(core::slice::from_ref(accumulator));
+    unsafe { dgpu_accumulator_membership_witnesses_g1(members.as_ptr() as *const u64, members.len(), alpha as *const Fr as *const u64, v.as_ptr(), 1, xy.as_mut_ptr(), inf.as_mut_ptr()) }
+}
+
 // ---- R1CS -> QAP witness map (legogroth16/src/r1cs_to_qap.rs:150-210) ---------------------------------------------------------------------------------
 /// one constraint matrix of ark-relations' `ConstraintMatrices` (`Matrix<F> = Vec<Vec<(F, usize)>>`) as the CSR arrays the ABI takes, with a 64-bit hash of
 /// its whole contents computed on the way (the copy reads every coefficient anyway)

@@ -29,6 +29,7 @@ use ark_std::vec::Vec;
 pub mod encode;
 pub mod generic;
 pub mod host;
+pub mod accumulator_issue;      // (issuing membership / non-membership witnesses: src/accumulator_issue.rs; cargo-side cases in tests/parity_accumulator_issue.rs)
 
 pub type G2Prepared = ArkG2Prepared<ark_bls12_381::Config>;
 
