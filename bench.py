@@ -9,7 +9,11 @@ MSM of 2^24 terms per step (configs[4]) by point-chunk sharding: each rank runs 
 2^24 / N terms, then an RCCL all_gather of the 144-byte partial points and a local fold (crypto_amd/sharded.py).
 value = (terms per step / 2^20) / seconds per step, i.e. n = 2^20-MSM equivalents per second for the whole job.
 
-Extra objects on the JSON line: "roofline" (dominant kernel = k_accumulate, algorithmic bytes = 128 B/term,
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what that figure needs and nothing else: set-up, the closed-form check of the step's
+result, the warm-up passes (W sequential steps, then every host thread and slot once, three sequential steps whose mean is latency_ms_one_in_flight,
+every thread and slot again), the K timed steps, --dump-outputs, the JSON line.  Everything below is measured AFTER the timed steps and only with --full.
+
+Extra objects on the JSON line with --full: "roofline" (dominant kernel = k_accumulate, algorithmic bytes = 128 B/term,
 duration from HIP events on the library's stream), "valu_roofline" (the same kernel against the measured
 v_mad_u64_u32 issue peak: the path is integer-multiply bound), "cpu_baseline" (the CPU oracle = arkworks-style
 Pippenger, one thread per window like rayon, timed on this box's host cores; kind "port"; plus one thread and the
@@ -181,10 +185,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2n", type=int, default=0, help="terms per GPU = 2^log2n; default: 20 at 1 GPU (BASELINE config 2), 24 - log2(gpus) at N > 1 (config 5: 2^24 in total)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary timings appended to the JSON line at N = 1")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run everything that is not the headline figure: the stage / roofline leg on the development twin, "
+                                                        "cpu_baseline and secondary (N = 1), scaling_base (N > 1); a run without it sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary timings appended to the JSON line at N = 1")
     ap.add_argument("--inflight", type=int, default=6, help="MSM calls in flight per GPU (host threads; each call owns a stream + workspace slot)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cpu-legs", action="store_true", help="skip secondary.cpu (the CPU path timed beside configs 3 and 4: about 10 s of host work)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and secondary.cpu")
+    ap.add_argument("--no-cpu-legs", action="store_true", help="with --full: skip secondary.cpu (the CPU path timed beside configs 3 and 4: about 10 s of host work)")
     ap.add_argument("--no-table", action="store_true", help="time the plain resident pipeline (no precomputed-multiples table)")
     ap.add_argument("--reduce-shift", type=int, default=-1, help="development: dgpu_set_reduce_shift (log2 buckets per lane of the bucket reduction; -1 = automatic)")
     ap.add_argument("--reduce-lanes", type=int, default=-1, help="development: dgpu_set_reduce_lanes (0 = bit marginals, the default; 1 / 4 = the scan form of rounds 1-4)")
@@ -346,8 +352,9 @@ def main():
     # the DEVELOPMENT surface (include/dock_gpu_dev.h), which the product library does not export.  So this leg — untimed, rank 0, after the
     # ranks' collectives — runs the same workload on the development twin (libdock_gpu_dev.so: the product's objects, kernels included, plus that surface) with its own copy of the
     # operands: one call in flight (stages_seq: the roofline's kernel duration) and the timed region's shape (stages: durations that overlap).
+    # A second copy of the operands and three more passes: not what the headline figure needs, so only under --full.
     stages_seq, stages = {}, {}
-    if rank == 0:
+    if rank == 0 and args.full:
         local_res = res if world == 1 else db.msm_resident(ds)        # this rank's own partial point (product library), before the twin takes over the wrappers
         with ca.twin():
             with FB.WindowTable(ca.G1, gen1[0]) as gtab_t:
@@ -369,28 +376,6 @@ def main():
         ms_step = dt / args.steps * 1e3
         terms = n * world
         value = (terms / float(1 << 20)) / (dt / args.steps)
-        # dominant kernel: duration from the one-call-in-flight pass (HIP events on the library's stream); inside the
-        # timed region up to `inflight` launches share the chip, so their event durations overlap and are reported separately
-        acc_ms = stages_seq.get("msm.accumulate", (0.0, 1))
-        acc_avg_ms = acc_ms[0] / max(1, acc_ms[1])
-        acc_ov = stages.get("msm.accumulate", (0.0, 1))
-        acc_ov_ms = acc_ov[0] / max(1, acc_ov[1])
-        alg_bytes = 128.0 * n                      # 32 B scalar + 96 B affine base per term, one launch = n terms
-        achieved = alg_bytes / (acc_avg_ms * 1e-3) / 1e9 if acc_avg_ms > 0 else 0.0
-        # HBM bytes per launch from the PMC counters: collected by separate rocprofv3 --pmc passes of THIS command (tools/dev/round4_profiles.sh ->
-        # tools/traffic_json.py), not inside this process; the file names the commit it was measured at
-        traffic, traffic_src = None, None
-        tj = os.path.join(ROOT, "profiles", "traffic_accumulate.json")
-        if os.path.exists(tj):
-            try:
-                tr = json.load(open(tj))
-                if tr.get("log2n") == args.log2n and bool(tr.get("table")) == use_table:
-                    traffic = tr.get("hbm_bytes_per_launch")
-                    traffic_src = "profiles/traffic_accumulate.json, measured at commit %s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --inflight 1`)" % tr.get("commit", "of round 3")
-            except Exception:
-                pass
-        shape = db.table_shape()                   # (rows, window bits, windows) when the handle is a table
-        windows = shape[2] if shape else (16 if args.log2n >= 17 else None)
         out = {
             "metric": "BLS12-381 G1 MSM/s at n=2^20 (1 GPU) and n=2^24 (8 GPU); bit-exact vs CPU",
             "value": round(value, 3), "unit": "MSM/s (n=2^20-term equivalents, whole job)",
@@ -409,48 +394,80 @@ def main():
                                 "values are a strong-scaling series; secondary.g1_2p24_single_gpu is the 1-GPU time of the same 2^24 terms"},
             "terms_per_s": round(terms / (dt / args.steps), 1),
             "inflight": inflight, "latency_ms_one_in_flight": round(latency_ms, 4), "device_allocations_in_timed_region": int(allocs_timed),
-            "stages_ms": {k.replace("msm.", ""): round(v[0] / max(1, v[1]), 4) for k, v in stages.items()},
-            "stages_ms_one_in_flight": {k.replace("msm.", ""): round(v[0] / max(1, v[1]), 4) for k, v in stages_seq.items()},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 6),
-                         "traffic": traffic, "traffic_source": traffic_src, "kernel": "msm::k_accumulate<msm::G1S, false>" if use_table else "msm::k_accumulate<msm::G1S, false> (plain pipeline)", "avg_ms": round(acc_avg_ms, 4), "avg_ms_overlapped": round(acc_ov_ms, 4),
-                         "note": "algorithmic 128 B/term x 2^log2n terms per launch; avg_ms = HIP-event duration on the library's stream with one call in flight "
-                                 "(same process, untimed pass on the development twin — the product's kernel objects plus the stage timers, which the product "
-                                 "library does not export; rocprof of `bench.py --inflight 1` agrees), avg_ms_overlapped = the same with the timed region's "
-                                 "calls in flight, where launches share the chip; the kernel is integer-multiply bound: see valu_roofline"},
         }
-        if acc_avg_ms > 0 and windows:
-            mads = float(n) * windows * MADS_PER_MIXED_ADD
-            out["valu_roofline"] = {"bound": "v_mad_i64_i32 (same issue rate as v_mad_u64_u32)", "achieved": round(mads / (acc_avg_ms * 1e-3) / 1e12, 3), "peak": MAD_PEAK, "unit": "Tmad/s",
-                                    "frac": round(mads / (acc_avg_ms * 1e-3) / 1e12 / MAD_PEAK, 4), "mixed_additions_per_launch": int(n) * windows,
-                                    "note": "%d windows x n mixed additions x %d 32 x 32 -> 64-bit multiply-adds each (13 x 30-bit signed limbs since round 3: 13.8 %% fewer than the 3542 of the 14 x 29-bit field, so the same kernel time is a LOWER fraction); peak = measured issue rate, profiles/r01h_instr_rate_ubench.txt" % (
-                                        windows, MADS_PER_MIXED_ADD)}
+        if args.full:
+            out.update(stage_objects(args, n, use_table, db.table_shape(), stages_seq, stages))
         if dev_run:
             out["library"] = "libdock_gpu_dev.so (development twin: --reduce-shift / --reduce-lanes set a knob the product does not have)"
         if STUB:
             out["data"] = "STUB (tests/bench_stub.py: control-flow test on CPU ranks, not a measurement)"
-        if not args.no_cpu_baseline and not STUB and world == 1:        # (the contract: on rank 0 at N = 1 only)
+        if args.full and not args.no_cpu_baseline and not STUB and world == 1:        # (the contract: on rank 0 at N = 1 only)
             out["cpu_baseline"] = cpu_baseline(ca, gen1, ks, scalars, db, ds, args.log2n, ncpu)
-        if world == 1 and not args.no_secondary and not STUB:
+        if args.full and world == 1 and not args.no_secondary and not STUB:
             try:
                 out["secondary"] = secondary_configs(args.log2n, ks, scalars, db, ds, pool, cpu_legs=not (args.no_cpu_baseline or args.no_cpu_legs), ncpu=ncpu)
             except Exception as e:                      # never let the secondary numbers take the headline line down
                 out["secondary"] = {"error": repr(e)}
-        # scaling_base: the 1-GPU rate on config 5's 2^24 terms, in the unit of `value` — what value(N > 1) must be divided by (the N = 1 line is config 2:
-        # 2^20 terms with six independent calls in flight, a different workload).  At N = 1 it comes out of the secondary leg; at N > 1 rank 0 measures it
-        # on its own GPU after the timed region (one 28-GB table, ~3 s), so that every line of the driver's SCALE run carries its own denominator.
-        sb = None
-        try:
-            if world == 1 and isinstance(out.get("secondary"), dict):
-                sb = out["secondary"].get("g1_2p24_single_gpu", {}).get("msm_2p20_equivalents_per_s")
-            elif world > 1 and not STUB and not os.environ.get("DGPU_BENCH_NO_SCALING_BASE"):
-                sb = single_gpu_2p24(ca, FB, gen1, pool).get("msm_2p20_equivalents_per_s")
-        except Exception as e:                          # noqa: BLE001
-            out["scaling_base_error"] = repr(e)
-        out["scaling_base"] = sb
-        out["scaling_base_note"] = "MSM/s (2^20-term equivalents) of ONE GPU computing config 5's 2^24 terms (table resident, four calls in flight): speed-up at N GPUs = value / scaling_base"
+        if args.full:
+            # scaling_base: the 1-GPU rate on config 5's 2^24 terms, in the unit of `value` — what value(N > 1) must be divided by (the N = 1 line is config 2:
+            # 2^20 terms with six independent calls in flight, a different workload).  At N = 1 it comes out of the secondary leg; at N > 1 rank 0 measures it
+            # on its own GPU after the timed region (one 28-GB table, ~3 s), so that every line of the driver's SCALE run carries its own denominator.
+            sb = None
+            try:
+                if world == 1 and isinstance(out.get("secondary"), dict):
+                    sb = out["secondary"].get("g1_2p24_single_gpu", {}).get("msm_2p20_equivalents_per_s")
+                elif world > 1 and not STUB and not os.environ.get("DGPU_BENCH_NO_SCALING_BASE"):
+                    sb = single_gpu_2p24(ca, FB, gen1, pool).get("msm_2p20_equivalents_per_s")
+            except Exception as e:                          # noqa: BLE001
+                out["scaling_base_error"] = repr(e)
+            out["scaling_base"] = sb
+            out["scaling_base_note"] = "MSM/s (2^20-term equivalents) of ONE GPU computing config 5's 2^24 terms (table resident, four calls in flight): speed-up at N GPUs = value / scaling_base"
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+def stage_objects(args, n, use_table, shape, stages_seq, stages):
+    """--full: the stage breakdown and the rooflines of the dominant kernel, from the stage timers of the development twin's passes
+    (stages_seq: one call in flight; stages: the timed region's shape); shape = the handle's (rows, window bits, windows) when it is a table"""
+    # dominant kernel: duration from the one-call-in-flight pass (HIP events on the library's stream); inside the
+    # timed region up to `inflight` launches share the chip, so their event durations overlap and are reported separately
+    acc_ms = stages_seq.get("msm.accumulate", (0.0, 1))
+    acc_avg_ms = acc_ms[0] / max(1, acc_ms[1])
+    acc_ov = stages.get("msm.accumulate", (0.0, 1))
+    acc_ov_ms = acc_ov[0] / max(1, acc_ov[1])
+    alg_bytes = 128.0 * n                      # SURVEY.md 8(d): 32 B scalar + 96 B affine base per term, one launch = n terms
+    achieved = alg_bytes / (acc_avg_ms * 1e-3) / 1e9 if acc_avg_ms > 0 else 0.0
+    # HBM bytes per launch from the PMC counters: collected by separate rocprofv3 --pmc passes of THIS command (tools/dev/round4_profiles.sh ->
+    # tools/traffic_json.py), not inside this process; the file names the commit it was measured at
+    traffic, traffic_src = None, None
+    tj = os.path.join(ROOT, "profiles", "traffic_accumulate.json")
+    if os.path.exists(tj):
+        try:
+            tr = json.load(open(tj))
+            if tr.get("log2n") == args.log2n and bool(tr.get("table")) == use_table:
+                traffic = tr.get("hbm_bytes_per_launch")
+                traffic_src = "profiles/traffic_accumulate.json, measured at commit %s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --inflight 1`)" % tr.get("commit", "of round 3")
+        except Exception:
+            pass
+    windows = shape[2] if shape else (16 if args.log2n >= 17 else None)
+    out = {
+        "stages_ms": {k.replace("msm.", ""): round(v[0] / max(1, v[1]), 4) for k, v in stages.items()},
+        "stages_ms_one_in_flight": {k.replace("msm.", ""): round(v[0] / max(1, v[1]), 4) for k, v in stages_seq.items()},
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 6),
+                     "traffic": traffic, "traffic_source": traffic_src, "kernel": "msm::k_accumulate<msm::G1S, false>" if use_table else "msm::k_accumulate<msm::G1S, false> (plain pipeline)", "avg_ms": round(acc_avg_ms, 4), "avg_ms_overlapped": round(acc_ov_ms, 4),
+                     "note": "algorithmic 128 B/term x 2^log2n terms per launch; avg_ms = HIP-event duration on the library's stream with one call in flight "
+                             "(same process, untimed pass on the development twin — the product's kernel objects plus the stage timers, which the product "
+                             "library does not export; rocprof of `bench.py --inflight 1` agrees), avg_ms_overlapped = the same with the timed region's "
+                             "calls in flight, where launches share the chip; the kernel is integer-multiply bound: see valu_roofline"},
+    }
+    if acc_avg_ms > 0 and windows:
+        mads = float(n) * windows * MADS_PER_MIXED_ADD
+        out["valu_roofline"] = {"bound": "v_mad_i64_i32 (same issue rate as v_mad_u64_u32)", "achieved": round(mads / (acc_avg_ms * 1e-3) / 1e12, 3), "peak": MAD_PEAK, "unit": "Tmad/s",
+                                "frac": round(mads / (acc_avg_ms * 1e-3) / 1e12 / MAD_PEAK, 4), "mixed_additions_per_launch": int(n) * windows,
+                                "note": "%d windows x n mixed additions x %d 32 x 32 -> 64-bit multiply-adds each (13 x 30-bit signed limbs since round 3: 13.8 %% fewer than the 3542 of the 14 x 29-bit field, so the same kernel time is a LOWER fraction); peak = measured issue rate, profiles/r01h_instr_rate_ubench.txt" % (
+                                    windows, MADS_PER_MIXED_ADD)}
+    return out
 
 
 def cpu_baseline(ca, gen1, ks, scalars, db, ds, log2n, ncpu):

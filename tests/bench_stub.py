@@ -65,6 +65,8 @@ class ca:                               # noqa: N801  (plays the module crypto_a
     @staticmethod
     def twin():
         import contextlib
+        import sys
+        print("bench_stub: twin entered", file=sys.stderr)      # (tests/test_bench_multi_rank_cpu.py: a run without --full never gets here)
         return contextlib.nullcontext()
     DeviceScalars = _Scalars
     @staticmethod

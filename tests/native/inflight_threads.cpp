@@ -1,6 +1,6 @@
 // tests/native/inflight_threads.cpp — compiled host driver over the C ABI (GPU box): COUNT resident 2^20-term G1 MSMs from T NATIVE host threads — what a Rust
 // host's rayon workers are — per "T,COUNT" argument, three passes each: total time, ms per call, the longest single call, results compared with the first
-// call's.  bench.py runs it for `secondary.native_host_threads` (the headline's workload without an interpreter between the calls); __graft_entry__.build()
+// call's.  bench.py --full runs it for `secondary.native_host_threads` (the headline's workload without an interpreter between the calls); __graft_entry__.build()
 // compiles it (tests/test_gpu_cpp_api.py build_inflight_driver).
 #include <atomic>
 #include <chrono>

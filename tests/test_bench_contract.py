@@ -1,4 +1,4 @@
-"""CPU: the bench line's contract, checked on the last line recorded under profiles/ (bench.py itself needs a GPU): the keys the driver
+"""CPU: the bench line's contract, checked on the last line recorded under profiles/ (bench.py itself needs a GPU; a recorded line is a `--full` line): the keys the driver
 reads, and the internal consistency of the roofline / cpu_baseline objects (frac = achieved / peak, achieved = algorithmic bytes per launch
 / the dominant kernel's duration, throughput = terms per step / ms per step)."""
 import glob

@@ -1,7 +1,7 @@
 """GPU (-m gpu): bench.py's N > 1 path end to end on the box's ONE GPU — two ranks launched exactly as the driver launches them
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 …`), both on device 0 (DGPU_BENCH_SAME_DEVICE) and with gloo as the collective backend
 (RCCL refuses two ranks on one device): per-rank tables, the timed region with its barriers, the all_gather + fold of the partial points, the closed
-form over both ranks' terms, rank 0's stage leg on the development twin AFTER the collectives, and `scaling_base` (rank 0 alone computes config 5's 2^24
+form over both ranks' terms, and what `--full` adds after the timed steps: rank 0's stage leg on the development twin AFTER the collectives, and `scaling_base` (rank 0 alone computes config 5's 2^24
 terms on its GPU while rank 1 leaves).  A plumbing test, not a measurement: the 1 -> 8 curve is the driver's SCALE run."""
 import json
 import os
@@ -18,7 +18,7 @@ def test_two_ranks_on_one_gpu_print_one_valid_line():
     assert torch.cuda.is_available()
     env = dict(os.environ, DGPU_BENCH_SAME_DEVICE="1", DGPU_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29537",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--log2n", "18"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "1", "--log2n", "18"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

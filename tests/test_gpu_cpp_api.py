@@ -21,7 +21,7 @@ def build_driver():
 
 
 def build_inflight_driver():
-    """tests/native/inflight_threads.cpp: the headline's workload from native host threads (bench.py secondary.native_host_threads)"""
+    """tests/native/inflight_threads.cpp: the headline's workload from native host threads (bench.py --full: secondary.native_host_threads)"""
     exe = os.path.join(ROOT, "tests", "native", "inflight_threads")
     src = exe + ".cpp"
     hdr = os.path.join(ROOT, "include", "dock_gpu.h")

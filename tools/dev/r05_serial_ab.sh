@@ -10,7 +10,7 @@ mkdir -p tools/ubench/bin
 for v in "base:" "alt:-DFS_ALT_HIGH" "ser:-DFS_SERIAL_LOW" "ser2:-DFS_SERIAL_LOW -DFS_ALT_HIGH"; do n=${v%%:*}; [ -x tools/ubench/bin/madd_$n ] || hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-pass-failed ${v#*:} tools/ubench/madd_rate.hip -o tools/ubench/bin/madd_$n 2>/dev/null; done
 for v in base alt ser ser2; do echo "== ubench $v"; tools/ubench/bin/madd_$v | grep "madd_s"; done
 run() { # $1 label, env already set
-  for i in 1 2; do python bench.py --no-secondary --no-cpu-baseline --inflight 1 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 inflight1', d['value'], d['stages_ms_one_in_flight'])"; done
+  for i in 1 2; do python bench.py --full --no-secondary --no-cpu-baseline --inflight 1 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 inflight1', d['value'], d['stages_ms_one_in_flight'])"; done
   for i in 1 2; do python bench.py --no-secondary --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 default', d['value'], d['ms_per_step'], d['latency_ms_one_in_flight'], d['config']['bit_exact_vs_closed_form'])"; done
 }
 run base

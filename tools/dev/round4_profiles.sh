@@ -6,7 +6,7 @@ TAG=${TAG:-r04}
 COMMIT=${COMMIT:-unknown}
 O=/root/repo/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="python /root/repo/bench.py --steps 20 --no-secondary --no-cpu-baseline"
+B="python ${O%/*}/bench.py --full --steps 20 --no-secondary --no-cpu-baseline"      # (--full: the recorded line carries the stage timers and the roofline; $O lies in the repository root)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof1 -- $B --inflight 1 > $O/${TAG}_bench_inflight1_under_rocprof.json 2>/dev/null
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof6 -- $B > $O/${TAG}_bench_inflight6_under_rocprof.json 2>/dev/null
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_profg2 -- python /root/repo/tools/dev/g2_loop.py > $O/${TAG}_g2_loop.txt 2>/dev/null

@@ -9,7 +9,7 @@ for rep in 1 2; do
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lib inflight=$inf', d['value'], d['ms_per_step'])"
     done
-    python bench.py --no-cpu-baseline --no-cpu-legs 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-cpu-legs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['secondary']
 print('$lib bench', d['value'], s['g2_msm_ms_per_msm_4_in_flight'], s['miller_loop_1024_pairs_ms_per_call_6_in_flight'], s['prove_2p20_ms'], s['prove_2p20_ms_per_proof_4_in_flight'], s['snarkpack_aggregate_1024_proofs_ms'])"
