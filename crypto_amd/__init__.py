@@ -15,3 +15,4 @@ from .pairing_check import RandomizedPairingChecker  # noqa: F401,E402
 from . import qap  # noqa: F401,E402
 from . import serde  # noqa: F401,E402
 from . import accumulator  # noqa: F401,E402
+from . import bbs_plus  # noqa: F401,E402

@@ -1,0 +1,125 @@
+"""Mirror of the plain G1 BBS+ signature (bbs_plus/src/signature.rs:138-296: SignatureG1, SignatureParamsG1, PublicKeyG2) in bulk on the C ABI.
+
+    SignatureParamsG1 { g1, g2, h_0, h } + PublicKeyG2(w)     -> Params(g1, h_0, h, g2, w)          uploads [g1, h_0, h ..], prepares w and g2
+    SignatureG1::new(rng, messages, sk, params), n times      -> sign_many(params, sk, messages, e, s)       returns (A, bad)
+    sig.verify(messages, pk, params), n times                 -> verify_each(params, A, e, s, messages)      returns ok, one byte per signature
+    the same through RandomizedPairingChecker                 -> verify_batch(params, A, e, s, messages, random)     returns True / False
+
+`e` and `s` stand in for the two `rand` draws of SignatureG1::new, so signing is deterministic.  Scalars are (n, 4) uint64 limb arrays or Python ints, canonical
+unless `montgomery=True` (then ark-ff Montgomery limbs); messages are an (n, L) array of Python ints or an (n, L, 4) limb array (a view with a longer row
+stride is passed as it is: what lies between the rows is never read).  Points are affine Montgomery limbs, (n, 12) uint64; an identity is all-zero words.
+"""
+import ctypes as C
+import numpy as np
+from ._native import lib, DockGpuError
+from .msm import G1, _ensure, DeviceBases
+from .fixed_base import _scalars_to_limbs, _p
+from .pairing import G2Prepared
+
+
+class Params:
+    """The signature parameters and the public key of one issuer on the device: a plain G1 bases handle holding [g1, h_0, h_1 .. h_L] and the prepared
+    coefficients of w and g2.  free() (or leaving a `with` block) releases the handle."""
+
+    def __init__(self, g1, h_0, h, g2, w):
+        _ensure()
+        h = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, 12)
+        self.L = len(h)
+        if self.L == 0:
+            raise ValueError("NoMessageToSign")                                  # signature.rs:150-152
+        pts = np.concatenate([np.asarray(g1, dtype=np.uint64).reshape(1, 12), np.asarray(h_0, dtype=np.uint64).reshape(1, 12), h])
+        self.bases = DeviceBases(G1, pts)
+        pc = G2Prepared.from_affine(np.stack([np.asarray(w, dtype=np.uint64).reshape(24), np.asarray(g2, dtype=np.uint64).reshape(24)]))
+        self.pk_pc, self.g2_pc = np.ascontiguousarray(pc.coeffs[0]), np.ascontiguousarray(pc.coeffs[1])
+
+    @property
+    def handle(self):
+        return self.bases.handle
+
+    def free(self):
+        if self.bases is not None:
+            self.bases.free()
+            self.bases = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+def _messages(messages, L):
+    """(array, row stride in scalars, rows): an (n, L, 4) uint64 array — C-contiguous, or a view whose rows are contiguous and a whole number of scalars apart —
+    or anything that lists n rows of L integers"""
+    if isinstance(messages, np.ndarray) and messages.dtype == np.uint64 and messages.ndim == 3:
+        m = messages
+        if m.shape[1] != L or m.shape[2] != 4:
+            raise ValueError("MessageCountIncompatibleWithSigParams: rows of %d messages for %d generators" % (m.shape[1], L))      # signature.rs:153-158
+        if len(m) == 0:
+            return m, L, 0
+        if m.strides[2] == 8 and m.strides[1] == 32 and m.strides[0] % 32 == 0 and m.strides[0] >= 32 * L:
+            return m, m.strides[0] // 32, len(m)
+        return np.ascontiguousarray(m), L, len(m)
+    rows = [list(r) for r in messages]
+    for r in rows:
+        if len(r) != L:
+            raise ValueError("MessageCountIncompatibleWithSigParams: a row of %d messages for %d generators" % (len(r), L))
+    flat = _scalars_to_limbs([v for r in rows for v in r]) if rows else np.zeros((0, 4), np.uint64)
+    return flat.reshape(len(rows), L, 4), L, len(rows)
+
+
+def _rows(params, e, s, messages):
+    m, stride, n = _messages(messages, params.L)
+    e = _scalars_to_limbs(e) if n else np.zeros((0, 4), np.uint64)
+    s = _scalars_to_limbs(s) if n else np.zeros((0, 4), np.uint64)
+    if len(e) != n or len(s) != n:
+        raise ValueError("%d rows of messages, %d values of e, %d of s" % (n, len(e), len(s)))
+    return m, stride, n, e, s
+
+
+def sign_many(params, sk, messages, e, s, montgomery=False):
+    """(A, bad): A_i = (sk + e_i)^-1 (g1 + s_i h_0 + sum_j m_ij h_j) as an (n, 12) array; bad[i] = 1 (and zero words) where no signature exists:
+    sk + e_i = 0, where the reference draws e again, or an identity b_i"""
+    _ensure()
+    m, stride, n, e, s = _rows(params, e, s, messages)
+    x = _scalars_to_limbs([sk] if isinstance(sk, int) else sk).reshape(4)
+    out, bad = np.zeros((n, 12), np.uint64), np.zeros(n, np.uint8)
+    rc = lib().dgpu_bbs_plus_sign_many_g1(params.handle, params.L, _p(x), _p(m) if n else None, stride, _p(e) if n else None, _p(s) if n else None, n,
+                                          1 if montgomery else 0, _p(out) if n else None, _p(bad) if n else None)
+    if rc:
+        raise DockGpuError(rc, "dgpu_bbs_plus_sign_many_g1")
+    return out, bad
+
+
+def _sigs(sig_a, n):
+    a = np.ascontiguousarray(sig_a, dtype=np.uint64).reshape(-1, 12)
+    if len(a) != n:
+        raise ValueError("%d signatures for %d rows of messages" % (len(a), n))
+    return a
+
+
+def verify_each(params, sig_a, e, s, messages, montgomery=False):
+    """ok, an (n,) uint8 array: ok[i] = 1 iff A_i is not the identity and e(A_i, w) e(e_i A_i - b_i, g2) = 1 (signature.rs:272-296)"""
+    _ensure()
+    m, stride, n, e, s = _rows(params, e, s, messages)
+    a = _sigs(sig_a, n)
+    ok = np.zeros(n, np.uint8)
+    rc = lib().dgpu_bbs_plus_verify_each_g1(params.handle, params.L, _p(params.pk_pc), _p(params.g2_pc), _p(a) if n else None, _p(e) if n else None,
+                                            _p(s) if n else None, _p(m) if n else None, stride, n, 1 if montgomery else 0, _p(ok) if n else None)
+    if rc:
+        raise DockGpuError(rc, "dgpu_bbs_plus_verify_each_g1")
+    return ok
+
+
+def verify_batch(params, sig_a, e, s, messages, random, montgomery=False):
+    """True iff every signature verifies, by one pairing check over the random linear combination with the weights random^i (non-zero modulo r)"""
+    _ensure()
+    m, stride, n, e, s = _rows(params, e, s, messages)
+    a = _sigs(sig_a, n)
+    rho = _scalars_to_limbs([random] if isinstance(random, int) else random).reshape(4)
+    ok = C.c_int32(0)
+    rc = lib().dgpu_bbs_plus_verify_batch_g1(params.handle, params.L, _p(params.pk_pc), _p(params.g2_pc), _p(a) if n else None, _p(e) if n else None,
+                                             _p(s) if n else None, _p(m) if n else None, stride, n, 1 if montgomery else 0, _p(rho), C.byref(ok))
+    if rc:
+        raise DockGpuError(rc, "dgpu_bbs_plus_verify_batch_g1")
+    return bool(ok.value)

@@ -28,6 +28,11 @@ inline FrH fr_plus(const FrH &a, const FrH &b) {                 // both < r
     return s;
 }
 inline void wipe(void *p, size_t bytes) { volatile uint8_t *q = (volatile uint8_t *)p; for (size_t i = 0; i < bytes; i++) q[i] = 0; }
+// host words that depend on the secret key (the inverses 1 / (y + alpha), 1 / (x + e)): wiped when the call ends
+struct SecretWords {
+    std::vector<uint64_t> w;
+    ~SecretWords() { if (!w.empty()) wipe(w.data(), w.size() * 8); }
+};
 // the host's tables as ark-ff Montgomery words, [a | F | r | G | Phi]; wiped when the call ends
 struct Tables {
     std::vector<uint64_t> w;
@@ -63,18 +68,24 @@ inline int32_t build_tables(const uint64_t *additions, size_t na, const uint64_t
 }
 // the host's share of issuing witnesses (universal.rs:511-513, positive.rs:375-376): t_i = 1 / (y_i + alpha) for the entries [lo, hi), as ark-ff Montgomery
 // words at t + 4 i, with ONE inversion (Montgomery's trick: t holds the prefix products in between).  DGPU_E_BADARG for a y_i equal to -alpha, which has no
-// inverse (the reference's batch_inversion would leave a zero there and issue the identity)
-inline int32_t issue_inverses(const uint64_t *ys, size_t lo, size_t hi, const uint64_t alpha[4], bool mont, uint64_t *t) {
+// inverse (the reference's batch_inversion would leave a zero there and issue the identity).  zero != NULL (BBS+ signing, dock_bbs.hip: x + e_i = 0 is where
+// SignatureG1::new draws e again, bbs_plus/src/signature.rs:178-181): such an entry is no error; zero[i] = 1 and t_i = 0 mark it, it stays out of the running
+// product, and every other entry gets zero[i] = 0 and its inverse
+inline int32_t issue_inverses(const uint64_t *ys, size_t lo, size_t hi, const uint64_t alpha[4], bool mont, uint64_t *t, uint8_t *zero = nullptr) {
     FrH al = fr_in(alpha, mont), acc = FrH::from_u64(1);
     int32_t rc = DGPU_OK;
     for (size_t i = lo; i < hi && !rc; i++) {
         const FrH u = fr_plus(fr_in(ys + 4 * i, mont), al);
-        if (fr_is_zero(u)) rc = DGPU_E_BADARG;
-        memcpy(t + 4 * i, acc.l, 32); acc = acc * u;
+        const bool z = fr_is_zero(u);
+        if (zero) zero[i] = z ? 1 : 0;
+        else if (z) rc = DGPU_E_BADARG;
+        memcpy(t + 4 * i, acc.l, 32);
+        if (!z) acc = acc * u;
     }
     if (!rc && hi > lo) {
         FrH inv = acc.inv();
         for (size_t i = hi; i-- > lo;) {
+            if (zero && zero[i]) { memset(t + 4 * i, 0, 32); continue; }
             FrH u = fr_plus(fr_in(ys + 4 * i, mont), al), pre; memcpy(pre.l, t + 4 * i, 32);
             const FrH o = inv * pre; inv = inv * u;
             memcpy(t + 4 * i, o.l, 32);

@@ -18,25 +18,6 @@ using namespace acch;
 
 namespace {
 
-// zeroes the device buffers that held what depends on the secret key (the tables; Omega's chunk results, evaluations and coefficients) on every return
-// path, before the slot goes back
-struct DeviceWipe {
-    Slot &sl; struct Region { void *p; size_t bytes; }; std::vector<Region> r;
-    explicit DeviceWipe(Slot &s) : sl(s) {}
-    void add(void *p, size_t bytes) { if (p && bytes) r.push_back(Region{p, bytes}); }
-    ~DeviceWipe() {
-        if (r.empty()) return;
-        for (const Region &k : r) (void)hipMemsetAsync(k.p, 0, k.bytes, sl.stream);
-        (void)hipStreamSynchronize(sl.stream);
-    }
-};
-// a return before the call's last synchronisation (an error path) waits for the slot's streams first: asynchronous copies may still be queued into or out of
-// host vectors declared BEFORE this guard, which leave scope after it
-struct DrainUnlessDone {
-    Slot &sl; bool done = false;
-    explicit DrainUnlessDone(Slot &s) : sl(s) {}
-    ~DrainUnlessDone() { if (!done) drain(sl); }
-};
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 bool bad_sizes(size_t na, size_t nr, size_t m) { return m >= (1ull << 31) || na >= (1ull << 31) || nr >= (1ull << 31) || na + nr >= (1ull << 31); }
@@ -457,10 +438,6 @@ int32_t d_for_batch(const uint64_t *members, bool resident, uint64_t handle, siz
 //   device  s_i as canonical words straight into the multiplication's scalar buffer, and the zero-d flags        k_acc_issue_scalars
 //   device  s_i B from a window table of B built in the slot's workspace, normalised affine points              k_fb_table, k_fb_mul
 // The device copies of t, the scalars and the table are zeroed on every return path, the host copy of t too.
-struct SecretWords {
-    std::vector<uint64_t> w;
-    ~SecretWords() { if (!w.empty()) wipe(w.data(), w.size() * 8); }
-};
 int32_t issue_witnesses(bool with_d, const uint64_t *d, const uint64_t *ys, size_t m, const uint64_t *f_V, const uint64_t *alpha, const uint64_t *base, bool mont,
                         uint64_t *out, uint8_t *out_inf, uint8_t *ok) {
     if (m == 0) return DGPU_OK;

@@ -1,0 +1,394 @@
+// crypto_amd/csrc/dock_bbs.hip — BBS+ signatures in bulk (include/dock_gpu.h: dgpu_bbs_plus_sign_many_g1, dgpu_bbs_plus_verify_each_g1,
+// dgpu_bbs_plus_verify_batch_g1): SignatureG1::new and SignatureG1::verify (bbs_plus/src/signature.rs:138-211, 272-296) for many signatures of one key, each
+// call ONE device pipeline per chunk of rows.  The signature parameters are a plain G1 bases handle [g1, h_0, h_1 .. h_L]; b_i = g1 + s_i h_0 + sum_j m_ij h_j
+// (bbs_plus/src/setup.rs:128-146) is the small MSM of the row (1, s_i, m_i1 .. m_iL) over its small-path table.
+//   sign     host    t_i = 1 / (x + e_i): one batch inversion per share of the host threads (acc_host_tables.hpp issue_inverses); x never leaves the host
+//            device  row i = t_i (1, s_i, m_i ..) as canonical words                                     k_bbs_rows
+//            device  A_i = <row_i, params>, normalised                                                    k_many_tree, k_many_fold (msm_many.hip.h many_rows_resident)
+//   each     host    the GLV split of -e_i (an input: nothing of the device is waited for)
+//            device  row i = (1, s_i, m_i ..), b_i = <row_i, params>                                      k_bbs_rows, k_many_tree, k_many_fold
+//            device  d_i = -((-e_i) A_i + b_i) = e_i A_i - b_i: the kernel's negation of its result, free  k_g1_scale_quad
+//            device  e(A_i, w) e(d_i, g2): lines of the two prepared points shared by every row, the products of every slice (i, i + m), the loop's tail, the
+//                    final exponentiation compared with one                                                k_lines_from_prepared x 2, k_line_products, k_miller_tail, k_final_exp
+//   batch    device  c_k = sum_i rho^i row_ik, rho^i, rho^i e_i                                           k_bbs_col_sums, k_bbs_col_finish
+//            device  P1 = sum rho^i A_i, P2 = sum (rho^i e_i) A_i + sum (-c_k) H_k: two MSMs per chunk over the A_i, ONE over the parameters; the host adds the
+//                    chunks' points
+//            device  e(P1, w) e(P2, g2) against one, as above with one slice
+// Only verdict bytes (each, batch) or the signatures (sign) come back.  The device copies of the inverses and of the rows that carry them are zeroed on every return
+// path before the slot is released, the host copy too.
+#include <chrono>
+#include "msm_many.hip.h"
+#include "qap_launch.hip.h"
+#include "fixed_launch.hip.h"
+#include "pairing_launch.hip.h"
+#include "gt_launch.hip.h"
+#include "bbs_launch.hip.h"
+#include "acc_host_tables.hpp"
+using namespace dock;
+using namespace acch;
+using namespace mlk;
+
+namespace {
+
+double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+bool zero_words(const uint64_t *w, int k) { uint64_t o = 0; for (int i = 0; i < k; i++) o |= w[i]; return o == 0; }
+
+constexpr size_t PT = 96;                 // bytes of an affine G1 point of the ABI
+
+// what the three calls share: the rows' inputs and how they are cut
+struct Rows {
+    const uint64_t *messages, *e, *s; size_t L, stride, n; bool mont;
+    size_t nn() const { return L + 2; }
+};
+// the argument checks that come before the device is looked at (n > 0)
+bool bad_rows(const Rows &r) {
+    return r.L == 0 || !r.messages || !r.e || !r.s || r.stride < r.L || r.n >= (1ull << 31) || r.L >= (1ull << 31) - 2 || r.stride >= (1ull << 31);
+}
+// the parameters: a plain G1 bases handle of exactly L + 2 points, pinned for the call
+bool params_ok(const HandleRef &hb, size_t L) { return hb.ok && hb.h.kind == 1 && hb.h.n == L + 2; }
+
+// How the b_i of a chunk are made: the many-row kernels over the handle's small-path table, or (rows beyond their reach, dgpu_set_small_msm_max(0), no memory for the
+// table) the single-row driver row by row, normalised on the host.
+struct BPath {
+    bool many; SmallSub sub; ManyGeom geom; const uint32_t *rec; size_t nn, chunk;
+    int32_t workspace(Slot &o) const {
+        if (many) return ws_many<G1>(o, nn, chunk, geom);
+        int32_t e;
+        if ((e = ws_for<G1>(o, 2, nn, 0, nullptr))) return e;
+        if ((e = o.in_scalars.ensure(chunk * nn * 32))) return e;
+        return o.flags.ensure(64);
+    }
+};
+int32_t b_path(Slot &sl, uint64_t params, const Handle &h, size_t nn, size_t cap, size_t n, BPath &bp) {
+    bp.nn = nn; bp.rec = (const uint32_t *)h.p; bp.geom = many_geometry(nn);
+    bp.many = h.n <= SMALL_MSM_MAX_N && nn <= gs.small_max.load() && small_sub_for<G1>(sl, params, h, 0, nn, bp.sub, true);
+    const size_t per = bp.many ? many_chunk_rows(nn) : std::max<size_t>(1, ((size_t)1 << 21) / nn);      // rows per launch / per 64 MB of scalars
+    bp.chunk = std::min(n, std::min(per, cap));
+    return DGPU_OK;
+}
+// the rows at d_rows (canonical words, packed) -> dB (affine words; an identity: zero words) and dBinf.  The host vectors are the slow path's and live until the
+// caller's next synchronisation.
+int32_t b_points(Slot &sl, const BPath &bp, const uint32_t *d_rows, size_t rows, uint32_t *d_bad, uint8_t *dB, uint8_t *dBinf, std::vector<uint64_t> &jac, std::vector<uint8_t> &binf) {
+    hipStream_t s = sl.stream;
+    int32_t rc;
+    if (bp.many) {
+        if ((rc = many_rows_resident<G1>(sl, bp.sub, d_rows, bp.nn, rows, bp.geom, d_bad))) return rc;
+        // the normalised Jacobian rows (X, Y, 1) -> X and Y of every row, and its identity flag
+        HIPCHK(hipMemcpy2DAsync(dB, PT, sl.win.p, 3 * PT / 2, PT, rows, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(dBinf, sl.win_inf.p, rows, hipMemcpyDeviceToDevice, s));
+        return DGPU_OK;
+    }
+    HIPCHK(hipGetLastError());
+    jac.resize(rows * 18); binf.resize(rows);
+    for (size_t i = 0; i < rows; i++)
+        if ((rc = msm_device<G1, hostf::Fq>(sl, bp.rec, d_rows + i * bp.nn * 8, bp.nn, jac.data() + 18 * i))) return rc;
+    for (size_t i = 0; i < rows; i++) {
+        uint64_t *p = jac.data() + 18 * i;
+        binf[i] = jac_is_identity(p, 18);
+        if (binf[i]) { memset(jac.data() + 12 * i, 0, PT); continue; }
+        hostf::Fq x, y, z; memcpy(&x, p, 48); memcpy(&y, p + 6, 48); memcpy(&z, p + 12, 48);
+        const hostf::Fq zi = z.inv(), zi2 = zi * zi;
+        x = x * zi2; y = y * zi2 * zi;
+        memcpy(jac.data() + 12 * i, &x, 48); memcpy(jac.data() + 12 * i + 6, &y, 48);      // (packed in place: 12 i + 12 <= 18 i)
+    }
+    HIPCHK(hipMemcpyAsync(dB, jac.data(), rows * PT, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dBinf, binf.data(), rows, hipMemcpyHostToDevice, s));
+    return DGPU_OK;
+}
+// s and the messages of the rows [r0, r0 + rows) to the device: the messages packed (what lies between the caller's rows never crosses)
+int32_t rows_up(Slot &sl, const Rows &r, size_t r0, size_t rows, void *d_s, void *d_m) {
+    hipStream_t s = sl.stream;
+    HIPCHK(hipMemcpyAsync(d_s, r.s + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
+    const uint64_t *src = r.messages + r0 * r.stride * 4;
+    if (r.stride == r.L) HIPCHK(hipMemcpyAsync(d_m, src, rows * r.L * 32, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpy2DAsync(d_m, r.L * 32, src, r.stride * 32, r.L * 32, rows, hipMemcpyHostToDevice, s));
+    return DGPU_OK;
+}
+
+// ---- SignatureG1::new for n rows (signature.rs:138-211): A_i = (x + e_i)^-1 b_i with the caller's e_i, s_i -------------------------------------------------
+int32_t sign_many(uint64_t params, const uint64_t *sk, const Rows &r, uint64_t *out_a, uint8_t *bad) {
+    if (r.n == 0) return DGPU_OK;
+    if (bad_rows(r) || !sk || !out_a || !bad) return DGPU_E_BADARG;
+    const size_t n = r.n, nn = r.nn();
+    SecretWords t;
+    t.w.assign(n * 4, 0);
+    std::vector<uint8_t> zero(n), binf(n);
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t parts = std::min<size_t>(16, (n + 1023) / 1024);
+    int32_t rc = par_run(parts, [&](size_t k) { return issue_inverses(r.e, n * k / parts, n * (k + 1) / parts, sk, r.mont, t.w.data(), zero.data()); });
+    if (rc) return rc;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    if (gs.prof) prof_add_host("bbs.host_inverses", ms_since(t0));
+    HandleRef hb(params);
+    if (!params_ok(hb, r.L)) return DGPU_E_BADARG;
+    CtxScope on_owner(hb.h.ctx);
+    SLOT_ACQUIRE(LK, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    BPath bp;
+    if ((rc = b_path(sl, params, hb.h, nn, ~(size_t)0, n, bp))) return rc;
+    const size_t chunk = bp.chunk;
+    // q[0]: t, q[1]: s, q[2]: the messages, q[4]: [A | identity flags]
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = o.q[0].ensure(chunk * 32))) return e;
+        if ((e = o.q[1].ensure(chunk * 32))) return e;
+        if ((e = o.q[2].ensure(chunk * r.L * 32))) return e;
+        if ((e = o.q[4].ensure(chunk * PT + chunk))) return e;
+        return bp.workspace(o);
+    };
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws(sl))) return rc;
+    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    hipStream_t s = sl.stream;
+    std::vector<uint64_t> jac; std::vector<uint8_t> hinf;
+    DrainUnlessDone guard(sl);
+    DeviceWipe dw(sl);
+    dw.add(sl.q[0].p, chunk * 32); dw.add(sl.in_scalars.p, chunk * nn * 32);
+    uint32_t *d_rows = sl.in_scalars.as<uint32_t>(), *d_bad = sl.flags.as<uint32_t>();
+    uint8_t *dA = sl.q[4].as<uint8_t>(), *dAinf = dA + chunk * PT;
+    HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));                              // (rows are canonical: the flag stays clear)
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t rows = std::min(chunk, n - r0);
+        HIPCHK(hipMemcpyAsync(sl.q[0].p, t.w.data() + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
+        if ((rc = rows_up(sl, r, r0, rows, sl.q[1].p, sl.q[2].p))) return rc;
+        { StageTimer st(sl, "bbs.rows"); bbsk::launch_bbs_rows(s, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), sl.q[0].as<uint32_t>(), r.mont ? 1 : 0, rows, nn, d_rows); }
+        if ((rc = b_points(sl, bp, d_rows, rows, d_bad, dA, dAinf, jac, hinf))) return rc;
+        HIPCHK(hipMemcpyAsync(out_a + 12 * r0, dA, rows * PT, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(binf.data() + r0, dAinf, rows, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));                                 // (the next chunk's operands overwrite this one's)
+        if (gs.prof) prof_flush(sl);
+    }
+    guard.done = true;
+    // no signature: x + e_i = 0 (the reference draws e again there), or b_i — and with it A_i — the identity
+    for (size_t i = 0; i < n; i++) {
+        bad[i] = (zero[i] || binf[i]) ? 1 : 0;
+        if (bad[i]) memset(out_a + 12 * i, 0, PT);
+    }
+    return DGPU_OK;
+}
+
+// ---- the pairing check of m = `cols` rows on the device: e(P1_i, w) e(P2_i, g2) == 1 ----------------------------------------------------------------------------
+// dP: [P1 | P2], cols affine points each; dsk: their skip flags in the same order (an identity contributes one, as everywhere in the library).  The coefficients
+// of w and g2 are in sl.ml_coeffs, the wanted value (one) behind the Miller outputs in sl.ml_out.  Verdicts: sl.flags.
+int32_t ws_check(Slot &o, size_t cols) {
+    int32_t e;
+    if ((e = o.ml_coeffs.ensure(2 * (size_t)DGPU_G2_PREPARED_WORDS * 8 + 16))) return e;
+    if ((e = o.ml_lines.ensure((size_t)N_LINES * LW * 2 * cols * 4))) return e;
+    if ((e = o.ml_partial.ensure((size_t)N_LINES * cols * F12W * 4))) return e;
+    if ((e = o.ml_out.ensure(cols * 576 + 576))) return e;
+    return o.flags.ensure(std::max<size_t>(cols, 64));
+}
+int32_t coeffs_up(Slot &sl, const uint64_t *pk_pc, const uint64_t *g2_pc, size_t cols) {
+    const size_t cw = (size_t)DGPU_G2_PREPARED_WORDS;
+    static const hostf::Fq12 one = hostf::Fq12::one();
+    HIPCHK(hipMemcpyAsync(sl.ml_coeffs.p, pk_pc, cw * 8, hipMemcpyHostToDevice, sl.stream));
+    HIPCHK(hipMemcpyAsync(sl.ml_coeffs.as<uint64_t>() + cw, g2_pc, cw * 8, hipMemcpyHostToDevice, sl.stream));
+    HIPCHK(hipMemcpyAsync(sl.ml_out.as<uint8_t>() + cols * 576, &one, 576, hipMemcpyHostToDevice, sl.stream));
+    return DGPU_OK;
+}
+void launch_check(Slot &sl, const uint32_t *dP1, const uint32_t *dP2, const uint8_t *dsk, size_t m, size_t cols) {
+    hipStream_t s = sl.stream;
+    const size_t cw = (size_t)DGPU_G2_PREPARED_WORDS, np = 2 * m;
+    uint32_t *lines = sl.ml_lines.as<uint32_t>(), *fout = sl.ml_out.as<uint32_t>();
+    { StageTimer st(sl, "bbs.lines");
+      launch_lines_from_prepared(s, dP1, sl.ml_coeffs.as<uint32_t>(), dsk, m, lines, np, nullptr, true);
+      launch_lines_from_prepared(s, dP2, sl.ml_coeffs.as<uint32_t>() + cw * 2, dsk + m, m, lines + m, np, nullptr, true); }
+    // one "segment" of 2 m pairs with slices of 2: slice i is the pairs i and i + m, i.e. the two lines of row i
+    { StageTimer st(sl, "bbs.products"); launch_line_products(s, gs.ml_mode.load(), lines, np, 2, (int)m, sl.ml_partial.as<uint32_t>(), nullptr, 1, 0, N_LINES, nullptr, false); }
+    { StageTimer st(sl, "bbs.tail"); gtk::launch_miller_tail(s, sl.ml_partial.as<uint32_t>(), m, fout); }
+    { StageTimer st(sl, "bbs.final_exp"); gtk::launch_final_exp(s, fout, m, (uint32_t *)nullptr, (uint8_t *)nullptr, fout + cols * 144, sl.flags.as<uint8_t>()); }
+}
+
+// (k1 | k2) of -e mod r: the scalar of the kernel that returns -((-e) A + b)
+void neg_split(const uint64_t *e, bool mont, uint64_t *out) {
+    uint64_t c[4];
+    fr_in(e, mont).to_canonical(c);
+    if (c[0] | c[1] | c[2] | c[3]) {
+        uint64_t br = 0;
+        for (int i = 0; i < 4; i++) { u128 d = (u128)FrH::MOD[i] - c[i] - br; c[i] = (uint64_t)d; br = (uint64_t)(d >> 64) & 1; }
+    }
+    hostf::glv_decompose(c, out, out + 2);
+}
+
+// ---- SignatureG1::verify for n rows (signature.rs:272-296), a verdict per row --------------------------------------------------------------------------------------
+int32_t verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const Rows &r, uint8_t *ok) {
+    if (r.n == 0) return DGPU_OK;
+    if (bad_rows(r) || !pk_pc || !g2_pc || !sig_a || !ok) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    const size_t n = r.n, nn = r.nn();
+    HandleRef hb(params);
+    if (!params_ok(hb, r.L)) return DGPU_E_BADARG;
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> split(n * 4);
+    std::vector<uint8_t> ainf(n);
+    const size_t parts = std::min<size_t>(16, (n + 4095) / 4096);
+    int32_t rc = par_run(parts, [&](size_t k) {
+        for (size_t i = n * k / parts; i < n * (k + 1) / parts; i++) { neg_split(r.e + 4 * i, r.mont, &split[4 * i]); ainf[i] = zero_words(sig_a + 12 * i, 12) ? 1 : 0; }
+        return (int32_t)DGPU_OK;
+    });
+    if (rc) return rc;
+    if (gs.prof) prof_add_host("bbs.glv_split", ms_since(t0));
+    CtxScope on_owner(hb.h.ctx);
+    SLOT_ACQUIRE(LK, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    BPath bp;
+    if ((rc = b_path(sl, params, hb.h, nn, bbsk::BBS_EACH_CHUNK, n, bp))) return rc;
+    const size_t chunk = bp.chunk;
+    // q[0]: the split -e, q[1]: s, q[2]: the messages, q[3]: A, q[4]: [b | identity flags], q[5]: d, q[6]: [skip flags of (A, d) | ones]
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = o.q[0].ensure(chunk * 32))) return e;
+        if ((e = o.q[1].ensure(chunk * 32))) return e;
+        if ((e = o.q[2].ensure(chunk * r.L * 32))) return e;
+        if ((e = o.q[3].ensure(chunk * PT))) return e;
+        if ((e = o.q[4].ensure(chunk * PT + chunk))) return e;
+        if ((e = o.q[5].ensure(chunk * PT))) return e;
+        if ((e = o.q[6].ensure(3 * chunk))) return e;
+        if ((e = ws_check(o, chunk))) return e;
+        return bp.workspace(o);
+    };
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws(sl))) return rc;
+    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    hipStream_t s = sl.stream;
+    std::vector<uint64_t> jac; std::vector<uint8_t> hinf;
+    DrainUnlessDone guard(sl);
+    uint32_t *d_rows = sl.in_scalars.as<uint32_t>(), *d_bad = sl.flags.as<uint32_t>();
+    uint8_t *dA = sl.q[3].as<uint8_t>(), *dB = sl.q[4].as<uint8_t>(), *dBinf = dB + chunk * PT, *dD = sl.q[5].as<uint8_t>(), *dsk = sl.q[6].as<uint8_t>(), *dones = dsk + 2 * chunk;
+    HIPCHK(hipMemsetAsync(dones, 1, chunk, s));
+    if ((rc = coeffs_up(sl, pk_pc, g2_pc, chunk))) return rc;
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t rows = std::min(chunk, n - r0);
+        HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));                          // (rows are canonical: the flag stays clear; sl.flags takes the verdicts afterwards)
+        HIPCHK(hipMemcpyAsync(sl.q[0].p, &split[4 * r0], rows * 32, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dA, sig_a + 12 * r0, rows * PT, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dsk, ainf.data() + r0, rows, hipMemcpyHostToDevice, s));
+        if ((rc = rows_up(sl, r, r0, rows, sl.q[1].p, sl.q[2].p))) return rc;
+        { StageTimer st(sl, "bbs.rows"); bbsk::launch_bbs_rows(s, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), nullptr, r.mont ? 1 : 0, rows, nn, d_rows); }
+        if ((rc = b_points(sl, bp, d_rows, rows, d_bad, dB, dBinf, jac, hinf))) return rc;
+        // d_i = -((-e_i) A_i + b_i); its identity flag is the second pair's skip flag
+        { StageTimer st(sl, "bbs.scale");
+          msm::launch_g1_scale_quad(s, (const uint32_t *)dA, dsk, sl.q[0].as<uint32_t>(), 8, dones, rows, (uint32_t *)dD, dsk + rows, (const uint32_t *)dB, dBinf); }
+        launch_check(sl, (const uint32_t *)dA, (const uint32_t *)dD, dsk, rows, chunk);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ok + r0, sl.flags.p, rows, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));                                 // (the next chunk's operands overwrite this one's)
+        if (gs.prof) prof_flush(sl);
+    }
+    guard.done = true;
+    for (size_t i = 0; i < n; i++) if (ainf[i]) ok[i] = 0;               // ZeroSignature (signature.rs:280-282)
+    return DGPU_OK;
+}
+
+// ---- one verdict for n rows: the random linear combination RandomizedPairingChecker forms (utils/src/randomized_pairing_check.rs), merged before the pairing ----------
+typedef hostf::HXyzz<hostf::Fq> HPoint;
+void add_jac(HPoint &acc, const uint64_t *jac) {
+    if (jac_is_identity(jac, 18)) return;
+    hostf::Fq x, y, z; memcpy(&x, jac, 48); memcpy(&y, jac + 6, 48); memcpy(&z, jac + 12, 48);
+    const hostf::Fq zz = z * z;
+    HPoint p; p.x = x; p.y = y; p.zz = zz; p.zzz = zz * z; p.inf = false;
+    acc.add_in_place(p);
+}
+int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const Rows &r, const uint64_t *random, int32_t *ok) {
+    if (r.n == 0) { if (ok) *ok = 1; return DGPU_OK; }
+    if (bad_rows(r) || !pk_pc || !g2_pc || !sig_a || !random || !ok) return DGPU_E_BADARG;
+    if (fr_is_zero(fr_in(random, r.mont))) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    const size_t n = r.n, nn = r.nn();
+    HandleRef hb(params);
+    if (!params_ok(hb, r.L)) return DGPU_E_BADARG;
+    for (size_t i = 0; i < n; i++) if (zero_words(sig_a + 12 * i, 12)) { *ok = 0; return DGPU_OK; }      // ZeroSignature
+    CtxScope on_owner(hb.h.ctx);
+    SLOT_ACQUIRE(LK, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    const int forced = gs.many_chunk.load();                              // (dgpu_set_many_chunk_rows of the development surface cuts this call's rows too)
+    const size_t chunk = std::min(n, forced > 0 ? (size_t)forced : std::min(bbsk::BBS_BATCH_CHUNK, std::max<size_t>(1, bbsk::BBS_BATCH_TERMS / r.L)));
+    const RawBases rb = RawBases::packed<G1>(sig_a, nullptr);
+    int32_t rc;
+    // q[0]: e, q[1]: s, q[2]: the messages, q[3]: [P1 | P2] and their skip flags, q[7]: the blocks' partial sums, q[8]: [-c | the running sums], q[9]: [rho^i | rho^i e_i],
+    // q[10]: the prepared records of the A_i
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = o.q[0].ensure(chunk * 32))) return e;
+        if ((e = o.q[1].ensure(chunk * 32))) return e;
+        if ((e = o.q[2].ensure(chunk * r.L * 32))) return e;
+        if ((e = o.q[3].ensure(2 * PT + 64))) return e;
+        if ((e = o.q[7].ensure(bbsk::bbs_col_part_words(chunk, nn) * 4))) return e;
+        if ((e = o.q[8].ensure(nn * 40 + nn * 32 + 64))) return e;
+        if ((e = o.q[9].ensure(2 * chunk * 32))) return e;
+        if ((e = o.q[10].ensure(chunk * G1::AFF_STRIDE * 4))) return e;
+        if ((e = ws_stage_bases<G1>(o, rb, chunk))) return e;
+        if ((e = ws_for<G1>(o, 2, std::max(chunk, nn), 0, nullptr))) return e;
+        if (chunk != nn && (e = ws_for<G1>(o, 2, std::min(chunk, nn), 0, nullptr))) return e;
+        return ws_check(o, 1);
+    };
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws(sl))) return rc;
+    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    hipStream_t s = sl.stream;
+    DrainUnlessDone guard(sl);
+    uint32_t *d_c = sl.q[8].as<uint32_t>(), *d_run = d_c + nn * 8, *d_w = sl.q[9].as<uint32_t>(), *d_we = d_w + chunk * 8, *d_rec = sl.q[10].as<uint32_t>();
+    HPoint P1 = HPoint::identity(), P2 = HPoint::identity();
+    uint64_t jac[18];
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t rows = std::min(chunk, n - r0);
+        HIPCHK(hipMemcpyAsync(sl.q[0].p, r.e + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
+        if ((rc = rows_up(sl, r, r0, rows, sl.q[1].p, sl.q[2].p))) return rc;
+        if ((rc = stage_bases<G1>(sl, rb.from(r0), rows, d_rec))) return rc;
+        { StageTimer st(sl, "bbs.columns");
+          bbsk::launch_bbs_columns(s, sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), (const uint32_t *)random, r.mont ? 1 : 0, rows, nn, r0, r0 == 0,
+                                   sl.q[7].as<uint32_t>(), d_run, d_w, d_we, d_c); }
+        HIPCHK(hipGetLastError());
+        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_w, rows, jac))) return rc;
+        add_jac(P1, jac);
+        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_we, rows, jac))) return rc;
+        add_jac(P2, jac);
+        if (gs.prof) prof_flush(sl);
+    }
+    // - sum_k c_k H_k: ONE MSM of L + 2 terms over the parameters
+    {
+        SmallSub sub;
+        const bool have = small_sub_for<G1>(sl, params, hb.h, 0, nn, sub, true);
+        if ((rc = msm_device<G1, hostf::Fq>(sl, (const uint32_t *)hb.h.p, d_c, nn, jac, have ? &sub : nullptr))) return rc;
+        add_jac(P2, jac);
+    }
+    // the two merged pairs (an identity member is skipped)
+    uint64_t pts[24 + 8] = {0};
+    uint8_t *sk = (uint8_t *)(pts + 24);
+    for (int k = 0; k < 2; k++) {
+        const HPoint &P = k ? P2 : P1;
+        sk[k] = P.inf ? 1 : 0;
+        if (P.inf) continue;
+        hostf::Fq X, Y, Z; P.to_normalised_jacobian(X, Y, Z);
+        memcpy(pts + 12 * k, &X, 48); memcpy(pts + 12 * k + 6, &Y, 48);
+    }
+    uint8_t verdict = 0;
+    uint32_t *dP = sl.q[3].as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(dP, pts, sizeof pts, hipMemcpyHostToDevice, s));
+    if ((rc = coeffs_up(sl, pk_pc, g2_pc, 1))) return rc;
+    launch_check(sl, dP, dP + 24, (const uint8_t *)(dP + 48), 1, 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&verdict, sl.flags.p, 1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    guard.done = true;
+    if (gs.prof) prof_flush(sl);
+    *ok = verdict ? 1 : 0;
+    return DGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+int32_t dgpu_bbs_plus_sign_many_g1(uint64_t params, size_t L, const uint64_t sk[4], const uint64_t *messages, size_t row_stride, const uint64_t *e, const uint64_t *s, size_t n,
+                                   int32_t montgomery, uint64_t *out_a, uint8_t *bad) {
+    return abi_guard([&] { return sign_many(params, sk, Rows{messages, e, s, L, row_stride, n, montgomery != 0}, out_a, bad); });
+}
+int32_t dgpu_bbs_plus_verify_each_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const uint64_t *e, const uint64_t *s,
+                                     const uint64_t *messages, size_t row_stride, size_t n, int32_t montgomery, uint8_t *ok) {
+    return abi_guard([&] { return verify_each(params, pk_pc, g2_pc, sig_a, Rows{messages, e, s, L, row_stride, n, montgomery != 0}, ok); });
+}
+int32_t dgpu_bbs_plus_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const uint64_t *e, const uint64_t *s,
+                                      const uint64_t *messages, size_t row_stride, size_t n, int32_t montgomery, const uint64_t random[4], int32_t *ok) {
+    return abi_guard([&] { return verify_batch(params, pk_pc, g2_pc, sig_a, Rows{messages, e, s, L, row_stride, n, montgomery != 0}, random, ok); });
+}
+}  // extern "C"

@@ -689,6 +689,25 @@ inline int32_t stage_scalars(Slot &sl, const uint64_t *h, size_t n, bool mont, u
 
 // error paths of calls that read the caller's memory: nothing of ours may still read the caller's buffers when the call returns
 inline void drain(Slot &sl) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); }
+// zeroes the device buffers that held what depends on a secret key (dock_accumulator.hip: the tables, Omega's chunk results, evaluations and coefficients;
+// dock_bbs.hip: the inverses and the rows that carry them) on every return path, before the slot goes back
+struct DeviceWipe {
+    Slot &sl; struct Region { void *p; size_t bytes; }; std::vector<Region> r;
+    explicit DeviceWipe(Slot &s) : sl(s) {}
+    void add(void *p, size_t bytes) { if (p && bytes) r.push_back(Region{p, bytes}); }
+    ~DeviceWipe() {
+        if (r.empty()) return;
+        for (const Region &k : r) (void)hipMemsetAsync(k.p, 0, k.bytes, sl.stream);
+        (void)hipStreamSynchronize(sl.stream);
+    }
+};
+// a return before the call's last synchronisation (an error path) waits for the slot's streams first: asynchronous copies may still be queued into or out of
+// host vectors declared BEFORE this guard, which leave scope after it
+struct DrainUnlessDone {
+    Slot &sl; bool done = false;
+    explicit DrainUnlessDone(Slot &s) : sl(s) {}
+    ~DrainUnlessDone() { if (!done) drain(sl); }
+};
 
 // ---- workspaces sized ahead of the calls (no hipMalloc on an MSM path in steady state) ---------------------------------------------------
 // what: 1 = one-shot call of n terms (raw bases of `stride` bytes + scalars + prepared records + plain pipeline), 2 = fresh host scalars on a

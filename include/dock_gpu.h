@@ -622,6 +622,59 @@ int32_t dgpu_accumulator_non_membership_witnesses_g1(const uint64_t *d /* m*4 */
 int32_t dgpu_accumulator_membership_witnesses_g1(const uint64_t *members /* m*4 */, size_t m, const uint64_t alpha[4], const uint64_t accumulator_xy[12],
                                                  int32_t montgomery, uint64_t *out_xy /* m*12 */, uint8_t *out_inf /* m */);
 
+/* ---- BBS+ signatures in bulk: sign many, verify many, a verdict per signature or one for all (crypto_amd/csrc/dock_bbs.hip, bbs_kernels.hip.h) ----
+ * SignatureG1 / SignatureParamsG1 / PublicKeyG2 of bbs_plus/src/signature.rs:138-296 for n signatures of ONE key, each call one device pipeline per chunk
+ * of rows instead of the caller's chain dgpu_msm_g1_handle_many -> dgpu_g1_mul_add_batch -> dgpu_multi_pairing_segments with a PCIe round trip between each.
+ *   params        a plain G1 bases handle (dgpu_bases_upload_g1) holding exactly [g1, h_0, h_1 .. h_L] (SignatureParamsG1 { g1, g2, h_0, h }): the call runs on
+ *                 the context that owns it and pins it.  A length other than L + 2 is the reference's MessageCountIncompatibleWithSigParams, L = 0 its
+ *                 NoMessageToSign: DGPU_E_BADARG, as is an unknown, busy, sharded or precomputed handle or one of another kind
+ *   messages      n rows of L scalars, row i at messages + 4 * row_stride * i (row_stride >= L, counted in scalars; what lies between rows is never read)
+ *   e, s, sk, random   4 words each (e, s: n x 4).  montgomery != 0: ark-ff `&[Fr]` limbs; else canonical words, any 256-bit value counting modulo r
+ *   sig_a, out_a  n x 12 words, affine Montgomery coordinates; all-zero words are the identity
+ *   pk_pc, g2_pc  the prepared coefficients (DGPU_G2_PREPARED_WORDS words each, dgpu_g2_prepare / ark-ec G2Prepared) of the public key w = x g2 and of g2
+ *
+ * dgpu_bbs_plus_sign_many_g1 is SignatureG1::new (signature.rs:138-211) with the caller's e_i and s_i in place of its two `rand` draws (:178, :187), so that
+ * the call is deterministic:
+ *     A_i = (x + e_i)^-1 (g1 + s_i h_0 + sum_j m_ij h_j)                    b_i: setup.rs:128-146, the inverse: signature.rs:201-206
+ * The inverses are made on the host (one batch inversion per share of the host threads; x is used on the host only), everything else on the device: row i of
+ * the many-row MSM's scalars becomes (x + e_i)^-1 (1, s_i, m_i1 .. m_iL) (k_bbs_rows), so the MSM over params yields A_i itself, normalised.
+ * bad[i] = 1 and zero words in out_a where no signature exists: x + e_i = 0 (the reference draws e again there) or b_i the identity; such a row does not
+ * disturb its neighbours and the call returns DGPU_OK.  The host copy of the inverses and the device copies of the inverses and of the rows that carry them are
+ * zeroed on every return path before the slot is released; nothing is cached.
+ *
+ * dgpu_bbs_plus_verify_each_g1 is SignatureG1::verify (signature.rs:272-296) once per row, in the form the reference uses (:284-295):
+ *     ok[i] = 1  iff  A_i is not the identity (ZeroSignature, :280-282)  and  e(A_i, w) e(e_i A_i - b_i, g2) = 1
+ * b_i comes from the many-row MSM over params, e_i A_i - b_i from k_g1_scale_quad with b_i as its addend (the host splits -e_i, an input, and the kernel negates
+ * its result: nothing of the device is waited for), the lines of w and g2 are shared by every row (k_lines_from_prepared), the products run over slices of two,
+ * the Miller loop's tail and the final exponentiation on the device compare with one: only the n verdict bytes come back.  A zero Miller output is a rejection;
+ * a pair whose G1 member is the identity contributes one, as everywhere in the library.  The points are taken as members of the curve's prime-order subgroup
+ * (k_g1_scale_quad's endomorphism and the pairing assume it, as dgpu_legogroth16_verify_each does): validate untrusted ones first (dgpu_g1_validate_batch).
+ *
+ * dgpu_bbs_plus_verify_batch_g1: ONE verdict for all rows by the random linear combination the reference reaches through RandomizedPairingChecker
+ * (utils/src/randomized_pairing_check.rs:96-158); row i has the weight rho^i, rho = random (rho = 0 mod r: DGPU_E_BADARG, decided on the host).  The pairs that
+ * share w and g2 are merged before the pairing:
+ *     P1 = sum rho^i A_i,   P2 = sum rho^i e_i A_i - sum_k c_k H_k,   c = sum_i rho^i (1, s_i, m_i1 .. m_iL),   H = the L + 2 points of params
+ * — the column sums c_k, the weights and rho^i e_i on the device (k_bbs_col_sums, k_bbs_col_finish: two passes, no atomics), two variable-base MSMs of n terms
+ * over the A_i, ONE MSM of L + 2 terms over params, one two-pair Miller loop and one final exponentiation.  *ok = 1 iff the result is one and no A_i is the
+ * identity; n = 0 gives *ok = 1.  rho = 1 adds the rows up unweighted: errors that cancel between rows pass, as they would in the reference with that scalar.
+ *
+ * All three: n = 0 is DGPU_OK without touching a device or any pointer.  With n > 0 a NULL pointer, row_stride < L, L = 0, n or row_stride >= 2^31 is
+ * DGPU_E_BADARG, decided before the device is looked at; DGPU_E_NODEVICE comes before anything the device would decide (the handle).  Never DGPU_E_TOO_SMALL.
+ * Thread-safe like every entry point; one slot per call; a second call of a shape allocates nothing.  Rows travel in chunks so that the slot's grow-only
+ * workspace stays bounded whatever n: sign min(4096, 2^17 / (L + 2)) rows (below ~80 MB), verify_each the same (at most 4096 rows: 91 KB of lines and
+ * products per row, below ~0.5 GB), verify_batch min(65536, 2^20 / L) rows (below ~0.2 GB).  Rows longer than the many-row kernels accept (L + 2 above
+ * dgpu_set_small_msm_max, or with it set to 0) take the single-row MSM driver row by row inside the call: correct, not fast.  Stage timers bbs.host_inverses,
+ * bbs.glv_split, bbs.rows, bbs.columns, bbs.scale, bbs.lines, bbs.products, bbs.tail, bbs.final_exp beside those of the MSM. */
+int32_t dgpu_bbs_plus_sign_many_g1(uint64_t params, size_t L, const uint64_t sk[4], const uint64_t *messages /* n rows */, size_t row_stride,
+                                   const uint64_t *e /* n*4 */, const uint64_t *s /* n*4 */, size_t n, int32_t montgomery,
+                                   uint64_t *out_a /* n*12 */, uint8_t *bad /* n */);
+int32_t dgpu_bbs_plus_verify_each_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a /* n*12 */,
+                                     const uint64_t *e /* n*4 */, const uint64_t *s /* n*4 */, const uint64_t *messages /* n rows */, size_t row_stride,
+                                     size_t n, int32_t montgomery, uint8_t *ok /* n */);
+int32_t dgpu_bbs_plus_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a /* n*12 */,
+                                      const uint64_t *e /* n*4 */, const uint64_t *s /* n*4 */, const uint64_t *messages /* n rows */, size_t row_stride,
+                                      size_t n, int32_t montgomery, const uint64_t random[4], int32_t *ok);
+
 /* ---- the LegoGroth16 prover as one call ----
  * replaces create_proof_and_committed_witnesses_with_assignment (legogroth16/src/prover.rs:267-383, with calculate_coeff :585-594) and — when
  * the circuit is resident (r1cs != 0) — the QAP::witness_map call in front of it (create_proof_with_reduction, :153-180): the whole schedule

@@ -288,6 +288,24 @@ pub(crate) fn raw_accumulator_membership_witnesses(members: &[Fr], alpha: &Fr, a
     unsafe { dgpu_accumulator_membership_witnesses_g1(members.as_ptr() as *const u64, members.len(), alpha as *const Fr as *const u64, v.as_ptr(), 1, xy.as_mut_ptr(), inf.as_mut_ptr()) }
 }
 
+// ---- BBS+ signatures in bulk: the raw callers behind src/bbs_plus.rs (the typed API and its documentation live there) -------------------------------------
+/// `A_i = (sk + e_i)^-1 (g1 + s_i h_0 + sum_j m_ij h_j)`; `params`: a plain bases handle holding `[g1, h_0, h ..]`, `messages`: n rows of `l`, packed;
+/// `out_a`: n x 12 words, `bad`: n bytes
+pub(crate) fn raw_bbs_plus_sign_many(params: u64, l: usize, sk: &Fr, messages: &[Fr], e: &[Fr], s: &[Fr], out_a: &mut [u64], bad: &mut [u8]) -> i32 {
+    unsafe { dgpu_bbs_plus_sign_many_g1(params, l, sk as *const Fr as *const u64, messages.as_ptr() as *const u64, l, e.as_ptr() as *const u64, s.as_ptr() as *const u64, e.len(), 1,
+                                        out_a.as_mut_ptr(), bad.as_mut_ptr()) }
+}
+/// `ok[i] = (A_i != O and e(A_i, w) e(e_i A_i - b_i, g2) == 1)`; `pk_pc`, `g2_pc`: the prepared coefficients of `w` and `g2`
+pub(crate) fn raw_bbs_plus_verify_each(params: u64, l: usize, pk_pc: &[u64], g2_pc: &[u64], sig_a: &[u64], e: &[Fr], s: &[Fr], messages: &[Fr], ok: &mut [u8]) -> i32 {
+    unsafe { dgpu_bbs_plus_verify_each_g1(params, l, pk_pc.as_ptr(), g2_pc.as_ptr(), sig_a.as_ptr(), e.as_ptr() as *const u64, s.as_ptr() as *const u64, messages.as_ptr() as *const u64, l,
+                                          e.len(), 1, ok.as_mut_ptr()) }
+}
+/// one verdict for all rows under the weights `random^i`
+pub(crate) fn raw_bbs_plus_verify_batch(params: u64, l: usize, pk_pc: &[u64], g2_pc: &[u64], sig_a: &[u64], e: &[Fr], s: &[Fr], messages: &[Fr], random: &Fr, ok: &mut i32) -> i32 {
+    unsafe { dgpu_bbs_plus_verify_batch_g1(params, l, pk_pc.as_ptr(), g2_pc.as_ptr(), sig_a.as_ptr(), e.as_ptr() as *const u64, s.as_ptr() as *const u64, messages.as_ptr() as *const u64, l,
+                                           e.len(), 1, random as *const Fr as *const u64, ok) }
+}
+
 // ---- R1CS -> QAP witness map (legogroth16/src/r1cs_to_qap.rs:150-210) ---------------------------------------------------------------------------------
 /// one constraint matrix of ark-relations' `ConstraintMatrices` (`Matrix<F> = Vec<Vec<(F, usize)>>`) as the CSR arrays the ABI takes, with a 64-bit hash of
 /// its whole contents computed on the way (the copy reads every coefficient anyway)

@@ -30,6 +30,8 @@ pub mod encode;
 pub mod generic;
 pub mod host;
 pub mod accumulator_issue;      // (issuing membership / non-membership witnesses: src/accumulator_issue.rs; cargo-side cases in tests/parity_accumulator_issue.rs)
+#[cfg(feature = "bbs-plus")]
+pub mod bbs_plus;               // (BBS+ signatures in bulk behind the reference's own types: src/bbs_plus.rs; the case in tests/parity.rs runs under the same feature)
 
 pub type G2Prepared = ArkG2Prepared<ark_bls12_381::Config>;
 

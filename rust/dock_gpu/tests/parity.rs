@@ -719,3 +719,41 @@ fn gt_powers_on_the_device() {
     let ok = dock_gpu::host::gt_in_subgroup_device(&bases).unwrap();
     for (i, b) in bases.iter().enumerate() { assert_eq!(ok[i], !b.0.is_zero() && b.check().is_ok(), "element {i}"); }
 }
+
+// BBS+ in bulk against the reference's own SignatureG1::new / verify (bbs_plus/src/signature.rs:138-296): the e, s the reference drew go back in, so the A must agree
+#[cfg(feature = "bbs-plus")]
+#[test]
+fn bbs_plus_bulk_equals_the_reference() {
+    use bbs_plus::prelude::{KeypairG2, SignatureG1, SignatureParamsG1};
+    use dock_gpu::bbs_plus::{sign_many, verify_batch, verify_each, GpuSignatureParams};
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5EED0BB5);
+    for &(l, n) in &[(1usize, 3usize), (5, 65), (30, 257)] {
+        let params = SignatureParamsG1::<Bls12_381>::generate_using_rng(&mut rng, l as u32);
+        let keypair = KeypairG2::<Bls12_381>::generate_using_rng(&mut rng, &params);
+        let msgs: Vec<Vec<Fr>> = (0..n).map(|_| frs(&mut rng, l)).collect();
+        let rows: Vec<&[Fr]> = msgs.iter().map(|m| m.as_slice()).collect();
+        let sigs: Vec<SignatureG1<Bls12_381>> = msgs.iter().map(|m| SignatureG1::new(&mut rng, m, &keypair.secret_key, &params).unwrap()).collect();
+        let (e, s): (Vec<Fr>, Vec<Fr>) = sigs.iter().map(|x| (x.e, x.s)).unzip();
+        let gp = GpuSignatureParams::new(&params, &keypair.public_key).expect("parameters");
+        assert_eq!(gp.supported_message_count(), l);
+        let mine = sign_many(&gp, &keypair.secret_key, &rows, &e, &s).expect("sign_many");
+        for i in 0..n { assert_eq!(mine[i].as_ref().expect("a signature"), &sigs[i], "l = {l}, row {i}"); }
+        // a row the reference would draw e again for
+        let mut e2 = e.clone(); e2[n - 1] = -keypair.secret_key.0;
+        let flagged = sign_many(&gp, &keypair.secret_key, &rows, &e2, &s).expect("sign_many");
+        assert!(flagged[n - 1].is_none() && flagged[..n - 1].iter().zip(sigs.iter()).all(|(a, b)| a.as_ref() == Some(b)));
+        // verdicts: the reference's verify, signature by signature, on a batch with a wrong message, a wrong e and a swapped A
+        let mut bad = sigs.clone();
+        let mut bad_msgs = msgs.clone();
+        bad_msgs[0][0] += Fr::from(1u64);
+        if n > 2 { bad[1].e += Fr::from(1u64); let a = bad[n - 1].A; bad[n - 1].A = bad[n - 2].A; bad[n - 2].A = a; }
+        let bad_rows: Vec<&[Fr]> = bad_msgs.iter().map(|m| m.as_slice()).collect();
+        let want: Vec<bool> = bad.iter().zip(bad_msgs.iter()).map(|(x, m)| x.verify(m, keypair.public_key.clone(), params.clone()).is_ok()).collect();
+        assert_eq!(verify_each(&gp, &bad, &bad_rows).expect("verify_each"), want);
+        assert!(verify_each(&gp, &sigs, &rows).expect("verify_each").iter().all(|&k| k));
+        let rho = Fr::rand(&mut rng);
+        assert_eq!(verify_batch(&gp, &sigs, &rows, &rho), Some(true));
+        assert_eq!(verify_batch(&gp, &bad, &bad_rows, &rho), Some(false));
+    }
+}
