@@ -4,6 +4,11 @@
     SignatureG1::new(rng, messages, sk, params), n times      -> sign_many(params, sk, messages, e, s)       returns (A, bad)
     sig.verify(messages, pk, params), n times                 -> verify_each(params, A, e, s, messages)      returns ok, one byte per signature
     the same through RandomizedPairingChecker                 -> verify_batch(params, A, e, s, messages, random)     returns True / False
+    proof.verify(revealed, challenge, pk, params), n times    -> pok_verify_each(params, points, resp_fixed, values, revealed, challenge)     returns status, one byte per proof
+    the same with one verdict for all                         -> pok_verify_batch(.., random)                returns True / False
+    proof.challenge_contribution(revealed, params, writer)    -> challenge_contribution(param_points, proof_points, revealed_row, values_row)     returns bytes
+
+The proofs are PoKOfSignatureG1Proof (bbs_plus/src/proof.rs:355-611): what a verifier of presentations checks, who never sees e, s or the hidden messages.
 
 `e` and `s` stand in for the two `rand` draws of SignatureG1::new, so signing is deterministic.  Scalars are (n, 4) uint64 limb arrays or Python ints, canonical
 unless `montgomery=True` (then ark-ff Montgomery limbs); messages are an (n, L) array of Python ints or an (n, L, 4) limb array (a view with a longer row
@@ -28,6 +33,7 @@ class Params:
         if self.L == 0:
             raise ValueError("NoMessageToSign")                                  # signature.rs:150-152
         pts = np.concatenate([np.asarray(g1, dtype=np.uint64).reshape(1, 12), np.asarray(h_0, dtype=np.uint64).reshape(1, 12), h])
+        self.h_0 = np.ascontiguousarray(pts[1])                                  # (the proof-of-knowledge calls pass it beside the handle)
         self.bases = DeviceBases(G1, pts)
         pc = G2Prepared.from_affine(np.stack([np.asarray(w, dtype=np.uint64).reshape(24), np.asarray(g2, dtype=np.uint64).reshape(24)]))
         self.pk_pc, self.g2_pc = np.ascontiguousarray(pc.coeffs[0]), np.ascontiguousarray(pc.coeffs[1])
@@ -123,3 +129,73 @@ def verify_batch(params, sig_a, e, s, messages, random, montgomery=False):
     if rc:
         raise DockGpuError(rc, "dgpu_bbs_plus_verify_batch_g1")
     return bool(ok.value)
+
+
+# ---- proofs of knowledge of a signature (PoKOfSignatureG1Proof) -------------------------------------------------------------------------------------------
+STATUS = {0: "verified", 1: "ZeroSignature", 2: "FirstSchnorrVerificationFailed", 3: "SecondSchnorrVerificationFailed", 4: "PairingCheckFailed"}
+
+
+def _proofs(params, points, resp_fixed, values, revealed, challenge):
+    v, stride, n = _messages(values, params.L)
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 5, 12)
+    flat = resp_fixed if isinstance(resp_fixed, np.ndarray) and resp_fixed.dtype == np.uint64 else [z for r in resp_fixed for z in r]
+    fixed = _scalars_to_limbs(flat).reshape(-1, 4, 4) if n else np.zeros((0, 4, 4), np.uint64)
+    rev = np.ascontiguousarray(np.asarray(revealed) != 0, dtype=np.uint8).reshape(-1, params.L) if n else np.zeros((0, params.L), np.uint8)
+    c = _scalars_to_limbs(challenge) if n else np.zeros((0, 4), np.uint64)
+    if not (len(pts) == len(fixed) == len(rev) == len(c) == n):
+        raise ValueError("%d rows of values, %d proofs' points, %d of fixed responses, %d masks, %d challenges" % (n, len(pts), len(fixed), len(rev), len(c)))
+    return v, stride, n, pts, fixed, rev, c
+
+
+def pok_verify_each(params, points, resp_fixed, values, revealed, challenge, montgomery=False):
+    """status, an (n,) uint8 array: 0 where PoKOfSignatureG1Proof::verify accepts proof i, else the first of its errors in the order it returns them (STATUS):
+    1 ZeroSignature (A' is the identity), 2 the first Schnorr check z1 A' + z2 h_0 - c (Abar - d) = T1, 3 the second, sum_hidden z_j h_j + z3 d + z4 h_0 +
+    c (g1 + sum_revealed m_j h_j) = T2, 4 the pairing e(A', w) e(-Abar, g2) = 1.
+
+    points: (n, 5, 12), A', Abar, d, T1 (sc_resp_1.t), T2.  resp_fixed: (n, 4) scalars z1, z2 (sc_resp_1.response1 / .response2), z3 (the response over d),
+    z4 (over h_0).  values: n rows of L scalars as `messages` above; entry j is the revealed message where revealed[i][j] is non-zero, else the response of
+    the hidden message j.  A proof with partial responses (sc_partial_resp_2 and missing_responses) needs no path of its own: write the missing responses into
+    the row.  The points are taken as validated members of the subgroup, as the reference takes them (crypto_amd.serde.validate)."""
+    _ensure()
+    v, stride, n, pts, fixed, rev, c = _proofs(params, points, resp_fixed, values, revealed, challenge)
+    status = np.zeros(n, np.uint8)
+    rc = lib().dgpu_bbs_plus_pok_verify_each_g1(params.handle, params.L, _p(params.h_0), _p(params.pk_pc), _p(params.g2_pc), _p(pts) if n else None, _p(fixed) if n else None,
+                                                _p(v) if n else None, stride, _p(rev) if n else None, _p(c) if n else None, n, 1 if montgomery else 0, _p(status) if n else None)
+    if rc:
+        raise DockGpuError(rc, "dgpu_bbs_plus_pok_verify_each_g1")
+    return status
+
+
+def pok_verify_batch(params, points, resp_fixed, values, revealed, challenge, random, montgomery=False):
+    """True iff every proof verifies, by ONE G1 equation and one pairing check over the random linear combination with the weights random^(2i) on the first
+    Schnorr check of proof i, random^(2i+1) on the second and random^i on the pairing (random non-zero modulo r; an empty batch verifies).  A batch with a
+    failing proof passes with probability at most 3n / r per equation over the choice of `random`."""
+    _ensure()
+    v, stride, n, pts, fixed, rev, c = _proofs(params, points, resp_fixed, values, revealed, challenge)
+    rho = _scalars_to_limbs([random] if isinstance(random, int) else random).reshape(4)
+    ok = C.c_int32(0)
+    rc = lib().dgpu_bbs_plus_pok_verify_batch_g1(params.handle, params.L, _p(params.h_0), _p(params.pk_pc), _p(params.g2_pc), _p(pts) if n else None, _p(fixed) if n else None,
+                                                 _p(v) if n else None, stride, _p(rev) if n else None, _p(c) if n else None, n, 1 if montgomery else 0, _p(rho), C.byref(ok))
+    if rc:
+        raise DockGpuError(rc, "dgpu_bbs_plus_pok_verify_batch_g1")
+    return bool(ok.value)
+
+
+def challenge_contribution(param_points, proof_points, revealed_row, values_row):
+    """The bytes PoKOfSignatureG1Protocol::compute_challenge_contribution writes for one proof (proof.rs:328-352): A', Abar, d, h_0, g1, T1, T2 compressed, then
+    every h_j compressed, followed by m_j as 32 little-endian bytes where j is revealed.  param_points: (L + 2, 12) = [g1, h_0, h ..]; proof_points: (5, 12);
+    values_row: L canonical integers (only the revealed entries are read).  Hashing the bytes to a challenge stays with the caller."""
+    from . import serde
+    P = np.ascontiguousarray(param_points, dtype=np.uint64).reshape(-1, 12)
+    Q = np.ascontiguousarray(proof_points, dtype=np.uint64).reshape(5, 12)
+    L = len(P) - 2
+    if len(revealed_row) != L or len(values_row) != L:
+        raise ValueError("a row of %d mask bytes and %d values for %d generators" % (len(revealed_row), len(values_row), L))
+    head = serde.serialize(G1, np.stack([Q[0], Q[1], Q[2], P[1], P[0], Q[3], Q[4]]))
+    hs = serde.serialize(G1, P[2:])
+    out = [head]
+    for j in range(L):
+        out.append(hs[48 * j:48 * j + 48])
+        if revealed_row[j]:
+            out.append(int(values_row[j]).to_bytes(32, "little"))
+    return b"".join(out)

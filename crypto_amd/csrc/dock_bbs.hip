@@ -14,6 +14,16 @@
 //            device  P1 = sum rho^i A_i, P2 = sum (rho^i e_i) A_i + sum (-c_k) H_k: two MSMs per chunk over the A_i, ONE over the parameters; the host adds the
 //                    chunks' points
 //            device  e(P1, w) e(P2, g2) against one, as above with one slice
+// Proofs of knowledge of a signature (dgpu_bbs_plus_pok_verify_each_g1, dgpu_bbs_plus_pok_verify_batch_g1): PoKOfSignatureG1Proof::verify (bbs_plus/src/proof.rs:529-611)
+// for many proofs under one key; the verifier sees no e, s or hidden message, so none of the above serves it.
+//   pok each   device  row i = (c_i, z4_i, y_i ..), the own-point scalars (z1, z2, -c, c, -1 | z3, -1)         k_bbs_pok_rows, k_bbs_pok_own
+//              device  the bases of the row's two segments, A' and -Abar for the pairing                          k_bbs_pok_stage
+//              device  P_i = <row_i, params>                                                                      k_many_tree, k_many_fold
+//              device  [A', h_0, Abar, d, T1] . (z1, z2, -c, c, -1) and z3 d - T2 per row                         k_small_table, k_seg_tree, k_seg_fold (seg_rows_resident)
+//              device  e(A'_i, w) e(-Abar_i, g2), as above; the four checks into a status byte                    .., k_bbs_pok_verdict
+//   pok batch  device  C_k, the weights over the own points, +-rho^i                                              k_bbs_pok_col_sums, k_bbs_pok_col_finish
+//              device  one MSM over the chunk's 5 n own points, one each over the A' and the Abar; ONE over the parameters; the host adds the chunks' points
+//              device  e(sum rho^i A'_i, w) e(-sum rho^i Abar_i, g2) against one
 // Only verdict bytes (each, batch) or the signatures (sign) come back.  The device copies of the inverses and of the rows that carry them are zeroed on every return
 // path before the slot is released, the host copy too.
 #include <chrono>
@@ -23,6 +33,7 @@
 #include "pairing_launch.hip.h"
 #include "gt_launch.hip.h"
 #include "bbs_launch.hip.h"
+#include "bbs_pok_launch.hip.h"
 #include "acc_host_tables.hpp"
 using namespace dock;
 using namespace acch;
@@ -34,6 +45,7 @@ double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::
 bool zero_words(const uint64_t *w, int k) { uint64_t o = 0; for (int i = 0; i < k; i++) o |= w[i]; return o == 0; }
 
 constexpr size_t PT = 96;                 // bytes of an affine G1 point of the ABI
+constexpr size_t NPTS = 5;                // points of a proof of knowledge: A', Abar, d, T1, T2
 
 // what the three calls share: the rows' inputs and how they are cut
 struct Rows {
@@ -376,6 +388,196 @@ int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_
     return DGPU_OK;
 }
 
+// ---- PoKOfSignatureG1Proof::verify for n proofs (proof.rs:529-611) -------------------------------------------------------------------------------------------------
+struct Proofs {
+    const uint64_t *h0, *points, *fixed, *values; const uint8_t *revealed; const uint64_t *challenge; size_t L, stride, n; bool mont;
+    size_t nn() const { return L + 2; }
+};
+bool bad_proofs(const Proofs &p) {
+    return p.L == 0 || !p.h0 || !p.points || !p.fixed || !p.values || !p.revealed || !p.challenge || p.stride < p.L || p.n >= (1ull << 31) || p.L >= (1ull << 31) - 2 ||
+           p.stride >= (1ull << 31);
+}
+// q[0]: the challenges, q[1]: z1 .. z4, q[2]: the values, q[3]: the mask, q[5]: the points of the rows [r0, r0 + rows); the values packed
+int32_t ws_proofs(Slot &o, const Proofs &p, size_t chunk) {
+    int32_t e;
+    if ((e = o.q[0].ensure(chunk * 32))) return e;
+    if ((e = o.q[1].ensure(chunk * 4 * 32))) return e;
+    if ((e = o.q[2].ensure(chunk * p.L * 32))) return e;
+    if ((e = o.q[3].ensure(chunk * p.L))) return e;
+    return o.q[5].ensure(chunk * NPTS * PT);
+}
+int32_t proofs_up(Slot &sl, const Proofs &p, size_t r0, size_t rows, bbspk::PokDev &dev) {
+    hipStream_t s = sl.stream;
+    HIPCHK(hipMemcpyAsync(sl.q[0].p, p.challenge + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sl.q[1].p, p.fixed + 16 * r0, rows * 4 * 32, hipMemcpyHostToDevice, s));
+    const uint64_t *src = p.values + r0 * p.stride * 4;
+    if (p.stride == p.L) HIPCHK(hipMemcpyAsync(sl.q[2].p, src, rows * p.L * 32, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpy2DAsync(sl.q[2].p, p.L * 32, src, p.stride * 32, p.L * 32, rows, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sl.q[3].p, p.revealed + r0 * p.L, rows * p.L, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sl.q[5].p, p.points + r0 * NPTS * 12, rows * NPTS * PT, hipMemcpyHostToDevice, s));
+    dev = bbspk::PokDev{sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), sl.q[3].as<uint8_t>(), p.L, p.mont ? 1 : 0};
+    return DGPU_OK;
+}
+// the two segments of every row of a chunk, 5 and 2 terms: the layout depends on the row count alone
+void own_layout(size_t rows, SegLayout &lay) {
+    std::vector<uint64_t> ends(2 * rows);
+    for (size_t i = 0; i < rows; i++) { ends[2 * i] = 7 * i + 5; ends[2 * i + 1] = 7 * i + 7; }
+    seg_layout(ends.data(), 0, 2 * rows, lay);
+}
+
+int32_t pok_verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const Proofs &p, uint8_t *status) {
+    if (p.n == 0) return DGPU_OK;
+    if (bad_proofs(p) || !pk_pc || !g2_pc || !status) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    const size_t n = p.n, nn = p.nn();
+    HandleRef hb(params);
+    if (!params_ok(hb, p.L)) return DGPU_E_BADARG;
+    CtxScope on_owner(hb.h.ctx);
+    SLOT_ACQUIRE(LK, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    BPath bp;
+    int32_t rc;
+    if ((rc = b_path(sl, params, hb.h, nn, bbspk::POK_EACH_CHUNK, n, bp))) return rc;
+    const size_t chunk = bp.chunk;
+    SegLayout lay, lay_tail;
+    own_layout(chunk, lay);
+    if (n % chunk) own_layout(n % chunk, lay_tail);
+    // q[0 .. 3], q[5]: the proofs (ws_proofs); q[4]: [P | identity flags], q[6]: the own-point scalars, q[7]: the own points in segment order, q[8]: [A' | -Abar],
+    // q[9]: [skip flags of (A', -Abar) | status]
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = ws_proofs(o, p, chunk))) return e;
+        if ((e = o.q[4].ensure(chunk * PT + chunk))) return e;
+        if ((e = o.q[6].ensure(chunk * 7 * 32))) return e;
+        if ((e = o.q[7].ensure(chunk * 7 * PT))) return e;
+        if ((e = o.q[8].ensure(2 * chunk * PT))) return e;
+        if ((e = o.q[9].ensure(3 * chunk))) return e;
+        if ((e = ws_check(o, chunk))) return e;
+        if ((e = ws_seg_resident<G1>(o, 7 * chunk, 2 * chunk, lay.blocks))) return e;
+        return bp.workspace(o);
+    };
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws(sl))) return rc;
+    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    hipStream_t s = sl.stream;
+    std::vector<uint64_t> jac; std::vector<uint8_t> hinf;
+    DrainUnlessDone guard(sl);
+    uint32_t *d_rows = sl.in_scalars.as<uint32_t>(), *d_bad = sl.flags.as<uint32_t>(), *d_own = sl.q[6].as<uint32_t>(), *d_opts = sl.q[7].as<uint32_t>();
+    uint32_t *dPa = sl.q[8].as<uint32_t>(), *dPb = dPa + chunk * (PT / 4);
+    uint8_t *dB = sl.q[4].as<uint8_t>(), *dBinf = dB + chunk * PT, *dsk = sl.q[9].as<uint8_t>(), *dstatus = dsk + 2 * chunk;
+    if ((rc = coeffs_up(sl, pk_pc, g2_pc, chunk))) return rc;
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t rows = std::min(chunk, n - r0);
+        bbspk::PokDev dev;
+        HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));                          // (rows are canonical: the flag stays clear; sl.flags takes the pairing's verdicts afterwards)
+        if ((rc = proofs_up(sl, p, r0, rows, dev))) return rc;
+        { StageTimer st(sl, "bbs.pok_rows"); bbspk::launch_pok_rows(s, dev, rows, d_rows, d_own); }
+        { StageTimer st(sl, "bbs.pok_stage"); bbspk::launch_pok_stage(s, sl.q[5].as<uint32_t>(), (const uint32_t *)p.h0, rows, d_opts, dPa, dPb, dsk); }
+        if ((rc = b_points(sl, bp, d_rows, rows, d_bad, dB, dBinf, jac, hinf))) return rc;
+        if ((rc = seg_rows_resident<G1>(sl, (const uint8_t *)d_opts, PT, d_own, 7 * rows, 2 * rows, rows == chunk ? lay : lay_tail, d_bad))) return rc;
+        launch_check(sl, dPa, dPb, dsk, rows, chunk);
+        { StageTimer st(sl, "bbs.pok_verdict");
+          bbspk::launch_pok_verdict(s, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>(), (const uint32_t *)dB, dBinf, sl.flags.as<uint8_t>(), dsk, rows, dstatus); }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(status + r0, dstatus, rows, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));                                 // (the next chunk's operands overwrite this one's)
+        if (gs.prof) prof_flush(sl);
+    }
+    guard.done = true;
+    return DGPU_OK;
+}
+
+// one verdict for n proofs: row i weighs its first Schnorr check with u_i = rho^(2 i), its second with v_i = rho^(2 i + 1), its pairing with t_i = rho^i
+int32_t pok_verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const Proofs &p, const uint64_t *random, int32_t *ok) {
+    if (p.n == 0) { if (ok) *ok = 1; return DGPU_OK; }
+    if (bad_proofs(p) || !pk_pc || !g2_pc || !random || !ok) return DGPU_E_BADARG;
+    if (fr_is_zero(fr_in(random, p.mont))) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    const size_t n = p.n, nn = p.nn();
+    HandleRef hb(params);
+    if (!params_ok(hb, p.L)) return DGPU_E_BADARG;
+    for (size_t i = 0; i < n; i++) if (zero_words(p.points + NPTS * 12 * i, 12)) { *ok = 0; return DGPU_OK; }      // ZeroSignature
+    CtxScope on_owner(hb.h.ctx);
+    SLOT_ACQUIRE(LK, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    const int forced = gs.many_chunk.load();                              // (dgpu_set_many_chunk_rows of the development surface cuts this call's rows too)
+    const size_t chunk = std::min(n, forced > 0 ? (size_t)forced : std::min(bbspk::POK_BATCH_CHUNK, std::max<size_t>(1, bbsk::BBS_BATCH_TERMS / p.L)));
+    int32_t rc;
+    // q[0 .. 3], q[5]: the proofs (ws_proofs); q[4]: [P1 | P2] and their skip flags, q[6]: the weights over the own points, q[7]: the blocks' partial sums,
+    // q[8]: [C | the running sums], q[9]: [rho^i | -rho^i], q[10]: the prepared records of the own points, q[11]: those of [the A' | the Abar]
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = ws_proofs(o, p, chunk))) return e;
+        if ((e = o.q[4].ensure(2 * PT + 64))) return e;
+        if ((e = o.q[6].ensure(chunk * NPTS * 32))) return e;
+        if ((e = o.q[7].ensure(bbsk::bbs_col_part_words(chunk, nn) * 4))) return e;
+        if ((e = o.q[8].ensure(nn * 40 + nn * 32 + 64))) return e;
+        if ((e = o.q[9].ensure(2 * chunk * 32))) return e;
+        if ((e = o.q[10].ensure(chunk * NPTS * G1::AFF_STRIDE * 4))) return e;
+        if ((e = o.q[11].ensure(2 * chunk * G1::AFF_STRIDE * 4))) return e;
+        for (size_t terms : {NPTS * chunk, chunk, nn}) if ((e = ws_for<G1>(o, 2, terms, 0, nullptr))) return e;
+        return ws_check(o, 1);
+    };
+    const uint64_t allocs0 = g_dev_allocs.load();
+    if ((rc = ws(sl))) return rc;
+    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    hipStream_t s = sl.stream;
+    DrainUnlessDone guard(sl);
+    uint32_t *d_c = sl.q[8].as<uint32_t>(), *d_run = d_c + nn * 8, *d_w5 = sl.q[6].as<uint32_t>(), *d_tp = sl.q[9].as<uint32_t>(), *d_tn = d_tp + chunk * 8;
+    uint32_t *d_rec = sl.q[10].as<uint32_t>(), *d_reca = sl.q[11].as<uint32_t>(), *d_recb = d_reca + chunk * G1::AFF_STRIDE;
+    HPoint Gsum = HPoint::identity(), P1 = HPoint::identity(), P2 = HPoint::identity();
+    uint64_t jac[18];
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t rows = std::min(chunk, n - r0);
+        bbspk::PokDev dev;
+        if ((rc = proofs_up(sl, p, r0, rows, dev))) return rc;
+        const uint8_t *raw = sl.q[5].as<uint8_t>();
+        { StageTimer st(sl, "msm.prep_bases");
+          msm::launch_prep_bases_raw<G1>(s, raw, PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, NPTS * rows, d_rec);
+          msm::launch_prep_bases_raw<G1>(s, raw, NPTS * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_reca);
+          msm::launch_prep_bases_raw<G1>(s, raw + PT, NPTS * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_recb); }
+        { StageTimer st(sl, "bbs.pok_columns");
+          bbspk::launch_pok_columns(s, dev, (const uint32_t *)random, rows, r0, r0 == 0, sl.q[7].as<uint32_t>(), d_run, d_w5, d_tp, d_tn, d_c); }
+        HIPCHK(hipGetLastError());
+        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_w5, NPTS * rows, jac))) return rc;
+        add_jac(Gsum, jac);
+        if ((rc = msm_device<G1, hostf::Fq>(sl, d_reca, d_tp, rows, jac))) return rc;
+        add_jac(P1, jac);
+        if ((rc = msm_device<G1, hostf::Fq>(sl, d_recb, d_tn, rows, jac))) return rc;
+        add_jac(P2, jac);
+        if (gs.prof) prof_flush(sl);
+    }
+    // sum_k C_k H_k: ONE MSM of L + 2 terms over the parameters
+    {
+        SmallSub sub;
+        const bool have = small_sub_for<G1>(sl, params, hb.h, 0, nn, sub, true);
+        if ((rc = msm_device<G1, hostf::Fq>(sl, (const uint32_t *)hb.h.p, d_c, nn, jac, have ? &sub : nullptr))) return rc;
+        add_jac(Gsum, jac);
+    }
+    if (!Gsum.inf) { HIPCHK(hipStreamSynchronize(s)); guard.done = true; *ok = 0; return DGPU_OK; }      // the G1 equation fails: the pairing cannot mend it
+    uint64_t pts[24 + 8] = {0};
+    uint8_t *sk = (uint8_t *)(pts + 24);
+    for (int k = 0; k < 2; k++) {
+        const HPoint &P = k ? P2 : P1;
+        sk[k] = P.inf ? 1 : 0;
+        if (P.inf) continue;
+        hostf::Fq X, Y, Z; P.to_normalised_jacobian(X, Y, Z);
+        memcpy(pts + 12 * k, &X, 48); memcpy(pts + 12 * k + 6, &Y, 48);
+    }
+    uint8_t verdict = 0;
+    uint32_t *dP = sl.q[4].as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(dP, pts, sizeof pts, hipMemcpyHostToDevice, s));
+    if ((rc = coeffs_up(sl, pk_pc, g2_pc, 1))) return rc;
+    launch_check(sl, dP, dP + 24, (const uint8_t *)(dP + 48), 1, 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&verdict, sl.flags.p, 1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    guard.done = true;
+    if (gs.prof) prof_flush(sl);
+    *ok = verdict ? 1 : 0;
+    return DGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -390,5 +592,17 @@ int32_t dgpu_bbs_plus_verify_each_g1(uint64_t params, size_t L, const uint64_t *
 int32_t dgpu_bbs_plus_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const uint64_t *e, const uint64_t *s,
                                       const uint64_t *messages, size_t row_stride, size_t n, int32_t montgomery, const uint64_t random[4], int32_t *ok) {
     return abi_guard([&] { return verify_batch(params, pk_pc, g2_pc, sig_a, Rows{messages, e, s, L, row_stride, n, montgomery != 0}, random, ok); });
+}
+int32_t dgpu_bbs_plus_pok_verify_each_g1(uint64_t params, size_t L, const uint64_t h_0[12], const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points,
+                                         const uint64_t *resp_fixed, const uint64_t *values, size_t row_stride, const uint8_t *revealed, const uint64_t *challenge, size_t n,
+                                         int32_t montgomery, uint8_t *status) {
+    return abi_guard([&] { return pok_verify_each(params, pk_pc, g2_pc, Proofs{h_0, points, resp_fixed, values, revealed, challenge, L, row_stride, n, montgomery != 0}, status); });
+}
+int32_t dgpu_bbs_plus_pok_verify_batch_g1(uint64_t params, size_t L, const uint64_t h_0[12], const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points,
+                                          const uint64_t *resp_fixed, const uint64_t *values, size_t row_stride, const uint8_t *revealed, const uint64_t *challenge, size_t n,
+                                          int32_t montgomery, const uint64_t random[4], int32_t *ok) {
+    return abi_guard([&] {
+        return pok_verify_batch(params, pk_pc, g2_pc, Proofs{h_0, points, resp_fixed, values, revealed, challenge, L, row_stride, n, montgomery != 0}, random, ok);
+    });
 }
 }  // extern "C"

@@ -200,6 +200,48 @@ int32_t msm_seg_chunk(Slot &sl, const RawBases &rb, const uint64_t *scalars, con
     }
     return DGPU_OK;
 }
+// The device-resident entry of a chunk (dock_bbs.hip: proofs of knowledge, whose segments' scalars are made on the device): T raw points on the device (`stride`
+// bytes apart, x then y, zero words an identity) and their canonical scalars d_sc, laid out over ns segments by `lay` (no multi-block segment: lay.pslots == 0).
+// Table, tree, device fold: the segments' normalised Jacobian results are left in sl.win, their identity flags in sl.win_inf, *d_bad |= a scalar >= 2^255.
+template <class C> int32_t ws_seg_resident(Slot &sl, size_t terms, size_t nseg, size_t blocks) {
+    int32_t rc;
+    typedef typename C::ACC A;
+    constexpr size_t W = SMALL_MSM_W, WIN_BYTES = std::max<size_t>(A::XW * 4, 4 * C::ABI_W * 4);
+    if ((rc = sl.flags.ensure(64))) return rc;
+    if ((rc = sl.prepped.ensure(terms * C::AFF_STRIDE * 4))) return rc;
+    if ((rc = sl.bucket.ensure(terms * SMALL_MSM_E * A::XW * 4))) return rc;
+    if ((rc = sl.bucket_inf.ensure(terms * SMALL_MSM_E))) return rc;
+    if ((rc = sl.entries.ensure(blocks * 64 * sizeof(SegDesc)))) return rc;
+    if ((rc = sl.l1.ensure(nseg * W * WIN_BYTES))) return rc;
+    if ((rc = sl.l1_inf.ensure(nseg * W))) return rc;
+    if ((rc = sl.win.ensure(nseg * 3 * C::ABI_W * 4))) return rc;
+    return sl.win_inf.ensure(nseg);
+}
+template <class C>
+int32_t seg_rows_resident(Slot &sl, const uint8_t *d_raw, size_t stride, const uint32_t *d_sc, size_t T, size_t ns, const SegLayout &lay, uint32_t *d_bad) {
+    hipStream_t s = sl.stream;
+    if (lay.pslots) return DGPU_E_BADARG;
+    HIPCHK(hipMemcpyAsync(sl.entries.p, lay.desc.data(), lay.blocks * 64 * sizeof(SegDesc), hipMemcpyHostToDevice, s));
+    {
+        StageTimer st(sl, "msm.prep_bases");
+        launch_prep_bases_raw<C>(s, d_raw, stride, 0, (size_t)C::ABI_W * 4, msm::NO_INF_OFF, nullptr, T, sl.prepped.as<uint32_t>());
+    }
+    {
+        StageTimer st(sl, "msm.small_table");
+        launch_small_table<C>(s, sl.prepped.as<uint32_t>(), T, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>());
+    }
+    {
+        StageTimer st(sl, "msm.seg_tree");
+        launch_seg_tree<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_sc, sl.entries.p, lay.blocks, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(),
+                           sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), false, d_bad);
+    }
+    {
+        StageTimer st(sl, "msm.seg_fold");
+        launch_seg_fold<C>(s, sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), ns, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
+    }
+    HIPCHK(hipGetLastError());
+    return DGPU_OK;
+}
 template <class C, class HF>
 int32_t msm_segments(const uint64_t *bases, const uint8_t *is_inf, const uint64_t *scalars, size_t N, const uint64_t *seg_end, size_t nseg, int mont, uint64_t *out, uint8_t *out_inf) {
     if (nseg == 0) return DGPU_OK;

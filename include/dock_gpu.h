@@ -675,6 +675,53 @@ int32_t dgpu_bbs_plus_verify_batch_g1(uint64_t params, size_t L, const uint64_t 
                                       const uint64_t *e /* n*4 */, const uint64_t *s /* n*4 */, const uint64_t *messages /* n rows */, size_t row_stride,
                                       size_t n, int32_t montgomery, const uint64_t random[4], int32_t *ok);
 
+/* ---- BBS+ proofs of knowledge in bulk: a verdict per proof, or one for all (crypto_amd/csrc/dock_bbs.hip, bbs_pok_kernels.hip.h) ----
+ * PoKOfSignatureG1Proof::verify (bbs_plus/src/proof.rs:529-611, schnorr_pok/src/discrete_log.rs:248-253) for n proofs under ONE key: what the verifier of
+ * presentations runs per credential shown.  It sees no e, s or hidden message, so the three calls above do not serve it.  params, pk_pc, g2_pc, montgomery,
+ * row_stride and the identity as all-zero words are as above; further
+ *   h_0          the second point of params again, 12 words (the caller has it; the driver need not read it back out of the prepared records)
+ *   points       n x 5 x 12 words: A', Abar, d, T1 (sc_resp_1.t), T2 of proof i at points + 60 i
+ *   resp_fixed   n x 4 scalars: z1, z2 (sc_resp_1.response1 / .response2, over A' and h_0), z3 (over d, for -r3), z4 (over h_0, for s')
+ *   values       n rows of L scalars, row i at values + 4 * row_stride * i: entry j is the revealed message m_ij, or the response z_ij of a hidden one.  A proof
+ *                with partial responses (sc_partial_resp_2 and missing_responses) needs no path of its own: the caller writes the missing responses into the row
+ *   revealed     n x L bytes, non-zero = revealed; every row carries its own pattern
+ *   challenge    n scalars
+ * The reference's four checks, with the second Schnorr check in row form over params: row i = (c_i, z4_i, y_i1 .. y_iL), y_ij = c_i m_ij where j is revealed and
+ * z_ij where it is hidden, P_i = <row_i, params>:
+ *     1  A'_i != O                                                                    else ZeroSignature
+ *     2  z1 A' + z2 h_0 - c (Abar - d) - T1 = O                                       else FirstSchnorrVerificationFailed
+ *     3  P_i + z3_i d_i - T2_i = O                                                    else SecondSchnorrVerificationFailed
+ *     4  e(A'_i, w) e(-Abar_i, g2) = 1                                                else PairingCheckFailed
+ *
+ * dgpu_bbs_plus_pok_verify_each_g1 writes status[i] = 0 (verified) or the number of the FIRST check that fails, in the order the reference returns its errors.
+ * Per chunk of rows one device pipeline: the rows and the own-point scalars (k_bbs_pok_rows, k_bbs_pok_own), P_i by the many-row MSM, the five-term sum of check 2
+ * and z3 d - T2 as two segments per row of the segmented small MSM over points staged on the device (k_bbs_pok_stage: -Abar is a flip of y there), the
+ * two-pair pairing check with the shared lines of w and g2, and k_bbs_pok_verdict; only the n status bytes come back.
+ *
+ * dgpu_bbs_plus_pok_verify_batch_g1: ONE verdict.  With rho = random (rho = 0 mod r: DGPU_E_BADARG, decided on the host) row i weighs check 2 with
+ * u_i = rho^(2i), check 3 with v_i = rho^(2i+1) and the pairing with t_i = rho^i; *ok = 1 iff no A'_i is the identity and
+ *     sum_k C_k H_k + sum_i [ u_i z1_i A'_i - u_i c_i Abar_i + (u_i c_i + v_i z3_i) d_i - u_i T1_i - v_i T2_i ] = O,
+ *         C_0 = sum v_i c_i,  C_1 = sum (u_i z2_i + v_i z4_i),  C_(j+1) = sum v_i y_ij,  H = the L + 2 points of params
+ *     e(sum t_i A'_i, w) e(-sum t_i Abar_i, g2) = 1
+ * — the C_k and every weight on the device (k_bbs_pok_col_sums, k_bbs_pok_col_finish: two passes, no atomics), one variable-base MSM over the chunk's 5 n own
+ * points and one each over the A' and the Abar, ONE MSM over params, one two-pair Miller loop and final exponentiation.  n = 0 gives *ok = 1.  For a random
+ * rho a batch with a failing proof passes with probability at most 3n / r per equation (the G1 equation is a polynomial of degree < 2n in rho, the pairing's of
+ * degree < n); rho = 1 adds the rows up unweighted, so errors that cancel between rows pass, as they would in the reference with that scalar.
+ *
+ * Both take the points as members of the prime-order subgroup, as the reference does after deserialising with validation: validate untrusted ones first
+ * (dgpu_g1_validate_batch).  n = 0 is DGPU_OK without touching a device or any pointer; with n > 0 a NULL pointer, row_stride < L, L = 0, n or row_stride
+ * >= 2^31 is DGPU_E_BADARG before the device is looked at; then DGPU_E_NODEVICE, then the handle.  Never DGPU_E_TOO_SMALL.  Chunks: each
+ * min(4096, 2^17 / (L + 2)) rows (below ~0.6 GB), batch min(65536, 2^20 / L); the development surface's dgpu_set_many_chunk_rows cuts both.  Nothing secret passes through.
+ * Stage timers bbs.pok_rows, bbs.pok_stage, bbs.pok_verdict, bbs.pok_columns beside bbs.lines .. bbs.final_exp and those of the MSMs. */
+int32_t dgpu_bbs_plus_pok_verify_each_g1(uint64_t params, size_t L, const uint64_t h_0[12], const uint64_t *pk_pc, const uint64_t *g2_pc,
+                                         const uint64_t *points /* n*60 */, const uint64_t *resp_fixed /* n*16 */, const uint64_t *values /* n rows */,
+                                         size_t row_stride, const uint8_t *revealed /* n*L */, const uint64_t *challenge /* n*4 */, size_t n,
+                                         int32_t montgomery, uint8_t *status /* n */);
+int32_t dgpu_bbs_plus_pok_verify_batch_g1(uint64_t params, size_t L, const uint64_t h_0[12], const uint64_t *pk_pc, const uint64_t *g2_pc,
+                                          const uint64_t *points /* n*60 */, const uint64_t *resp_fixed /* n*16 */, const uint64_t *values /* n rows */,
+                                          size_t row_stride, const uint8_t *revealed /* n*L */, const uint64_t *challenge /* n*4 */, size_t n,
+                                          int32_t montgomery, const uint64_t random[4], int32_t *ok);
+
 /* ---- the LegoGroth16 prover as one call ----
  * replaces create_proof_and_committed_witnesses_with_assignment (legogroth16/src/prover.rs:267-383, with calculate_coeff :585-594) and — when
  * the circuit is resident (r1cs != 0) — the QAP::witness_map call in front of it (create_proof_with_reduction, :153-180): the whole schedule

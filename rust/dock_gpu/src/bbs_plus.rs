@@ -3,21 +3,23 @@
 //!   `SignatureG1::new(rng, messages, sk, params)`, n times (bbs_plus/src/signature.rs:138-211)   -> `sign_many`, with the caller's `e_i`, `s_i` for the two draws
 //!   `sig.verify(messages, pk, params)`, n times (signature.rs:272-296)                            -> `verify_each`: one verdict per signature
 //!   the same through `RandomizedPairingChecker`                                                   -> `verify_batch`: one verdict for all
+//!   `proof.verify(revealed, challenge, pk, params)`, n times (bbs_plus/src/proof.rs:355-611)      -> `pok_verify_each`: the reference's first error per proof
+//!   the same with one verdict for all                                                             -> `pok_verify_batch`
 //!
 //! `GpuSignatureParams` keeps `[g1, h_0, h ..]` resident on the device and the prepared coefficients of `w` and `g2` beside it: one upload per issuer.
 //! Every function answers `None` when the library declines (no device, a bad argument), so that the caller stays on the arkworks path it replaced.
-//! NOT compiled in the build image (no Rust toolchain there); `tests/parity.rs` `bbs_plus_bulk_equals_the_reference` compares with the reference's own
-//! `new` / `verify`.
+//! NOT compiled in the build image (no Rust toolchain there); `tests/parity.rs` `bbs_plus_bulk_equals_the_reference` and
+//! `bbs_plus_pok_bulk_equals_the_reference` compare with the reference's own `new` / `verify` and `PoKOfSignatureG1Proof::verify`.
 use crate::ffi::*;
-use crate::host::{raw_bbs_plus_sign_many, raw_bbs_plus_verify_batch, raw_bbs_plus_verify_each};
+use crate::host::{raw_bbs_plus_pok_verify_batch, raw_bbs_plus_pok_verify_each, raw_bbs_plus_sign_many, raw_bbs_plus_verify_batch, raw_bbs_plus_verify_each};
 use crate::{g1_affine, pack_g1, pack_g2, ResidentG1, G2_PREPARED_WORDS};
 use ark_bls12_381::{Bls12_381, Fr, G1Affine};
 use ark_ec::AffineRepr;
-use ark_std::vec::Vec;
-use bbs_plus::prelude::{PublicKeyG2, SecretKey, SignatureG1, SignatureParamsG1};
+use ark_std::{collections::BTreeMap, vec::Vec};
+use bbs_plus::prelude::{BBSPlusError, PoKOfSignatureG1Proof, PublicKeyG2, SecretKey, SignatureG1, SignatureParamsG1};
 
 /// the parameters and the public key of one issuer on the device
-pub struct GpuSignatureParams { bases: ResidentG1, l: usize, pk_pc: Vec<u64>, g2_pc: Vec<u64> }
+pub struct GpuSignatureParams { bases: ResidentG1, l: usize, h_0: Vec<u64>, pk_pc: Vec<u64>, g2_pc: Vec<u64> }
 impl GpuSignatureParams {
     /// `None` for parameters without a message generator (`NoMessageToSign`), an identity `w` or `g2`, or when the library declines
     pub fn new(params: &SignatureParamsG1<Bls12_381>, pk: &PublicKeyG2<Bls12_381>) -> Option<Self> {
@@ -31,7 +33,7 @@ impl GpuSignatureParams {
         let g2_pc = co.split_off(G2_PREPARED_WORDS);
         let bases = ResidentG1::upload(&pts, None);              // a plain handle: the calls refuse a precomputed table
         if bases.handle() == 0 { return None; }
-        Some(GpuSignatureParams { bases, l, pk_pc: co, g2_pc })
+        Some(GpuSignatureParams { bases, l, h_0: pack_g1(&[params.h_0]).0, pk_pc: co, g2_pc })
     }
     pub fn supported_message_count(&self) -> usize { self.l }
 }
@@ -78,5 +80,76 @@ pub fn verify_batch(params: &GpuSignatureParams, sigs: &[SignatureG1<Bls12_381>]
     let (a, e, s) = split(sigs);
     let mut ok = 0i32;
     if raw_bbs_plus_verify_batch(params.bases.handle(), params.l, &params.pk_pc, &params.g2_pc, &a, &e, &s, &flat, random, &mut ok) != DGPU_OK { return None; }
+    Some(ok != 0)
+}
+
+// ---- proofs of knowledge of a signature -------------------------------------------------------------------------------------------------------------------
+/// the arrays of the C ABI for n proofs: the five points, (z1, z2, z3, z4), the rows of values (the revealed message, or the hidden one's response: from the
+/// proof's full response, or from its partial response completed by `missing[i]`, keyed by message index as `verify_partial` takes them) and the masks.
+/// `None` where the reference answers with an error that is not one of the four checks (a revealed index out of range, neither or both responses, a response
+/// that is missing or of another count).
+struct Packed { points: Vec<u64>, fixed: Vec<Fr>, values: Vec<Fr>, revealed: Vec<u8> }
+fn pack_proofs(l: usize, proofs: &[PoKOfSignatureG1Proof<Bls12_381>], revealed: &[&BTreeMap<usize, Fr>], missing: Option<&[&BTreeMap<usize, Fr>]>) -> Option<Packed> {
+    let n = proofs.len();
+    let (mut pts, mut fixed, mut values, mut mask) = (Vec::with_capacity(5 * n), Vec::with_capacity(4 * n), Vec::with_capacity(n * l), ark_std::vec![0u8; n * l]);
+    for (i, p) in proofs.iter().enumerate() {
+        let rev = revealed[i];
+        if rev.keys().any(|&j| j >= l) { return None; }
+        let hidden = l - rev.len();
+        // the responses of the second protocol in its own order: the hidden messages ascending, then -r3 (over d), then s' (over h_0)
+        let resp = |k: usize| -> Option<Fr> {
+            match (&p.sc_resp_2, &p.sc_partial_resp_2) {
+                (Some(full), None) => if missing.is_some() || full.0.len() != hidden + 2 { None } else { Some(full.0[k]) },
+                // (a partial response without missing responses is the reference's MissingResponsesNeededForPartialSchnorrProofVerification, proof.rs:594-596)
+                (None, Some(part)) => if missing.is_none() || part.total_responses != hidden + 2 { None } else { part.responses.get(&k).copied() },
+                _ => None,
+            }
+        };
+        pts.extend_from_slice(&[p.A_prime, p.A_bar, p.d, p.sc_resp_1.t, p.T2]);
+        fixed.extend_from_slice(&[p.sc_resp_1.response1, p.sc_resp_1.response2, resp(hidden)?, resp(hidden + 1)?]);
+        let mut k = 0;
+        for j in 0..l {
+            if let Some(m) = rev.get(&j) { values.push(*m); mask[i * l + j] = 1; continue; }
+            let given = missing.and_then(|ms| ms[i].get(&j).copied());
+            values.push(match given { Some(z) => z, None => resp(k)? });
+            k += 1;
+        }
+    }
+    Some(Packed { points: pack_g1(&pts).0, fixed, values, revealed: mask })      // identity: zero words
+}
+fn status_to_result(status: u8) -> Result<(), BBSPlusError> {
+    match status {
+        0 => Ok(()),
+        1 => Err(BBSPlusError::ZeroSignature),
+        2 => Err(BBSPlusError::FirstSchnorrVerificationFailed),
+        3 => Err(BBSPlusError::SecondSchnorrVerificationFailed),
+        _ => Err(BBSPlusError::PairingCheckFailed),
+    }
+}
+
+/// `proofs[i].verify(revealed[i], &challenges[i], pk, params)` for every i (`verify_partial` with `missing[i]` where given): `Ok(())` or the reference's first
+/// error among `ZeroSignature`, `FirstSchnorrVerificationFailed`, `SecondSchnorrVerificationFailed`, `PairingCheckFailed`.  The points are taken as validated,
+/// as the reference takes them.
+pub fn pok_verify_each(params: &GpuSignatureParams, proofs: &[PoKOfSignatureG1Proof<Bls12_381>], revealed: &[&BTreeMap<usize, Fr>], challenges: &[Fr],
+                       missing: Option<&[&BTreeMap<usize, Fr>]>) -> Option<Vec<Result<(), BBSPlusError>>> {
+    let n = proofs.len();
+    if revealed.len() != n || challenges.len() != n || missing.map_or(false, |m| m.len() != n) { return None; }
+    let pk = pack_proofs(params.l, proofs, revealed, missing)?;
+    let mut status = ark_std::vec![0u8; n];
+    if raw_bbs_plus_pok_verify_each(params.bases.handle(), params.l, &params.h_0, &params.pk_pc, &params.g2_pc, &pk.points, &pk.fixed, &pk.values, &pk.revealed, challenges, &mut status)
+        != DGPU_OK { return None; }
+    Some(status.into_iter().map(status_to_result).collect())
+}
+
+/// all of them at once: one G1 equation and one pairing check under the weights `random^(2i)` (first Schnorr check), `random^(2i+1)` (second) and `random^i`
+/// (pairing), `random` non-zero; no proofs at all verify.  A batch with a failing proof passes with probability at most 3n / r per equation.
+pub fn pok_verify_batch(params: &GpuSignatureParams, proofs: &[PoKOfSignatureG1Proof<Bls12_381>], revealed: &[&BTreeMap<usize, Fr>], challenges: &[Fr],
+                        missing: Option<&[&BTreeMap<usize, Fr>]>, random: &Fr) -> Option<bool> {
+    let n = proofs.len();
+    if revealed.len() != n || challenges.len() != n || missing.map_or(false, |m| m.len() != n) { return None; }
+    let pk = pack_proofs(params.l, proofs, revealed, missing)?;
+    let mut ok = 0i32;
+    if raw_bbs_plus_pok_verify_batch(params.bases.handle(), params.l, &params.h_0, &params.pk_pc, &params.g2_pc, &pk.points, &pk.fixed, &pk.values, &pk.revealed, challenges, random, &mut ok)
+        != DGPU_OK { return None; }
     Some(ok != 0)
 }

@@ -306,6 +306,20 @@ pub(crate) fn raw_bbs_plus_verify_batch(params: u64, l: usize, pk_pc: &[u64], g2
                                            e.len(), 1, random as *const Fr as *const u64, ok) }
 }
 
+/// `PoKOfSignatureG1Proof::verify` per proof: `status[i]` = 0, or the first failing check (1 ZeroSignature, 2 / 3 the Schnorr checks, 4 the pairing).  `h_0`: 12
+/// words; `points`: n x 5 x 12 words (A', Abar, d, T1, T2); `resp_fixed`: n x 4 (z1, z2, z3, z4); `values`: n rows of `l`, packed; `revealed`: n x l bytes
+pub(crate) fn raw_bbs_plus_pok_verify_each(params: u64, l: usize, h_0: &[u64], pk_pc: &[u64], g2_pc: &[u64], points: &[u64], resp_fixed: &[Fr], values: &[Fr], revealed: &[u8],
+                                           challenge: &[Fr], status: &mut [u8]) -> i32 {
+    unsafe { dgpu_bbs_plus_pok_verify_each_g1(params, l, h_0.as_ptr(), pk_pc.as_ptr(), g2_pc.as_ptr(), points.as_ptr(), resp_fixed.as_ptr() as *const u64, values.as_ptr() as *const u64, l,
+                                              revealed.as_ptr(), challenge.as_ptr() as *const u64, challenge.len(), 1, status.as_mut_ptr()) }
+}
+/// one verdict for all proofs under the weights `random^(2i)`, `random^(2i+1)`, `random^i`
+pub(crate) fn raw_bbs_plus_pok_verify_batch(params: u64, l: usize, h_0: &[u64], pk_pc: &[u64], g2_pc: &[u64], points: &[u64], resp_fixed: &[Fr], values: &[Fr], revealed: &[u8],
+                                            challenge: &[Fr], random: &Fr, ok: &mut i32) -> i32 {
+    unsafe { dgpu_bbs_plus_pok_verify_batch_g1(params, l, h_0.as_ptr(), pk_pc.as_ptr(), g2_pc.as_ptr(), points.as_ptr(), resp_fixed.as_ptr() as *const u64, values.as_ptr() as *const u64, l,
+                                               revealed.as_ptr(), challenge.as_ptr() as *const u64, challenge.len(), 1, random as *const Fr as *const u64, ok) }
+}
+
 // ---- R1CS -> QAP witness map (legogroth16/src/r1cs_to_qap.rs:150-210) ---------------------------------------------------------------------------------
 /// one constraint matrix of ark-relations' `ConstraintMatrices` (`Matrix<F> = Vec<Vec<(F, usize)>>`) as the CSR arrays the ABI takes, with a 64-bit hash of
 /// its whole contents computed on the way (the copy reads every coefficient anyway)

@@ -757,3 +757,55 @@ fn bbs_plus_bulk_equals_the_reference() {
         assert_eq!(verify_batch(&gp, &bad, &bad_rows, &rho), Some(false));
     }
 }
+
+// BBS+ proofs of knowledge in bulk against the reference's own PoKOfSignatureG1Proof::verify (bbs_plus/src/proof.rs:355-611): the same Ok / first error, proof by proof
+#[cfg(feature = "bbs-plus")]
+#[test]
+fn bbs_plus_pok_bulk_equals_the_reference() {
+    use bbs_plus::prelude::{KeypairG2, MessageOrBlinding, PoKOfSignatureG1Proof, PoKOfSignatureG1Protocol, SignatureG1, SignatureParamsG1};
+    use dock_gpu::bbs_plus::{pok_verify_batch, pok_verify_each, GpuSignatureParams};
+    use std::collections::{BTreeMap, BTreeSet};
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5EED0B0C);
+    for &(l, n) in &[(1usize, 3usize), (5, 65), (30, 257)] {
+        let params = SignatureParamsG1::<Bls12_381>::generate_using_rng(&mut rng, l as u32);
+        let keypair = KeypairG2::<Bls12_381>::generate_using_rng(&mut rng, &params);
+        let gp = GpuSignatureParams::new(&params, &keypair.public_key).expect("parameters");
+        let (mut proofs, mut revealed, mut challenges): (Vec<PoKOfSignatureG1Proof<Bls12_381>>, Vec<BTreeMap<usize, Fr>>, Vec<Fr>) = (vec![], vec![], vec![]);
+        for i in 0..n {
+            let msgs = frs(&mut rng, l);
+            let sig = SignatureG1::new(&mut rng, &msgs, &keypair.secret_key, &params).unwrap();
+            // every proof its own pattern: nothing revealed, everything, every (i % 5 + 2)-th message
+            let ids: BTreeSet<usize> = match i % 3 { 0 => BTreeSet::new(), 1 => (0..l).collect(), _ => (0..l).filter(|j| j % (i % 5 + 2) == 0).collect() };
+            let protocol = PoKOfSignatureG1Protocol::init(&mut rng, &sig, &params,
+                msgs.iter().enumerate().map(|(j, m)| if ids.contains(&j) { MessageOrBlinding::RevealMessage(m) } else { MessageOrBlinding::BlindMessageRandomly(m) })).unwrap();
+            let c = Fr::rand(&mut rng);
+            proofs.push(protocol.gen_proof(&c).unwrap());
+            revealed.push(ids.iter().map(|&j| (j, msgs[j])).collect());
+            challenges.push(c);
+        }
+        let maps: Vec<&BTreeMap<usize, Fr>> = revealed.iter().collect();
+        let all = pok_verify_each(&gp, &proofs, &maps, &challenges, None).expect("pok_verify_each");
+        assert!(all.iter().all(|r| r.is_ok()), "l = {l}");
+        let rho = Fr::rand(&mut rng);
+        assert_eq!(pok_verify_batch(&gp, &proofs, &maps, &challenges, None, &rho), Some(true));
+        // one tamper of every kind the reference tells apart, and the reference's verdict beside ours
+        let mut bad = proofs.clone();
+        let mut bad_c = challenges.clone();
+        bad[0].sc_resp_1.response1 += Fr::from(1u64);
+        if n > 4 {
+            bad[1].T2 = bad[2].T2;
+            bad[2].A_prime = G1Affine::zero();
+            let (a, b) = (bad[3].A_prime, bad[3].A_bar);
+            bad[3].A_bar = (b + a).into_affine();
+            bad_c[4] += Fr::from(1u64);
+        }
+        let mine = pok_verify_each(&gp, &bad, &maps, &bad_c, None).expect("pok_verify_each");
+        for i in 0..n {
+            let theirs = bad[i].verify(&revealed[i], &bad_c[i], keypair.public_key.clone(), params.clone());
+            assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "l = {l}, proof {i}");
+        }
+        assert!(mine[0].is_err());
+        assert_eq!(pok_verify_batch(&gp, &bad, &maps, &bad_c, None, &rho), Some(false));
+    }
+}
