@@ -7,7 +7,6 @@
 //   host    the GLV split of every f_i (the caller gets f anyway: 64 bytes per holder come back)
 //   device  T_i = g_i V from a window table of V (k_fb_mul), C_i' = T_i + f_i C_i (k_g1_scale_quad with T as the addend)
 // The device copy of the tables is zeroed before the slot is released; nothing of a call is kept.
-#include <chrono>
 #include "msm_many.hip.h"
 #include "qap_launch.hip.h"
 #include "fixed_launch.hip.h"
@@ -18,7 +17,7 @@ using namespace acch;
 
 namespace {
 
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+constexpr size_t PT = 96;                 // bytes of an affine G1 point of the ABI
 
 bool bad_sizes(size_t na, size_t nr, size_t m) { return m >= (1ull << 31) || na >= (1ull << 31) || nr >= (1ull << 31) || na + nr >= (1ull << 31); }
 
@@ -95,15 +94,14 @@ int32_t update_witnesses(const uint64_t *additions, size_t na, const uint64_t *r
     SLOT_ACQUIRE(L, sl);
     HIPCHK(hipSetDevice(cur().device));
     if ((rc = factors_on_slot(sl, t, na, nr, elements, m, mont, fg))) { if (gs.prof) prof_flush(sl); return rc; }
-    const size_t pt = 96;
     // in_bases: [witnesses | T], in_inf: T's identity flags, in_scalars: the split f, prepped: [out | out_inf]
-    if ((rc = sl.in_bases.ensure(2 * m * pt))) return rc;
+    if ((rc = sl.in_bases.ensure(2 * m * PT))) return rc;
     if ((rc = sl.in_inf.ensure(m))) return rc;
     if ((rc = sl.in_scalars.ensure(m * 32))) return rc;
-    if ((rc = sl.prepped.ensure(m * pt + m))) return rc;
+    if ((rc = sl.prepped.ensure(m * PT + m))) return rc;
     hipStream_t s = sl.stream;
-    uint8_t *dC = sl.in_bases.as<uint8_t>(), *dT = dC + m * pt, *dTinf = sl.in_inf.as<uint8_t>(), *dout_inf = sl.prepped.as<uint8_t>() + m * pt;
-    HIPCHK(hipMemcpyAsync(dC, witnesses, m * pt, hipMemcpyHostToDevice, s));
+    uint8_t *dC = sl.in_bases.as<uint8_t>(), *dT = dC + m * PT, *dTinf = sl.in_inf.as<uint8_t>(), *dout_inf = sl.prepped.as<uint8_t>() + m * PT;
+    HIPCHK(hipMemcpyAsync(dC, witnesses, m * PT, hipMemcpyHostToDevice, s));
     { StageTimer st(sl, "acc.table_mul");          // runs under the host's split of f
       msm::launch_fb_mul<msm::G1>(s, (const uint32_t *)tref.h.p, sl.q[3].as<uint32_t>() + m * 8, m, (uint32_t *)dT, dTinf); }
     HIPCHK(hipGetLastError());
@@ -121,7 +119,7 @@ int32_t update_witnesses(const uint64_t *additions, size_t na, const uint64_t *r
     { StageTimer st(sl, "acc.scale");
       msm::launch_g1_scale_quad(s, (const uint32_t *)dC, nullptr, sl.in_scalars.as<uint32_t>(), 8, nullptr, m, sl.prepped.as<uint32_t>(), dout_inf, (const uint32_t *)dT, dTinf); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, sl.prepped.p, m * pt, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, sl.prepped.p, m * PT, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out_inf, dout_inf, m, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (gs.prof) prof_flush(sl);
@@ -160,7 +158,7 @@ int32_t omega_g1(const uint64_t *additions, size_t na, const uint64_t *removals,
     HIPCHK(hipSetDevice(cur().device));
     NttDomain dom;
     if (logn >= 2 && (rc = get_domain(sl, logn, dom))) return rc;
-    const size_t ne = acck::acc_table_entries(na, nr), words_b = (ne * 32 + 255) & ~(size_t)255, tab_b = (ne * 40 + 255) & ~(size_t)255, esz = ntt::FR_WORDS * 4, pt = 96;
+    const size_t ne = acck::acc_table_entries(na, nr), words_b = (ne * 32 + 255) & ~(size_t)255, tab_b = (ne * 40 + 255) & ~(size_t)255, esz = ntt::FR_WORDS * 4;
     const acck::AccShape sh = acck::acc_shape(N, na, nr, gs.acc_split.load());
     gs.acc_last_split = (int)sh.K;
     // q[0]: the tables (words | internal form), q[1]: chunk results, q[3]: the coefficients, q[5]: the constants, q[6]: the roots, q[7]: the evaluations,
@@ -175,13 +173,11 @@ int32_t omega_g1(const uint64_t *additions, size_t na, const uint64_t *removals,
         if ((e = o.q[7].ensure(N * esz))) return e;
         if ((e = o.q[8].ensure(L))) return e;
         if ((e = o.q[9].ensure(window_table_g1_bytes()))) return e;
-        if ((e = o.q[10].ensure(L * pt + L))) return e;
+        if ((e = o.q[10].ensure(L * PT + L))) return e;
         if ((e = o.prepped.ensure(32 * G1::AFF_STRIDE * 4))) return e;                  // (the window table's scratch)
         return o.in_bases.ensure(32 * 2 * G1::ABI_W * 4 + 16);
     };
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws(sl))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
     std::vector<uint64_t> window_bases;                       // (host words of the table's upload: they live until the call's synchronisation)
     std::vector<uint8_t> nz(L);
@@ -190,7 +186,7 @@ int32_t omega_g1(const uint64_t *additions, size_t na, const uint64_t *removals,
     DeviceWipe dw(sl);
     dw.add(sl.q[0].p, words_b + tab_b); dw.add(sl.q[1].p, acck::acc_part_bytes(N, sh)); dw.add(sl.q[7].p, N * esz); dw.add(sl.q[3].p, L * 32); dw.add(sl.q[8].p, L);
     uint32_t *d_words = sl.q[0].as<uint32_t>(), *d_tab = (uint32_t *)(sl.q[0].as<uint8_t>() + words_b), *d_c = sl.q[5].as<uint32_t>(), *d_ev = sl.q[7].as<uint32_t>();
-    uint8_t *d_out = sl.q[10].as<uint8_t>(), *d_inf = d_out + L * pt;
+    uint8_t *d_out = sl.q[10].as<uint8_t>(), *d_inf = d_out + L * PT;
     HIPCHK(hipMemcpyAsync(d_words, t.w.data(), ne * 32, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_c, consts, sizeof consts, hipMemcpyHostToDevice, s));
     { StageTimer st(sl, "acc.prep"); acck::launch_acc_prep(s, d_words, ne, d_tab); ntt::launch_fr_powers(s, d_c, d_c + 8, N, sl.q[6].as<uint32_t>()); }
@@ -200,7 +196,7 @@ int32_t omega_g1(const uint64_t *additions, size_t na, const uint64_t *removals,
       acck::launch_acc_omega_coeffs(s, d_ev, logn, (const uint32_t *)consts[2], L, sl.q[3].as<uint32_t>(), sl.q[8].as<uint8_t>()); }
     { StageTimer st(sl, "acc.omega_mul"); msm::launch_fb_mul<msm::G1>(s, sl.q[9].as<uint32_t>(), sl.q[3].as<uint32_t>(), L, (uint32_t *)d_out, d_inf); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_out, L * pt, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, d_out, L * PT, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out_inf, d_inf, L, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(nz.data(), sl.q[8].p, L, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -208,7 +204,7 @@ int32_t omega_g1(const uint64_t *additions, size_t na, const uint64_t *removals,
     if (gs.prof) prof_flush(sl);
     // ark-poly drops trailing zero coefficients; a zero coefficient below the last non-zero one, and every entry of an identity accumulator, is an identity
     size_t len = L; while (len && !nz[len - 1]) len--;
-    for (size_t j = 0; j < L; j++) if (j >= len || !nz[j] || out_inf[j]) { memset(out + 12 * j, 0, pt); out_inf[j] = 1; }
+    for (size_t j = 0; j < L; j++) if (j >= len || !nz[j] || out_inf[j]) { memset(out + 12 * j, 0, PT); out_inf[j] = 1; }
     *out_len = len;
     return DGPU_OK;
 }
@@ -216,14 +212,14 @@ int32_t omega_g1(const uint64_t *additions, size_t na, const uint64_t *removals,
 // The holders' half, m times Witness::compute_update_using_public_info_after_batch_updates (witness.rs:292-314) with Omega::evaluate (batch_utils.rs:664-691):
 //   device  f_i = d_A(y_i) / d_D(y_i), s_i = 1 / d_D(y_i)                                  k_acc_prep, k_acc_pub_factors [, k_acc_pub_combine]
 //   device  row i = [s_i, s_i y_i, ..] straight into the many-row MSM's scalar buffer      k_acc_pub_rows
-//   device  T_i = <row_i, omega> over the small-path table of omega                        k_many_tree, k_many_fold (msm_many.hip.h many_rows_resident)
+//   device  T_i = <row_i, omega> over the small-path table of omega                        k_many_tree, k_many_fold (msm_many.hip.h RowMsm)
 //   host    the GLV split of every f_i, under the MSM
 //   device  C_i' = T_i + f_i C_i                                                           k_g1_scale_quad
 // omega's prepared records and their table live in the slot's workspace for the call (no handle, so nothing to free and no allocation in steady state).  Beyond
 // the many-row kernels' reach a row runs through the single-row driver with its scalars where k_acc_pub_rows left them.
 int32_t public_on_slot(Slot &sl, const uint64_t *additions, size_t na, const uint64_t *removals, size_t nr, const uint64_t *omega, const uint8_t *oinf, size_t n,
                        const uint64_t *elements, const uint64_t *witnesses, size_t m, bool mont, uint64_t *d_factors, uint64_t *out, uint8_t *out_inf, uint8_t *ok) {
-    const size_t pt = 96, nl = na + nr, words_b = (std::max<size_t>(nl, 1) * 32 + 255) & ~(size_t)255, lists_b = (std::max<size_t>(nl, 1) * 40 + 255) & ~(size_t)255;
+    const size_t nl = na + nr, words_b = (std::max<size_t>(nl, 1) * 32 + 255) & ~(size_t)255, lists_b = (std::max<size_t>(nl, 1) * 40 + 255) & ~(size_t)255;
     const size_t reach = std::min<size_t>(SMALL_MSM_MAX_N, gs.small_max.load());
     const bool many = n && n <= reach;
     const acck::AccShape sh = acck::acc_shape(m, na, nr, gs.acc_split.load());
@@ -232,8 +228,7 @@ int32_t public_on_slot(Slot &sl, const uint64_t *additions, size_t na, const uin
     // q[0]: the lists (words | internal form), q[1]: chunk results, q[2]: scratch slots, q[3]: f | s, q[4]: the elements, q[5]: the split f, q[6]: [witnesses | T],
     // q[7]: [out | out_inf], q[8]: [T's identity flags | ok], q[9]: omega's prepared records, q[10]: their small-path table
     const RawBases rb = RawBases::packed<G1>(omega, oinf);
-    const ManyGeom geom = many_geometry(std::max<size_t>(n, 1));
-    const size_t chunk = !n ? m : many ? std::min(m, many_chunk_rows(n)) : std::min(m, std::max<size_t>(1, ((size_t)1 << 21) / n));      // rows per launch / per 64 MB of scalars
+    RowMsm<G1> tm(many, n, m, ~(size_t)0);                       // the T_i: omega's records are staged into q[9], their table (many) is built in q[10]
     auto ws = [&](Slot &o) -> int32_t {
         int32_t e;
         if ((e = o.q[0].ensure(words_b + lists_b))) return e;
@@ -242,29 +237,25 @@ int32_t public_on_slot(Slot &sl, const uint64_t *additions, size_t na, const uin
         if ((e = o.q[3].ensure(2 * m * 32))) return e;
         if ((e = o.q[4].ensure(m * 32))) return e;
         if ((e = o.q[5].ensure(m * 32))) return e;
-        if ((e = o.q[6].ensure(2 * m * pt))) return e;
-        if ((e = o.q[7].ensure(m * pt + m))) return e;
+        if ((e = o.q[6].ensure(2 * m * PT))) return e;
+        if ((e = o.q[7].ensure(m * PT + m))) return e;
         if ((e = o.q[8].ensure(2 * m))) return e;
         if ((e = o.q[9].ensure(std::max<size_t>(n, 1) * G1::AFF_STRIDE * 4))) return e;
         if (!n) return DGPU_OK;
         if ((e = ws_stage_bases<G1>(o, rb, n))) return e;
-        if (many) { if ((e = o.q[10].ensure(small_sub_bytes<G1>(n)))) return e; return ws_many<G1>(o, n, chunk, geom); }
-        if ((e = ws_for<G1>(o, 2, n, 0, nullptr))) return e;
-        if ((e = o.in_scalars.ensure(chunk * n * 32))) return e;
-        return o.flags.ensure(64);
+        if (many && (e = o.q[10].ensure(small_sub_bytes<G1>(n)))) return e;
+        return tm.workspace(o);
     };
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws(sl))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
-    std::vector<uint64_t> f_host(m * 4), split(m * 4), jac; std::vector<uint8_t> tinf;      // targets and sources of asynchronous copies ...
+    std::vector<uint64_t> f_host(m * 4), split(m * 4);                                        // targets and sources of asynchronous copies ...
     DrainUnlessDone guard(sl);                                                                // ... so an early return waits for them
     uint32_t *d_words = sl.q[0].as<uint32_t>(), *d_lists = (uint32_t *)(sl.q[0].as<uint8_t>() + words_b), *d_fs = sl.q[3].as<uint32_t>(), *d_el = sl.q[4].as<uint32_t>();
-    uint8_t *dC = sl.q[6].as<uint8_t>(), *dT = dC + m * pt, *dTinf = sl.q[8].as<uint8_t>(), *d_ok = dTinf + m, *dout_inf = sl.q[7].as<uint8_t>() + m * pt;
+    uint8_t *dC = sl.q[6].as<uint8_t>(), *dT = dC + m * PT, *dTinf = sl.q[8].as<uint8_t>(), *d_ok = dTinf + m, *dout_inf = sl.q[7].as<uint8_t>() + m * PT;
     if (na) HIPCHK(hipMemcpyAsync(d_words, additions, na * 32, hipMemcpyHostToDevice, s));
     if (nr) HIPCHK(hipMemcpyAsync(d_words + na * 8, removals, nr * 32, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_el, elements, m * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dC, witnesses, m * pt, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dC, witnesses, m * PT, hipMemcpyHostToDevice, s));
     if (nl) { StageTimer st(sl, "acc.prep"); acck::launch_acc_prep(s, d_words, nl, d_lists, mont ? 1 : 0); }
     { StageTimer st(sl, "acc.pub_factors");
       acck::launch_acc_pub_factors(s, d_lists, na, nr, d_el, mont ? 1 : 0, m, sh, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), d_fs, d_ok); }
@@ -281,39 +272,16 @@ int32_t public_on_slot(Slot &sl, const uint64_t *additions, size_t na, const uin
         uint32_t *d_rec = sl.q[9].as<uint32_t>(), *d_rows = sl.in_scalars.as<uint32_t>(), *d_bad = sl.flags.as<uint32_t>();
         if ((rc = stage_bases<G1>(sl, rb, n, d_rec))) return rc;
         HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));                  // (rows are canonical: the flag stays clear)
-        SmallSub sub{nullptr, nullptr};
+        tm.rec = d_rec;
         if (many) {
-            sub = SmallSub{sl.q[10].as<uint32_t>(), sl.q[10].as<uint8_t>() + small_sub_tab_bytes<G1>(n)};
+            tm.sub = SmallSub{sl.q[10].as<uint32_t>(), sl.q[10].as<uint8_t>() + small_sub_tab_bytes<G1>(n)};
             StageTimer st(sl, "msm.small_subtable");
             launch_small_subtable<G1>(s, d_rec, n, sl.q[10].as<uint32_t>(), sl.q[10].as<uint8_t>() + small_sub_tab_bytes<G1>(n));
         }
-        for (size_t r0 = 0; r0 < m; r0 += chunk) {
-            const size_t rows = std::min(chunk, m - r0);
+        for (size_t r0 = 0; r0 < m; r0 += tm.chunk) {
+            const size_t rows = std::min(tm.chunk, m - r0);
             { StageTimer st(sl, "acc.pub_rows"); acck::launch_acc_pub_rows(s, d_el + r0 * 8, mont ? 1 : 0, d_fs + (m + r0) * 8, rows, n, d_rows); }
-            if (many) {
-                if ((rc = many_rows_resident<G1>(sl, sub, d_rows, n, rows, geom, d_bad))) return rc;
-                // the normalised Jacobian rows (X, Y, 1) -> the affine addends: X and Y of every row, and its identity flag
-                HIPCHK(hipMemcpy2DAsync(dT + r0 * pt, pt, sl.win.p, 3 * pt / 2, pt, rows, hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(dTinf + r0, sl.win_inf.p, rows, hipMemcpyDeviceToDevice, s));
-                continue;
-            }
-            // the single-row driver, row by row; its Jacobian results are normalised on the host
-            HIPCHK(hipGetLastError());
-            jac.resize(rows * 18); tinf.resize(rows);
-            for (size_t i = 0; i < rows; i++)
-                if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_rows + i * n * 8, n, jac.data() + 18 * i))) return rc;
-            for (size_t i = 0; i < rows; i++) {
-                uint64_t *p = jac.data() + 18 * i;
-                tinf[i] = jac_is_identity(p, 18);
-                if (tinf[i]) { memset(p, 0, pt); continue; }
-                hostf::Fq x, y, z; memcpy(&x, p, 48); memcpy(&y, p + 6, 48); memcpy(&z, p + 12, 48);
-                const hostf::Fq zi = z.inv(), zi2 = zi * zi;
-                x = x * zi2; y = y * zi2 * zi;
-                memcpy(jac.data() + 12 * i, &x, 48); memcpy(jac.data() + 12 * i + 6, &y, 48);      // (packed in place: 12 i + 12 <= 18 i)
-            }
-            HIPCHK(hipMemcpyAsync(dT + r0 * pt, jac.data(), rows * pt, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(dTinf + r0, tinf.data(), rows, hipMemcpyHostToDevice, s));
-            HIPCHK(hipStreamSynchronize(s));                     // (the next chunk reuses the host vectors)
+            if ((rc = tm.points(sl, d_rows, rows, d_bad, dT + r0 * PT, dTinf + r0))) return rc;
         }
     }
     HIPCHK(hipEventSynchronize(have_f));
@@ -330,14 +298,14 @@ int32_t public_on_slot(Slot &sl, const uint64_t *additions, size_t na, const uin
     { StageTimer st(sl, "acc.scale");
       msm::launch_g1_scale_quad(s, (const uint32_t *)dC, nullptr, sl.q[5].as<uint32_t>(), 8, nullptr, m, sl.q[7].as<uint32_t>(), dout_inf, (const uint32_t *)dT, dTinf); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, sl.q[7].p, m * pt, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, sl.q[7].p, m * PT, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out_inf, dout_inf, m, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     guard.done = true;
     // a zero d_D is the reference's Err(CannotBeZero) for that holder alone: ok = 0, a zero factor, the identity
     for (size_t i = 0; i < m; i++) {
         if (!ok[i]) { memset(f_host.data() + 4 * i, 0, 32); out_inf[i] = 1; }
-        if (out_inf[i]) memset(out + 12 * i, 0, pt);
+        if (out_inf[i]) memset(out + 12 * i, 0, PT);
     }
     factors_out(f_host.data(), m, mont, d_factors);
     return DGPU_OK;
@@ -388,9 +356,7 @@ int32_t d_on_slot(Slot &sl, const uint64_t *members, const uint32_t *resident, s
         return o.q[8].ensure(m);
     };
     int32_t rc;
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws(sl))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
     DrainUnlessDone guard(sl);
     uint32_t *d_words = sl.q[0].as<uint32_t>(), *d_tab = (uint32_t *)(sl.q[0].as<uint8_t>() + words_b), *d_el = sl.q[4].as<uint32_t>();
@@ -452,7 +418,6 @@ int32_t issue_witnesses(bool with_d, const uint64_t *d, const uint64_t *ys, size
     if (gs.prof) prof_add_host("acc.host_inverses", ms_since(t0));
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    const size_t pt = 96;
     // q[0]: t, q[3]: the scalars, q[4]: d, q[8]: the zero-d flags, q[9]: the window table of B, q[10]: [s_i B | identity flags]
     auto ws = [&](Slot &o) -> int32_t {
         int32_t e;
@@ -461,13 +426,11 @@ int32_t issue_witnesses(bool with_d, const uint64_t *d, const uint64_t *ys, size
         if ((e = o.q[4].ensure(m * 32))) return e;
         if ((e = o.q[8].ensure(m))) return e;
         if ((e = o.q[9].ensure(window_table_g1_bytes()))) return e;
-        if ((e = o.q[10].ensure(m * pt + m))) return e;
+        if ((e = o.q[10].ensure(m * PT + m))) return e;
         if ((e = o.prepped.ensure(32 * G1::AFF_STRIDE * 4))) return e;                  // (the window table's scratch)
         return o.in_bases.ensure(32 * 2 * G1::ABI_W * 4 + 16);
     };
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws(sl))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
     std::vector<uint64_t> window_bases;                       // (host words of the table's upload: they live until the call's synchronisation)
     std::vector<uint8_t> zero(m);
@@ -475,14 +438,14 @@ int32_t issue_witnesses(bool with_d, const uint64_t *d, const uint64_t *ys, size
     DeviceWipe dw(sl);
     dw.add(sl.q[0].p, m * 32); dw.add(sl.q[3].p, m * 32); dw.add(sl.q[9].p, window_table_g1_bytes());
     if ((rc = window_table_g1_on_slot(sl, base, sl.q[9].p, window_bases))) return rc;
-    uint8_t *d_out = sl.q[10].as<uint8_t>(), *d_inf = d_out + m * pt;
+    uint8_t *d_out = sl.q[10].as<uint8_t>(), *d_inf = d_out + m * PT;
     HIPCHK(hipMemcpyAsync(sl.q[0].p, t.w.data(), m * 32, hipMemcpyHostToDevice, s));
     if (with_d) HIPCHK(hipMemcpyAsync(sl.q[4].p, d, m * 32, hipMemcpyHostToDevice, s));
     { StageTimer st(sl, "acc.issue_scalars");
       acck::launch_acc_issue_scalars(s, with_d ? sl.q[4].as<uint32_t>() : nullptr, sl.q[0].as<uint32_t>(), (const uint32_t *)f_V, mont ? 1 : 0, m, sl.q[3].as<uint32_t>(), sl.q[8].as<uint8_t>()); }
     { StageTimer st(sl, "acc.table_mul"); msm::launch_fb_mul<msm::G1>(s, sl.q[9].as<uint32_t>(), sl.q[3].as<uint32_t>(), m, (uint32_t *)d_out, d_inf); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_out, m * pt, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, d_out, m * PT, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out_inf, d_inf, m, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(zero.data(), sl.q[8].p, m, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -491,7 +454,7 @@ int32_t issue_witnesses(bool with_d, const uint64_t *d, const uint64_t *ys, size
     // a zero d is the reference's Err(CannotBeZero) for that entry alone: ok = 0 and the identity; an identity (a zero scalar, an identity base) is zero words
     for (size_t i = 0; i < m; i++) {
         if (with_d) ok[i] = zero[i] ? 0 : 1;
-        if (zero[i] || out_inf[i]) { memset(out + 12 * i, 0, pt); out_inf[i] = 1; }
+        if (zero[i] || out_inf[i]) { memset(out + 12 * i, 0, PT); out_inf[i] = 1; }
     }
     return DGPU_OK;
 }

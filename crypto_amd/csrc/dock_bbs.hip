@@ -26,7 +26,6 @@
 //              device  e(sum rho^i A'_i, w) e(-sum rho^i Abar_i, g2) against one
 // Only verdict bytes (each, batch) or the signatures (sign) come back.  The device copies of the inverses and of the rows that carry them are zeroed on every return
 // path before the slot is released, the host copy too.
-#include <chrono>
 #include "msm_many.hip.h"
 #include "qap_launch.hip.h"
 #include "fixed_launch.hip.h"
@@ -41,7 +40,6 @@ using namespace mlk;
 
 namespace {
 
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 bool zero_words(const uint64_t *w, int k) { uint64_t o = 0; for (int i = 0; i < k; i++) o |= w[i]; return o == 0; }
 
 constexpr size_t PT = 96;                 // bytes of an affine G1 point of the ABI
@@ -59,62 +57,19 @@ bool bad_rows(const Rows &r) {
 // the parameters: a plain G1 bases handle of exactly L + 2 points, pinned for the call
 bool params_ok(const HandleRef &hb, size_t L) { return hb.ok && hb.h.kind == 1 && hb.h.n == L + 2; }
 
-// How the b_i of a chunk are made: the many-row kernels over the handle's small-path table, or (rows beyond their reach, dgpu_set_small_msm_max(0), no memory for the
-// table) the single-row driver row by row, normalised on the host.
-struct BPath {
-    bool many; SmallSub sub; ManyGeom geom; const uint32_t *rec; size_t nn, chunk;
-    int32_t workspace(Slot &o) const {
-        if (many) return ws_many<G1>(o, nn, chunk, geom);
-        int32_t e;
-        if ((e = ws_for<G1>(o, 2, nn, 0, nullptr))) return e;
-        if ((e = o.in_scalars.ensure(chunk * nn * 32))) return e;
-        return o.flags.ensure(64);
-    }
-};
-int32_t b_path(Slot &sl, uint64_t params, const Handle &h, size_t nn, size_t cap, size_t n, BPath &bp) {
-    bp.nn = nn; bp.rec = (const uint32_t *)h.p; bp.geom = many_geometry(nn);
-    bp.many = h.n <= SMALL_MSM_MAX_N && nn <= gs.small_max.load() && small_sub_for<G1>(sl, params, h, 0, nn, bp.sub, true);
-    const size_t per = bp.many ? many_chunk_rows(nn) : std::max<size_t>(1, ((size_t)1 << 21) / nn);      // rows per launch / per 64 MB of scalars
-    bp.chunk = std::min(n, std::min(per, cap));
-    return DGPU_OK;
-}
-// the rows at d_rows (canonical words, packed) -> dB (affine words; an identity: zero words) and dBinf.  The host vectors are the slow path's and live until the
-// caller's next synchronisation.
-int32_t b_points(Slot &sl, const BPath &bp, const uint32_t *d_rows, size_t rows, uint32_t *d_bad, uint8_t *dB, uint8_t *dBinf, std::vector<uint64_t> &jac, std::vector<uint8_t> &binf) {
-    hipStream_t s = sl.stream;
-    int32_t rc;
-    if (bp.many) {
-        if ((rc = many_rows_resident<G1>(sl, bp.sub, d_rows, bp.nn, rows, bp.geom, d_bad))) return rc;
-        // the normalised Jacobian rows (X, Y, 1) -> X and Y of every row, and its identity flag
-        HIPCHK(hipMemcpy2DAsync(dB, PT, sl.win.p, 3 * PT / 2, PT, rows, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(dBinf, sl.win_inf.p, rows, hipMemcpyDeviceToDevice, s));
-        return DGPU_OK;
-    }
-    HIPCHK(hipGetLastError());
-    jac.resize(rows * 18); binf.resize(rows);
-    for (size_t i = 0; i < rows; i++)
-        if ((rc = msm_device<G1, hostf::Fq>(sl, bp.rec, d_rows + i * bp.nn * 8, bp.nn, jac.data() + 18 * i))) return rc;
-    for (size_t i = 0; i < rows; i++) {
-        uint64_t *p = jac.data() + 18 * i;
-        binf[i] = jac_is_identity(p, 18);
-        if (binf[i]) { memset(jac.data() + 12 * i, 0, PT); continue; }
-        hostf::Fq x, y, z; memcpy(&x, p, 48); memcpy(&y, p + 6, 48); memcpy(&z, p + 12, 48);
-        const hostf::Fq zi = z.inv(), zi2 = zi * zi;
-        x = x * zi2; y = y * zi2 * zi;
-        memcpy(jac.data() + 12 * i, &x, 48); memcpy(jac.data() + 12 * i + 6, &y, 48);      // (packed in place: 12 i + 12 <= 18 i)
-    }
-    HIPCHK(hipMemcpyAsync(dB, jac.data(), rows * PT, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dBinf, binf.data(), rows, hipMemcpyHostToDevice, s));
-    return DGPU_OK;
+// How the b_i (the P_i of a proof) of a chunk are made: RowMsm (msm_many.hip.h) over the parameters' handle, whose small-path table serves the many-row kernels
+RowMsm<G1> param_rows(Slot &sl, uint64_t params, const Handle &h, size_t nn, size_t cap, size_t n) {
+    SmallSub sub{nullptr, nullptr};
+    const bool many = h.n <= SMALL_MSM_MAX_N && nn <= gs.small_max.load() && small_sub_for<G1>(sl, params, h, 0, nn, sub, true);
+    RowMsm<G1> rm(many, nn, n, cap);
+    rm.sub = sub; rm.rec = (const uint32_t *)h.p;
+    return rm;
 }
 // s and the messages of the rows [r0, r0 + rows) to the device: the messages packed (what lies between the caller's rows never crosses)
 int32_t rows_up(Slot &sl, const Rows &r, size_t r0, size_t rows, void *d_s, void *d_m) {
     hipStream_t s = sl.stream;
     HIPCHK(hipMemcpyAsync(d_s, r.s + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
-    const uint64_t *src = r.messages + r0 * r.stride * 4;
-    if (r.stride == r.L) HIPCHK(hipMemcpyAsync(d_m, src, rows * r.L * 32, hipMemcpyHostToDevice, s));
-    else HIPCHK(hipMemcpy2DAsync(d_m, r.L * 32, src, r.stride * 32, r.L * 32, rows, hipMemcpyHostToDevice, s));
-    return DGPU_OK;
+    return upload_rows_packed(s, d_m, r.messages + r0 * r.stride * 4, r.L, r.stride, rows);
 }
 
 // ---- SignatureG1::new for n rows (signature.rs:138-211): A_i = (x + e_i)^-1 b_i with the caller's e_i, s_i -------------------------------------------------
@@ -136,8 +91,7 @@ int32_t sign_many(uint64_t params, const uint64_t *sk, const Rows &r, uint64_t *
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    BPath bp;
-    if ((rc = b_path(sl, params, hb.h, nn, ~(size_t)0, n, bp))) return rc;
+    const RowMsm<G1> bp = param_rows(sl, params, hb.h, nn, ~(size_t)0, n);
     const size_t chunk = bp.chunk;
     // q[0]: t, q[1]: s, q[2]: the messages, q[4]: [A | identity flags]
     auto ws = [&](Slot &o) -> int32_t {
@@ -148,11 +102,8 @@ int32_t sign_many(uint64_t params, const uint64_t *sk, const Rows &r, uint64_t *
         if ((e = o.q[4].ensure(chunk * PT + chunk))) return e;
         return bp.workspace(o);
     };
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws(sl))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
-    std::vector<uint64_t> jac; std::vector<uint8_t> hinf;
     DrainUnlessDone guard(sl);
     DeviceWipe dw(sl);
     dw.add(sl.q[0].p, chunk * 32); dw.add(sl.in_scalars.p, chunk * nn * 32);
@@ -164,7 +115,7 @@ int32_t sign_many(uint64_t params, const uint64_t *sk, const Rows &r, uint64_t *
         HIPCHK(hipMemcpyAsync(sl.q[0].p, t.w.data() + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
         if ((rc = rows_up(sl, r, r0, rows, sl.q[1].p, sl.q[2].p))) return rc;
         { StageTimer st(sl, "bbs.rows"); bbsk::launch_bbs_rows(s, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), sl.q[0].as<uint32_t>(), r.mont ? 1 : 0, rows, nn, d_rows); }
-        if ((rc = b_points(sl, bp, d_rows, rows, d_bad, dA, dAinf, jac, hinf))) return rc;
+        if ((rc = bp.points(sl, d_rows, rows, d_bad, dA, dAinf))) return rc;
         HIPCHK(hipMemcpyAsync(out_a + 12 * r0, dA, rows * PT, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(binf.data() + r0, dAinf, rows, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));                                 // (the next chunk's operands overwrite this one's)
@@ -243,8 +194,7 @@ int32_t verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_p
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    BPath bp;
-    if ((rc = b_path(sl, params, hb.h, nn, bbsk::BBS_EACH_CHUNK, n, bp))) return rc;
+    const RowMsm<G1> bp = param_rows(sl, params, hb.h, nn, bbsk::BBS_EACH_CHUNK, n);
     const size_t chunk = bp.chunk;
     // q[0]: the split -e, q[1]: s, q[2]: the messages, q[3]: A, q[4]: [b | identity flags], q[5]: d, q[6]: [skip flags of (A, d) | ones]
     auto ws = [&](Slot &o) -> int32_t {
@@ -259,11 +209,8 @@ int32_t verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_p
         if ((e = ws_check(o, chunk))) return e;
         return bp.workspace(o);
     };
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws(sl))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
-    std::vector<uint64_t> jac; std::vector<uint8_t> hinf;
     DrainUnlessDone guard(sl);
     uint32_t *d_rows = sl.in_scalars.as<uint32_t>(), *d_bad = sl.flags.as<uint32_t>();
     uint8_t *dA = sl.q[3].as<uint8_t>(), *dB = sl.q[4].as<uint8_t>(), *dBinf = dB + chunk * PT, *dD = sl.q[5].as<uint8_t>(), *dsk = sl.q[6].as<uint8_t>(), *dones = dsk + 2 * chunk;
@@ -277,7 +224,7 @@ int32_t verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_p
         HIPCHK(hipMemcpyAsync(dsk, ainf.data() + r0, rows, hipMemcpyHostToDevice, s));
         if ((rc = rows_up(sl, r, r0, rows, sl.q[1].p, sl.q[2].p))) return rc;
         { StageTimer st(sl, "bbs.rows"); bbsk::launch_bbs_rows(s, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), nullptr, r.mont ? 1 : 0, rows, nn, d_rows); }
-        if ((rc = b_points(sl, bp, d_rows, rows, d_bad, dB, dBinf, jac, hinf))) return rc;
+        if ((rc = bp.points(sl, d_rows, rows, d_bad, dB, dBinf))) return rc;
         // d_i = -((-e_i) A_i + b_i); its identity flag is the second pair's skip flag
         { StageTimer st(sl, "bbs.scale");
           msm::launch_g1_scale_quad(s, (const uint32_t *)dA, dsk, sl.q[0].as<uint32_t>(), 8, dones, rows, (uint32_t *)dD, dsk + rows, (const uint32_t *)dB, dBinf); }
@@ -301,6 +248,48 @@ void add_jac(HPoint &acc, const uint64_t *jac) {
     HPoint p; p.x = x; p.y = y; p.zz = zz; p.zzz = zz * z; p.inf = false;
     acc.add_in_place(p);
 }
+// rows per chunk of the batch calls: their kernels' cap and BBS_BATCH_TERMS scalars (dgpu_set_many_chunk_rows of the development surface cuts these calls' rows too)
+size_t batch_chunk(size_t n, size_t L, size_t cap) {
+    const int forced = gs.many_chunk.load();
+    return std::min(n, forced > 0 ? (size_t)forced : std::min(cap, std::max<size_t>(1, bbsk::BBS_BATCH_TERMS / L)));
+}
+// acc += sum_k c_k H_k: ONE MSM of nn = L + 2 terms over the parameters, the scalars at d_c
+int32_t params_msm(Slot &sl, uint64_t params, const Handle &h, const uint32_t *d_c, size_t nn, HPoint &acc) {
+    SmallSub sub;
+    uint64_t jac[18];
+    int32_t rc;
+    const bool have = small_sub_for<G1>(sl, params, h, 0, nn, sub, true);
+    if ((rc = msm_device<G1, hostf::Fq>(sl, (const uint32_t *)h.p, d_c, nn, jac, have ? &sub : nullptr))) return rc;
+    add_jac(acc, jac);
+    return DGPU_OK;
+}
+// *ok = [e(P1, w) e(P2, g2) == 1] for the two merged points of a batch (an identity member is skipped); scratch: 2 PT + 64 bytes of the slot
+int32_t merged_pair_verdict(Slot &sl, const HPoint &P1, const HPoint &P2, const uint64_t *pk_pc, const uint64_t *g2_pc, Buf &scratch, int32_t *ok) {
+    hipStream_t s = sl.stream;
+    int32_t rc;
+    uint64_t pts[24 + 8] = {0};
+    uint8_t *sk = (uint8_t *)(pts + 24);
+    for (int k = 0; k < 2; k++) {
+        const HPoint &P = k ? P2 : P1;
+        sk[k] = P.inf ? 1 : 0;
+        if (P.inf) continue;
+        hostf::Fq X, Y, Z; P.to_normalised_jacobian(X, Y, Z);
+        memcpy(pts + 12 * k, &X, 48); memcpy(pts + 12 * k + 6, &Y, 48);
+    }
+    uint8_t verdict = 0;
+    DrainUnlessDone own(sl);                                             // (pts and verdict are this frame's)
+    uint32_t *dP = scratch.as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(dP, pts, sizeof pts, hipMemcpyHostToDevice, s));
+    if ((rc = coeffs_up(sl, pk_pc, g2_pc, 1))) return rc;
+    launch_check(sl, dP, dP + 24, (const uint8_t *)(dP + 48), 1, 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&verdict, sl.flags.p, 1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    own.done = true;
+    if (gs.prof) prof_flush(sl);
+    *ok = verdict ? 1 : 0;
+    return DGPU_OK;
+}
 int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const Rows &r, const uint64_t *random, int32_t *ok) {
     if (r.n == 0) { if (ok) *ok = 1; return DGPU_OK; }
     if (bad_rows(r) || !pk_pc || !g2_pc || !sig_a || !random || !ok) return DGPU_E_BADARG;
@@ -313,8 +302,7 @@ int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    const int forced = gs.many_chunk.load();                              // (dgpu_set_many_chunk_rows of the development surface cuts this call's rows too)
-    const size_t chunk = std::min(n, forced > 0 ? (size_t)forced : std::min(bbsk::BBS_BATCH_CHUNK, std::max<size_t>(1, bbsk::BBS_BATCH_TERMS / r.L)));
+    const size_t chunk = batch_chunk(n, r.L, bbsk::BBS_BATCH_CHUNK);
     const RawBases rb = RawBases::packed<G1>(sig_a, nullptr);
     int32_t rc;
     // q[0]: e, q[1]: s, q[2]: the messages, q[3]: [P1 | P2] and their skip flags, q[7]: the blocks' partial sums, q[8]: [-c | the running sums], q[9]: [rho^i | rho^i e_i],
@@ -334,9 +322,7 @@ int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_
         if (chunk != nn && (e = ws_for<G1>(o, 2, std::min(chunk, nn), 0, nullptr))) return e;
         return ws_check(o, 1);
     };
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws(sl))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
     DrainUnlessDone guard(sl);
     uint32_t *d_c = sl.q[8].as<uint32_t>(), *d_run = d_c + nn * 8, *d_w = sl.q[9].as<uint32_t>(), *d_we = d_w + chunk * 8, *d_rec = sl.q[10].as<uint32_t>();
@@ -357,34 +343,9 @@ int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_
         add_jac(P2, jac);
         if (gs.prof) prof_flush(sl);
     }
-    // - sum_k c_k H_k: ONE MSM of L + 2 terms over the parameters
-    {
-        SmallSub sub;
-        const bool have = small_sub_for<G1>(sl, params, hb.h, 0, nn, sub, true);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, (const uint32_t *)hb.h.p, d_c, nn, jac, have ? &sub : nullptr))) return rc;
-        add_jac(P2, jac);
-    }
-    // the two merged pairs (an identity member is skipped)
-    uint64_t pts[24 + 8] = {0};
-    uint8_t *sk = (uint8_t *)(pts + 24);
-    for (int k = 0; k < 2; k++) {
-        const HPoint &P = k ? P2 : P1;
-        sk[k] = P.inf ? 1 : 0;
-        if (P.inf) continue;
-        hostf::Fq X, Y, Z; P.to_normalised_jacobian(X, Y, Z);
-        memcpy(pts + 12 * k, &X, 48); memcpy(pts + 12 * k + 6, &Y, 48);
-    }
-    uint8_t verdict = 0;
-    uint32_t *dP = sl.q[3].as<uint32_t>();
-    HIPCHK(hipMemcpyAsync(dP, pts, sizeof pts, hipMemcpyHostToDevice, s));
-    if ((rc = coeffs_up(sl, pk_pc, g2_pc, 1))) return rc;
-    launch_check(sl, dP, dP + 24, (const uint8_t *)(dP + 48), 1, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&verdict, sl.flags.p, 1, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = params_msm(sl, params, hb.h, d_c, nn, P2))) return rc;       // - sum_k c_k H_k
+    if ((rc = merged_pair_verdict(sl, P1, P2, pk_pc, g2_pc, sl.q[3], ok))) return rc;
     guard.done = true;
-    if (gs.prof) prof_flush(sl);
-    *ok = verdict ? 1 : 0;
     return DGPU_OK;
 }
 
@@ -410,9 +371,8 @@ int32_t proofs_up(Slot &sl, const Proofs &p, size_t r0, size_t rows, bbspk::PokD
     hipStream_t s = sl.stream;
     HIPCHK(hipMemcpyAsync(sl.q[0].p, p.challenge + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(sl.q[1].p, p.fixed + 16 * r0, rows * 4 * 32, hipMemcpyHostToDevice, s));
-    const uint64_t *src = p.values + r0 * p.stride * 4;
-    if (p.stride == p.L) HIPCHK(hipMemcpyAsync(sl.q[2].p, src, rows * p.L * 32, hipMemcpyHostToDevice, s));
-    else HIPCHK(hipMemcpy2DAsync(sl.q[2].p, p.L * 32, src, p.stride * 32, p.L * 32, rows, hipMemcpyHostToDevice, s));
+    int32_t rc;
+    if ((rc = upload_rows_packed(s, sl.q[2].p, p.values + r0 * p.stride * 4, p.L, p.stride, rows))) return rc;
     HIPCHK(hipMemcpyAsync(sl.q[3].p, p.revealed + r0 * p.L, rows * p.L, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(sl.q[5].p, p.points + r0 * NPTS * 12, rows * NPTS * PT, hipMemcpyHostToDevice, s));
     dev = bbspk::PokDev{sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), sl.q[3].as<uint8_t>(), p.L, p.mont ? 1 : 0};
@@ -435,10 +395,9 @@ int32_t pok_verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    BPath bp;
-    int32_t rc;
-    if ((rc = b_path(sl, params, hb.h, nn, bbspk::POK_EACH_CHUNK, n, bp))) return rc;
+    const RowMsm<G1> bp = param_rows(sl, params, hb.h, nn, bbspk::POK_EACH_CHUNK, n);
     const size_t chunk = bp.chunk;
+    int32_t rc;
     SegLayout lay, lay_tail;
     own_layout(chunk, lay);
     if (n % chunk) own_layout(n % chunk, lay_tail);
@@ -456,11 +415,8 @@ int32_t pok_verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *
         if ((e = ws_seg_resident<G1>(o, 7 * chunk, 2 * chunk, lay.blocks))) return e;
         return bp.workspace(o);
     };
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws(sl))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
-    std::vector<uint64_t> jac; std::vector<uint8_t> hinf;
     DrainUnlessDone guard(sl);
     uint32_t *d_rows = sl.in_scalars.as<uint32_t>(), *d_bad = sl.flags.as<uint32_t>(), *d_own = sl.q[6].as<uint32_t>(), *d_opts = sl.q[7].as<uint32_t>();
     uint32_t *dPa = sl.q[8].as<uint32_t>(), *dPb = dPa + chunk * (PT / 4);
@@ -473,7 +429,7 @@ int32_t pok_verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *
         if ((rc = proofs_up(sl, p, r0, rows, dev))) return rc;
         { StageTimer st(sl, "bbs.pok_rows"); bbspk::launch_pok_rows(s, dev, rows, d_rows, d_own); }
         { StageTimer st(sl, "bbs.pok_stage"); bbspk::launch_pok_stage(s, sl.q[5].as<uint32_t>(), (const uint32_t *)p.h0, rows, d_opts, dPa, dPb, dsk); }
-        if ((rc = b_points(sl, bp, d_rows, rows, d_bad, dB, dBinf, jac, hinf))) return rc;
+        if ((rc = bp.points(sl, d_rows, rows, d_bad, dB, dBinf))) return rc;
         if ((rc = seg_rows_resident<G1>(sl, (const uint8_t *)d_opts, PT, d_own, 7 * rows, 2 * rows, rows == chunk ? lay : lay_tail, d_bad))) return rc;
         launch_check(sl, dPa, dPb, dsk, rows, chunk);
         { StageTimer st(sl, "bbs.pok_verdict");
@@ -500,8 +456,7 @@ int32_t pok_verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t 
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    const int forced = gs.many_chunk.load();                              // (dgpu_set_many_chunk_rows of the development surface cuts this call's rows too)
-    const size_t chunk = std::min(n, forced > 0 ? (size_t)forced : std::min(bbspk::POK_BATCH_CHUNK, std::max<size_t>(1, bbsk::BBS_BATCH_TERMS / p.L)));
+    const size_t chunk = batch_chunk(n, p.L, bbspk::POK_BATCH_CHUNK);
     int32_t rc;
     // q[0 .. 3], q[5]: the proofs (ws_proofs); q[4]: [P1 | P2] and their skip flags, q[6]: the weights over the own points, q[7]: the blocks' partial sums,
     // q[8]: [C | the running sums], q[9]: [rho^i | -rho^i], q[10]: the prepared records of the own points, q[11]: those of [the A' | the Abar]
@@ -518,9 +473,7 @@ int32_t pok_verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t 
         for (size_t terms : {NPTS * chunk, chunk, nn}) if ((e = ws_for<G1>(o, 2, terms, 0, nullptr))) return e;
         return ws_check(o, 1);
     };
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws(sl))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);      // a new shape: the next call, on another slot, allocates nothing
+    if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
     DrainUnlessDone guard(sl);
     uint32_t *d_c = sl.q[8].as<uint32_t>(), *d_run = d_c + nn * 8, *d_w5 = sl.q[6].as<uint32_t>(), *d_tp = sl.q[9].as<uint32_t>(), *d_tn = d_tp + chunk * 8;
@@ -547,34 +500,10 @@ int32_t pok_verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t 
         add_jac(P2, jac);
         if (gs.prof) prof_flush(sl);
     }
-    // sum_k C_k H_k: ONE MSM of L + 2 terms over the parameters
-    {
-        SmallSub sub;
-        const bool have = small_sub_for<G1>(sl, params, hb.h, 0, nn, sub, true);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, (const uint32_t *)hb.h.p, d_c, nn, jac, have ? &sub : nullptr))) return rc;
-        add_jac(Gsum, jac);
-    }
+    if ((rc = params_msm(sl, params, hb.h, d_c, nn, Gsum))) return rc;     // sum_k C_k H_k
     if (!Gsum.inf) { HIPCHK(hipStreamSynchronize(s)); guard.done = true; *ok = 0; return DGPU_OK; }      // the G1 equation fails: the pairing cannot mend it
-    uint64_t pts[24 + 8] = {0};
-    uint8_t *sk = (uint8_t *)(pts + 24);
-    for (int k = 0; k < 2; k++) {
-        const HPoint &P = k ? P2 : P1;
-        sk[k] = P.inf ? 1 : 0;
-        if (P.inf) continue;
-        hostf::Fq X, Y, Z; P.to_normalised_jacobian(X, Y, Z);
-        memcpy(pts + 12 * k, &X, 48); memcpy(pts + 12 * k + 6, &Y, 48);
-    }
-    uint8_t verdict = 0;
-    uint32_t *dP = sl.q[4].as<uint32_t>();
-    HIPCHK(hipMemcpyAsync(dP, pts, sizeof pts, hipMemcpyHostToDevice, s));
-    if ((rc = coeffs_up(sl, pk_pc, g2_pc, 1))) return rc;
-    launch_check(sl, dP, dP + 24, (const uint8_t *)(dP + 48), 1, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&verdict, sl.flags.p, 1, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = merged_pair_verdict(sl, P1, P2, pk_pc, g2_pc, sl.q[4], ok))) return rc;
     guard.done = true;
-    if (gs.prof) prof_flush(sl);
-    *ok = verdict ? 1 : 0;
     return DGPU_OK;
 }
 

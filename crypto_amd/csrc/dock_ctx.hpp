@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -216,6 +217,51 @@ inline void prof_flush(Slot &sl) {
     }
     sl.prof_pending.clear();
 }
+inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// ---- what every driver that takes a slot shares: the guards of its return paths and the workspace step ------------------------------------------
+// error paths of calls that read the caller's memory: nothing of ours may still read the caller's buffers when the call returns
+inline void drain(Slot &sl) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); }
+// zeroes the device buffers that held what depends on a secret key (dock_accumulator.hip: the tables, Omega's chunk results, evaluations and coefficients;
+// dock_bbs.hip: the inverses and the rows that carry them) on every return path, before the slot goes back
+struct DeviceWipe {
+    Slot &sl; struct Region { void *p; size_t bytes; }; std::vector<Region> r;
+    explicit DeviceWipe(Slot &s) : sl(s) {}
+    void add(void *p, size_t bytes) { if (p && bytes) r.push_back(Region{p, bytes}); }
+    ~DeviceWipe() {
+        if (r.empty()) return;
+        for (const Region &k : r) (void)hipMemsetAsync(k.p, 0, k.bytes, sl.stream);
+        (void)hipStreamSynchronize(sl.stream);
+    }
+};
+// a return before the call's last synchronisation (an error path) waits for the slot's streams first: asynchronous copies may still be queued into or out of
+// host vectors declared BEFORE this guard, which leave scope after it
+struct DrainUnlessDone {
+    Slot &sl; bool done = false;
+    explicit DrainUnlessDone(Slot &s) : sl(s) {}
+    ~DrainUnlessDone() { if (!done) drain(sl); }
+};
+// `ws(slot)`, the workspace function of a call's shape, on the slots that are idle right now (called by a call that had to grow its own slot: the other host
+// threads of the caller — rayon workers — will come with the same shape next, and would each stall the device in hipMalloc / hipFree).  A failure (out of
+// memory) is not an error of the call that triggered the reservation: the slot grows on its first use instead
+template <class WS> void reserve_idle_slots(const Slot *mine, WS ws) {
+    Ctx &cx = cur();
+    for (int k = 0; k < N_SLOTS; k++) {
+        Slot &o = cx.slots[k];
+        if (&o == mine || !o.mu.try_lock()) continue;
+        (void)ws(o);
+        o.mu.unlock();
+    }
+}
+// the workspace step of a call: ws(sl), and if that allocated — a new shape — ws on every idle slot too, so that the next call, on another slot, allocates
+// nothing.  Returns ws(sl)'s code.  (A call that reserves the idle slots only after its own work keeps the flag and calls reserve_idle_slots itself.)
+template <class WS> int32_t ensure_workspace(Slot &sl, WS ws) {
+    const uint64_t allocs0 = g_dev_allocs.load();
+    const int32_t rc = ws(sl);
+    if (!rc && g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, ws);
+    return rc;
+}
+
 // peek (no pin): for argument checks only
 inline bool lookup_handle(uint64_t h, Handle &out) {
     std::lock_guard<std::mutex> lk(gs.mu);

@@ -30,16 +30,6 @@ int32_t gt_ws(Slot &sl, int what, size_t ch, size_t nch) {
     if (what == 2 && (rc = sl.ml_state.ensure((ch + fold_a(ch) + fold_b(ch) + nch + fold_a(nch) + fold_b(nch)) * ELW))) return rc;
     return DGPU_OK;
 }
-// the slots that are idle right now get the same workspace: the caller's other host threads come with the same shape next
-void gt_ws_idle(const Slot *mine, int what, size_t ch, size_t nch) {
-    Ctx &cx = cur();
-    for (int k = 0; k < N_SLOTS; k++) {
-        Slot &o = cx.slots[k];
-        if (&o == mine || !o.mu.try_lock()) continue;
-        (void)gt_ws(o, what, ch, nch);
-        o.mu.unlock();
-    }
-}
 // in (internal form, m elements) folded level by level; the last level writes ONE element to `last` (ABI if last_abi).  a / b: two scratch regions
 // of fold_a(m) and fold_b(m) elements.  m == 1 still runs one level (a copy, converting the form).
 void fold_to_one(hipStream_t s, const uint32_t *in, size_t m, uint32_t *a, uint32_t *b, uint32_t *last, bool last_abi) {
@@ -80,7 +70,7 @@ int32_t dgpu_fp12_pow_batch(const uint64_t *a, const uint64_t *e, size_t e_strid
     }
     HIPCHK(hipStreamSynchronize(s));
     if (gs.prof) prof_flush(sl);
-    if (grew) gt_ws_idle(&sl, 1, ch, 1);
+    if (grew) reserve_idle_slots(&sl, [&](Slot &o) { return gt_ws(o, 1, ch, 1); });      // (the caller's other host threads come with the same shape next)
     return DGPU_OK;
 }
 
@@ -114,7 +104,7 @@ int32_t dgpu_fp12_multi_pow_device(const uint64_t *a, const uint64_t *e, size_t 
     HIPCHK(hipMemcpyAsync(out, dout, ABIB, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (gs.prof) prof_flush(sl);
-    if (grew) gt_ws_idle(&sl, 2, ch, nch);
+    if (grew) reserve_idle_slots(&sl, [&](Slot &o) { return gt_ws(o, 2, ch, nch); });
     return DGPU_OK;
 }
 
@@ -140,7 +130,7 @@ int32_t dgpu_gt_in_subgroup_device(const uint64_t *a, size_t n, uint8_t *ok) {
     }
     HIPCHK(hipStreamSynchronize(s));
     if (gs.prof) prof_flush(sl);
-    if (grew) gt_ws_idle(&sl, 3, ch, 1);
+    if (grew) reserve_idle_slots(&sl, [&](Slot &o) { return gt_ws(o, 3, ch, 1); });
     return DGPU_OK;
 }
 

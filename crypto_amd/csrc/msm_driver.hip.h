@@ -687,28 +687,6 @@ inline int32_t stage_scalars(Slot &sl, const uint64_t *h, size_t lo, size_t hi, 
 }
 inline int32_t stage_scalars(Slot &sl, const uint64_t *h, size_t n, bool mont, uint32_t *d_out) { return stage_scalars(sl, h, 0, n, mont, d_out); }
 
-// error paths of calls that read the caller's memory: nothing of ours may still read the caller's buffers when the call returns
-inline void drain(Slot &sl) { (void)hipStreamSynchronize(sl.cstream); (void)hipStreamSynchronize(sl.stream); }
-// zeroes the device buffers that held what depends on a secret key (dock_accumulator.hip: the tables, Omega's chunk results, evaluations and coefficients;
-// dock_bbs.hip: the inverses and the rows that carry them) on every return path, before the slot goes back
-struct DeviceWipe {
-    Slot &sl; struct Region { void *p; size_t bytes; }; std::vector<Region> r;
-    explicit DeviceWipe(Slot &s) : sl(s) {}
-    void add(void *p, size_t bytes) { if (p && bytes) r.push_back(Region{p, bytes}); }
-    ~DeviceWipe() {
-        if (r.empty()) return;
-        for (const Region &k : r) (void)hipMemsetAsync(k.p, 0, k.bytes, sl.stream);
-        (void)hipStreamSynchronize(sl.stream);
-    }
-};
-// a return before the call's last synchronisation (an error path) waits for the slot's streams first: asynchronous copies may still be queued into or out of
-// host vectors declared BEFORE this guard, which leave scope after it
-struct DrainUnlessDone {
-    Slot &sl; bool done = false;
-    explicit DrainUnlessDone(Slot &s) : sl(s) {}
-    ~DrainUnlessDone() { if (!done) drain(sl); }
-};
-
 // ---- workspaces sized ahead of the calls (no hipMalloc on an MSM path in steady state) ---------------------------------------------------
 // what: 1 = one-shot call of n terms (raw bases of `stride` bytes + scalars + prepared records + plain pipeline), 2 = fresh host scalars on a
 // plain handle of n terms, 3 = the same on a table (pt)
@@ -742,19 +720,6 @@ template <class C> int32_t reserve_slots(int what, size_t n, size_t stride, cons
     }
     return first;
 }
-// the same for the slots that are idle right now (called by a one-shot call that had to grow its own slot: the other host threads of the
-// caller — rayon workers — will come with the same size next, and would each stall the device in hipMalloc / hipFree)
-// (`ws(slot)`: the workspace function of the shape)
-template <class WS> void reserve_idle_slots(const Slot *mine, WS ws) {
-    Ctx &cx = cur();
-    for (int k = 0; k < N_SLOTS; k++) {
-        Slot &o = cx.slots[k];
-        if (&o == mine || !o.mu.try_lock()) continue;
-        (void)ws(o);
-        o.mu.unlock();
-    }
-}
-
 // one-shot MSM on the calling thread's context (no size threshold: the callers apply it)
 template <class C, class HF>
 int32_t msm_oneshot_here(const RawBases &rb, const uint64_t *scalars, size_t n, bool mont, uint64_t *out) {

@@ -31,8 +31,8 @@ template <class C> int32_t ws_many(Slot &sl, size_t n, size_t rows, const ManyGe
     return sl.win_inf.ensure(rows);
 }
 // one chunk whose canonical scalars are on the device already (rows packed; the workspace is ws_many's): tree, fold.  The rows' normalised Jacobian results
-// are left in sl.win, their identity flags in sl.win_inf, *d_bad |= a scalar >= 2^255.  Shared by msm_device_many and the accumulator's public update
-// (dock_accumulator.hip), whose rows are made on the device.
+// are left in sl.win, their identity flags in sl.win_inf, *d_bad |= a scalar >= 2^255.  Shared by msm_device_many and RowMsm below,
+// whose rows are made on the device.
 template <class C>
 int32_t many_rows_resident(Slot &sl, const SmallSub &sub, const uint32_t *d_sc, size_t n, size_t rows, const ManyGeom &g, uint32_t *d_bad) {
     hipStream_t s = sl.stream;
@@ -48,26 +48,28 @@ int32_t many_rows_resident(Slot &sl, const SmallSub &sub, const uint32_t *d_sc, 
     HIPCHK(hipGetLastError());
     return DGPU_OK;
 }
-// the rows on the device, chunk by chunk: scalars up (rows packed: what lies between them in the caller's memory never crosses), tree, fold, results down
+// `rows` rows of L scalars, `stride` scalars apart in the caller's memory, packed on the device: what lies between the caller's rows never crosses
+inline int32_t upload_rows_packed(hipStream_t s, void *dst, const uint64_t *src, size_t L, size_t stride, size_t rows) {
+    if (stride == L) HIPCHK(hipMemcpyAsync(dst, src, rows * L * 32, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpy2DAsync(dst, L * 32, src, stride * 32, L * 32, rows, hipMemcpyHostToDevice, s));
+    return DGPU_OK;
+}
+// the rows on the device, chunk by chunk: scalars up, tree, fold, results down
 template <class C>
 int32_t msm_device_many(Slot &sl, const SmallSub &sub, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, bool mont, uint64_t *out, uint8_t *out_inf) {
     int32_t rc;
     constexpr size_t JW = 3 * C::ABI_W / 2;                                               // u64 words per result
     const ManyGeom g = many_geometry(n);
     const size_t chunk = std::min(m, many_chunk_rows(n));
-    const uint64_t allocs0 = g_dev_allocs.load();
-    if ((rc = ws_many<C>(sl, n, chunk, g))) return rc;
-    if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, [&](Slot &o) { return ws_many<C>(o, n, chunk, g); });      // a new shape: the caller's other host threads come with it next
+    if ((rc = ensure_workspace(sl, [&](Slot &o) { return ws_many<C>(o, n, chunk, g); }))) return rc;
     hipStream_t s = sl.stream;
     uint32_t *const d_sc = sl.in_scalars.as<uint32_t>(), *const d_bad = sl.flags.as<uint32_t>();
     HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
     uint32_t *const hbad = (uint32_t *)sl.hpin;
     for (size_t r0 = 0; r0 < m; r0 += chunk) {
         const size_t rows = std::min(chunk, m - r0);
-        const uint64_t *src = scalars + r0 * row_stride * 4;
         hipEvent_t ev = sl.copy_ev[sl.ev_next++ % (Slot::N_COPY_EV + 1)];
-        if (row_stride == n) HIPCHK(hipMemcpyAsync(d_sc, src, rows * n * 32, hipMemcpyHostToDevice, sl.cstream));
-        else HIPCHK(hipMemcpy2DAsync(d_sc, n * 32, src, row_stride * 32, n * 32, rows, hipMemcpyHostToDevice, sl.cstream));
+        if ((rc = upload_rows_packed(sl.cstream, d_sc, scalars + r0 * row_stride * 4, n, row_stride, rows))) return rc;
         HIPCHK(hipEventRecord(ev, sl.cstream));
         HIPCHK(hipStreamWaitEvent(s, ev, 0));
         if (mont) ntt::launch_fr_mont_to_canonical(s, d_sc, rows * n);
@@ -81,6 +83,62 @@ int32_t msm_device_many(Slot &sl, const SmallSub &sub, const uint64_t *scalars, 
     }
     return DGPU_OK;
 }
+// Jacobian rows (X, Y, Z: 18 words) -> affine rows (x, y: 12 words) packed in place (12 i + 12 <= 18 i), an identity: zero words, and inf[i] its flag
+inline void jac_rows_to_affine(uint64_t *jac, size_t rows, uint8_t *inf) {
+    for (size_t i = 0; i < rows; i++) {
+        const uint64_t *p = jac + 18 * i;
+        uint64_t *q = jac + 12 * i;
+        inf[i] = jac_is_identity(p, 18);
+        if (inf[i]) { memset(q, 0, 96); continue; }
+        hostf::Fq x, y, z; memcpy(&x, p, 48); memcpy(&y, p + 6, 48); memcpy(&z, p + 12, 48);
+        const hostf::Fq zi = z.inv(), zi2 = zi * zi;
+        x = x * zi2; y = y * zi2 * zi;
+        memcpy(q, &x, 48); memcpy(q + 6, &y, 48);
+    }
+}
+// Rows of n scalars made on the device, over one small set of G1 bases -> affine points and identity flags on the device (dock_bbs.hip: the b_i and P_i over the
+// parameters; dock_accumulator.hip: the T_i over omega).  The many-row kernels over the bases' small-path table `sub` where they reach; beyond (rows longer than
+// dgpu_set_small_msm_max allows, no memory for the table) the single-row driver over the prepared records `rec`, row by row, normalised on the host.  The caller
+// says which, and fills in `sub` or `rec` before points(): a handle's table comes from small_sub_for, a call's own table is built in its workspace.
+template <class C> struct RowMsm {
+    static_assert(C::NFP == 1, "G1: the slow path normalises over Fq");
+    static constexpr size_t PT = 2 * C::ABI_W * 4;        // bytes of an affine point of the ABI
+    bool many; ManyGeom geom; size_t n, chunk;            // terms per row, rows per chunk
+    SmallSub sub{nullptr, nullptr}; const uint32_t *rec = nullptr;
+    // rows per chunk: the caller's cap, a launch of the many-row kernels, or 64 MB of scalars on the slow path (n = 0: no row is ever run)
+    RowMsm(bool many_, size_t n_, size_t rows, size_t cap)
+        : many(many_), geom(many_geometry(std::max<size_t>(n_, 1))), n(n_),
+          chunk(std::min(rows, std::min(cap, many_ ? many_chunk_rows(n_) : std::max<size_t>(1, ((size_t)1 << 21) / std::max<size_t>(n_, 1))))) {}
+    int32_t workspace(Slot &o) const {
+        if (many) return ws_many<C>(o, n, chunk, geom);
+        int32_t e;
+        if ((e = ws_for<C>(o, 2, n, 0, nullptr))) return e;
+        if ((e = o.in_scalars.ensure(chunk * n * 32))) return e;
+        return o.flags.ensure(64);
+    }
+    // the rows at d_rows (canonical words, packed) -> dOut (affine words; an identity: zero words) and dInf
+    int32_t points(Slot &sl, const uint32_t *d_rows, size_t rows, uint32_t *d_bad, uint8_t *dOut, uint8_t *dInf) const {
+        hipStream_t s = sl.stream;
+        int32_t rc;
+        if (many) {
+            if ((rc = many_rows_resident<C>(sl, sub, d_rows, n, rows, geom, d_bad))) return rc;
+            // the normalised Jacobian rows (X, Y, 1) -> X and Y of every row, and its identity flag
+            HIPCHK(hipMemcpy2DAsync(dOut, PT, sl.win.p, 3 * PT / 2, PT, rows, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(dInf, sl.win_inf.p, rows, hipMemcpyDeviceToDevice, s));
+            return DGPU_OK;
+        }
+        HIPCHK(hipGetLastError());
+        std::vector<uint64_t> jac(rows * 18); std::vector<uint8_t> inf(rows);
+        for (size_t i = 0; i < rows; i++)
+            if ((rc = msm_device<C, hostf::Fq>(sl, rec, d_rows + i * n * 8, n, jac.data() + 18 * i))) return rc;
+        jac_rows_to_affine(jac.data(), rows, inf.data());
+        hipError_t up = hipMemcpyAsync(dOut, jac.data(), rows * PT, hipMemcpyHostToDevice, s);
+        if (up == hipSuccess) up = hipMemcpyAsync(dInf, inf.data(), rows, hipMemcpyHostToDevice, s);
+        const hipError_t waited = hipStreamSynchronize(s);      // (the host vectors end here, whatever the copies answered)
+        HIPCHK(up); HIPCHK(waited);
+        return DGPU_OK;
+    }
+};
 template <class C, class HF>
 int32_t msm_handle_many(uint64_t bases, size_t offset, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, int mont, uint64_t *out, uint8_t *out_inf, int kind) {
     if (m == 0) return DGPU_OK;
@@ -126,26 +184,57 @@ int32_t msm_handle_many(uint64_t bases, size_t offset, const uint64_t *scalars, 
 // chunk through par_run: several calls in flight with few segments each share the host's cores).
 constexpr size_t SEG_CHUNK_TERMS = (size_t)1 << 16, SEG_CHUNK_SEGS = 4096;
 constexpr size_t SEG_DEVICE_FOLD_MIN = 24;              // PROVISIONAL, not measured: the crossover is what tests/perf/msm_segments_timing.py's fold sweep finds on an MI355X
-template <class C> int32_t ws_seg(Slot &sl, const RawBases &rb, size_t terms, size_t nseg, size_t blocks, size_t pslots) {
+// what every chunk needs whatever brings its operands: the prepared records, the table of eight multiples per base and its identity flags, the descriptors, the
+// window sums and the results with their flags
+template <class C> int32_t ws_seg_resident(Slot &sl, size_t terms, size_t nseg, size_t blocks) {
     int32_t rc;
     typedef typename C::ACC A;
     constexpr size_t W = SMALL_MSM_W, WIN_BYTES = std::max<size_t>(A::XW * 4, 4 * C::ABI_W * 4);      // a window sum in either form
     if ((rc = sl.flags.ensure(64))) return rc;
+    if ((rc = sl.prepped.ensure(terms * C::AFF_STRIDE * 4))) return rc;
+    if ((rc = sl.bucket.ensure(terms * SMALL_MSM_E * A::XW * 4))) return rc;
+    if ((rc = sl.bucket_inf.ensure(terms * SMALL_MSM_E))) return rc;
+    if ((rc = sl.entries.ensure(blocks * 64 * sizeof(SegDesc)))) return rc;
+    if ((rc = sl.l1.ensure(nseg * W * WIN_BYTES))) return rc;
+    if ((rc = sl.l1_inf.ensure(nseg * W))) return rc;
+    if ((rc = sl.win.ensure(nseg * 3 * C::ABI_W * 4))) return rc;
+    return sl.win_inf.ensure(nseg);
+}
+// ... and what a chunk from the host adds: its scalars, its staged bases, and the partial slots of segments longer than a block
+template <class C> int32_t ws_seg(Slot &sl, const RawBases &rb, size_t terms, size_t nseg, size_t blocks, size_t pslots) {
+    int32_t rc;
+    constexpr size_t W = SMALL_MSM_W;
+    if ((rc = ws_seg_resident<C>(sl, terms, nseg, blocks))) return rc;
     if ((rc = sl.in_scalars.ensure(terms * 32))) return rc;
     if ((rc = ws_stage_bases<C>(sl, rb, terms))) return rc;
-    if ((rc = sl.prepped.ensure(terms * C::AFF_STRIDE * 4))) return rc;
-    if ((rc = sl.bucket.ensure(terms * SMALL_MSM_E * A::XW * 4))) return rc;               // the table and its identity flags
-    if ((rc = sl.bucket_inf.ensure(terms * SMALL_MSM_E))) return rc;
-    if ((rc = sl.entries.ensure(blocks * 64 * sizeof(SegDesc)))) return rc;                 // the descriptors
-    if ((rc = sl.l1.ensure(nseg * W * WIN_BYTES))) return rc;                               // the window sums and their flags
-    if ((rc = sl.l1_inf.ensure(nseg * W))) return rc;
     if (pslots) {
-        if ((rc = sl.head.ensure(pslots * W * A::XW * 4))) return rc;                       // the blocks' partials, their flags, the per-window block counters
+        if ((rc = sl.head.ensure(pslots * W * C::ACC::XW * 4))) return rc;                  // the blocks' partials, their flags, the per-window block counters
         if ((rc = sl.part_inf.ensure(pslots * W))) return rc;
         if ((rc = sl.cnt.ensure(pslots * W * 4))) return rc;
     }
-    if ((rc = sl.win.ensure(nseg * 3 * C::ABI_W * 4))) return rc;                           // the results and their identity flags
-    return sl.win_inf.ensure(nseg);
+    return DGPU_OK;
+}
+// the launches of a chunk of T terms in ns segments whose prepared records are in sl.prepped and whose descriptors are on their way to sl.entries: table, tree,
+// and (device_fold) the fold that leaves the normalised Jacobian results in sl.win and their identity flags in sl.win_inf; *d_bad |= a scalar >= 2^255
+template <class C>
+int32_t seg_launches(Slot &sl, const uint32_t *d_sc, size_t T, size_t ns, const SegLayout &lay, bool device_fold, uint32_t *d_bad) {
+    hipStream_t s = sl.stream;
+    {
+        StageTimer st(sl, "msm.small_table");
+        launch_small_table<C>(s, sl.prepped.as<uint32_t>(), T, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>());
+    }
+    if (lay.pslots) HIPCHK(hipMemsetAsync(sl.cnt.p, 0, lay.pslots * SMALL_MSM_W * 4, s));
+    {
+        StageTimer st(sl, "msm.seg_tree");
+        launch_seg_tree<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_sc, sl.entries.p, lay.blocks, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(),
+                           sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), !device_fold, d_bad);
+    }
+    if (device_fold) {
+        StageTimer st(sl, "msm.seg_fold");
+        launch_seg_fold<C>(s, sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), ns, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
+    }
+    HIPCHK(hipGetLastError());
+    return DGPU_OK;
 }
 // segments [s0, s1) (all within the small path's reach, T > 0 terms in all) on the device: one upload, table, tree, fold (device or host), results down
 template <class C, class HF>
@@ -161,26 +250,11 @@ int32_t msm_seg_chunk(Slot &sl, const RawBases &rb, const uint64_t *scalars, con
     HIPCHK(hipMemcpyAsync(sl.entries.p, lay.desc.data(), lay.blocks * 64 * sizeof(SegDesc), hipMemcpyHostToDevice, sl.cstream));      // (ordered before the scalars' event)
     if ((rc = stage_scalars(sl, scalars + t0 * 4, T, mont, d_sc))) return rc;
     if ((rc = stage_bases<C>(sl, rb.from(t0), T, sl.prepped.as<uint32_t>()))) return rc;
-    {
-        StageTimer st(sl, "msm.small_table");
-        launch_small_table<C>(s, sl.prepped.as<uint32_t>(), T, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>());
-    }
-    if (lay.pslots) HIPCHK(hipMemsetAsync(sl.cnt.p, 0, lay.pslots * W * 4, s));
-    {
-        StageTimer st(sl, "msm.seg_tree");
-        launch_seg_tree<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_sc, sl.entries.p, lay.blocks, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(),
-                           sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), !device_fold, d_bad);
-    }
+    if ((rc = seg_launches<C>(sl, d_sc, T, ns, lay, device_fold, d_bad))) return rc;
     if (device_fold) {
-        {
-            StageTimer st(sl, "msm.seg_fold");
-            launch_seg_fold<C>(s, sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), ns, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
-        }
-        HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out + s0 * JW, sl.win.p, ns * JW * 8, hipMemcpyDeviceToHost, s));
         if (out_inf) HIPCHK(hipMemcpyAsync(out_inf + s0, sl.win_inf.p, ns, hipMemcpyDeviceToHost, s));
     } else {
-        HIPCHK(hipGetLastError());
         hwin.resize(ns * W * WW); hinf.resize(ns * W);
         HIPCHK(hipMemcpyAsync(hwin.data(), sl.l1.p, ns * W * WW * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(hinf.data(), sl.l1_inf.p, ns * W, hipMemcpyDeviceToHost, s));
@@ -202,21 +276,7 @@ int32_t msm_seg_chunk(Slot &sl, const RawBases &rb, const uint64_t *scalars, con
 }
 // The device-resident entry of a chunk (dock_bbs.hip: proofs of knowledge, whose segments' scalars are made on the device): T raw points on the device (`stride`
 // bytes apart, x then y, zero words an identity) and their canonical scalars d_sc, laid out over ns segments by `lay` (no multi-block segment: lay.pslots == 0).
-// Table, tree, device fold: the segments' normalised Jacobian results are left in sl.win, their identity flags in sl.win_inf, *d_bad |= a scalar >= 2^255.
-template <class C> int32_t ws_seg_resident(Slot &sl, size_t terms, size_t nseg, size_t blocks) {
-    int32_t rc;
-    typedef typename C::ACC A;
-    constexpr size_t W = SMALL_MSM_W, WIN_BYTES = std::max<size_t>(A::XW * 4, 4 * C::ABI_W * 4);
-    if ((rc = sl.flags.ensure(64))) return rc;
-    if ((rc = sl.prepped.ensure(terms * C::AFF_STRIDE * 4))) return rc;
-    if ((rc = sl.bucket.ensure(terms * SMALL_MSM_E * A::XW * 4))) return rc;
-    if ((rc = sl.bucket_inf.ensure(terms * SMALL_MSM_E))) return rc;
-    if ((rc = sl.entries.ensure(blocks * 64 * sizeof(SegDesc)))) return rc;
-    if ((rc = sl.l1.ensure(nseg * W * WIN_BYTES))) return rc;
-    if ((rc = sl.l1_inf.ensure(nseg * W))) return rc;
-    if ((rc = sl.win.ensure(nseg * 3 * C::ABI_W * 4))) return rc;
-    return sl.win_inf.ensure(nseg);
-}
+// Table, tree, device fold (seg_launches); the workspace is ws_seg_resident's.
 template <class C>
 int32_t seg_rows_resident(Slot &sl, const uint8_t *d_raw, size_t stride, const uint32_t *d_sc, size_t T, size_t ns, const SegLayout &lay, uint32_t *d_bad) {
     hipStream_t s = sl.stream;
@@ -226,21 +286,7 @@ int32_t seg_rows_resident(Slot &sl, const uint8_t *d_raw, size_t stride, const u
         StageTimer st(sl, "msm.prep_bases");
         launch_prep_bases_raw<C>(s, d_raw, stride, 0, (size_t)C::ABI_W * 4, msm::NO_INF_OFF, nullptr, T, sl.prepped.as<uint32_t>());
     }
-    {
-        StageTimer st(sl, "msm.small_table");
-        launch_small_table<C>(s, sl.prepped.as<uint32_t>(), T, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>());
-    }
-    {
-        StageTimer st(sl, "msm.seg_tree");
-        launch_seg_tree<C>(s, sl.bucket.as<uint32_t>(), sl.bucket_inf.as<uint8_t>(), d_sc, sl.entries.p, lay.blocks, sl.head.as<uint32_t>(), sl.part_inf.as<uint8_t>(), sl.cnt.as<uint32_t>(),
-                           sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), false, d_bad);
-    }
-    {
-        StageTimer st(sl, "msm.seg_fold");
-        launch_seg_fold<C>(s, sl.l1.as<uint32_t>(), sl.l1_inf.as<uint8_t>(), ns, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>());
-    }
-    HIPCHK(hipGetLastError());
-    return DGPU_OK;
+    return seg_launches<C>(sl, d_sc, T, ns, lay, true, d_bad);
 }
 template <class C, class HF>
 int32_t msm_segments(const uint64_t *bases, const uint8_t *is_inf, const uint64_t *scalars, size_t N, const uint64_t *seg_end, size_t nseg, int mont, uint64_t *out, uint8_t *out_inf) {
@@ -278,9 +324,7 @@ int32_t msm_segments(const uint64_t *bases, const uint8_t *is_inf, const uint64_
             mt = std::max(mt, T); ms = std::max(ms, c.s1 - c.s0); mb = std::max(mb, lay.blocks); mp = std::max(mp, lay.pslots);
         }
         int32_t rc;
-        const uint64_t allocs0 = g_dev_allocs.load();
-        if (mt && (rc = ws_seg<C>(sl, rb, mt, ms, mb, mp))) return rc;
-        if (g_dev_allocs.load() != allocs0) reserve_idle_slots(&sl, [&](Slot &o) { return ws_seg<C>(o, rb, mt, ms, mb, mp); });      // a new shape: the caller's other host threads come with it next
+        if (mt && (rc = ensure_workspace(sl, [&](Slot &o) { return ws_seg<C>(o, rb, mt, ms, mb, mp); }))) return rc;
         std::vector<uint64_t> hwin; std::vector<uint8_t> hinf;
         for (const Chunk &c : chunks) {
             const size_t T = seg_end[c.s1 - 1] - (c.s0 ? seg_end[c.s0 - 1] : 0), ns = c.s1 - c.s0;

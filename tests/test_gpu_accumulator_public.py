@@ -275,6 +275,24 @@ def test_the_single_row_route_beyond_the_many_row_kernels_reach():
     assert same(got, want) and (got[2] == want[2]).all()
 
 
+def test_identity_rows_on_the_single_row_route():
+    """three holders against an omega of 17 identities: every T_i is the identity, the rows at index 1 and 2 among them, so the witness is f_i C_i; the
+    single-row route gives the bytes of the many-row route"""
+    S = scenario()
+    na, nr = lists_for(17)
+    adds, rems, ys, C_ = S.adds[:na], S.rems[:nr], S.ys[:3], S.C[:3]
+    om = (np.zeros((17, 12), np.uint64), np.ones(17, np.uint8))
+    want = ACC.update_witnesses_public(adds, rems, om, ys, C_)
+    w0 = U.mul_add_oracle(G, C_, None, want[0], None, None)
+    assert want[2].all() and len(U.first_bad(want[1][0], want[1][1], w0[0], w0[1])) == 0
+    try:
+        assert lib().dgpu_set_small_msm_max(16) == 0
+        got = ACC.update_witnesses_public(adds, rems, om, ys, C_)
+    finally:
+        lib().dgpu_set_small_msm_max(8192)
+    assert same(got, want) and (got[2] == want[2]).all()
+
+
 def test_inputs_above_r_and_montgomery_words_give_the_same_points():
     S, adds, rems, ys, C_ = edge_case()
     om = S.omega(5, 3)

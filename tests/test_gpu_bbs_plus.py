@@ -339,6 +339,24 @@ def test_handles_the_calls_refuse():
         pre.free(); g2b.free()
 
 
+def test_a_second_call_of_a_shape_allocates_nothing():
+    """eight rows of two messages: after one warming call of each of the three calls (it readies the context's idle slots too) a second identical call
+    leaves dgpu_device_alloc_count where it was"""
+    S = scenario()
+    L, n = 2, 8
+    e, s, m = S.rows(L, n)
+    good = S.sigs(L)[:n]
+    with S.params(L) as P:
+        calls = [("sign_many", lambda: BBS.sign_many(P, S.key.x, m, e, s)[0], good), ("verify_each", lambda: BBS.verify_each(P, good, e, s, m), np.ones(n, np.uint8)),
+                 ("verify_batch", lambda: np.array([BBS.verify_batch(P, good, e, s, m, 0x5EED)]), np.array([True]))]
+        for name, call, want in calls:
+            assert (call() == want).all(), name
+            before = lib().dgpu_device_alloc_count()
+            got = call()
+            assert lib().dgpu_device_alloc_count() == before, name
+            assert (got == want).all(), name
+
+
 def test_the_b_inside_agree_with_the_many_row_msm_of_the_pieces():
     """n = 65, L = 30: b_i from a direct dgpu_msm_g1_handle_many on the rows (1, s_i, m_i ..), d_i = e_i A_i - b_i from dgpu_g1_mul_add_batch, the verdicts from
     dgpu_multi_pairing_segments — the caller's chain — equal verify_each's on rows with planted faults"""

@@ -351,6 +351,21 @@ def test_rows_longer_than_the_many_row_kernels_accept():
             lib().dgpu_set_small_msm_max(8192)
 
 
+def test_a_second_call_of_a_shape_allocates_nothing():
+    """eight proofs of two messages: after one warming call of each of the two calls (it readies the context's idle slots too) a second identical call leaves
+    dgpu_device_alloc_count where it was"""
+    S = scenario()
+    L, n = 2, 8
+    proofs, pts = S.proofs(L)[:n], S.points(L)[:n]
+    with S.params(L) as P:
+        for name, call, want in (("pok_verify_each", lambda: each(P, proofs, pts), [0] * n), ("pok_verify_batch", lambda: batch(P, proofs, pts, RHO), True)):
+            assert call() == want, name
+            before = lib().dgpu_device_alloc_count()
+            got = call()
+            assert lib().dgpu_device_alloc_count() == before, name
+            assert got == want, name
+
+
 def test_four_threads_at_once_give_the_same_bytes():
     S = scenario()
     L = 30
