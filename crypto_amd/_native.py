@@ -100,6 +100,8 @@ SYMBOLS = [
     "dgpu_fold_g1", "dgpu_fold_g2", "dgpu_lincomb_g1", "dgpu_lincomb_g2", "dgpu_multi_miller_loop", "dgpu_multi_miller_loop_sharded", "dgpu_bases_table_shape", "dgpu_scalars_sort", "dgpu_msm_g1_sorted", "dgpu_msm_g2_sorted", "dgpu_multi_miller_loop_segments", "dgpu_multi_pairing_segments", "dgpu_g2_prepare", "dgpu_multi_miller_loop_prepared", "dgpu_multi_miller_loop_mixed", "dgpu_multi_miller_loop_scaled", "dgpu_final_exponentiation", "dgpu_final_exponentiation_batch", "dgpu_g1_scale_batch", "dgpu_fp12_mul", "dgpu_fp12_pow", "dgpu_fp12_multi_pow", "dgpu_fp12_pow_batch", "dgpu_fp12_multi_pow_device", "dgpu_gt_in_subgroup_device", "dgpu_gt_in_subgroup", "dgpu_g1_serialize", "dgpu_g1_deserialize", "dgpu_g2_serialize", "dgpu_g2_deserialize", "dgpu_g1_deserialize_device", "dgpu_g2_deserialize_device", "dgpu_bases_upload_g1_serialized", "dgpu_bases_upload_g2_serialized", "dgpu_g1_validate_batch", "dgpu_g2_validate_batch", "dgpu_g1_serialize_device", "dgpu_g2_serialize_device", "dgpu_bases_read_g1", "dgpu_bases_read_g2", "dgpu_bases_serialize_g1", "dgpu_bases_serialize_g2", "dgpu_witness_map", "dgpu_r1cs_upload", "dgpu_r1cs_free", "dgpu_r1cs_shape", "dgpu_witness_map_r1cs", "dgpu_witness_map_r1cs_resident", "dgpu_witness_map_r1cs_many", "dgpu_qap_instance_map", "dgpu_legogroth16_setup",
     "dgpu_accumulator_update_factors", "dgpu_accumulator_update_witnesses_g1", "dgpu_accumulator_omega_g1", "dgpu_accumulator_update_witnesses_public_g1",
     "dgpu_accumulator_d_for_batch", "dgpu_accumulator_d_for_batch_resident", "dgpu_accumulator_non_membership_witnesses_g1", "dgpu_accumulator_membership_witnesses_g1",
+    "dgpu_accumulator_membership_proofs_verify_each_g1", "dgpu_accumulator_membership_proofs_verify_batch_g1",
+    "dgpu_accumulator_non_membership_proofs_verify_each_g1", "dgpu_accumulator_non_membership_proofs_verify_batch_g1",
     "dgpu_bbs_plus_sign_many_g1", "dgpu_bbs_plus_verify_each_g1", "dgpu_bbs_plus_verify_batch_g1", "dgpu_bbs_plus_pok_verify_each_g1", "dgpu_bbs_plus_pok_verify_batch_g1",
     "dgpu_window_table_g1", "dgpu_window_table_g2", "dgpu_window_table_free", "dgpu_window_table_mul_g1", "dgpu_window_table_mul_g2", "dgpu_window_table_mul_to_bases_g1", "dgpu_window_table_mul_to_bases_g2", "dgpu_fixed_base_g1", "dgpu_fixed_base_g2", "dgpu_g1_mul_add_batch", "dgpu_g2_mul_add_batch",
     "dgpu_legogroth16_prove", "dgpu_legogroth16_prove_host", "dgpu_legogroth16_verify", "dgpu_legogroth16_verify_batch", "dgpu_legogroth16_verify_each", "dgpu_handle_len", "dgpu_handle_context", "dgpu_shard_count", "dgpu_shard_part",
@@ -283,6 +285,10 @@ def _load(path):
         L.dgpu_accumulator_d_for_batch_resident.argtypes = [C.c_uint64, sz, sz, vp, sz, C.c_int32, vp, vp, vp]
         L.dgpu_accumulator_non_membership_witnesses_g1.argtypes = [vp, vp, sz, vp, vp, vp, C.c_int32, vp, vp, vp]
         L.dgpu_accumulator_membership_witnesses_g1.argtypes = [vp, sz, vp, vp, C.c_int32, vp, vp]
+        L.dgpu_accumulator_membership_proofs_verify_each_g1.argtypes = [vp, vp, vp, vp, vp, vp, sz, C.c_int32, vp]
+        L.dgpu_accumulator_membership_proofs_verify_batch_g1.argtypes = [vp, vp, vp, vp, vp, vp, sz, C.c_int32, vp, C.POINTER(C.c_int32)]
+        L.dgpu_accumulator_non_membership_proofs_verify_each_g1.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_int32, vp]
+        L.dgpu_accumulator_non_membership_proofs_verify_batch_g1.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_int32, vp, C.POINTER(C.c_int32)]
         L.dgpu_bbs_plus_sign_many_g1.argtypes = [u64, sz, vp, vp, sz, vp, vp, sz, C.c_int32, vp, vp]
         L.dgpu_bbs_plus_verify_each_g1.argtypes = [u64, sz, vp, vp, vp, vp, vp, vp, sz, sz, C.c_int32, vp]
         L.dgpu_bbs_plus_verify_batch_g1.argtypes = [u64, sz, vp, vp, vp, vp, vp, vp, sz, sz, C.c_int32, vp, C.POINTER(C.c_int32)]

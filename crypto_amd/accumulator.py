@@ -19,6 +19,15 @@
     PositiveAccumulator::compute_membership_witnesses_for_batch(members, sk) (positive.rs:369-381)
         -> membership_witnesses(members, alpha, accumulator)                                returns (points, identity_mask)
 
+    MembershipProof::verify(V, challenge, pk, params), n times (vb_accumulator/src/proofs_cdh.rs:138-149)
+        -> membership_proofs_verify_each(key, accumulator, points, responses, challenge)      returns status, one byte per proof
+    the same with one verdict for all                          -> membership_proofs_verify_batch(.., random)       returns True / False
+    NonMembershipProof::verify(V, challenge, pk, params, Q), n times (proofs_cdh.rs:365-387, :481-523)
+        -> non_membership_proofs_verify_each(key, accumulator, P, Q, points, responses, challenge)
+    the same with one verdict for all                          -> non_membership_proofs_verify_batch(.., random)
+    proof.challenge_contribution(V, writer) / (V, params, Q, writer)
+        -> membership_challenge_contribution(accumulator, proof_points) / non_membership_challenge_contribution(accumulator, P, Q, proof_points)     return bytes
+
 Field elements are (n, 4) uint64 limb arrays or Python ints, canonical unless `montgomery=True` (then ark-ff Montgomery limbs in and out).  Witnesses
 and the accumulator are G1 affine Montgomery limbs, (m, 12) and (12,) uint64; an identity is all-zero words.  New witnesses come back normalised
 (G::Group::normalize_batch, witness.rs:284) as an (m, 12) array plus a uint8 identity mask: a holder whose element was removed gets d_factor = 0 and
@@ -199,3 +208,110 @@ def get_non_membership_witnesses_for_batch(members, non_members, f_V, alpha, par
     if not ok.all():
         raise ValueError("CannotBeZero")
     return d, wits
+
+
+# ---- the CDH proofs of membership and non-membership in bulk (vb_accumulator/src/proofs_cdh.rs) ------------------------------------------------------------
+MEMBERSHIP_STATUS = {0: "verified", 1: "InvalidProof: A' is the identity", 2: "InvalidProof: the Schnorr check", 3: "InvalidProof: the pairing"}
+NON_MEMBERSHIP_STATUS = {0: "verified", 1: "CannotBeZero: C' is the identity", 2: "CannotBeZero: J is the identity", 3: "IncorrectRandomizedWitness: J over Q",
+                         4: "SchnorrError(InvalidResponse)", 5: "IncorrectRandomizedWitness: the pairing"}
+
+
+class VerifierKey:
+    """The verifier's half of an accumulator key, prepared once: the coefficients of pk = alpha P~ and of P~ (SetupParams.P_tilde), as bbs_plus.Params holds
+    those of w and g2."""
+
+    def __init__(self, pk, p_tilde):
+        from .pairing import G2Prepared
+        _ensure()
+        pc = G2Prepared.from_affine(np.stack([np.asarray(pk, dtype=np.uint64).reshape(24), np.asarray(p_tilde, dtype=np.uint64).reshape(24)]))
+        self.pk_pc, self.ptilde_pc = np.ascontiguousarray(pc.coeffs[0]), np.ascontiguousarray(pc.coeffs[1])
+
+
+def _point(p):
+    return np.ascontiguousarray(p, dtype=np.uint64).reshape(12)
+
+
+def _acc_proofs(points, npts, responses, nresp, challenge):
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, npts, 12)
+    n = len(pts)
+    flat = responses if isinstance(responses, np.ndarray) and responses.dtype == np.uint64 else [z for r in responses for z in r]
+    resp = _scalars_to_limbs(flat).reshape(-1, nresp, 4) if n else np.zeros((0, nresp, 4), np.uint64)
+    c = _scalars_to_limbs(challenge) if n else np.zeros((0, 4), np.uint64)
+    if not (len(resp) == len(c) == n):
+        raise ValueError("%d proofs' points, %d rows of responses, %d challenges" % (n, len(resp), len(c)))
+    return n, pts, resp, c
+
+
+def _each(name, head, n, pts, resp, c, montgomery):
+    status = np.zeros(n, np.uint8)
+    rc = getattr(lib(), name)(*head, _p(pts) if n else None, _p(resp) if n else None, _p(c) if n else None, n, 1 if montgomery else 0, _p(status) if n else None)
+    if rc:
+        raise DockGpuError(rc, name)
+    return status
+
+
+def _batch(name, head, n, pts, resp, c, random, montgomery):
+    rho = _scalars_to_limbs([random] if isinstance(random, int) else random).reshape(4)
+    ok = C.c_int32(0)
+    rc = getattr(lib(), name)(*head, _p(pts) if n else None, _p(resp) if n else None, _p(c) if n else None, n, 1 if montgomery else 0, _p(rho), C.byref(ok))
+    if rc:
+        raise DockGpuError(rc, name)
+    return bool(ok.value)
+
+
+def membership_proofs_verify_each(key, accumulator, points, responses, challenge, montgomery=False):
+    """status, an (n,) uint8 array: 0 where MembershipProof::verify accepts proof i against the accumulator value V, else the first failing check in the
+    reference's order (MEMBERSHIP_STATUS): 1 A' is the identity, 2 z1 V - z2 A' - c Abar = T, 3 e(A', pk) e(-Abar, P~) = 1.
+
+    points: (n, 3, 12), A', Abar, T (sc.t).  responses: (n, 2) scalars z1 (response1, over V) and z2 (response2, over -A'; for a partial proof the caller
+    writes resp_for_element there).  The points are taken as validated members of the subgroup, as the reference takes them (crypto_amd.serde.validate)."""
+    _ensure()
+    n, pts, resp, c = _acc_proofs(points, 3, responses, 2, challenge)
+    return _each("dgpu_accumulator_membership_proofs_verify_each_g1", (_p(_point(accumulator)), _p(key.pk_pc), _p(key.ptilde_pc)), n, pts, resp, c, montgomery)
+
+
+def membership_proofs_verify_batch(key, accumulator, points, responses, challenge, random, montgomery=False):
+    """True iff every proof verifies, by ONE G1 equation and one pairing check over the random linear combination with the weights random^i (random non-zero
+    modulo r; an empty batch verifies; an identity A' anywhere refuses)"""
+    _ensure()
+    n, pts, resp, c = _acc_proofs(points, 3, responses, 2, challenge)
+    return _batch("dgpu_accumulator_membership_proofs_verify_batch_g1", (_p(_point(accumulator)), _p(key.pk_pc), _p(key.ptilde_pc)), n, pts, resp, c, random, montgomery)
+
+
+def non_membership_proofs_verify_each(key, accumulator, P, Q, points, responses, challenge, montgomery=False):
+    """status, an (n,) uint8 array: 0 where NonMembershipProof::verify accepts proof i, else the first failing check in the reference's order
+    (NON_MEMBERSHIP_STATUS): 1 C' is the identity, 2 J is, 3 s_d Q - c J = T2, 4 s_r V - s_y C' - s_d P - c Cbar = T1, 5 e(C', pk) e(-Cbar, P~) = 1.
+
+    P: params.P; Q: the second generator.  points: (n, 5, 12), C', Cbar, J, T1 (t_1), T2 (sc_2.t).  responses: (n, 3) scalars s_r, s_y (responses 0 and 1 of
+    sc_resp_1; for a partial proof the caller writes resp_for_element into s_y) and s_d (sc_2.response)."""
+    _ensure()
+    n, pts, resp, c = _acc_proofs(points, 5, responses, 3, challenge)
+    head = (_p(_point(accumulator)), _p(_point(P)), _p(_point(Q)), _p(key.pk_pc), _p(key.ptilde_pc))
+    return _each("dgpu_accumulator_non_membership_proofs_verify_each_g1", head, n, pts, resp, c, montgomery)
+
+
+def non_membership_proofs_verify_batch(key, accumulator, P, Q, points, responses, challenge, random, montgomery=False):
+    """True iff every proof verifies, by ONE G1 equation and one pairing check: the weights random^(2i) on check 4 of proof i, random^(2i+1) on check 3,
+    random^i on the pairing (random non-zero modulo r; an empty batch verifies; an identity C' or J anywhere refuses)"""
+    _ensure()
+    n, pts, resp, c = _acc_proofs(points, 5, responses, 3, challenge)
+    head = (_p(_point(accumulator)), _p(_point(P)), _p(_point(Q)), _p(key.pk_pc), _p(key.ptilde_pc))
+    return _batch("dgpu_accumulator_non_membership_proofs_verify_batch_g1", head, n, pts, resp, c, random, montgomery)
+
+
+def membership_challenge_contribution(accumulator, proof_points):
+    """The bytes PoKOfSignatureG1Protocol::compute_challenge_contribution writes for one membership proof (short_group_sig/src/weak_bb_sig_pok_cdh.rs:129-141):
+    Abar, A', V, T compressed.  proof_points: (3, 12) = A', Abar, T.  Hashing the bytes to a challenge stays with the caller."""
+    from . import serde
+    from .msm import G1
+    Q = np.ascontiguousarray(proof_points, dtype=np.uint64).reshape(3, 12)
+    return serde.serialize(G1, np.stack([Q[1], Q[0], _point(accumulator), Q[2]]))
+
+
+def non_membership_challenge_contribution(accumulator, P, Q, proof_points):
+    """The bytes NonMembershipProofProtocol::compute_challenge_contribution writes for one proof (proofs_cdh.rs:326-346): Cbar, C', J, V, P, Q, T1, T2
+    compressed.  proof_points: (5, 12) = C', Cbar, J, T1, T2."""
+    from . import serde
+    from .msm import G1
+    W = np.ascontiguousarray(proof_points, dtype=np.uint64).reshape(5, 12)
+    return serde.serialize(G1, np.stack([W[1], W[0], W[2], _point(accumulator), _point(P), _point(Q), W[3], W[4]]))

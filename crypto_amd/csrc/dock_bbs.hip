@@ -34,15 +34,14 @@
 #include "bbs_launch.hip.h"
 #include "bbs_pok_launch.hip.h"
 #include "acc_host_tables.hpp"
+#include "pair_check.hip.h"             // zero_words, ws_check, coeffs_up, launch_check, add_jac, merged_pair_verdict: shared with dock_acc_pok.hip
 using namespace dock;
 using namespace acch;
 using namespace mlk;
 
 namespace {
 
-bool zero_words(const uint64_t *w, int k) { uint64_t o = 0; for (int i = 0; i < k; i++) o |= w[i]; return o == 0; }
-
-constexpr size_t PT = 96;                 // bytes of an affine G1 point of the ABI
+constexpr size_t PT = 96;                // bytes of an affine G1 point of the ABI
 constexpr size_t NPTS = 5;                // points of a proof of knowledge: A', Abar, d, T1, T2
 
 // what the three calls share: the rows' inputs and how they are cut
@@ -130,37 +129,7 @@ int32_t sign_many(uint64_t params, const uint64_t *sk, const Rows &r, uint64_t *
     return DGPU_OK;
 }
 
-// ---- the pairing check of m = `cols` rows on the device: e(P1_i, w) e(P2_i, g2) == 1 ----------------------------------------------------------------------------
-// dP: [P1 | P2], cols affine points each; dsk: their skip flags in the same order (an identity contributes one, as everywhere in the library).  The coefficients
-// of w and g2 are in sl.ml_coeffs, the wanted value (one) behind the Miller outputs in sl.ml_out.  Verdicts: sl.flags.
-int32_t ws_check(Slot &o, size_t cols) {
-    int32_t e;
-    if ((e = o.ml_coeffs.ensure(2 * (size_t)DGPU_G2_PREPARED_WORDS * 8 + 16))) return e;
-    if ((e = o.ml_lines.ensure((size_t)N_LINES * LW * 2 * cols * 4))) return e;
-    if ((e = o.ml_partial.ensure((size_t)N_LINES * cols * F12W * 4))) return e;
-    if ((e = o.ml_out.ensure(cols * 576 + 576))) return e;
-    return o.flags.ensure(std::max<size_t>(cols, 64));
-}
-int32_t coeffs_up(Slot &sl, const uint64_t *pk_pc, const uint64_t *g2_pc, size_t cols) {
-    const size_t cw = (size_t)DGPU_G2_PREPARED_WORDS;
-    static const hostf::Fq12 one = hostf::Fq12::one();
-    HIPCHK(hipMemcpyAsync(sl.ml_coeffs.p, pk_pc, cw * 8, hipMemcpyHostToDevice, sl.stream));
-    HIPCHK(hipMemcpyAsync(sl.ml_coeffs.as<uint64_t>() + cw, g2_pc, cw * 8, hipMemcpyHostToDevice, sl.stream));
-    HIPCHK(hipMemcpyAsync(sl.ml_out.as<uint8_t>() + cols * 576, &one, 576, hipMemcpyHostToDevice, sl.stream));
-    return DGPU_OK;
-}
-void launch_check(Slot &sl, const uint32_t *dP1, const uint32_t *dP2, const uint8_t *dsk, size_t m, size_t cols) {
-    hipStream_t s = sl.stream;
-    const size_t cw = (size_t)DGPU_G2_PREPARED_WORDS, np = 2 * m;
-    uint32_t *lines = sl.ml_lines.as<uint32_t>(), *fout = sl.ml_out.as<uint32_t>();
-    { StageTimer st(sl, "bbs.lines");
-      launch_lines_from_prepared(s, dP1, sl.ml_coeffs.as<uint32_t>(), dsk, m, lines, np, nullptr, true);
-      launch_lines_from_prepared(s, dP2, sl.ml_coeffs.as<uint32_t>() + cw * 2, dsk + m, m, lines + m, np, nullptr, true); }
-    // one "segment" of 2 m pairs with slices of 2: slice i is the pairs i and i + m, i.e. the two lines of row i
-    { StageTimer st(sl, "bbs.products"); launch_line_products(s, gs.ml_mode.load(), lines, np, 2, (int)m, sl.ml_partial.as<uint32_t>(), nullptr, 1, 0, N_LINES, nullptr, false); }
-    { StageTimer st(sl, "bbs.tail"); gtk::launch_miller_tail(s, sl.ml_partial.as<uint32_t>(), m, fout); }
-    { StageTimer st(sl, "bbs.final_exp"); gtk::launch_final_exp(s, fout, m, (uint32_t *)nullptr, (uint8_t *)nullptr, fout + cols * 144, sl.flags.as<uint8_t>()); }
-}
+// (the pairing check of a chunk's rows — ws_check, coeffs_up, launch_check — is pair_check.hip.h's)
 
 // (k1 | k2) of -e mod r: the scalar of the kernel that returns -((-e) A + b)
 void neg_split(const uint64_t *e, bool mont, uint64_t *out) {
@@ -239,15 +208,8 @@ int32_t verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_p
     return DGPU_OK;
 }
 
-// ---- one verdict for n rows: the random linear combination RandomizedPairingChecker forms (utils/src/randomized_pairing_check.rs), merged before the pairing ----------
-typedef hostf::HXyzz<hostf::Fq> HPoint;
-void add_jac(HPoint &acc, const uint64_t *jac) {
-    if (jac_is_identity(jac, 18)) return;
-    hostf::Fq x, y, z; memcpy(&x, jac, 48); memcpy(&y, jac + 6, 48); memcpy(&z, jac + 12, 48);
-    const hostf::Fq zz = z * z;
-    HPoint p; p.x = x; p.y = y; p.zz = zz; p.zzz = zz * z; p.inf = false;
-    acc.add_in_place(p);
-}
+// ---- one verdict for n rows: the random linear combination RandomizedPairingChecker forms (utils/src/randomized_pairing_check.rs), merged before the pairing
+// (HPoint, add_jac and merged_pair_verdict: pair_check.hip.h) ----------
 // rows per chunk of the batch calls: their kernels' cap and BBS_BATCH_TERMS scalars (dgpu_set_many_chunk_rows of the development surface cuts these calls' rows too)
 size_t batch_chunk(size_t n, size_t L, size_t cap) {
     const int forced = gs.many_chunk.load();
@@ -261,33 +223,6 @@ int32_t params_msm(Slot &sl, uint64_t params, const Handle &h, const uint32_t *d
     const bool have = small_sub_for<G1>(sl, params, h, 0, nn, sub, true);
     if ((rc = msm_device<G1, hostf::Fq>(sl, (const uint32_t *)h.p, d_c, nn, jac, have ? &sub : nullptr))) return rc;
     add_jac(acc, jac);
-    return DGPU_OK;
-}
-// *ok = [e(P1, w) e(P2, g2) == 1] for the two merged points of a batch (an identity member is skipped); scratch: 2 PT + 64 bytes of the slot
-int32_t merged_pair_verdict(Slot &sl, const HPoint &P1, const HPoint &P2, const uint64_t *pk_pc, const uint64_t *g2_pc, Buf &scratch, int32_t *ok) {
-    hipStream_t s = sl.stream;
-    int32_t rc;
-    uint64_t pts[24 + 8] = {0};
-    uint8_t *sk = (uint8_t *)(pts + 24);
-    for (int k = 0; k < 2; k++) {
-        const HPoint &P = k ? P2 : P1;
-        sk[k] = P.inf ? 1 : 0;
-        if (P.inf) continue;
-        hostf::Fq X, Y, Z; P.to_normalised_jacobian(X, Y, Z);
-        memcpy(pts + 12 * k, &X, 48); memcpy(pts + 12 * k + 6, &Y, 48);
-    }
-    uint8_t verdict = 0;
-    DrainUnlessDone own(sl);                                             // (pts and verdict are this frame's)
-    uint32_t *dP = scratch.as<uint32_t>();
-    HIPCHK(hipMemcpyAsync(dP, pts, sizeof pts, hipMemcpyHostToDevice, s));
-    if ((rc = coeffs_up(sl, pk_pc, g2_pc, 1))) return rc;
-    launch_check(sl, dP, dP + 24, (const uint8_t *)(dP + 48), 1, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&verdict, sl.flags.p, 1, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    own.done = true;
-    if (gs.prof) prof_flush(sl);
-    *ok = verdict ? 1 : 0;
     return DGPU_OK;
 }
 int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const Rows &r, const uint64_t *random, int32_t *ok) {

@@ -622,6 +622,68 @@ int32_t dgpu_accumulator_non_membership_witnesses_g1(const uint64_t *d /* m*4 */
 int32_t dgpu_accumulator_membership_witnesses_g1(const uint64_t *members /* m*4 */, size_t m, const uint64_t alpha[4], const uint64_t accumulator_xy[12],
                                                  int32_t montgomery, uint64_t *out_xy /* m*12 */, uint8_t *out_inf /* m */);
 
+/* ---- accumulator proofs in bulk: a status per proof, or one verdict (crypto_amd/csrc/dock_acc_pok.hip, acc_pok_kernels.hip.h) ----
+ * The CDH proofs of the VB accumulator (vb_accumulator/src/proofs_cdh.rs: MembershipProof::verify :138-149, NonMembershipProof::verify with
+ * verify_except_pairing :365-387, :481-523, over short_group_sig/src/weak_bb_sig_pok_cdh.rs:145-287, schnorr_pok/src/discrete_log.rs:247-253 and
+ * schnorr_pok/src/partial.rs:149-166) for n proofs against ONE accumulator value V and one key: the revocation half of what the verifier of presentations runs
+ * per credential shown (the BBS+ half: dgpu_bbs_plus_pok_verify_each_g1 below).  A verifier groups its presentations by accumulator epoch; per-row accumulator
+ * values are not served.  The KB universal accumulator's CDH proofs wrap the same MembershipProof (kb_universal_accumulator/proofs_cdh.rs), so the membership
+ * calls serve both of its proof kinds.
+ *   accumulator_xy, p_xy, q_xy   V, params.P and Q: 12 words each, affine Montgomery coordinates; all-zero words are the identity
+ *   pk_pc, ptilde_pc  the prepared coefficients (DGPU_G2_PREPARED_WORDS words each, dgpu_g2_prepare / ark-ec G2Prepared) of pk = alpha P~ and of P~
+ *   points       membership: n x 3 x 12 words, A', Abar, T (sc.t) of proof i at points + 36 i
+ *                non-membership: n x 5 x 12 words, C', Cbar, J, T1 (t_1), T2 (sc_2.t) of proof i at points + 60 i
+ *   responses    membership: n x 2 scalars, z1 (sc.response1, over V) and z2 (sc.response2, over -A')
+ *                non-membership: n x 3 scalars, s_r and s_y (responses 0 and 1 of sc_resp_1) and s_d (sc_2.response, also response 2 of the first relation)
+ *                A partial proof (verify_partial, resp_for_element) needs no path of its own: the caller writes the element's response into z2 or s_y
+ *   challenge    n scalars.  montgomery != 0: ark-ff `&[Fr]` limbs; else canonical words, any 256-bit value counting modulo r
+ * The reference's checks, in the order it returns their errors:
+ *   membership        1  A' != O                                                      else InvalidProof
+ *                     2  z1 V - z2 A' - c Abar - T = O                                else InvalidProof
+ *                     3  e(A', pk) e(-Abar, P~) = 1                                   else InvalidProof        (the reference's e(Abar, P~) e(-A', pk) = 1 inverted)
+ *   non-membership    1  C' != O                                                      else CannotBeZero
+ *                     2  J != O                                                       else CannotBeZero
+ *                     3  s_d Q - c J - T2 = O                                         else IncorrectRandomizedWitness
+ *                     4  s_r V - s_y C' - s_d P - c Cbar - T1 = O                     else SchnorrError(InvalidResponse)
+ *                     5  e(C', pk) e(-Cbar, P~) = 1                                   else IncorrectRandomizedWitness
+ *
+ * The two ..._verify_each_g1 calls write status[i] = 0 (verified) or the number of the FIRST check that fails.  Per chunk of rows one device pipeline: the own
+ * scalars (z1, -z2, -c, -1), respectively (s_d, -c, -1 | s_r, -s_y, -s_d, -c, -1) (k_acc_pok_own), the bases [V, A', Abar, T], respectively
+ * [Q, J, T2 | V, C', P, Cbar, T1] and the two sides of the pairing (k_acc_pok_stage: the shared points are copied into every row, -Abar is a flip of y), one
+ * 4-term segment per row, respectively a 3-term and a 5-term one, of the segmented small MSM, the two-pair pairing check with the shared lines of pk and P~, and
+ * k_acc_pok_verdict; only the n status bytes come back.
+ *
+ * The two ..._verify_batch_g1 calls: ONE verdict.  With rho = random (rho = 0 mod r: DGPU_E_BADARG, decided on the host); an identity A', C' or J anywhere gives
+ * *ok = 0, decided on the host on the zero words.  Membership, u_i = t_i = rho^i: *ok = 1 iff
+ *     (sum u_i z1_i) V + sum_i [ -u_i z2_i A'_i - u_i c_i Abar_i - u_i T_i ] = O      and      e(sum t_i A'_i, pk) e(-sum t_i Abar_i, P~) = 1
+ * Non-membership, u_i = rho^(2i) on check 4, v_i = rho^(2i+1) on check 3, t_i = rho^i on the pairing: *ok = 1 iff
+ *     (sum u_i s_r_i) V - (sum u_i s_d_i) P + (sum v_i s_d_i) Q + sum_i [ -u_i s_y_i C'_i - u_i c_i Cbar_i - v_i c_i J_i - u_i T1_i - v_i T2_i ] = O
+ *     e(sum t_i C'_i, pk) e(-sum t_i Cbar_i, P~) = 1
+ * — the one (three) shared-point coefficients and every weight on the device (k_acc_pok_col_sums, k_acc_pok_col_finish: two passes, no atomics), one variable-base
+ * MSM over the chunk's 3 n (5 n) own points and one each over the two pairing sides, ONE small MSM over the shared points, one two-pair Miller loop and final
+ * exponentiation.  n = 0 gives *ok = 1.  For a random rho a batch with a failing proof passes with probability at most 2n / r per equation; rho = 1 adds the rows
+ * up unweighted, so errors that cancel between rows pass, as they would in the reference with that scalar.
+ *
+ * All four take the points as members of the prime-order subgroup, as the reference does after deserialising with validation: validate untrusted ones first
+ * (dgpu_g1_validate_batch).  n = 0 is DGPU_OK without touching a device or any pointer; with n > 0 a NULL pointer or n >= 2^31 is DGPU_E_BADARG before the device
+ * is looked at; then DGPU_E_NODEVICE.  Never DGPU_E_TOO_SMALL.  Thread-safe; one slot per call; a second call of a shape allocates nothing.  Chunks: each 4096
+ * rows (91 KB of lines and products per row), batch 65536; the development surface's dgpu_set_many_chunk_rows cuts both.  Nothing secret passes through.  Stage
+ * timers acc.pok_own, acc.pok_stage, acc.pok_verdict, acc.pok_columns beside bbs.lines .. bbs.final_exp (the shared pairing check) and those of the MSMs. */
+int32_t dgpu_accumulator_membership_proofs_verify_each_g1(const uint64_t accumulator_xy[12], const uint64_t *pk_pc, const uint64_t *ptilde_pc,
+                                                          const uint64_t *points /* n*36 */, const uint64_t *responses /* n*8 */,
+                                                          const uint64_t *challenge /* n*4 */, size_t n, int32_t montgomery, uint8_t *status /* n */);
+int32_t dgpu_accumulator_membership_proofs_verify_batch_g1(const uint64_t accumulator_xy[12], const uint64_t *pk_pc, const uint64_t *ptilde_pc,
+                                                           const uint64_t *points /* n*36 */, const uint64_t *responses /* n*8 */,
+                                                           const uint64_t *challenge /* n*4 */, size_t n, int32_t montgomery, const uint64_t random[4], int32_t *ok);
+int32_t dgpu_accumulator_non_membership_proofs_verify_each_g1(const uint64_t accumulator_xy[12], const uint64_t p_xy[12], const uint64_t q_xy[12],
+                                                              const uint64_t *pk_pc, const uint64_t *ptilde_pc, const uint64_t *points /* n*60 */,
+                                                              const uint64_t *responses /* n*12 */, const uint64_t *challenge /* n*4 */, size_t n,
+                                                              int32_t montgomery, uint8_t *status /* n */);
+int32_t dgpu_accumulator_non_membership_proofs_verify_batch_g1(const uint64_t accumulator_xy[12], const uint64_t p_xy[12], const uint64_t q_xy[12],
+                                                               const uint64_t *pk_pc, const uint64_t *ptilde_pc, const uint64_t *points /* n*60 */,
+                                                               const uint64_t *responses /* n*12 */, const uint64_t *challenge /* n*4 */, size_t n,
+                                                               int32_t montgomery, const uint64_t random[4], int32_t *ok);
+
 /* ---- BBS+ signatures in bulk: sign many, verify many, a verdict per signature or one for all (crypto_amd/csrc/dock_bbs.hip, bbs_kernels.hip.h) ----
  * SignatureG1 / SignatureParamsG1 / PublicKeyG2 of bbs_plus/src/signature.rs:138-296 for n signatures of ONE key, each call one device pipeline per chunk
  * of rows instead of the caller's chain dgpu_msm_g1_handle_many -> dgpu_g1_mul_add_batch -> dgpu_multi_pairing_segments with a PCIe round trip between each.

@@ -288,6 +288,39 @@ pub(crate) fn raw_accumulator_membership_witnesses(members: &[Fr], alpha: &Fr, a
     unsafe { dgpu_accumulator_membership_witnesses_g1(members.as_ptr() as *const u64, members.len(), alpha as *const Fr as *const u64, v.as_ptr(), 1, xy.as_mut_ptr(), inf.as_mut_ptr()) }
 }
 
+// ---- accumulator proofs in bulk: the raw callers behind src/accumulator_proofs.rs (the typed API and its documentation live there) ------------------------------
+/// `MembershipProof::verify` per proof: `status[i]` = 0, or the first failing check (1 A' is the identity, 2 the Schnorr check, 3 the pairing).  `points`: n x 3 x 12
+/// words (A', Abar, T); `responses`: n x 2 (z1, z2); `pk_pc`, `ptilde_pc`: the prepared coefficients of `pk` and `P~`
+pub(crate) fn raw_accumulator_membership_proofs_verify_each(accumulator: &G1Affine, pk_pc: &[u64], ptilde_pc: &[u64], points: &[u64], responses: &[Fr], challenge: &[Fr],
+                                                            status: &mut [u8]) -> i32 {
+    let (v, _) = pack_g1(core::slice::from_ref(accumulator));           // identity: zero words
+    unsafe { dgpu_accumulator_membership_proofs_verify_each_g1(v.as_ptr(), pk_pc.as_ptr(), ptilde_pc.as_ptr(), points.as_ptr(), responses.as_ptr() as *const u64,
+                                                               challenge.as_ptr() as *const u64, challenge.len(), 1, status.as_mut_ptr()) }
+}
+/// one verdict for all membership proofs under the weights `random^i`
+pub(crate) fn raw_accumulator_membership_proofs_verify_batch(accumulator: &G1Affine, pk_pc: &[u64], ptilde_pc: &[u64], points: &[u64], responses: &[Fr], challenge: &[Fr],
+                                                             random: &Fr, ok: &mut i32) -> i32 {
+    let (v, _) = pack_g1(core::slice::from_ref(accumulator));
+    unsafe { dgpu_accumulator_membership_proofs_verify_batch_g1(v.as_ptr(), pk_pc.as_ptr(), ptilde_pc.as_ptr(), points.as_ptr(), responses.as_ptr() as *const u64,
+                                                                challenge.as_ptr() as *const u64, challenge.len(), 1, random as *const Fr as *const u64, ok) }
+}
+/// `NonMembershipProof::verify` per proof: `status[i]` = 0, or 1 C' is the identity, 2 J is, 3 the check of J over Q, 4 the five-term check, 5 the pairing.
+/// `points`: n x 5 x 12 words (C', Cbar, J, T1, T2); `responses`: n x 3 (s_r, s_y, s_d)
+pub(crate) fn raw_accumulator_non_membership_proofs_verify_each(accumulator: &G1Affine, p: &G1Affine, q: &G1Affine, pk_pc: &[u64], ptilde_pc: &[u64], points: &[u64],
+                                                                responses: &[Fr], challenge: &[Fr], status: &mut [u8]) -> i32 {
+    let (w, _) = pack_g1(&[*accumulator, *p, *q]);
+    unsafe { dgpu_accumulator_non_membership_proofs_verify_each_g1(w.as_ptr(), w[12..].as_ptr(), w[24..].as_ptr(), pk_pc.as_ptr(), ptilde_pc.as_ptr(), points.as_ptr(),
+                                                                   responses.as_ptr() as *const u64, challenge.as_ptr() as *const u64, challenge.len(), 1, status.as_mut_ptr()) }
+}
+/// one verdict for all non-membership proofs under the weights `random^(2i)`, `random^(2i+1)`, `random^i`
+pub(crate) fn raw_accumulator_non_membership_proofs_verify_batch(accumulator: &G1Affine, p: &G1Affine, q: &G1Affine, pk_pc: &[u64], ptilde_pc: &[u64], points: &[u64],
+                                                                 responses: &[Fr], challenge: &[Fr], random: &Fr, ok: &mut i32) -> i32 {
+    let (w, _) = pack_g1(&[*accumulator, *p, *q]);
+    unsafe { dgpu_accumulator_non_membership_proofs_verify_batch_g1(w.as_ptr(), w[12..].as_ptr(), w[24..].as_ptr(), pk_pc.as_ptr(), ptilde_pc.as_ptr(), points.as_ptr(),
+                                                                    responses.as_ptr() as *const u64, challenge.as_ptr() as *const u64, challenge.len(), 1,
+                                                                    random as *const Fr as *const u64, ok) }
+}
+
 // ---- BBS+ signatures in bulk: the raw callers behind src/bbs_plus.rs (the typed API and its documentation live there) -------------------------------------
 /// `A_i = (sk + e_i)^-1 (g1 + s_i h_0 + sum_j m_ij h_j)`; `params`: a plain bases handle holding `[g1, h_0, h ..]`, `messages`: n rows of `l`, packed;
 /// `out_a`: n x 12 words, `bad`: n bytes

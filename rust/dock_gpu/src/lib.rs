@@ -30,6 +30,8 @@ pub mod encode;
 pub mod generic;
 pub mod host;
 pub mod accumulator_issue;      // (issuing membership / non-membership witnesses: src/accumulator_issue.rs; cargo-side cases in tests/parity_accumulator_issue.rs)
+#[cfg(feature = "vb-accumulator")]
+pub mod accumulator_proofs;     // (verifying membership / non-membership proofs in bulk behind the reference's own types: src/accumulator_proofs.rs; the case in tests/parity.rs runs under the same feature)
 #[cfg(feature = "bbs-plus")]
 pub mod bbs_plus;               // (BBS+ signatures in bulk behind the reference's own types: src/bbs_plus.rs; the case in tests/parity.rs runs under the same feature)
 

@@ -809,3 +809,79 @@ fn bbs_plus_pok_bulk_equals_the_reference() {
         assert_eq!(pok_verify_batch(&gp, &bad, &maps, &bad_c, None, &rho), Some(false));
     }
 }
+
+// accumulator proofs in bulk against the reference's own MembershipProof::verify and NonMembershipProof::verify (vb_accumulator/src/proofs_cdh.rs:138-149, :365-387):
+// the same Ok / first error, proof by proof; one verdict for the batch
+#[cfg(feature = "vb-accumulator")]
+#[test]
+fn accumulator_proofs_bulk_equal_the_reference() {
+    use ark_ff::Field;
+    use dock_gpu::accumulator_proofs::{membership_verify_batch, membership_verify_each, non_membership_verify_batch, non_membership_verify_each, GpuAccumulatorVerifier};
+    use vb_accumulator::proofs_cdh::{MembershipProof, MembershipProofProtocol, NonMembershipProof, NonMembershipProofProtocol};
+    use vb_accumulator::setup::{Keypair, SetupParams};
+    use vb_accumulator::witness::{MembershipWitness, NonMembershipWitness};
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5EED0ACC);
+    let params = SetupParams::<Bls12_381>::generate_using_rng(&mut rng);
+    let keypair = Keypair::<Bls12_381>::generate_using_rng(&mut rng, &params);
+    let alpha = keypair.secret_key.0;
+    let key = GpuAccumulatorVerifier::new(&params, &keypair.public_key).expect("key");
+    let v = (params.P * Fr::rand(&mut rng)).into_affine();
+    let q = G1Affine::rand(&mut rng);
+    for &n in &[3usize, 65, 257] {
+        // membership: C = 1 / (y + alpha) V
+        let (mut proofs, mut challenges): (Vec<MembershipProof<Bls12_381>>, Vec<Fr>) = (vec![], vec![]);
+        for _ in 0..n {
+            let y = Fr::rand(&mut rng);
+            let wit = MembershipWitness((v * (y + alpha).inverse().unwrap()).into_affine());
+            let c = Fr::rand(&mut rng);
+            proofs.push(MembershipProofProtocol::<Bls12_381>::init(&mut rng, y, None, &v, &wit).gen_proof(&c).unwrap());
+            challenges.push(c);
+        }
+        let rho = Fr::rand(&mut rng);
+        assert!(membership_verify_each(&key, &v, &proofs, &challenges, None).expect("membership_verify_each").iter().all(|r| r.is_ok()), "n = {n}");
+        assert_eq!(membership_verify_batch(&key, &v, &proofs, &challenges, None, &rho), Some(true));
+        let (mut bad, mut bad_c) = (proofs.clone(), challenges.clone());
+        bad[0].0.sc.as_mut().unwrap().response1 += Fr::from(1u64);
+        bad[1].0.A_prime = G1Affine::zero();
+        let (a, b) = (bad[2].0.A_prime, bad[2].0.A_bar);
+        bad[2].0.A_bar = (b + a).into_affine();
+        if n > 3 { bad_c[3] += Fr::from(1u64); }
+        let mine = membership_verify_each(&key, &v, &bad, &bad_c, None).expect("membership_verify_each");
+        for i in 0..n {
+            let theirs = bad[i].verify(&v, &bad_c[i], keypair.public_key.clone(), params.clone());
+            assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "n = {n}, membership proof {i}");
+        }
+        assert!(mine[0].is_err());
+        assert_eq!(membership_verify_batch(&key, &v, &bad, &bad_c, None, &rho), Some(false));
+
+        // non-membership: C (y + alpha) + d P = V
+        let (mut proofs, mut challenges): (Vec<NonMembershipProof<Bls12_381>>, Vec<Fr>) = (vec![], vec![]);
+        for _ in 0..n {
+            let (y, d) = (Fr::rand(&mut rng), Fr::rand(&mut rng));
+            let wit = NonMembershipWitness { d, C: ((v.into_group() - params.P * d) * (y + alpha).inverse().unwrap()).into_affine() };
+            let c = Fr::rand(&mut rng);
+            proofs.push(NonMembershipProofProtocol::<Bls12_381>::init(&mut rng, y, None, v, &wit, &params, q).gen_proof(&c).unwrap());
+            challenges.push(c);
+        }
+        assert!(non_membership_verify_each(&key, &v, &q, &proofs, &challenges, None).expect("non_membership_verify_each").iter().all(|r| r.is_ok()), "n = {n}");
+        assert_eq!(non_membership_verify_batch(&key, &v, &q, &proofs, &challenges, None, &rho), Some(true));
+        let (mut bad, mut bad_c) = (proofs.clone(), challenges.clone());
+        bad[0].sc_2.response += Fr::from(1u64);
+        bad[1].J = G1Affine::zero();
+        bad[2].t_1 = bad[0].t_1;
+        if n > 3 {
+            bad[3].C_prime = G1Affine::zero();
+            let (a, b) = (bad[4].C_prime, bad[4].C_bar);
+            bad[4].C_bar = (b + a).into_affine();
+            bad_c[5] += Fr::from(1u64);
+        }
+        let mine = non_membership_verify_each(&key, &v, &q, &bad, &bad_c, None).expect("non_membership_verify_each");
+        for i in 0..n {
+            let theirs = bad[i].verify(v, &bad_c[i], keypair.public_key.clone(), params.clone(), q);
+            assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "n = {n}, non-membership proof {i}");
+        }
+        assert!(mine[0].is_err());
+        assert_eq!(non_membership_verify_batch(&key, &v, &q, &bad, &bad_c, None, &rho), Some(false));
+    }
+}
