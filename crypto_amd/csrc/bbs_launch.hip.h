@@ -12,14 +12,15 @@ namespace bbsk {
 //                    operands: at 16 the start costs at most 2 x 17 products against ~64.  A block covers 256 x 16 rows of one column.
 constexpr size_t BBS_EACH_CHUNK = 4096, BBS_BATCH_TERMS = (size_t)1 << 20, BBS_BATCH_CHUNK = 65536, BBS_COL_RUN = 16;
 // rows x n canonical words-of-8, packed, n = L + 2: row i = mult_i (1, s_i, m_i1 .. m_iL); s: rows x 8 words, msgs: rows x L x 8 words packed (mont: ark-ff
-// Montgomery form, else any 256-bit value); t_words: mult_i as ark-ff Montgomery words, or NULL for one
-void launch_bbs_rows(hipStream_t s, const uint32_t *s_words, const uint32_t *msgs, const uint32_t *t_words, int mont, size_t rows, size_t n, uint32_t *out_rows);
+// Montgomery form, else any 256-bit value); t_words: mult_i as ark-ff Montgomery words, or NULL for one.  fixed: the columns in front of the messages, 2 for
+// BBS+; 1 for the 2023 scheme: n = L + 1, row i = mult_i (1, m_i1 .. m_iL), s_words is not read (NULL)
+void launch_bbs_rows(hipStream_t s, const uint32_t *s_words, const uint32_t *msgs, const uint32_t *t_words, int mont, size_t rows, size_t n, size_t fixed, uint32_t *out_rows);
 // blocks of k_bbs_col_sums per column for a chunk of `rows`, and the words of its partial sums for n columns
 size_t bbs_col_blocks(size_t rows);
 size_t bbs_col_part_words(size_t rows, size_t n);
-// The chunk [i0, i0 + rows) of a batch: c_k += sum_i rho^(i0 + i) row_ik for the n = L + 2 columns (run_sums: n x 10 words, the sums between chunks; first: they
+// The chunk [i0, i0 + rows) of a batch: c_k += sum_i rho^(i0 + i) row_ik for the n = L + fixed columns (run_sums: n x 10 words, the sums between chunks; first: they
 // start from zero), wts[8 i ..] = rho^(i0 + i), we[8 i ..] = rho^(i0 + i) e_i (canonical words), c_words[8 k ..] = -c_k as it stands after this chunk.
 // Two launches: the partial sums of every block, then one lane per column that adds them in block order — no atomics, no dependence on the order of execution.
-void launch_bbs_columns(hipStream_t s, const uint32_t *e, const uint32_t *s_words, const uint32_t *msgs, const uint32_t rho_words[8], int mont, size_t rows, size_t n, size_t i0,
-                        bool first, uint32_t *part, uint32_t *run_sums, uint32_t *wts, uint32_t *we, uint32_t *c_words);
+void launch_bbs_columns(hipStream_t s, const uint32_t *e, const uint32_t *s_words, const uint32_t *msgs, const uint32_t rho_words[8], int mont, size_t rows, size_t n, size_t fixed,
+                        size_t i0, bool first, uint32_t *part, uint32_t *run_sums, uint32_t *wts, uint32_t *we, uint32_t *c_words);
 }  // namespace bbsk

@@ -10,10 +10,13 @@
 namespace bbsk {
 using namespace fr29;
 
-// entry k of row i before its multiplier: one, s_i, m_i(k-2).  s(i, Fr &) / m(i, j, Fr &) load products.
-template <class S, class M> FRD void row_value(Fr &v, size_t i, size_t k, S s, M m) {
-    if (k == 0) fr_one(v); else if (k == 1) s(i, v); else m(i, k - 2, v);
+// entry k of row i before its multiplier, with `fixed` columns in front of the messages: one, [s_i,] m_i(k-fixed).  fixed = 2: BBS+ (1, s_i, m_i ..);
+// fixed = 1: the 2023 scheme (1, m_i ..), where s is never called.  s(i, Fr &) / m(i, j, Fr &) load products.
+template <class S, class M> FRD void row_value_fixed(Fr &v, size_t i, size_t k, size_t fixed, S s, M m) {
+    if (k == 0) fr_one(v); else if (k < fixed) s(i, v); else m(i, k - fixed, v);
 }
+// the BBS+ row: one, s_i, m_i(k-2)
+template <class S, class M> FRD void row_value(Fr &v, size_t i, size_t k, S s, M m) { row_value_fixed(v, i, k, 2, s, m); }
 // o = mult v.  v, mult: products (mult: t_i, or one)
 FRD void row_entry(Fr &o, const Fr &v, const Fr &mult) { fr_mul(o, v, mult); }      // 2 r * 2 r
 // o = -v as a product.  v: a product; 512 r - v has limbs < 2^31 and value < 514 r: a first operand, no carry pass

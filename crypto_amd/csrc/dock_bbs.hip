@@ -24,6 +24,13 @@
 //   pok batch  device  C_k, the weights over the own points, +-rho^i                                              k_bbs_pok_col_sums, k_bbs_pok_col_finish
 //              device  one MSM over the chunk's 5 n own points, one each over the A' and the Abar; ONE over the parameters; the host adds the chunks' points
 //              device  e(sum rho^i A'_i, w) e(-sum rho^i Abar_i, g2) against one
+// The 2023 scheme (dgpu_bbs23_*: bbs_plus/src/signature_23.rs, proof_23_cdl.rs, proof_23_ietf.rs): parameters [g1, h_1 .. h_L], no s, no h_0.
+//   sign / each / batch   the three drivers above with ONE fixed column (Rows::fixed = 1): row i = mult_i (1, m_i ..), the same kernels
+//   pok each   device  row i = (c_i, y_i ..), the own scalars (z1, z2, -c, -1 | z3, -1) (CDL) or (z_a, z_b, -1) (IETF)   k_bbs23_rows, k_bbs23_own
+//              device  the bases [Abar, d, Bbar, T1 | d, T2] or [Abar, Bbar, T], Abar and -Bbar for the pairing             k_bbs23_stage
+//              device  P_i, the segments, the pairing as above; the checks into a status byte                              .., k_bbs23_verdict
+//   pok batch  device  C_k, the weights over the own points, +-rho^i                                                        k_bbs23_col_sums, k_bbs23_col_finish
+//              device  one MSM over the chunk's 5 n or 3 n own points, one each over the Abar and the Bbar; ONE over the parameters; the pairing as above
 // Only verdict bytes (each, batch) or the signatures (sign) come back.  The device copies of the inverses and of the rows that carry them are zeroed on every return
 // path before the slot is released, the host copy too.
 #include "msm_many.hip.h"
@@ -33,6 +40,7 @@
 #include "gt_launch.hip.h"
 #include "bbs_launch.hip.h"
 #include "bbs_pok_launch.hip.h"
+#include "bbs23_launch.hip.h"
 #include "acc_host_tables.hpp"
 #include "pair_check.hip.h"             // zero_words, ws_check, coeffs_up, launch_check, add_jac, merged_pair_verdict: shared with dock_acc_pok.hip
 using namespace dock;
@@ -44,17 +52,18 @@ namespace {
 constexpr size_t PT = 96;                // bytes of an affine G1 point of the ABI
 constexpr size_t NPTS = 5;                // points of a proof of knowledge: A', Abar, d, T1, T2
 
-// what the three calls share: the rows' inputs and how they are cut
+// what the three calls share: the rows' inputs and how they are cut.  fixed: the columns in front of the messages — 2 for BBS+ (1, s_i), parameters
+// [g1, h_0, h ..]; 1 for the 2023 scheme (1), parameters [g1, h ..], s = NULL
 struct Rows {
-    const uint64_t *messages, *e, *s; size_t L, stride, n; bool mont;
-    size_t nn() const { return L + 2; }
+    const uint64_t *messages, *e, *s; size_t L, stride, n; bool mont; size_t fixed;
+    size_t nn() const { return L + fixed; }
 };
 // the argument checks that come before the device is looked at (n > 0)
 bool bad_rows(const Rows &r) {
-    return r.L == 0 || !r.messages || !r.e || !r.s || r.stride < r.L || r.n >= (1ull << 31) || r.L >= (1ull << 31) - 2 || r.stride >= (1ull << 31);
+    return r.L == 0 || !r.messages || !r.e || (r.fixed == 2 && !r.s) || r.stride < r.L || r.n >= (1ull << 31) || r.L >= (1ull << 31) - 2 || r.stride >= (1ull << 31);
 }
-// the parameters: a plain G1 bases handle of exactly L + 2 points, pinned for the call
-bool params_ok(const HandleRef &hb, size_t L) { return hb.ok && hb.h.kind == 1 && hb.h.n == L + 2; }
+// the parameters: a plain G1 bases handle of exactly nn = L + 2 (2023: L + 1) points, pinned for the call
+bool params_ok(const HandleRef &hb, size_t nn) { return hb.ok && hb.h.kind == 1 && hb.h.n == nn; }
 
 // How the b_i (the P_i of a proof) of a chunk are made: RowMsm (msm_many.hip.h) over the parameters' handle, whose small-path table serves the many-row kernels
 RowMsm<G1> param_rows(Slot &sl, uint64_t params, const Handle &h, size_t nn, size_t cap, size_t n) {
@@ -64,10 +73,10 @@ RowMsm<G1> param_rows(Slot &sl, uint64_t params, const Handle &h, size_t nn, siz
     rm.sub = sub; rm.rec = (const uint32_t *)h.p;
     return rm;
 }
-// s and the messages of the rows [r0, r0 + rows) to the device: the messages packed (what lies between the caller's rows never crosses)
+// s (BBS+) and the messages of the rows [r0, r0 + rows) to the device: the messages packed (what lies between the caller's rows never crosses)
 int32_t rows_up(Slot &sl, const Rows &r, size_t r0, size_t rows, void *d_s, void *d_m) {
     hipStream_t s = sl.stream;
-    HIPCHK(hipMemcpyAsync(d_s, r.s + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
+    if (r.fixed == 2) HIPCHK(hipMemcpyAsync(d_s, r.s + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
     return upload_rows_packed(s, d_m, r.messages + r0 * r.stride * 4, r.L, r.stride, rows);
 }
 
@@ -86,7 +95,7 @@ int32_t sign_many(uint64_t params, const uint64_t *sk, const Rows &r, uint64_t *
     if (!cur().ready) return DGPU_E_NODEVICE;
     if (gs.prof) prof_add_host("bbs.host_inverses", ms_since(t0));
     HandleRef hb(params);
-    if (!params_ok(hb, r.L)) return DGPU_E_BADARG;
+    if (!params_ok(hb, nn)) return DGPU_E_BADARG;
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
@@ -113,7 +122,7 @@ int32_t sign_many(uint64_t params, const uint64_t *sk, const Rows &r, uint64_t *
         const size_t rows = std::min(chunk, n - r0);
         HIPCHK(hipMemcpyAsync(sl.q[0].p, t.w.data() + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
         if ((rc = rows_up(sl, r, r0, rows, sl.q[1].p, sl.q[2].p))) return rc;
-        { StageTimer st(sl, "bbs.rows"); bbsk::launch_bbs_rows(s, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), sl.q[0].as<uint32_t>(), r.mont ? 1 : 0, rows, nn, d_rows); }
+        { StageTimer st(sl, "bbs.rows"); bbsk::launch_bbs_rows(s, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), sl.q[0].as<uint32_t>(), r.mont ? 1 : 0, rows, nn, r.fixed, d_rows); }
         if ((rc = bp.points(sl, d_rows, rows, d_bad, dA, dAinf))) return rc;
         HIPCHK(hipMemcpyAsync(out_a + 12 * r0, dA, rows * PT, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(binf.data() + r0, dAinf, rows, hipMemcpyDeviceToHost, s));
@@ -149,7 +158,7 @@ int32_t verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_p
     if (!cur().ready) return DGPU_E_NODEVICE;
     const size_t n = r.n, nn = r.nn();
     HandleRef hb(params);
-    if (!params_ok(hb, r.L)) return DGPU_E_BADARG;
+    if (!params_ok(hb, nn)) return DGPU_E_BADARG;
     auto t0 = std::chrono::steady_clock::now();
     std::vector<uint64_t> split(n * 4);
     std::vector<uint8_t> ainf(n);
@@ -192,7 +201,7 @@ int32_t verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_p
         HIPCHK(hipMemcpyAsync(dA, sig_a + 12 * r0, rows * PT, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(dsk, ainf.data() + r0, rows, hipMemcpyHostToDevice, s));
         if ((rc = rows_up(sl, r, r0, rows, sl.q[1].p, sl.q[2].p))) return rc;
-        { StageTimer st(sl, "bbs.rows"); bbsk::launch_bbs_rows(s, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), nullptr, r.mont ? 1 : 0, rows, nn, d_rows); }
+        { StageTimer st(sl, "bbs.rows"); bbsk::launch_bbs_rows(s, sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), nullptr, r.mont ? 1 : 0, rows, nn, r.fixed, d_rows); }
         if ((rc = bp.points(sl, d_rows, rows, d_bad, dB, dBinf))) return rc;
         // d_i = -((-e_i) A_i + b_i); its identity flag is the second pair's skip flag
         { StageTimer st(sl, "bbs.scale");
@@ -232,7 +241,7 @@ int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_
     if (!cur().ready) return DGPU_E_NODEVICE;
     const size_t n = r.n, nn = r.nn();
     HandleRef hb(params);
-    if (!params_ok(hb, r.L)) return DGPU_E_BADARG;
+    if (!params_ok(hb, nn)) return DGPU_E_BADARG;
     for (size_t i = 0; i < n; i++) if (zero_words(sig_a + 12 * i, 12)) { *ok = 0; return DGPU_OK; }      // ZeroSignature
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
@@ -269,7 +278,7 @@ int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_
         if ((rc = rows_up(sl, r, r0, rows, sl.q[1].p, sl.q[2].p))) return rc;
         if ((rc = stage_bases<G1>(sl, rb.from(r0), rows, d_rec))) return rc;
         { StageTimer st(sl, "bbs.columns");
-          bbsk::launch_bbs_columns(s, sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), (const uint32_t *)random, r.mont ? 1 : 0, rows, nn, r0, r0 == 0,
+          bbsk::launch_bbs_columns(s, sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), (const uint32_t *)random, r.mont ? 1 : 0, rows, nn, r.fixed, r0, r0 == 0,
                                    sl.q[7].as<uint32_t>(), d_run, d_w, d_we, d_c); }
         HIPCHK(hipGetLastError());
         if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_w, rows, jac))) return rc;
@@ -326,7 +335,7 @@ int32_t pok_verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *
     if (!cur().ready) return DGPU_E_NODEVICE;
     const size_t n = p.n, nn = p.nn();
     HandleRef hb(params);
-    if (!params_ok(hb, p.L)) return DGPU_E_BADARG;
+    if (!params_ok(hb, nn)) return DGPU_E_BADARG;
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
@@ -386,7 +395,7 @@ int32_t pok_verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t 
     if (!cur().ready) return DGPU_E_NODEVICE;
     const size_t n = p.n, nn = p.nn();
     HandleRef hb(params);
-    if (!params_ok(hb, p.L)) return DGPU_E_BADARG;
+    if (!params_ok(hb, nn)) return DGPU_E_BADARG;
     for (size_t i = 0; i < n; i++) if (zero_words(p.points + NPTS * 12 * i, 12)) { *ok = 0; return DGPU_OK; }      // ZeroSignature
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
@@ -442,20 +451,226 @@ int32_t pok_verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t 
     return DGPU_OK;
 }
 
+// ---- the 2023 scheme's two PoKOfSignature23G1Proof::verify for n proofs (proof_23_cdl.rs:302-549, proof_23_ietf.rs:244-479) ---------------------------------------------
+// The signature calls of that scheme are sign_many / verify_each / verify_batch above with Rows::fixed = 1.  KIND: bbs23k::KIND_CDL / KIND_IETF
+struct Proofs23 {
+    const uint64_t *points, *fixed, *values; const uint8_t *revealed; const uint64_t *challenge; size_t L, stride, n; bool mont;
+    size_t nn() const { return L + 1; }
+};
+bool bad_proofs23(const Proofs23 &p) {
+    return p.L == 0 || !p.points || !p.fixed || !p.values || !p.revealed || !p.challenge || p.stride < p.L || p.n >= (1ull << 31) || p.L >= (1ull << 31) - 2 ||
+           p.stride >= (1ull << 31);
+}
+// q[0]: the challenges, q[1]: the fixed responses, q[2]: the values, q[3]: the mask, q[5]: the points of the rows [r0, r0 + rows); the values packed
+int32_t ws_proofs23(Slot &o, const Proofs23 &p, const bbs23k::KindShape &ks, size_t chunk) {
+    int32_t e;
+    if ((e = o.q[0].ensure(chunk * 32))) return e;
+    if ((e = o.q[1].ensure(chunk * ks.resp * 32))) return e;
+    if ((e = o.q[2].ensure(chunk * p.L * 32))) return e;
+    if ((e = o.q[3].ensure(chunk * p.L))) return e;
+    return o.q[5].ensure(chunk * ks.pts * PT);
+}
+int32_t proofs23_up(Slot &sl, const Proofs23 &p, int kind, const bbs23k::KindShape &ks, size_t r0, size_t rows, bbs23k::ProofDev &dev) {
+    hipStream_t s = sl.stream;
+    HIPCHK(hipMemcpyAsync(sl.q[0].p, p.challenge + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sl.q[1].p, p.fixed + 4 * ks.resp * r0, rows * ks.resp * 32, hipMemcpyHostToDevice, s));
+    int32_t rc;
+    if ((rc = upload_rows_packed(s, sl.q[2].p, p.values + r0 * p.stride * 4, p.L, p.stride, rows))) return rc;
+    HIPCHK(hipMemcpyAsync(sl.q[3].p, p.revealed + r0 * p.L, rows * p.L, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sl.q[5].p, p.points + r0 * ks.pts * 12, rows * ks.pts * PT, hipMemcpyHostToDevice, s));
+    dev = bbs23k::ProofDev{sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), sl.q[3].as<uint8_t>(), p.L, kind, p.mont ? 1 : 0};
+    return DGPU_OK;
+}
+// the segments of every row of a chunk — CDL: 4 and 2 terms, IETF: 3: the layout depends on the kind and the row count alone
+void own_layout23(const bbs23k::KindShape &ks, size_t rows, SegLayout &lay) {
+    std::vector<uint64_t> ends(ks.segs * rows);
+    for (size_t i = 0; i < rows; i++) {
+        if (ks.segs == 2) { ends[2 * i] = ks.own * i + 4; ends[2 * i + 1] = ks.own * (i + 1); }
+        else ends[i] = ks.own * (i + 1);
+    }
+    seg_layout(ends.data(), 0, ks.segs * rows, lay);
+}
+
+int32_t pok23_verify_each(int kind, uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const Proofs23 &p, uint8_t *status) {
+    if (p.n == 0) return DGPU_OK;
+    if (bad_proofs23(p) || !pk_pc || !g2_pc || !status) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    const size_t n = p.n, nn = p.nn();
+    HandleRef hb(params);
+    if (!params_ok(hb, nn)) return DGPU_E_BADARG;
+    CtxScope on_owner(hb.h.ctx);
+    SLOT_ACQUIRE(LK, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    const bbs23k::KindShape ks = bbs23k::kind_shape(kind);
+    const size_t own = ks.own, segs = ks.segs;
+    const RowMsm<G1> bp = param_rows(sl, params, hb.h, nn, bbs23k::BBS23_EACH_CHUNK, n);
+    const size_t chunk = bp.chunk;
+    int32_t rc;
+    SegLayout lay, lay_tail;
+    own_layout23(ks, chunk, lay);
+    if (n % chunk) own_layout23(ks, n % chunk, lay_tail);
+    // q[0 .. 3], q[5]: the proofs (ws_proofs23); q[4]: [P | identity flags], q[6]: the own scalars, q[7]: the own points in segment order, q[8]: [Abar | -Bbar],
+    // q[9]: [skip flags of (Abar, -Bbar) | status]
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = ws_proofs23(o, p, ks, chunk))) return e;
+        if ((e = o.q[4].ensure(chunk * PT + chunk))) return e;
+        if ((e = o.q[6].ensure(chunk * own * 32))) return e;
+        if ((e = o.q[7].ensure(chunk * own * PT))) return e;
+        if ((e = o.q[8].ensure(2 * chunk * PT))) return e;
+        if ((e = o.q[9].ensure(3 * chunk))) return e;
+        if ((e = ws_check(o, chunk))) return e;
+        if ((e = ws_seg_resident<G1>(o, own * chunk, segs * chunk, lay.blocks))) return e;
+        return bp.workspace(o);
+    };
+    if ((rc = ensure_workspace(sl, ws))) return rc;
+    hipStream_t s = sl.stream;
+    DrainUnlessDone guard(sl);
+    uint32_t *d_rows = sl.in_scalars.as<uint32_t>(), *d_bad = sl.flags.as<uint32_t>(), *d_own = sl.q[6].as<uint32_t>(), *d_opts = sl.q[7].as<uint32_t>();
+    uint32_t *dPa = sl.q[8].as<uint32_t>(), *dPb = dPa + chunk * (PT / 4);
+    uint8_t *dB = sl.q[4].as<uint8_t>(), *dBinf = dB + chunk * PT, *dsk = sl.q[9].as<uint8_t>(), *dstatus = dsk + 2 * chunk;
+    if ((rc = coeffs_up(sl, pk_pc, g2_pc, chunk))) return rc;
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t rows = std::min(chunk, n - r0);
+        bbs23k::ProofDev dev;
+        HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));                          // (rows are canonical: the flag stays clear; sl.flags takes the pairing's verdicts afterwards)
+        if ((rc = proofs23_up(sl, p, kind, ks, r0, rows, dev))) return rc;
+        { StageTimer st(sl, "bbs23.pok_rows"); bbs23k::launch_bbs23_rows(s, dev, rows, d_rows, d_own); }
+        { StageTimer st(sl, "bbs23.pok_stage"); bbs23k::launch_bbs23_stage(s, sl.q[5].as<uint32_t>(), kind, rows, d_opts, dPa, dPb, dsk); }
+        if ((rc = bp.points(sl, d_rows, rows, d_bad, dB, dBinf))) return rc;
+        if ((rc = seg_rows_resident<G1>(sl, (const uint8_t *)d_opts, PT, d_own, own * rows, segs * rows, rows == chunk ? lay : lay_tail, d_bad))) return rc;
+        launch_check(sl, dPa, dPb, dsk, rows, chunk);
+        { StageTimer st(sl, "bbs23.pok_verdict");
+          bbs23k::launch_bbs23_verdict(s, sl.win.as<uint32_t>(), sl.win_inf.as<uint8_t>(), (const uint32_t *)dB, dBinf, sl.flags.as<uint8_t>(), dsk, kind, rows, dstatus); }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(status + r0, dstatus, rows, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));                                 // (the next chunk's operands overwrite this one's)
+        if (gs.prof) prof_flush(sl);
+    }
+    guard.done = true;
+    return DGPU_OK;
+}
+
+// one verdict for n proofs — CDL: row i weighs its first Schnorr check with u_i = rho^(2 i), its second with v_i = rho^(2 i + 1), its pairing with t_i = rho^i;
+// IETF: its one Schnorr check and its pairing with rho^i
+int32_t pok23_verify_batch(int kind, uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const Proofs23 &p, const uint64_t *random, int32_t *ok) {
+    if (p.n == 0) { if (ok) *ok = 1; return DGPU_OK; }
+    if (bad_proofs23(p) || !pk_pc || !g2_pc || !random || !ok) return DGPU_E_BADARG;
+    if (fr_is_zero(fr_in(random, p.mont))) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    const size_t n = p.n, nn = p.nn();
+    HandleRef hb(params);
+    if (!params_ok(hb, nn)) return DGPU_E_BADARG;
+    const bbs23k::KindShape ks = bbs23k::kind_shape(kind);
+    const size_t npts = ks.pts;
+    for (size_t i = 0; i < n; i++) if (zero_words(p.points + npts * 12 * i, 12)) { *ok = 0; return DGPU_OK; }      // ZeroSignature
+    CtxScope on_owner(hb.h.ctx);
+    SLOT_ACQUIRE(LK, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    const size_t chunk = batch_chunk(n, p.L, bbs23k::BBS23_BATCH_CHUNK);
+    int32_t rc;
+    // q[0 .. 3], q[5]: the proofs (ws_proofs23); q[4]: [P1 | P2] and their skip flags, q[6]: the weights over the own points, q[7]: the blocks' partial sums,
+    // q[8]: [C | the running sums], q[9]: [rho^i | -rho^i], q[10]: the prepared records of the own points, q[11]: those of [the Abar | the Bbar]
+    auto ws = [&](Slot &o) -> int32_t {
+        int32_t e;
+        if ((e = ws_proofs23(o, p, ks, chunk))) return e;
+        if ((e = o.q[4].ensure(2 * PT + 64))) return e;
+        if ((e = o.q[6].ensure(chunk * npts * 32))) return e;
+        if ((e = o.q[7].ensure(bbsk::bbs_col_part_words(chunk, nn) * 4))) return e;
+        if ((e = o.q[8].ensure(nn * 40 + nn * 32 + 64))) return e;
+        if ((e = o.q[9].ensure(2 * chunk * 32))) return e;
+        if ((e = o.q[10].ensure(chunk * npts * G1::AFF_STRIDE * 4))) return e;
+        if ((e = o.q[11].ensure(2 * chunk * G1::AFF_STRIDE * 4))) return e;
+        for (size_t terms : {npts * chunk, chunk, nn}) if ((e = ws_for<G1>(o, 2, terms, 0, nullptr))) return e;
+        return ws_check(o, 1);
+    };
+    if ((rc = ensure_workspace(sl, ws))) return rc;
+    hipStream_t s = sl.stream;
+    DrainUnlessDone guard(sl);
+    uint32_t *d_c = sl.q[8].as<uint32_t>(), *d_run = d_c + nn * 8, *d_wts = sl.q[6].as<uint32_t>(), *d_tp = sl.q[9].as<uint32_t>(), *d_tn = d_tp + chunk * 8;
+    uint32_t *d_rec = sl.q[10].as<uint32_t>(), *d_reca = sl.q[11].as<uint32_t>(), *d_recb = d_reca + chunk * G1::AFF_STRIDE;
+    HPoint Gsum = HPoint::identity(), P1 = HPoint::identity(), P2 = HPoint::identity();
+    uint64_t jac[18];
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t rows = std::min(chunk, n - r0);
+        bbs23k::ProofDev dev;
+        if ((rc = proofs23_up(sl, p, kind, ks, r0, rows, dev))) return rc;
+        const uint8_t *raw = sl.q[5].as<uint8_t>();
+        { StageTimer st(sl, "msm.prep_bases");
+          msm::launch_prep_bases_raw<G1>(s, raw, PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, npts * rows, d_rec);
+          msm::launch_prep_bases_raw<G1>(s, raw, npts * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_reca);
+          msm::launch_prep_bases_raw<G1>(s, raw + PT, npts * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_recb); }
+        { StageTimer st(sl, "bbs23.pok_columns");
+          bbs23k::launch_bbs23_columns(s, dev, (const uint32_t *)random, rows, r0, r0 == 0, sl.q[7].as<uint32_t>(), d_run, d_wts, d_tp, d_tn, d_c); }
+        HIPCHK(hipGetLastError());
+        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_wts, npts * rows, jac))) return rc;
+        add_jac(Gsum, jac);
+        if ((rc = msm_device<G1, hostf::Fq>(sl, d_reca, d_tp, rows, jac))) return rc;
+        add_jac(P1, jac);
+        if ((rc = msm_device<G1, hostf::Fq>(sl, d_recb, d_tn, rows, jac))) return rc;
+        add_jac(P2, jac);
+        if (gs.prof) prof_flush(sl);
+    }
+    if ((rc = params_msm(sl, params, hb.h, d_c, nn, Gsum))) return rc;     // sum_k C_k H_k
+    if (!Gsum.inf) { HIPCHK(hipStreamSynchronize(s)); guard.done = true; *ok = 0; return DGPU_OK; }      // the G1 equation fails: the pairing cannot mend it
+    if ((rc = merged_pair_verdict(sl, P1, P2, pk_pc, g2_pc, sl.q[4], ok))) return rc;
+    guard.done = true;
+    return DGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
+int32_t dgpu_bbs23_sign_many_g1(uint64_t params, size_t L, const uint64_t sk[4], const uint64_t *messages, size_t row_stride, const uint64_t *e, size_t n, int32_t montgomery,
+                                uint64_t *out_a, uint8_t *bad) {
+    return abi_guard([&] { return sign_many(params, sk, Rows{messages, e, nullptr, L, row_stride, n, montgomery != 0, 1}, out_a, bad); });
+}
+int32_t dgpu_bbs23_verify_each_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const uint64_t *e, const uint64_t *messages,
+                                  size_t row_stride, size_t n, int32_t montgomery, uint8_t *ok) {
+    return abi_guard([&] { return verify_each(params, pk_pc, g2_pc, sig_a, Rows{messages, e, nullptr, L, row_stride, n, montgomery != 0, 1}, ok); });
+}
+int32_t dgpu_bbs23_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const uint64_t *e, const uint64_t *messages,
+                                   size_t row_stride, size_t n, int32_t montgomery, const uint64_t random[4], int32_t *ok) {
+    return abi_guard([&] { return verify_batch(params, pk_pc, g2_pc, sig_a, Rows{messages, e, nullptr, L, row_stride, n, montgomery != 0, 1}, random, ok); });
+}
+int32_t dgpu_bbs23_pok_verify_each_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points, const uint64_t *resp_fixed,
+                                      const uint64_t *values, size_t row_stride, const uint8_t *revealed, const uint64_t *challenge, size_t n, int32_t montgomery, uint8_t *status) {
+    return abi_guard([&] {
+        return pok23_verify_each(bbs23k::KIND_CDL, params, pk_pc, g2_pc, Proofs23{points, resp_fixed, values, revealed, challenge, L, row_stride, n, montgomery != 0}, status);
+    });
+}
+int32_t dgpu_bbs23_pok_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points, const uint64_t *resp_fixed,
+                                       const uint64_t *values, size_t row_stride, const uint8_t *revealed, const uint64_t *challenge, size_t n, int32_t montgomery,
+                                       const uint64_t random[4], int32_t *ok) {
+    return abi_guard([&] {
+        return pok23_verify_batch(bbs23k::KIND_CDL, params, pk_pc, g2_pc, Proofs23{points, resp_fixed, values, revealed, challenge, L, row_stride, n, montgomery != 0}, random, ok);
+    });
+}
+int32_t dgpu_bbs23_pok_ietf_verify_each_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points, const uint64_t *resp_fixed,
+                                           const uint64_t *values, size_t row_stride, const uint8_t *revealed, const uint64_t *challenge, size_t n, int32_t montgomery,
+                                           uint8_t *status) {
+    return abi_guard([&] {
+        return pok23_verify_each(bbs23k::KIND_IETF, params, pk_pc, g2_pc, Proofs23{points, resp_fixed, values, revealed, challenge, L, row_stride, n, montgomery != 0}, status);
+    });
+}
+int32_t dgpu_bbs23_pok_ietf_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points, const uint64_t *resp_fixed,
+                                            const uint64_t *values, size_t row_stride, const uint8_t *revealed, const uint64_t *challenge, size_t n, int32_t montgomery,
+                                            const uint64_t random[4], int32_t *ok) {
+    return abi_guard([&] {
+        return pok23_verify_batch(bbs23k::KIND_IETF, params, pk_pc, g2_pc, Proofs23{points, resp_fixed, values, revealed, challenge, L, row_stride, n, montgomery != 0}, random, ok);
+    });
+}
 int32_t dgpu_bbs_plus_sign_many_g1(uint64_t params, size_t L, const uint64_t sk[4], const uint64_t *messages, size_t row_stride, const uint64_t *e, const uint64_t *s, size_t n,
                                    int32_t montgomery, uint64_t *out_a, uint8_t *bad) {
-    return abi_guard([&] { return sign_many(params, sk, Rows{messages, e, s, L, row_stride, n, montgomery != 0}, out_a, bad); });
+    return abi_guard([&] { return sign_many(params, sk, Rows{messages, e, s, L, row_stride, n, montgomery != 0, 2}, out_a, bad); });
 }
 int32_t dgpu_bbs_plus_verify_each_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const uint64_t *e, const uint64_t *s,
                                      const uint64_t *messages, size_t row_stride, size_t n, int32_t montgomery, uint8_t *ok) {
-    return abi_guard([&] { return verify_each(params, pk_pc, g2_pc, sig_a, Rows{messages, e, s, L, row_stride, n, montgomery != 0}, ok); });
+    return abi_guard([&] { return verify_each(params, pk_pc, g2_pc, sig_a, Rows{messages, e, s, L, row_stride, n, montgomery != 0, 2}, ok); });
 }
 int32_t dgpu_bbs_plus_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const uint64_t *e, const uint64_t *s,
                                       const uint64_t *messages, size_t row_stride, size_t n, int32_t montgomery, const uint64_t random[4], int32_t *ok) {
-    return abi_guard([&] { return verify_batch(params, pk_pc, g2_pc, sig_a, Rows{messages, e, s, L, row_stride, n, montgomery != 0}, random, ok); });
+    return abi_guard([&] { return verify_batch(params, pk_pc, g2_pc, sig_a, Rows{messages, e, s, L, row_stride, n, montgomery != 0, 2}, random, ok); });
 }
 int32_t dgpu_bbs_plus_pok_verify_each_g1(uint64_t params, size_t L, const uint64_t h_0[12], const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points,
                                          const uint64_t *resp_fixed, const uint64_t *values, size_t row_stride, const uint8_t *revealed, const uint64_t *challenge, size_t n,

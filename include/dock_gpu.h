@@ -784,6 +784,77 @@ int32_t dgpu_bbs_plus_pok_verify_batch_g1(uint64_t params, size_t L, const uint6
                                           size_t row_stride, const uint8_t *revealed /* n*L */, const uint64_t *challenge /* n*4 */, size_t n,
                                           int32_t montgomery, const uint64_t random[4], int32_t *ok);
 
+/* ---- BBS (2023) in bulk: sign, verify, and both proofs of knowledge (crypto_amd/csrc/dock_bbs.hip, bbs_kernels.hip.h, bbs23_kernels.hip.h) ----
+ * The other half of the reference's bbs_plus crate: Signature23G1 (bbs_plus/src/signature_23.rs) and the two protocols that prove knowledge of one,
+ * proof_23_cdl.rs (the prelude's PoKOfSignature23G1Proof, proof_system's PoKBBSSignature23G1) and proof_23_ietf.rs (the IETF draft's, PoKBBSSignature23IETFG1).
+ * The scheme has no s and no h_0: params is a PLAIN G1 bases handle [g1, h_1 .. h_L] of exactly L + 1 points (another length, a precomputed handle or no
+ * handle: DGPU_E_BADARG); pk_pc, g2_pc, messages, row_stride, e, montgomery, random and the identity as all-zero words are as in the BBS+ calls above.
+ *
+ * dgpu_bbs23_sign_many_g1 is Signature23G1::new (signature_23.rs:38-103, commitment = O) for n rows: A_i = (x + e_i)^-1 (g1 + sum_j m_ij h_j), row i of the
+ * many-row MSM = (x + e_i)^-1 (1, m_i1 .. m_iL).  bad[i] = 1 and zero words where x + e_i = 0 or b_i = O.  The inverses are made on the host; their host and
+ * device copies and the rows that carry them are zeroed on every return path, as in dgpu_bbs_plus_sign_many_g1.
+ * dgpu_bbs23_verify_each_g1 is Signature23G1::verify (:136-160): ok[i] = 1 iff A_i != O and e(A_i, w) e(e_i A_i - b_i, g2) = 1.
+ * dgpu_bbs23_verify_batch_g1: one verdict under the weights rho^i — the L + 1 column sums c_k, P1 = sum rho^i A_i, P2 = sum rho^i e_i A_i - sum_k c_k H_k, one
+ * merged pair.  These three are the BBS+ drivers and kernels with ONE fixed column in front of the messages instead of two (k_bbs_rows, k_bbs_col_sums take
+ * the count), so chunks, stage timers and every remark of the BBS+ block hold with L + 1 in place of L + 2.
+ *
+ * The two proofs of knowledge, n proofs under ONE key; values, revealed, challenge as in dgpu_bbs_plus_pok_verify_each_g1; row i = (c_i, y_i1 .. y_iL),
+ * y_ij = c_i m_ij where j is revealed and z_ij where it is hidden, P_i = <row_i, params>:
+ *   CDL (dgpu_bbs23_pok_verify_*; proof_23_cdl.rs:302-549)
+ *     points      n x 5 x 12 words: Abar, Bbar, d, T1 (sc_resp_1.t), T2
+ *     resp_fixed  n x 3 scalars: z1 (sc_resp_1.response1, over Abar), z2 (.response2, over d), z3 (the last response of sc_resp_2, over d)
+ *     1  Abar != O                                                    else ZeroSignature
+ *     2  z1 Abar + z2 d - c Bbar - T1 = O                             else FirstSchnorrVerificationFailed
+ *     3  P_i + z3 d - T2 = O                                          else SecondSchnorrVerificationFailed
+ *     4  e(Abar, w) e(-Bbar, g2) = 1                                  else PairingCheckFailed
+ *   IETF (dgpu_bbs23_pok_ietf_verify_*; proof_23_ietf.rs:244-479)
+ *     points      n x 3 x 12 words: Abar, Bbar, T
+ *     resp_fixed  n x 2 scalars: z_a, z_b, the last two responses of sc_resp, over Abar and Bbar
+ *     1  Abar != O                                                    else ZeroSignature
+ *     3  P_i + z_a Abar + z_b Bbar - T = O                            else SecondSchnorrVerificationFailed (the name this protocol gives its only Schnorr check)
+ *     4  e(Abar, w) e(-Bbar, g2) = 1                                  else PairingCheckFailed
+ * ..._verify_each_g1 writes status[i] = 0 or the number of the FIRST failing check (the IETF call never writes 2).  Per chunk one device pipeline: the rows
+ * and the own scalars (z1, z2, -c, -1 | z3, -1), respectively (z_a, z_b, -1) (k_bbs23_rows, k_bbs23_own), the bases [Abar, d, Bbar, T1 | d, T2], respectively
+ * [Abar, Bbar, T] with Abar and -Bbar for the pairing (k_bbs23_stage), P_i by the many-row MSM, the segments by the segmented small MSM, the two-pair check,
+ * k_bbs23_verdict (the segment over the parameters' check is compared with -P_i); only the n status bytes come back.
+ * ..._verify_batch_g1: ONE verdict, rho = random (rho = 0 mod r: DGPU_E_BADARG).  *ok = 1 iff no Abar_i is the identity and
+ *   CDL, u_i = rho^(2i), v_i = rho^(2i+1), t_i = rho^i:
+ *     sum_k C_k H_k + sum_i [ u z1 Abar - u c Bbar + (u z2 + v z3) d - u T1 - v T2 ]_i = O,    C_0 = sum v_i c_i,  C_j = sum v_i y_ij
+ *   IETF, u_i = t_i = rho^i:
+ *     sum_k C_k H_k + sum_i u_i [ z_a Abar + z_b Bbar - T ]_i = O,                              C_0 = sum u_i c_i,  C_j = sum u_i y_ij
+ *   both: e(sum t_i Abar_i, w) e(-sum t_i Bbar_i, g2) = 1
+ * (k_bbs23_col_sums, k_bbs23_col_finish: two passes, no atomics; one MSM over the chunk's own points, one each over the Abar and the Bbar, ONE over params; a
+ * G1 sum that is not the identity refuses before the pairing).  For a random rho a batch with a failing proof passes with probability at most 2n / r (CDL) or
+ * n / r (IETF) per equation; rho = r - 1 makes every CDL u_i one and rho = 1 every IETF u_i: errors that cancel between rows then pass.
+ *
+ * All seven: n = 0 is DGPU_OK without touching a device or any pointer (an empty batch verifies); with n > 0 a NULL pointer, row_stride < L, L = 0, n or
+ * row_stride >= 2^31 is DGPU_E_BADARG before the device is looked at; then DGPU_E_NODEVICE, then the handle.  Points are taken as validated members of the
+ * subgroup.  Chunks (UNMEASURED): the BBS+ rules with L + 1 in place of L + 2; dgpu_set_many_chunk_rows of the development surface cuts all seven.  Stage
+ * timers bbs23.pok_rows, bbs23.pok_stage, bbs23.pok_verdict, bbs23.pok_columns beside the BBS+ block's. */
+int32_t dgpu_bbs23_sign_many_g1(uint64_t params, size_t L, const uint64_t sk[4], const uint64_t *messages /* n rows */, size_t row_stride,
+                                const uint64_t *e /* n*4 */, size_t n, int32_t montgomery, uint64_t *out_a /* n*12 */, uint8_t *bad /* n */);
+int32_t dgpu_bbs23_verify_each_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a /* n*12 */,
+                                  const uint64_t *e /* n*4 */, const uint64_t *messages /* n rows */, size_t row_stride, size_t n, int32_t montgomery,
+                                  uint8_t *ok /* n */);
+int32_t dgpu_bbs23_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a /* n*12 */,
+                                   const uint64_t *e /* n*4 */, const uint64_t *messages /* n rows */, size_t row_stride, size_t n, int32_t montgomery,
+                                   const uint64_t random[4], int32_t *ok);
+int32_t dgpu_bbs23_pok_verify_each_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points /* n*60 */,
+                                      const uint64_t *resp_fixed /* n*12 */, const uint64_t *values /* n rows */, size_t row_stride,
+                                      const uint8_t *revealed /* n*L */, const uint64_t *challenge /* n*4 */, size_t n, int32_t montgomery, uint8_t *status /* n */);
+int32_t dgpu_bbs23_pok_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points /* n*60 */,
+                                       const uint64_t *resp_fixed /* n*12 */, const uint64_t *values /* n rows */, size_t row_stride,
+                                       const uint8_t *revealed /* n*L */, const uint64_t *challenge /* n*4 */, size_t n, int32_t montgomery,
+                                       const uint64_t random[4], int32_t *ok);
+int32_t dgpu_bbs23_pok_ietf_verify_each_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points /* n*36 */,
+                                           const uint64_t *resp_fixed /* n*8 */, const uint64_t *values /* n rows */, size_t row_stride,
+                                           const uint8_t *revealed /* n*L */, const uint64_t *challenge /* n*4 */, size_t n, int32_t montgomery,
+                                           uint8_t *status /* n */);
+int32_t dgpu_bbs23_pok_ietf_verify_batch_g1(uint64_t params, size_t L, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *points /* n*36 */,
+                                            const uint64_t *resp_fixed /* n*8 */, const uint64_t *values /* n rows */, size_t row_stride,
+                                            const uint8_t *revealed /* n*L */, const uint64_t *challenge /* n*4 */, size_t n, int32_t montgomery,
+                                            const uint64_t random[4], int32_t *ok);
+
 /* ---- the LegoGroth16 prover as one call ----
  * replaces create_proof_and_committed_witnesses_with_assignment (legogroth16/src/prover.rs:267-383, with calculate_coeff :585-594) and — when
  * the circuit is resident (r1cs != 0) — the QAP::witness_map call in front of it (create_proof_with_reduction, :153-180): the whole schedule

@@ -153,3 +153,162 @@ pub fn pok_verify_batch(params: &GpuSignatureParams, proofs: &[PoKOfSignatureG1P
         != DGPU_OK { return None; }
     Some(ok != 0)
 }
+
+// ---- the 2023 scheme (bbs_plus/src/signature_23.rs, proof_23_cdl.rs, proof_23_ietf.rs): no s, no h_0 ------------------------------------------------------------
+//   `Signature23G1::new` / `verify`, n times                                  -> `sign_many_23`, `verify_each_23`, `verify_batch_23`
+//   proof_23_cdl's `PoKOfSignature23G1Proof::verify`, n times                 -> `pok_verify_each_23`, `pok_verify_batch_23`
+//   proof_23_ietf's `PoKOfSignature23G1Proof::verify`, n times                -> `pok_ietf_verify_each_23`, `pok_ietf_verify_batch_23`
+// `GpuSignatureParams23` keeps `[g1, h ..]` resident.  NOT compiled in the build image either; `tests/parity.rs` `bbs23_bulk_equals_the_reference` compares with the
+// reference's own `new` / `verify` and both proofs' `verify`.
+use crate::host::{raw_bbs23_pok_ietf_verify_batch, raw_bbs23_pok_ietf_verify_each, raw_bbs23_pok_verify_batch, raw_bbs23_pok_verify_each, raw_bbs23_sign_many, raw_bbs23_verify_batch,
+                  raw_bbs23_verify_each};
+use bbs_plus::proof_23_cdl::PoKOfSignature23G1Proof as CdlProof;
+use bbs_plus::proof_23_ietf::PoKOfSignature23G1Proof as IetfProof;
+use bbs_plus::setup::SignatureParams23G1;
+use bbs_plus::signature_23::Signature23G1;
+use schnorr_pok::{partial::PartialSchnorrResponse, SchnorrResponse};
+
+/// the 2023 parameters and the public key of one issuer on the device
+pub struct GpuSignatureParams23 { bases: ResidentG1, l: usize, pk_pc: Vec<u64>, g2_pc: Vec<u64> }
+impl GpuSignatureParams23 {
+    /// `None` for parameters without a message generator, an identity `w` or `g2`, or when the library declines
+    pub fn new(params: &SignatureParams23G1<Bls12_381>, pk: &PublicKeyG2<Bls12_381>) -> Option<Self> {
+        let l = params.h.len();
+        if l == 0 { return None; }
+        let mut pts = Vec::with_capacity(l + 1);
+        pts.push(params.g1); pts.extend_from_slice(&params.h);
+        let (q, qi) = pack_g2(&[pk.0, params.g2]);
+        let (mut co, mut inf) = (ark_std::vec![0u64; 2 * G2_PREPARED_WORDS], [0u8; 2]);
+        if unsafe { dgpu_g2_prepare(q.as_ptr(), qi.as_ptr(), 2, co.as_mut_ptr(), inf.as_mut_ptr()) } != DGPU_OK || inf != [0u8; 2] { return None; }
+        let g2_pc = co.split_off(G2_PREPARED_WORDS);
+        let bases = ResidentG1::upload(&pts, None);              // a plain handle: the calls refuse a precomputed table
+        if bases.handle() == 0 { return None; }
+        Some(GpuSignatureParams23 { bases, l, pk_pc: co, g2_pc })
+    }
+    pub fn supported_message_count(&self) -> usize { self.l }
+}
+fn split_23(sigs: &[Signature23G1<Bls12_381>]) -> (Vec<u64>, Vec<Fr>) {
+    let a: Vec<G1Affine> = sigs.iter().map(|x| x.A).collect();
+    (pack_g1(&a).0, sigs.iter().map(|x| x.e).collect())
+}
+
+/// `Signature23G1::new` for every row with `e[i]` in place of its draw.  `None` entries are rows without a signature: `sk + e_i = 0` or an identity `b_i`.
+pub fn sign_many_23(params: &GpuSignatureParams23, sk: &SecretKey<Fr>, messages: &[&[Fr]], e: &[Fr]) -> Option<Vec<Option<Signature23G1<Bls12_381>>>> {
+    let n = messages.len();
+    if e.len() != n { return None; }
+    let flat = pack_rows(messages, params.l)?;
+    let (mut xy, mut bad) = (ark_std::vec![0u64; n * 12], ark_std::vec![0u8; n]);
+    if raw_bbs23_sign_many(params.bases.handle(), params.l, &sk.0, &flat, e, &mut xy, &mut bad) != DGPU_OK { return None; }
+    Some((0..n).map(|i| if bad[i] != 0 { None } else { Some(Signature23G1 { A: g1_affine(xy[12 * i..12 * i + 12].try_into().unwrap(), 0), e: e[i] }) }).collect())
+}
+/// `sigs[i].verify(messages[i], pk, params).is_ok()` for every i
+pub fn verify_each_23(params: &GpuSignatureParams23, sigs: &[Signature23G1<Bls12_381>], messages: &[&[Fr]]) -> Option<Vec<bool>> {
+    let n = sigs.len();
+    if messages.len() != n { return None; }
+    let flat = pack_rows(messages, params.l)?;
+    let (a, e) = split_23(sigs);
+    let mut ok = ark_std::vec![0u8; n];
+    if raw_bbs23_verify_each(params.bases.handle(), params.l, &params.pk_pc, &params.g2_pc, &a, &e, &flat, &mut ok) != DGPU_OK { return None; }
+    Some(ok.iter().map(|&k| k != 0).collect())
+}
+/// all of them at once under the weights `random^i` (`random` non-zero); an identity `A` anywhere is a rejection, no signatures at all verify
+pub fn verify_batch_23(params: &GpuSignatureParams23, sigs: &[Signature23G1<Bls12_381>], messages: &[&[Fr]], random: &Fr) -> Option<bool> {
+    let n = sigs.len();
+    if messages.len() != n { return None; }
+    if sigs.iter().any(|x| x.A.is_zero()) { return Some(false); }
+    let flat = pack_rows(messages, params.l)?;
+    let (a, e) = split_23(sigs);
+    let mut ok = 0i32;
+    if raw_bbs23_verify_batch(params.bases.handle(), params.l, &params.pk_pc, &params.g2_pc, &a, &e, &flat, random, &mut ok) != DGPU_OK { return None; }
+    Some(ok != 0)
+}
+
+// one proof's row of values and its trailing responses: `tail` responses follow the hidden messages' in the protocol's own order (CDL: the one over d; IETF: the
+// two over Abar and Bbar).  `None` where the reference answers with an error that is not one of its checks.
+fn pack_row_23(l: usize, i: usize, full: &Option<SchnorrResponse<G1Affine>>, part: &Option<PartialSchnorrResponse<G1Affine>>, tail: usize, rev: &BTreeMap<usize, Fr>,
+               missing: Option<&[&BTreeMap<usize, Fr>]>, fixed: &mut Vec<Fr>, values: &mut Vec<Fr>, mask: &mut [u8]) -> Option<()> {
+    if rev.keys().any(|&j| j >= l) { return None; }
+    let hidden = l - rev.len();
+    let resp = |k: usize| -> Option<Fr> {
+        match (full, part) {
+            (Some(f), None) => if missing.is_some() || f.0.len() != hidden + tail { None } else { Some(f.0[k]) },
+            (None, Some(p)) => if missing.is_none() || p.total_responses != hidden + tail { None } else { p.responses.get(&k).copied() },
+            _ => None,
+        }
+    };
+    for t in 0..tail { fixed.push(resp(hidden + t)?); }
+    let mut k = 0;
+    for j in 0..l {
+        if let Some(m) = rev.get(&j) { values.push(*m); mask[i * l + j] = 1; continue; }
+        let given = missing.and_then(|ms| ms[i].get(&j).copied());
+        values.push(match given { Some(z) => z, None => resp(k)? });
+        k += 1;
+    }
+    Some(())
+}
+fn pack_cdl(l: usize, proofs: &[CdlProof<Bls12_381>], revealed: &[&BTreeMap<usize, Fr>], missing: Option<&[&BTreeMap<usize, Fr>]>) -> Option<Packed> {
+    let n = proofs.len();
+    let (mut pts, mut fixed, mut values, mut mask) = (Vec::with_capacity(5 * n), Vec::with_capacity(3 * n), Vec::with_capacity(n * l), ark_std::vec![0u8; n * l]);
+    for (i, p) in proofs.iter().enumerate() {
+        pts.extend_from_slice(&[p.A_bar, p.B_bar, p.d, p.sc_resp_1.t, p.T2]);
+        fixed.extend_from_slice(&[p.sc_resp_1.response1, p.sc_resp_1.response2]);
+        pack_row_23(l, i, &p.sc_resp_2, &p.sc_partial_resp_2, 1, revealed[i], missing, &mut fixed, &mut values, &mut mask)?;
+    }
+    Some(Packed { points: pack_g1(&pts).0, fixed, values, revealed: mask })
+}
+fn pack_ietf(l: usize, proofs: &[IetfProof<Bls12_381>], revealed: &[&BTreeMap<usize, Fr>], missing: Option<&[&BTreeMap<usize, Fr>]>) -> Option<Packed> {
+    let n = proofs.len();
+    let (mut pts, mut fixed, mut values, mut mask) = (Vec::with_capacity(3 * n), Vec::with_capacity(2 * n), Vec::with_capacity(n * l), ark_std::vec![0u8; n * l]);
+    for (i, p) in proofs.iter().enumerate() {
+        pts.extend_from_slice(&[p.A_bar, p.B_bar, p.T]);
+        pack_row_23(l, i, &p.sc_resp, &p.sc_partial_resp, 2, revealed[i], missing, &mut fixed, &mut values, &mut mask)?;
+    }
+    Some(Packed { points: pack_g1(&pts).0, fixed, values, revealed: mask })
+}
+fn counts_ok(n: usize, revealed: &[&BTreeMap<usize, Fr>], challenges: &[Fr], missing: Option<&[&BTreeMap<usize, Fr>]>) -> bool {
+    revealed.len() == n && challenges.len() == n && !missing.map_or(false, |m| m.len() != n)
+}
+
+/// proof_23_cdl: `proofs[i].verify(revealed[i], &challenges[i], pk, params)` for every i (`verify_partial` with `missing[i]` where given): `Ok(())` or the
+/// reference's first error.  The points are taken as validated, as the reference takes them.
+pub fn pok_verify_each_23(params: &GpuSignatureParams23, proofs: &[CdlProof<Bls12_381>], revealed: &[&BTreeMap<usize, Fr>], challenges: &[Fr],
+                          missing: Option<&[&BTreeMap<usize, Fr>]>) -> Option<Vec<Result<(), BBSPlusError>>> {
+    if !counts_ok(proofs.len(), revealed, challenges, missing) { return None; }
+    let pk = pack_cdl(params.l, proofs, revealed, missing)?;
+    let mut status = ark_std::vec![0u8; proofs.len()];
+    if raw_bbs23_pok_verify_each(params.bases.handle(), params.l, &params.pk_pc, &params.g2_pc, &pk.points, &pk.fixed, &pk.values, &pk.revealed, challenges, &mut status) != DGPU_OK {
+        return None;
+    }
+    Some(status.into_iter().map(status_to_result).collect())
+}
+/// proof_23_cdl, one verdict under the weights `random^(2i)`, `random^(2i+1)`, `random^i` (`random` non-zero); no proofs at all verify
+pub fn pok_verify_batch_23(params: &GpuSignatureParams23, proofs: &[CdlProof<Bls12_381>], revealed: &[&BTreeMap<usize, Fr>], challenges: &[Fr],
+                           missing: Option<&[&BTreeMap<usize, Fr>]>, random: &Fr) -> Option<bool> {
+    if !counts_ok(proofs.len(), revealed, challenges, missing) { return None; }
+    let pk = pack_cdl(params.l, proofs, revealed, missing)?;
+    let mut ok = 0i32;
+    if raw_bbs23_pok_verify_batch(params.bases.handle(), params.l, &params.pk_pc, &params.g2_pc, &pk.points, &pk.fixed, &pk.values, &pk.revealed, challenges, random, &mut ok) != DGPU_OK {
+        return None;
+    }
+    Some(ok != 0)
+}
+/// proof_23_ietf: as `pok_verify_each_23`; its only Schnorr check fails as `SecondSchnorrVerificationFailed`, the name the reference gives it
+pub fn pok_ietf_verify_each_23(params: &GpuSignatureParams23, proofs: &[IetfProof<Bls12_381>], revealed: &[&BTreeMap<usize, Fr>], challenges: &[Fr],
+                               missing: Option<&[&BTreeMap<usize, Fr>]>) -> Option<Vec<Result<(), BBSPlusError>>> {
+    if !counts_ok(proofs.len(), revealed, challenges, missing) { return None; }
+    let pk = pack_ietf(params.l, proofs, revealed, missing)?;
+    let mut status = ark_std::vec![0u8; proofs.len()];
+    if raw_bbs23_pok_ietf_verify_each(params.bases.handle(), params.l, &params.pk_pc, &params.g2_pc, &pk.points, &pk.fixed, &pk.values, &pk.revealed, challenges, &mut status)
+        != DGPU_OK { return None; }
+    Some(status.into_iter().map(status_to_result).collect())
+}
+/// proof_23_ietf, one verdict under the weights `random^i`
+pub fn pok_ietf_verify_batch_23(params: &GpuSignatureParams23, proofs: &[IetfProof<Bls12_381>], revealed: &[&BTreeMap<usize, Fr>], challenges: &[Fr],
+                                missing: Option<&[&BTreeMap<usize, Fr>]>, random: &Fr) -> Option<bool> {
+    if !counts_ok(proofs.len(), revealed, challenges, missing) { return None; }
+    let pk = pack_ietf(params.l, proofs, revealed, missing)?;
+    let mut ok = 0i32;
+    if raw_bbs23_pok_ietf_verify_batch(params.bases.handle(), params.l, &params.pk_pc, &params.g2_pc, &pk.points, &pk.fixed, &pk.values, &pk.revealed, challenges, random, &mut ok)
+        != DGPU_OK { return None; }
+    Some(ok != 0)
+}

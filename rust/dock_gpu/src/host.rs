@@ -353,6 +353,49 @@ pub(crate) fn raw_bbs_plus_pok_verify_batch(params: u64, l: usize, h_0: &[u64], 
                                                revealed.as_ptr(), challenge.as_ptr() as *const u64, challenge.len(), 1, random as *const Fr as *const u64, ok) }
 }
 
+// ---- the 2023 scheme in bulk: the raw callers behind the `..23` types of src/bbs_plus.rs.  `params`: a plain bases handle holding `[g1, h ..]`, l + 1 points
+/// `A_i = (sk + e_i)^-1 (g1 + sum_j m_ij h_j)`; `messages`: n rows of `l`, packed; `out_a`: n x 12 words, `bad`: n bytes
+pub(crate) fn raw_bbs23_sign_many(params: u64, l: usize, sk: &Fr, messages: &[Fr], e: &[Fr], out_a: &mut [u64], bad: &mut [u8]) -> i32 {
+    unsafe { dgpu_bbs23_sign_many_g1(params, l, sk as *const Fr as *const u64, messages.as_ptr() as *const u64, l, e.as_ptr() as *const u64, e.len(), 1, out_a.as_mut_ptr(),
+                                     bad.as_mut_ptr()) }
+}
+/// `ok[i] = (A_i != O and e(A_i, w) e(e_i A_i - b_i, g2) == 1)`
+pub(crate) fn raw_bbs23_verify_each(params: u64, l: usize, pk_pc: &[u64], g2_pc: &[u64], sig_a: &[u64], e: &[Fr], messages: &[Fr], ok: &mut [u8]) -> i32 {
+    unsafe { dgpu_bbs23_verify_each_g1(params, l, pk_pc.as_ptr(), g2_pc.as_ptr(), sig_a.as_ptr(), e.as_ptr() as *const u64, messages.as_ptr() as *const u64, l, e.len(), 1,
+                                       ok.as_mut_ptr()) }
+}
+/// one verdict for all rows under the weights `random^i`
+pub(crate) fn raw_bbs23_verify_batch(params: u64, l: usize, pk_pc: &[u64], g2_pc: &[u64], sig_a: &[u64], e: &[Fr], messages: &[Fr], random: &Fr, ok: &mut i32) -> i32 {
+    unsafe { dgpu_bbs23_verify_batch_g1(params, l, pk_pc.as_ptr(), g2_pc.as_ptr(), sig_a.as_ptr(), e.as_ptr() as *const u64, messages.as_ptr() as *const u64, l, e.len(), 1,
+                                        random as *const Fr as *const u64, ok) }
+}
+/// proof_23_cdl's `PoKOfSignature23G1Proof::verify` per proof: `status[i]` = 0, or the first failing check (1 ZeroSignature, 2 / 3 the Schnorr checks, 4 the
+/// pairing).  `points`: n x 5 x 12 words (Abar, Bbar, d, T1, T2); `resp_fixed`: n x 3 (z1, z2, z3); `values`: n rows of `l`, packed; `revealed`: n x l bytes
+pub(crate) fn raw_bbs23_pok_verify_each(params: u64, l: usize, pk_pc: &[u64], g2_pc: &[u64], points: &[u64], resp_fixed: &[Fr], values: &[Fr], revealed: &[u8], challenge: &[Fr],
+                                        status: &mut [u8]) -> i32 {
+    unsafe { dgpu_bbs23_pok_verify_each_g1(params, l, pk_pc.as_ptr(), g2_pc.as_ptr(), points.as_ptr(), resp_fixed.as_ptr() as *const u64, values.as_ptr() as *const u64, l,
+                                           revealed.as_ptr(), challenge.as_ptr() as *const u64, challenge.len(), 1, status.as_mut_ptr()) }
+}
+/// one verdict for all CDL proofs under the weights `random^(2i)`, `random^(2i+1)`, `random^i`
+pub(crate) fn raw_bbs23_pok_verify_batch(params: u64, l: usize, pk_pc: &[u64], g2_pc: &[u64], points: &[u64], resp_fixed: &[Fr], values: &[Fr], revealed: &[u8], challenge: &[Fr],
+                                         random: &Fr, ok: &mut i32) -> i32 {
+    unsafe { dgpu_bbs23_pok_verify_batch_g1(params, l, pk_pc.as_ptr(), g2_pc.as_ptr(), points.as_ptr(), resp_fixed.as_ptr() as *const u64, values.as_ptr() as *const u64, l,
+                                            revealed.as_ptr(), challenge.as_ptr() as *const u64, challenge.len(), 1, random as *const Fr as *const u64, ok) }
+}
+/// proof_23_ietf's `PoKOfSignature23G1Proof::verify` per proof: `status[i]` = 0, 1 ZeroSignature, 3 its Schnorr check, 4 the pairing.  `points`: n x 3 x 12 words
+/// (Abar, Bbar, T); `resp_fixed`: n x 2 (z_a, z_b)
+pub(crate) fn raw_bbs23_pok_ietf_verify_each(params: u64, l: usize, pk_pc: &[u64], g2_pc: &[u64], points: &[u64], resp_fixed: &[Fr], values: &[Fr], revealed: &[u8],
+                                             challenge: &[Fr], status: &mut [u8]) -> i32 {
+    unsafe { dgpu_bbs23_pok_ietf_verify_each_g1(params, l, pk_pc.as_ptr(), g2_pc.as_ptr(), points.as_ptr(), resp_fixed.as_ptr() as *const u64, values.as_ptr() as *const u64, l,
+                                                revealed.as_ptr(), challenge.as_ptr() as *const u64, challenge.len(), 1, status.as_mut_ptr()) }
+}
+/// one verdict for all IETF proofs under the weights `random^i`
+pub(crate) fn raw_bbs23_pok_ietf_verify_batch(params: u64, l: usize, pk_pc: &[u64], g2_pc: &[u64], points: &[u64], resp_fixed: &[Fr], values: &[Fr], revealed: &[u8],
+                                              challenge: &[Fr], random: &Fr, ok: &mut i32) -> i32 {
+    unsafe { dgpu_bbs23_pok_ietf_verify_batch_g1(params, l, pk_pc.as_ptr(), g2_pc.as_ptr(), points.as_ptr(), resp_fixed.as_ptr() as *const u64, values.as_ptr() as *const u64, l,
+                                                 revealed.as_ptr(), challenge.as_ptr() as *const u64, challenge.len(), 1, random as *const Fr as *const u64, ok) }
+}
+
 // ---- R1CS -> QAP witness map (legogroth16/src/r1cs_to_qap.rs:150-210) ---------------------------------------------------------------------------------
 /// one constraint matrix of ark-relations' `ConstraintMatrices` (`Matrix<F> = Vec<Vec<(F, usize)>>`) as the CSR arrays the ABI takes, with a 64-bit hash of
 /// its whole contents computed on the way (the copy reads every coefficient anyway)

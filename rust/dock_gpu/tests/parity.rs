@@ -810,6 +810,91 @@ fn bbs_plus_pok_bulk_equals_the_reference() {
     }
 }
 
+// the 2023 scheme in bulk against the reference's own Signature23G1::new / verify (bbs_plus/src/signature_23.rs) and both PoKOfSignature23G1Proof::verify
+// (proof_23_cdl.rs:302-549, proof_23_ietf.rs:244-479): the same A, the same Ok / first error, proof by proof; one verdict for the batch
+#[cfg(feature = "bbs-plus")]
+#[test]
+fn bbs23_bulk_equals_the_reference() {
+    use bbs_plus::prelude::{KeypairG2, MessageOrBlinding};
+    use bbs_plus::proof_23_cdl::{PoKOfSignature23G1Proof as CdlProof, PoKOfSignature23G1Protocol as CdlProtocol};
+    use bbs_plus::proof_23_ietf::{PoKOfSignature23G1Proof as IetfProof, PoKOfSignature23G1Protocol as IetfProtocol};
+    use bbs_plus::setup::SignatureParams23G1;
+    use bbs_plus::signature_23::Signature23G1;
+    use dock_gpu::bbs_plus::{pok_ietf_verify_batch_23, pok_ietf_verify_each_23, pok_verify_batch_23, pok_verify_each_23, sign_many_23, verify_batch_23, verify_each_23,
+                             GpuSignatureParams23};
+    use std::collections::{BTreeMap, BTreeSet};
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5EED2023);
+    for &(l, n) in &[(1usize, 3usize), (5, 65), (30, 257)] {
+        let params = SignatureParams23G1::<Bls12_381>::generate_using_rng(&mut rng, l as u32);
+        let keypair = KeypairG2::<Bls12_381>::generate_using_rng_and_bbs23_params(&mut rng, &params);
+        let msgs: Vec<Vec<Fr>> = (0..n).map(|_| frs(&mut rng, l)).collect();
+        let rows: Vec<&[Fr]> = msgs.iter().map(|m| m.as_slice()).collect();
+        let sigs: Vec<Signature23G1<Bls12_381>> = msgs.iter().map(|m| Signature23G1::new(&mut rng, m, &keypair.secret_key, &params).unwrap()).collect();
+        let e: Vec<Fr> = sigs.iter().map(|x| x.e).collect();
+        let gp = GpuSignatureParams23::new(&params, &keypair.public_key).expect("parameters");
+        assert_eq!(gp.supported_message_count(), l);
+        let mine = sign_many_23(&gp, &keypair.secret_key, &rows, &e).expect("sign_many_23");
+        for i in 0..n { assert_eq!(mine[i].as_ref().expect("a signature"), &sigs[i], "l = {l}, row {i}"); }
+        let mut e2 = e.clone(); e2[n - 1] = -keypair.secret_key.0;
+        let flagged = sign_many_23(&gp, &keypair.secret_key, &rows, &e2).expect("sign_many_23");
+        assert!(flagged[n - 1].is_none() && flagged[..n - 1].iter().zip(sigs.iter()).all(|(a, b)| a.as_ref() == Some(b)));
+        let mut bad = sigs.clone();
+        let mut bad_msgs = msgs.clone();
+        bad_msgs[0][0] += Fr::from(1u64);
+        if n > 2 { bad[1].e += Fr::from(1u64); let a = bad[n - 1].A; bad[n - 1].A = bad[n - 2].A; bad[n - 2].A = a; }
+        let bad_rows: Vec<&[Fr]> = bad_msgs.iter().map(|m| m.as_slice()).collect();
+        let want: Vec<bool> = bad.iter().zip(bad_msgs.iter()).map(|(x, m)| x.verify(m, keypair.public_key.clone(), params.clone()).is_ok()).collect();
+        assert_eq!(verify_each_23(&gp, &bad, &bad_rows).expect("verify_each_23"), want);
+        assert!(verify_each_23(&gp, &sigs, &rows).expect("verify_each_23").iter().all(|&k| k));
+        let rho = Fr::rand(&mut rng);
+        assert_eq!(verify_batch_23(&gp, &sigs, &rows, &rho), Some(true));
+        assert_eq!(verify_batch_23(&gp, &bad, &bad_rows, &rho), Some(false));
+
+        // proofs of both kinds over the same signatures, every proof its own pattern: nothing revealed, everything, every (i % 5 + 2)-th message
+        let (mut cdl, mut ietf, mut revealed, mut challenges): (Vec<CdlProof<Bls12_381>>, Vec<IetfProof<Bls12_381>>, Vec<BTreeMap<usize, Fr>>, Vec<Fr>) = (vec![], vec![], vec![], vec![]);
+        for i in 0..n {
+            let ids: BTreeSet<usize> = match i % 3 { 0 => BTreeSet::new(), 1 => (0..l).collect(), _ => (0..l).filter(|j| j % (i % 5 + 2) == 0).collect() };
+            let mb = |m: &Vec<Fr>| -> Vec<MessageOrBlinding<Fr>> {
+                m.iter().enumerate().map(|(j, v)| if ids.contains(&j) { MessageOrBlinding::RevealMessage(v) } else { MessageOrBlinding::BlindMessageRandomly(v) }).collect()
+            };
+            let c = Fr::rand(&mut rng);
+            cdl.push(CdlProtocol::init(&mut rng, &sigs[i], &params, mb(&msgs[i])).unwrap().gen_proof(&c).unwrap());
+            ietf.push(IetfProtocol::init(&mut rng, &sigs[i], &params, mb(&msgs[i])).unwrap().gen_proof(&c).unwrap());
+            revealed.push(ids.iter().map(|&j| (j, msgs[i][j])).collect());
+            challenges.push(c);
+        }
+        let maps: Vec<&BTreeMap<usize, Fr>> = revealed.iter().collect();
+        assert!(pok_verify_each_23(&gp, &cdl, &maps, &challenges, None).expect("pok_verify_each_23").iter().all(|r| r.is_ok()), "l = {l}");
+        assert!(pok_ietf_verify_each_23(&gp, &ietf, &maps, &challenges, None).expect("pok_ietf_verify_each_23").iter().all(|r| r.is_ok()), "l = {l}");
+        assert_eq!(pok_verify_batch_23(&gp, &cdl, &maps, &challenges, None, &rho), Some(true));
+        assert_eq!(pok_ietf_verify_batch_23(&gp, &ietf, &maps, &challenges, None, &rho), Some(true));
+        // one tamper of every kind the reference tells apart, and the reference's verdict beside ours
+        let (mut bad_cdl, mut bad_ietf, mut bad_c) = (cdl.clone(), ietf.clone(), challenges.clone());
+        bad_cdl[0].sc_resp_1.response1 += Fr::from(1u64);
+        bad_ietf[0].T = bad_ietf[1].T;
+        if n > 4 {
+            bad_cdl[1].T2 = bad_cdl[2].T2;
+            bad_cdl[2].A_bar = G1Affine::zero();
+            bad_ietf[2].A_bar = G1Affine::zero();
+            let (a, b) = (bad_cdl[3].A_bar, bad_cdl[3].B_bar);
+            bad_cdl[3].B_bar = (b + a).into_affine();
+            bad_c[4] += Fr::from(1u64);
+        }
+        let mine = pok_verify_each_23(&gp, &bad_cdl, &maps, &bad_c, None).expect("pok_verify_each_23");
+        let mine_ietf = pok_ietf_verify_each_23(&gp, &bad_ietf, &maps, &bad_c, None).expect("pok_ietf_verify_each_23");
+        for i in 0..n {
+            let theirs = bad_cdl[i].verify(&revealed[i], &bad_c[i], keypair.public_key.clone(), params.clone());
+            assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "CDL, l = {l}, proof {i}");
+            let theirs = bad_ietf[i].verify(&revealed[i], &bad_c[i], keypair.public_key.clone(), params.clone());
+            assert_eq!(format!("{:?}", mine_ietf[i]), format!("{:?}", theirs), "IETF, l = {l}, proof {i}");
+        }
+        assert!(mine[0].is_err() && mine_ietf[0].is_err());
+        assert_eq!(pok_verify_batch_23(&gp, &bad_cdl, &maps, &bad_c, None, &rho), Some(false));
+        assert_eq!(pok_ietf_verify_batch_23(&gp, &bad_ietf, &maps, &bad_c, None, &rho), Some(false));
+    }
+}
+
 // accumulator proofs in bulk against the reference's own MembershipProof::verify and NonMembershipProof::verify (vb_accumulator/src/proofs_cdh.rs:138-149, :365-387):
 // the same Ok / first error, proof by proof; one verdict for the batch
 #[cfg(feature = "vb-accumulator")]
