@@ -4,6 +4,7 @@
 #include "msm_driver.hip.h"
 #include "acc_launch.hip.h"
 #include "qap_launch.hip.h"
+#include "selftest_launch.hip.h"
 #include "../../include/dock_gpu_dev.h"
 
 using namespace dock;
@@ -60,7 +61,7 @@ int32_t dgpu_selftest_fp_mul(const uint64_t *a, const uint64_t *b, size_t n, uin
     void *da, *db, *dout;
     HIPCHK(dev_malloc(&da, n * 48 + 16)); HIPCHK(dev_malloc(&db, n * 48 + 16)); HIPCHK(dev_malloc(&dout, n * 48 + 16));
     HIPCHK(hipMemcpy(da, a, n * 48, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(db, b, n * 48, hipMemcpyHostToDevice));
-    launch_selftest_fp_mul(sl.stream, (const uint32_t *)da, (const uint32_t *)db, n, (uint32_t *)dout);
+    selftest::launch_selftest_fp_mul(sl.stream, (const uint32_t *)da, (const uint32_t *)db, n, (uint32_t *)dout);
     HIPCHK(hipStreamSynchronize(sl.stream));
     HIPCHK(hipMemcpy(out, dout, n * 48, hipMemcpyDeviceToHost));
     (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
@@ -74,13 +75,31 @@ int32_t dgpu_selftest_g1_sum(const uint64_t *pts, const uint8_t *neg, size_t n, 
     HIPCHK(dev_malloc(&dp, n * 96 + 16)); HIPCHK(dev_malloc(&dn, n + 16)); HIPCHK(dev_malloc(&dout, 4 * 48)); HIPCHK(dev_malloc(&dinf, 16));
     HIPCHK(hipMemcpy(dp, pts, n * 96, hipMemcpyHostToDevice));
     if (neg) HIPCHK(hipMemcpy(dn, neg, n, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(dn, 0, n + 16));
-    launch_selftest_g1_sum(sl.stream, (const uint32_t *)dp, (const uint8_t *)dn, n, (uint32_t *)dout, (uint8_t *)dinf);
+    selftest::launch_selftest_g1_sum(sl.stream, (const uint32_t *)dp, (const uint8_t *)dn, n, (uint32_t *)dout, (uint8_t *)dinf);
     HIPCHK(hipStreamSynchronize(sl.stream));
     uint64_t w[24]; uint8_t inf;
     HIPCHK(hipMemcpy(w, dout, 4 * 48, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&inf, dinf, 1, hipMemcpyDeviceToHost));
     (void)hipFree(dp); (void)hipFree(dn); (void)hipFree(dout); (void)hipFree(dinf);
     uint8_t finf = inf;
     host_fold<hostf::Fq>(w, &finf, 1, 1, out);
+    return DGPU_OK;
+}
+// one arithmetic function of the device headers per call (selftest_kernels.hip.h): n rows of in_words u64 in, out_words u64 out
+int32_t dgpu_selftest_arith(int32_t op, int32_t stress, const uint64_t *in, size_t in_words, size_t n, uint64_t *out, size_t out_words) {
+    size_t iw = 0, ow = 0;
+    if (!selftest::selftest_arith_shape(op, stress, &iw, &ow) || iw != in_words || ow != out_words || (n && (!in || !out)) || n > ((size_t)1 << 24)) return DGPU_E_BADARG;
+    if (!cur().ready) return DGPU_E_NODEVICE;
+    if (!n) return DGPU_OK;
+    SLOT_ACQUIRE(L, sl);
+    HIPCHK(hipSetDevice(cur().device));
+    void *din, *dout;
+    HIPCHK(dev_malloc(&din, n * iw * 8 + 16)); HIPCHK(dev_malloc(&dout, n * ow * 8 + 16));
+    HIPCHK(hipMemcpy(din, in, n * iw * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dout, 0, n * ow * 8));
+    selftest::launch_selftest_arith(sl.stream, op, stress, (const uint32_t *)din, n, (uint32_t *)dout);
+    HIPCHK(hipStreamSynchronize(sl.stream));
+    HIPCHK(hipMemcpy(out, dout, n * ow * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(din); (void)hipFree(dout);
     return DGPU_OK;
 }
 // host self-test hook: the GLV split the scaling kernel is fed with (k mod r = k1 + k2 lambda, both < 2^128)

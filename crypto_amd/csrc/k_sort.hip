@@ -1,4 +1,4 @@
-// crypto_amd/csrc/k_sort.hip — translation unit of the curve-independent kernels (digits, counting sort, scan, self-tests).
+// crypto_amd/csrc/k_sort.hip — translation unit of the curve-independent kernels (digits, counting sort, scan).
 #include "sort_kernels.hip.h"
 #include "sort_launch.hip.h"
 
@@ -31,11 +31,5 @@ void launch_flag_heavy(hipStream_t s, const uint32_t *off, uint32_t NB, const ui
 void launch_g1_scale(hipStream_t s, const uint32_t *p_abi, const uint8_t *is_inf, const uint32_t *scalars, int scalar_stride, const uint8_t *negate, size_t n, uint32_t *out_abi, uint8_t *out_inf,
                      const uint32_t *add_abi, const uint8_t *add_inf) {
     hipLaunchKernelGGL(k_g1_scale, dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, s, p_abi, is_inf, scalars, scalar_stride, negate, n, out_abi, out_inf, add_abi, add_inf);
-}
-void launch_selftest_fp_mul(hipStream_t s, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out) {
-    hipLaunchKernelGGL(k_selftest_fp_mul, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, a, b, n, out);
-}
-void launch_selftest_g1_sum(hipStream_t s, const uint32_t *pts, const uint8_t *neg, size_t n, uint32_t *out, uint8_t *out_inf) {
-    hipLaunchKernelGGL(k_selftest_g1_sum, dim3(1), dim3(64), 0, s, pts, neg, n, out, out_inf);
 }
 }  // namespace msm

@@ -1,5 +1,5 @@
 // crypto_amd/csrc/sort_kernels.hip.h — curve-independent kernels of the MSM pipeline: signed-digit recoding, the LDS
-// counting sort (K2/K4), the histogram scan (K3) and the device self-tests.  Included by k_sort.hip only.
+// counting sort (K2/K4) and the histogram scan (K3).  Included by k_sort.hip only.
 #pragma once
 #include "dyn_chunk.hip.h"
 #include <hip/hip_runtime.h>
@@ -165,27 +165,6 @@ __global__ void __launch_bounds__(256) k_flag_heavy(const uint32_t *__restrict__
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= NB) return;
     if (off[b + 1] - off[b] >= dyn[DYN_HEAVY]) { uint32_t h = atomicAdd(&heavy[0], 1u); if (h < heavy_cap) heavy[1 + h] = b; }
-}
-
-// ---- self-test kernels (tests/: device arithmetic vs oracle without the MSM plumbing) ------------------------
-__global__ void k_selftest_fp_mul(const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fp x, y, r; fp_from_abi(x, a + 12 * i); fp_from_abi(y, b + 12 * i);
-    fp_mul(r, x, y);
-    fp_to_abi(out + 12 * i, r);
-}
-// one thread: sum of (+/-) points by mixed additions, result in ABI XYZZ form
-__global__ void k_selftest_g1_sum(const uint32_t *pts_abi, const uint8_t *neg, size_t n, uint32_t *out, uint8_t *out_inf) {
-    if (blockIdx.x || threadIdx.x) return;
-    Xyzz<Fp> acc; bool inf = true;
-    fzero(acc.x); fzero(acc.y); fzero(acc.zz); fzero(acc.zzz);
-    for (size_t i = 0; i < n; i++) {
-        Aff<Fp> p; fp_from_abi(p.x, pts_abi + 24 * i); fp_from_abi(p.y, pts_abi + 24 * i + 12);
-        xyzz_madd(acc, inf, p, neg && neg[i]);
-    }
-    *out_inf = inf;
-    if (!inf) { fp_to_abi(out, acc.x); fp_to_abi(out + 12, acc.y); fp_to_abi(out + 24, acc.zz); fp_to_abi(out + 36, acc.zzz); }
 }
 
 // ---- batched G1 scalar multiplication: out_i = s_i * P_i (affine, ABI form) --------------------------------------

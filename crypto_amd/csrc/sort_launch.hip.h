@@ -1,5 +1,5 @@
 // crypto_amd/csrc/sort_launch.hip.h — host-callable launchers of the curve-independent kernels (k_sort.hip): digit recoding,
-// LDS counting sort, histogram scan, batched G1 scaling, device self-tests.
+// LDS counting sort, histogram scan, batched G1 scaling.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -54,7 +54,5 @@ void launch_id_flags(hipStream_t s, const uint32_t *bases, int aff_stride, int f
 void launch_raw_record_hash(hipStream_t s, const uint8_t *raw, size_t stride, size_t x_off, size_t y_off, size_t inf_off, const uint8_t *is_inf, int words, size_t n, uint64_t *out);
 void launch_g1_scale(hipStream_t s, const uint32_t *p_abi, const uint8_t *is_inf, const uint32_t *scalars, int scalar_stride, const uint8_t *negate, size_t n, uint32_t *out_abi, uint8_t *out_inf,
                      const uint32_t *add_abi = nullptr, const uint8_t *add_inf = nullptr);
-void launch_selftest_fp_mul(hipStream_t s, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out);
-void launch_selftest_g1_sum(hipStream_t s, const uint32_t *pts, const uint8_t *neg, size_t n, uint32_t *out, uint8_t *out_inf);
 
 }  // namespace msm

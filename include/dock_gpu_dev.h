@@ -96,6 +96,11 @@ int32_t dgpu_selftest_glv_decompose(const uint64_t k[4], uint64_t k1[2], uint64_
 int32_t dgpu_selftest_gls4_decompose(const uint64_t k[4], uint64_t d[4]);
 int32_t dgpu_selftest_fp_mul(const uint64_t *a /* n*6 */, const uint64_t *b /* n*6 */, size_t n, uint64_t *out /* n*6 */);
 int32_t dgpu_selftest_g1_sum(const uint64_t *pts_xy /* n*12 */, const uint8_t *neg, size_t n, uint64_t out_xyz[18]);
+/* One arithmetic function of the device headers per call, one kernel per op (crypto_amd/csrc/selftest_kernels.hip.h lists the ops and their row
+ * shapes): n rows of in_words u64 in and out_words u64 out, in the ABI forms of dock_gpu.h (field elements * 2^384 mod p, Fr as 256-bit words,
+ * points out as X, Y, ZZ, ZZZ).  stress = k: an operand is added to itself k - 1 times, un-normalised, before the operation (for the Fr word ops
+ * it is the Montgomery flag, for the chains a repetition count).  DGPU_E_BADARG: unknown op, or a row shape that is not the op's. */
+int32_t dgpu_selftest_arith(int32_t op, int32_t stress, const uint64_t *in, size_t in_words, size_t n, uint64_t *out, size_t out_words);
 
 /* ---- fault injection (tests/test_gpu_fault_paths.py): the k-th hipMalloc from now and the count - 1 after it fail ---- */
 int32_t dgpu_dev_fail_alloc_after(int64_t k, int64_t count);

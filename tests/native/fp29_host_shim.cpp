@@ -10,6 +10,7 @@
 #include "../../crypto_amd/csrc/host_field.hpp"
 #include "../../crypto_amd/csrc/fr29.hip.h"
 #include "../../crypto_amd/csrc/fp_safegcd.hip.h"
+#include "../../crypto_amd/csrc/selftest_kernels.hip.h"
 #include <vector>
 #include <string.h>
 using namespace bls29;
@@ -293,4 +294,34 @@ void shim_fr_butterflies(const uint32_t *a, const uint32_t *b, const uint32_t *w
     for (int i = 0; i < reps; i++) { fr29::fr_mul(t, y, tw); fr29::fr_add(u, x, t); fr29::fr_sub(v, x, t); fr29::fr_norm(x, u); fr29::fr_norm(y, v); }
     fr29::fr_to_words(out_x, x, 0); fr29::fr_to_words(out_y, y, 0);
 }
+
+}  // extern "C"
+
+// ---- the wrappers of the device self-tests (selftest_kernels.hip.h), the same bodies the GPU kernels run, under the bound tracker: n rows of in_words
+// u64 in, out_words u64 out.  0: done; -3: unknown op, an op with a lane exchange (device only), or a row shape that is not the op's ----
+template <int OP> static int st_rows(int stress, const uint64_t *in, size_t in_words, size_t n, uint64_t *out, size_t out_words) {
+    using O = selftest::StOp<OP>;
+    if (in_words != (size_t)O::IN64 || out_words != (size_t)O::OUT64) return -3;
+    for (size_t i = 0; i < n; i++) O::run(reinterpret_cast<const uint32_t *>(in + i * in_words), reinterpret_cast<uint32_t *>(out + i * out_words), stress);
+    return 0;
+}
+extern "C" int shim_selftest_arith(int op, int stress, const uint64_t *in, size_t in_words, size_t n, uint64_t *out, size_t out_words) {
+    using namespace selftest;
+    switch (op) {
+#define X(ID) case ID: return st_rows<ID>(stress, in, in_words, n, out, out_words);
+        X(ST_FP_ROUNDTRIP) X(ST_FP_MUL) X(ST_FP_SQR) X(ST_FP_MUL2) X(ST_FP_MUL_SUB) X(ST_FP_MUL12) X(ST_FP_CANON) X(ST_FP_ISZERO) X(ST_FP_INV) X(ST_FP_SUBMUL)
+        X(ST_FS_ROUNDTRIP) X(ST_FS_MUL) X(ST_FS_SQR) X(ST_FS_MUL2) X(ST_FS_MUL_SUB) X(ST_FS_NEG) X(ST_FS_BAL) X(ST_FS_BAL_WIDE) X(ST_FS_ISZERO) X(ST_FS_VIA_FP) X(ST_FS_SUBMUL)
+        X(ST_FP2_MUL) X(ST_FP2_SQR) X(ST_FS2_MUL) X(ST_FS2_SQR)
+        X(ST_FR_ROUNDTRIP) X(ST_FR_MUL) X(ST_FR_BUTTERFLIES) X(ST_FR_CANON) X(ST_FR_INV)
+        X(ST_G1_MADD) X(ST_G1_TREE) X(ST_G1_DBL) X(ST_G1S_MADD) X(ST_G1S_TREE) X(ST_G1S_DBL) X(ST_G1S_TREE_ROUNDS) X(ST_G1S_DBL_ROUNDS)
+        X(ST_G2_MADD) X(ST_G2_TREE) X(ST_G2_DBL) X(ST_G2S_MADD) X(ST_G2S_MADD_EARLY) X(ST_G2S_TREE) X(ST_G2S_DBL) X(ST_G2S_TREE_ROUNDS) X(ST_G2S_DBL_ROUNDS)
+        X(ST_F12_MUL) X(ST_F12_MUL_ROLES) X(ST_F12_MUL_BY_014)
+#undef X
+        case ST_FR_BATCH_INV: {
+            if (stress < 1 || stress > ST_MAX_SHARE || in_words != 4 * (size_t)stress || out_words != in_words) return -3;
+            for (size_t g = 0; g < n; g++) st_fr_batch_inv_lane(reinterpret_cast<const uint32_t *>(in), reinterpret_cast<uint32_t *>(out), g, n, stress);
+            return 0;
+        }
+        default: return -3;
+    }
 }

@@ -45,6 +45,19 @@ def test_development_surface_lives_in_the_twin_only():
     assert exported("libdock_gpu_dev.so") == sorted(SYMBOLS + DEV_SYMBOLS)
 
 
+def test_device_self_tests_live_in_the_twin_only():
+    """dgpu_selftest_arith (one arithmetic function of the device headers per kernel, crypto_amd/csrc/k_selftest.hip) is exported by the twin alone, refuses an
+    unknown op or a row shape that is not the op's before it looks for a device, and the product library carries no self-test kernel at all"""
+    L, T = lib(), dev_lib()
+    assert "dgpu_selftest_arith" in DEV_SYMBOLS and hasattr(T, "dgpu_selftest_arith") and not hasattr(L, "dgpu_selftest_arith")
+    z = np.zeros(16, np.uint64)
+    p = z.ctypes.data_as(C.c_void_p)
+    assert T.dgpu_selftest_arith(9999, 1, p, 6, 1, p, 6) == -3
+    assert T.dgpu_selftest_arith(1, 1, p, 11, 1, p, 6) == -3           # fp_mul takes 12 words a row
+    blob = lambda so: open(os.path.join(ROOT, "crypto_amd", so), "rb").read()
+    assert b"k_selftest" not in blob("libdock_gpu.so") and b"k_selftest_arith" in blob("libdock_gpu_dev.so")
+
+
 def test_error_strings():
     L = lib()
     for code in range(0, -8, -1):
