@@ -105,6 +105,7 @@ SYMBOLS = [
     "dgpu_bbs_plus_sign_many_g1", "dgpu_bbs_plus_verify_each_g1", "dgpu_bbs_plus_verify_batch_g1", "dgpu_bbs_plus_pok_verify_each_g1", "dgpu_bbs_plus_pok_verify_batch_g1",
     "dgpu_bbs23_sign_many_g1", "dgpu_bbs23_verify_each_g1", "dgpu_bbs23_verify_batch_g1", "dgpu_bbs23_pok_verify_each_g1", "dgpu_bbs23_pok_verify_batch_g1",
     "dgpu_bbs23_pok_ietf_verify_each_g1", "dgpu_bbs23_pok_ietf_verify_batch_g1",
+    "dgpu_ps_sign_many_g1", "dgpu_ps_verify_each", "dgpu_ps_verify_batch", "dgpu_ps_pok_verify_each",
     "dgpu_window_table_g1", "dgpu_window_table_g2", "dgpu_window_table_free", "dgpu_window_table_mul_g1", "dgpu_window_table_mul_g2", "dgpu_window_table_mul_to_bases_g1", "dgpu_window_table_mul_to_bases_g2", "dgpu_fixed_base_g1", "dgpu_fixed_base_g2", "dgpu_g1_mul_add_batch", "dgpu_g2_mul_add_batch",
     "dgpu_legogroth16_prove", "dgpu_legogroth16_prove_host", "dgpu_legogroth16_verify", "dgpu_legogroth16_verify_batch", "dgpu_legogroth16_verify_each", "dgpu_handle_len", "dgpu_handle_context", "dgpu_shard_count", "dgpu_shard_part",
     "dgpu_snarkpack_proof_words", "dgpu_snarkpack_aggregate", "dgpu_snarkpack_verify",
@@ -303,6 +304,10 @@ def _load(path):
             getattr(L, name).argtypes = [u64, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, C.c_int32, vp]
         for name in ("dgpu_bbs23_pok_verify_batch_g1", "dgpu_bbs23_pok_ietf_verify_batch_g1"):
             getattr(L, name).argtypes = [u64, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, C.c_int32, vp, C.POINTER(C.c_int32)]
+        L.dgpu_ps_sign_many_g1.argtypes = [u64, sz, vp, vp, sz, vp, sz, C.c_int32, vp, vp]
+        L.dgpu_ps_verify_each.argtypes = [u64, sz, vp, vp, vp, sz, sz, C.c_int32, vp]
+        L.dgpu_ps_verify_batch.argtypes = [u64, sz, vp, vp, vp, sz, sz, C.c_int32, vp, C.POINTER(C.c_int32)]
+        L.dgpu_ps_pok_verify_each.argtypes = [u64, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, C.c_int32, vp]
         L.dgpu_witness_map.argtypes = [vp, vp, vp, sz] * 3 + [vp, sz, sz, sz, C.c_int32, vp, C.POINTER(u64), C.POINTER(sz)]
         for name in ("dgpu_window_table_g1", "dgpu_window_table_g2"):
             getattr(L, name).argtypes = [vp, C.POINTER(u64)]

@@ -65,14 +65,7 @@ bool bad_rows(const Rows &r) {
 // the parameters: a plain G1 bases handle of exactly nn = L + 2 (2023: L + 1) points, pinned for the call
 bool params_ok(const HandleRef &hb, size_t nn) { return hb.ok && hb.h.kind == 1 && hb.h.n == nn; }
 
-// How the b_i (the P_i of a proof) of a chunk are made: RowMsm (msm_many.hip.h) over the parameters' handle, whose small-path table serves the many-row kernels
-RowMsm<G1> param_rows(Slot &sl, uint64_t params, const Handle &h, size_t nn, size_t cap, size_t n) {
-    SmallSub sub{nullptr, nullptr};
-    const bool many = h.n <= SMALL_MSM_MAX_N && nn <= gs.small_max.load() && small_sub_for<G1>(sl, params, h, 0, nn, sub, true);
-    RowMsm<G1> rm(many, nn, n, cap);
-    rm.sub = sub; rm.rec = (const uint32_t *)h.p;
-    return rm;
-}
+// (how the b_i, the P_i of a proof, of a chunk are made: param_rows<G1>, msm_many.hip.h)
 // s (BBS+) and the messages of the rows [r0, r0 + rows) to the device: the messages packed (what lies between the caller's rows never crosses)
 int32_t rows_up(Slot &sl, const Rows &r, size_t r0, size_t rows, void *d_s, void *d_m) {
     hipStream_t s = sl.stream;
@@ -99,7 +92,7 @@ int32_t sign_many(uint64_t params, const uint64_t *sk, const Rows &r, uint64_t *
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    const RowMsm<G1> bp = param_rows(sl, params, hb.h, nn, ~(size_t)0, n);
+    const RowMsm<G1> bp = param_rows<G1>(sl, params, hb.h, nn, ~(size_t)0, n);
     const size_t chunk = bp.chunk;
     // q[0]: t, q[1]: s, q[2]: the messages, q[4]: [A | identity flags]
     auto ws = [&](Slot &o) -> int32_t {
@@ -172,7 +165,7 @@ int32_t verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_p
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    const RowMsm<G1> bp = param_rows(sl, params, hb.h, nn, bbsk::BBS_EACH_CHUNK, n);
+    const RowMsm<G1> bp = param_rows<G1>(sl, params, hb.h, nn, bbsk::BBS_EACH_CHUNK, n);
     const size_t chunk = bp.chunk;
     // q[0]: the split -e, q[1]: s, q[2]: the messages, q[3]: A, q[4]: [b | identity flags], q[5]: d, q[6]: [skip flags of (A, d) | ones]
     auto ws = [&](Slot &o) -> int32_t {
@@ -339,7 +332,7 @@ int32_t pok_verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *
     CtxScope on_owner(hb.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    const RowMsm<G1> bp = param_rows(sl, params, hb.h, nn, bbspk::POK_EACH_CHUNK, n);
+    const RowMsm<G1> bp = param_rows<G1>(sl, params, hb.h, nn, bbspk::POK_EACH_CHUNK, n);
     const size_t chunk = bp.chunk;
     int32_t rc;
     SegLayout lay, lay_tail;
@@ -503,7 +496,7 @@ int32_t pok23_verify_each(int kind, uint64_t params, const uint64_t *pk_pc, cons
     HIPCHK(hipSetDevice(cur().device));
     const bbs23k::KindShape ks = bbs23k::kind_shape(kind);
     const size_t own = ks.own, segs = ks.segs;
-    const RowMsm<G1> bp = param_rows(sl, params, hb.h, nn, bbs23k::BBS23_EACH_CHUNK, n);
+    const RowMsm<G1> bp = param_rows<G1>(sl, params, hb.h, nn, bbs23k::BBS23_EACH_CHUNK, n);
     const size_t chunk = bp.chunk;
     int32_t rc;
     SegLayout lay, lay_tail;

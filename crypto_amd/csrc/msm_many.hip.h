@@ -1,6 +1,7 @@
 // crypto_amd/csrc/msm_many.hip.h — many small MSMs in one call (templated on the curve): rows of scalars over one plain handle, segments over their own bases.
 #pragma once
 #include <thread>
+#include <type_traits>
 #include "msm_driver.hip.h"
 
 namespace dock {
@@ -83,25 +84,27 @@ int32_t msm_device_many(Slot &sl, const SmallSub &sub, const uint64_t *scalars, 
     }
     return DGPU_OK;
 }
-// Jacobian rows (X, Y, Z: 18 words) -> affine rows (x, y: 12 words) packed in place (12 i + 12 <= 18 i), an identity: zero words, and inf[i] its flag
-inline void jac_rows_to_affine(uint64_t *jac, size_t rows, uint8_t *inf) {
+// Jacobian rows (X, Y, Z: 3 F) -> affine rows (x, y: 2 F) packed in place (2 i + 2 <= 3 i), an identity: zero words, and inf[i] its flag.  F: hostf::Fq (G1:
+// 18 -> 12 words) or hostf::Fq2 (G2: 36 -> 24)
+template <class F> inline void jac_rows_to_affine(uint64_t *jac, size_t rows, uint8_t *inf) {
+    constexpr size_t FW = sizeof(F) / 8;
     for (size_t i = 0; i < rows; i++) {
-        const uint64_t *p = jac + 18 * i;
-        uint64_t *q = jac + 12 * i;
-        inf[i] = jac_is_identity(p, 18);
-        if (inf[i]) { memset(q, 0, 96); continue; }
-        hostf::Fq x, y, z; memcpy(&x, p, 48); memcpy(&y, p + 6, 48); memcpy(&z, p + 12, 48);
-        const hostf::Fq zi = z.inv(), zi2 = zi * zi;
+        const uint64_t *p = jac + 3 * FW * i;
+        uint64_t *q = jac + 2 * FW * i;
+        inf[i] = jac_is_identity(p, 3 * FW);
+        if (inf[i]) { memset(q, 0, 2 * sizeof(F)); continue; }
+        F x, y, z; memcpy(&x, p, sizeof(F)); memcpy(&y, p + FW, sizeof(F)); memcpy(&z, p + 2 * FW, sizeof(F));
+        const F zi = z.inv(), zi2 = zi * zi;
         x = x * zi2; y = y * zi2 * zi;
-        memcpy(q, &x, 48); memcpy(q + 6, &y, 48);
+        memcpy(q, &x, sizeof(F)); memcpy(q + FW, &y, sizeof(F));
     }
 }
-// Rows of n scalars made on the device, over one small set of G1 bases -> affine points and identity flags on the device (dock_bbs.hip: the b_i and P_i over the
-// parameters; dock_accumulator.hip: the T_i over omega).  The many-row kernels over the bases' small-path table `sub` where they reach; beyond (rows longer than
+// Rows of n scalars made on the device, over one small set of G1 or G2 bases -> affine points and identity flags on the device (dock_bbs.hip: the b_i and P_i over
+// the parameters; dock_accumulator.hip: the T_i over omega; dock_ps.hip: the Q_i, S_i, R_i over the public key in G2).  The many-row kernels over the bases' small-path table `sub` where they reach; beyond (rows longer than
 // dgpu_set_small_msm_max allows, no memory for the table) the single-row driver over the prepared records `rec`, row by row, normalised on the host.  The caller
 // says which, and fills in `sub` or `rec` before points(): a handle's table comes from small_sub_for, a call's own table is built in its workspace.
 template <class C> struct RowMsm {
-    static_assert(C::NFP == 1, "G1: the slow path normalises over Fq");
+    typedef typename std::conditional<C::NFP == 1, hostf::Fq, hostf::Fq2>::type HF;      // the slow path normalises over the curve's base field
     static constexpr size_t PT = 2 * C::ABI_W * 4;        // bytes of an affine point of the ABI
     bool many; ManyGeom geom; size_t n, chunk;            // terms per row, rows per chunk
     SmallSub sub{nullptr, nullptr}; const uint32_t *rec = nullptr;
@@ -128,10 +131,11 @@ template <class C> struct RowMsm {
             return DGPU_OK;
         }
         HIPCHK(hipGetLastError());
-        std::vector<uint64_t> jac(rows * 18); std::vector<uint8_t> inf(rows);
+        constexpr size_t JW = 3 * sizeof(HF) / 8;
+        std::vector<uint64_t> jac(rows * JW); std::vector<uint8_t> inf(rows);
         for (size_t i = 0; i < rows; i++)
-            if ((rc = msm_device<C, hostf::Fq>(sl, rec, d_rows + i * n * 8, n, jac.data() + 18 * i))) return rc;
-        jac_rows_to_affine(jac.data(), rows, inf.data());
+            if ((rc = msm_device<C, HF>(sl, rec, d_rows + i * n * 8, n, jac.data() + JW * i))) return rc;
+        jac_rows_to_affine<HF>(jac.data(), rows, inf.data());
         hipError_t up = hipMemcpyAsync(dOut, jac.data(), rows * PT, hipMemcpyHostToDevice, s);
         if (up == hipSuccess) up = hipMemcpyAsync(dInf, inf.data(), rows, hipMemcpyHostToDevice, s);
         const hipError_t waited = hipStreamSynchronize(s);      // (the host vectors end here, whatever the copies answered)
@@ -139,6 +143,17 @@ template <class C> struct RowMsm {
         return DGPU_OK;
     }
 };
+// How the rows over a plain bases handle `h` (pinned by the caller) are made: RowMsm over its first nn points, whose small-path table serves the many-row kernels
+// where they reach (dock_bbs.hip: the signature parameters in G1; dock_ps.hip: the public key in G2).  group: MSM rows that belong together (dock_ps.hip: the
+// two rows of a proof) — the chunk is a whole number of groups and at least one, so a forced chunk that is no multiple of it is rounded down, and up to one group
+template <class C> RowMsm<C> param_rows(Slot &sl, uint64_t params, const Handle &h, size_t nn, size_t cap, size_t n, size_t group = 1) {
+    SmallSub sub{nullptr, nullptr};
+    const bool many = h.n <= SMALL_MSM_MAX_N && nn <= gs.small_max.load() && small_sub_for<C>(sl, params, h, 0, nn, sub, true);
+    RowMsm<C> rm(many, nn, n, cap);
+    rm.sub = sub; rm.rec = (const uint32_t *)h.p;
+    rm.chunk = std::max(group, rm.chunk - rm.chunk % group);
+    return rm;
+}
 template <class C, class HF>
 int32_t msm_handle_many(uint64_t bases, size_t offset, const uint64_t *scalars, size_t row_stride, size_t n, size_t m, int mont, uint64_t *out, uint8_t *out_inf, int kind) {
     if (m == 0) return DGPU_OK;

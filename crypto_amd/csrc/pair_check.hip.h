@@ -12,7 +12,7 @@ namespace {
 
 bool zero_words(const uint64_t *w, int k) { uint64_t o = 0; for (int i = 0; i < k; i++) o |= w[i]; return o == 0; }
 
-// ---- the pairing check of m = `cols` rows on the device: e(P1_i, w) e(P2_i, g2) == 1 ----------------------------------------------------------------------------
+// ---- the pairing check of m <= `cols` rows on the device: e(P1_i, w) e(P2_i, g2) == 1 ---------------------------------------------------------------------------
 // dP: [P1 | P2], cols affine points each; dsk: their skip flags in the same order (an identity contributes one, as everywhere in the library).  The coefficients
 // of w and g2 are in sl.ml_coeffs, the wanted value (one) behind the Miller outputs in sl.ml_out.  Verdicts: sl.flags.
 int32_t ws_check(Slot &o, size_t cols) {
@@ -21,27 +21,50 @@ int32_t ws_check(Slot &o, size_t cols) {
     if ((e = o.ml_lines.ensure((size_t)N_LINES * LW * 2 * cols * 4))) return e;
     if ((e = o.ml_partial.ensure((size_t)N_LINES * cols * F12W * 4))) return e;
     if ((e = o.ml_out.ensure(cols * 576 + 576))) return e;
+    if ((e = o.ml_state.ensure((size_t)PXY_W * 2 * cols * 4))) return e;      // px, py of every pair: the affine-first-side form leaves its lines unevaluated
     return o.flags.ensure(std::max<size_t>(cols, 64));
 }
+// pk_pc == nullptr: the second set alone (the affine-first-side form has no fixed first point)
 int32_t coeffs_up(Slot &sl, const uint64_t *pk_pc, const uint64_t *g2_pc, size_t cols) {
     const size_t cw = (size_t)DGPU_G2_PREPARED_WORDS;
     static const hostf::Fq12 one = hostf::Fq12::one();
-    HIPCHK(hipMemcpyAsync(sl.ml_coeffs.p, pk_pc, cw * 8, hipMemcpyHostToDevice, sl.stream));
+    if (pk_pc) HIPCHK(hipMemcpyAsync(sl.ml_coeffs.p, pk_pc, cw * 8, hipMemcpyHostToDevice, sl.stream));
     HIPCHK(hipMemcpyAsync(sl.ml_coeffs.as<uint64_t>() + cw, g2_pc, cw * 8, hipMemcpyHostToDevice, sl.stream));
     HIPCHK(hipMemcpyAsync(sl.ml_out.as<uint8_t>() + cols * 576, &one, 576, hipMemcpyHostToDevice, sl.stream));
     return DGPU_OK;
 }
+// what follows the 2 m pairs' lines in sl.ml_lines, whoever wrote them: one "segment" of 2 m pairs with slices of 2 — slice i is the pairs i and i + m, i.e. the
+// two lines of row i — the loop's tail, the final exponentiation compared with one.  pxy: the pairs' px, py where the lines came unevaluated, else nullptr
+void check_tail(Slot &sl, size_t m, size_t cols, const uint32_t *pxy) {
+    hipStream_t s = sl.stream;
+    uint32_t *fout = sl.ml_out.as<uint32_t>();
+    { StageTimer st(sl, "bbs.products");
+      launch_line_products(s, gs.ml_mode.load(), sl.ml_lines.as<uint32_t>(), 2 * m, 2, (int)m, sl.ml_partial.as<uint32_t>(), nullptr, 1, 0, N_LINES, pxy, false); }
+    { StageTimer st(sl, "bbs.tail"); gtk::launch_miller_tail(s, sl.ml_partial.as<uint32_t>(), m, fout); }
+    { StageTimer st(sl, "bbs.final_exp"); gtk::launch_final_exp(s, fout, m, (uint32_t *)nullptr, (uint8_t *)nullptr, fout + cols * 144, sl.flags.as<uint8_t>()); }
+}
 void launch_check(Slot &sl, const uint32_t *dP1, const uint32_t *dP2, const uint8_t *dsk, size_t m, size_t cols) {
     hipStream_t s = sl.stream;
     const size_t cw = (size_t)DGPU_G2_PREPARED_WORDS, np = 2 * m;
-    uint32_t *lines = sl.ml_lines.as<uint32_t>(), *fout = sl.ml_out.as<uint32_t>();
+    uint32_t *lines = sl.ml_lines.as<uint32_t>();
     { StageTimer st(sl, "bbs.lines");
       launch_lines_from_prepared(s, dP1, sl.ml_coeffs.as<uint32_t>(), dsk, m, lines, np, nullptr, true);
       launch_lines_from_prepared(s, dP2, sl.ml_coeffs.as<uint32_t>() + cw * 2, dsk + m, m, lines + m, np, nullptr, true); }
-    // one "segment" of 2 m pairs with slices of 2: slice i is the pairs i and i + m, i.e. the two lines of row i
-    { StageTimer st(sl, "bbs.products"); launch_line_products(s, gs.ml_mode.load(), lines, np, 2, (int)m, sl.ml_partial.as<uint32_t>(), nullptr, 1, 0, N_LINES, nullptr, false); }
-    { StageTimer st(sl, "bbs.tail"); gtk::launch_miller_tail(s, sl.ml_partial.as<uint32_t>(), m, fout); }
-    { StageTimer st(sl, "bbs.final_exp"); gtk::launch_final_exp(s, fout, m, (uint32_t *)nullptr, (uint8_t *)nullptr, fout + cols * 144, sl.flags.as<uint8_t>()); }
+    check_tail(sl, m, cols, nullptr);
+}
+// The second form: e(P1_i, Q_i) e(P2_i, g2) == 1 with a G2 point of its own per row (dock_ps.hip: PS signatures, whose verification lives in G2).  dQ: m affine
+// G2 points on the device (48 words each) with their identity flags dQ_inf: such a pair is skipped, and so is one whose P is zero words (both line kernels
+// see that themselves).  The first side runs the fused prepare + line kernel the mixed Miller loop runs for its affine pairs (one launch: no state between
+// pieces), its lines unevaluated; the second side's prepared lines join them with neutral px, py; the product kernel evaluates.  m <= 8192 (the callers'
+// chunks are at most 4096 rows).
+void launch_check(Slot &sl, const uint32_t *dP1, const uint32_t *dQ, const uint8_t *dQ_inf, const uint32_t *dP2, size_t m, size_t cols) {
+    hipStream_t s = sl.stream;
+    const size_t cw = (size_t)DGPU_G2_PREPARED_WORDS, np = 2 * m;
+    uint32_t *lines = sl.ml_lines.as<uint32_t>(), *pxy = sl.ml_state.as<uint32_t>();
+    { StageTimer st(sl, "ps.lines");
+      launch_lines_uneval(s, gs.ml_mode.load(), dP1, dQ, dQ_inf, m, lines, np, 62, 0, 0, nullptr, pxy);
+      launch_lines_from_prepared(s, dP2, sl.ml_coeffs.as<uint32_t>() + cw * 2, nullptr, m, lines + m, np, pxy + m, true); }
+    check_tail(sl, m, cols, pxy);
 }
 
 // ---- one verdict for n rows: the random linear combination RandomizedPairingChecker forms (utils/src/randomized_pairing_check.rs), merged before the pairing ----------

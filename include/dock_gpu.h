@@ -855,6 +855,61 @@ int32_t dgpu_bbs23_pok_ietf_verify_batch_g1(uint64_t params, size_t L, const uin
                                             const uint8_t *revealed /* n*L */, const uint64_t *challenge /* n*4 */, size_t n, int32_t montgomery,
                                             const uint64_t random[4], int32_t *ok);
 
+/* ---- PS (Coconut) signatures in bulk: sign, verify, proofs of knowledge (crypto_amd/csrc/dock_ps.hip, ps_kernels.hip.h) ----
+ * The Pointcheval-Sanders signature of the reference's coconut crate (coconut/src/signature/ps_signature.rs, proof_system's PoKPSSignature) and the proof of
+ * knowledge of one (coconut/src/proof/signature_pok/).  A signature is TWO G1 points (sigma_1, sigma_2), 2 x 12 words; its verification lives in G2:
+ *   pk_g2   ONE plain G2 bases handle [alpha_tilde, beta_tilde_1 .. beta_tilde_L, g_tilde] of exactly L + 2 points (another length, a precomputed handle, a G1
+ *           handle or no handle: DGPU_E_BADARG).  PublicKey::beta, the G1 copies, is needed by none of the four calls.
+ *   g_table a dgpu_window_table_g1 handle of SignatureParams::g.
+ *   g_tilde_pc / all_pc   the prepared coefficients (dgpu_g2_prepare) of g_tilde, respectively of all L + 2 points in the handle's order.
+ * messages, row_stride, montgomery, random and the identity as all-zero words are as in the BBS+ calls above.
+ *
+ * dgpu_ps_sign_many_g1 is Signature::new (ps_signature.rs:46-64) for n rows with r_i standing in for its `rand` draw: sigma_1_i = r_i g and
+ * sigma_2_i = (r_i (x + sum_j y_j m_ij)) g — the reference's h = g r; sigma_2 = h (..) as the same group elements, hence the same bytes.  sk = (x, y_1 .. y_L).
+ * The 2n scalars are made on the device (k_ps_sign_rows), the points are fixed-base products over g's window table.  bad[i] = 1 where either element is the
+ * identity (r_i = 0, or x + sum y_j m_ij = 0): the reference returns such a signature and every verifier refuses it.  The device copies of sk, r and the u_i
+ * are zeroed on every return path; the host makes no copy of them.
+ * dgpu_ps_verify_each is Signature::verify (:95-142): ok[i] = 1 iff neither element is the identity (ZeroSignature) and
+ *   e(sigma_1_i, alpha_tilde + sum_j m_ij beta_tilde_j) e(-sigma_2_i, g_tilde) = 1.
+ * Per chunk one device pipeline: the rows (1, m_i ..), Q_i by the many-row G2 MSM over pk_g2[0 .. L], the first pair through the fused prepare + line kernel,
+ * the second through the lines of the prepared g_tilde, the products of every slice, the loop's tail, the final exponentiation.  An identity Q_i is skipped
+ * like every identity in the library: the row then fails on its second pair, as in the reference.
+ * dgpu_ps_verify_batch: ONE verdict, rho = random (rho = 0 mod r: DGPU_E_BADARG), w_i = rho^i.  *ok = 1 iff no signature element is the identity and
+ *   e(sum_i w_i sigma_1_i, alpha_tilde) prod_j e(sum_i w_i m_ij sigma_1_i, beta_tilde_j) e(-sum_i w_i sigma_2_i, g_tilde) = 1
+ * — L + 2 pairs whose G2 sides are fixed: L + 2 MSMs of n terms per chunk (k_ps_col_scalars writes their scalars), the host adds the chunks' points, one
+ * multi-pairing, one final exponentiation.  The exponent is a polynomial of degree < n in rho: a batch with a failing row passes with probability at most n / r;
+ * rho = 1 lets errors that cancel unweighted pass.
+ * dgpu_ps_pok_verify_each is SignaturePoK::verify (proof_system's PoKPSSignature; proof.rs:32-56) for n proofs:
+ *   sigs       n x 2 x 12 words: the randomized signature sigma_1', sigma_2'
+ *   g2_points  n x 2 x 24 words: k_i (the proof's K) and t_i (the Schnorr commitment)
+ *   resp_r     n scalars: the last response, over g_tilde
+ *   values, revealed, challenge   as in dgpu_bbs_plus_pok_verify_each_g1: entry j is the revealed message where revealed[i][j] != 0, else the response of the
+ *              hidden message j (a dense mask: the reference's index-order and length errors cannot occur)
+ *   3  sum_hidden z_ij beta_tilde_j + z_r,i g_tilde - c_i k_i = t_i                                  else the Schnorr error (this protocol's only one)
+ *   1  sigma_1' != O and sigma_2' != O                                                               else ZeroSignature
+ *   4  e(sigma_1', alpha_tilde + sum_revealed m_ij beta_tilde_j + k_i) e(-sigma_2', g_tilde) = 1     else PairingCheckFailed
+ * status[i] = 0 or the number of the first failing check IN THIS ORDER, 3 before 1 before 4: the reference returns proof_res.and(sig_res) (proof.rs:46-55).
+ * This is not the order of the BBS calls; 2 is never written.  Per chunk: two rows of L + 2 entries per proof (k_ps_pok_rows), ONE many-row G2 MSM of both,
+ * two launches of the GLS mul-add kernel (S_i + (-c_i) k_i; R_i + k_i), the pairing check above, k_ps_verdict.
+ *
+ * All four: n = 0 is DGPU_OK without touching a device or any pointer (an empty batch verifies); with n > 0 a NULL pointer, row_stride < L, L = 0 (the
+ * reference's NoMessages), n or row_stride >= 2^31 is DGPU_E_BADARG before the device is looked at; then DGPU_E_NODEVICE, then the handle.  Points are taken
+ * as validated members of the subgroups.  A row count or L + 2 beyond the many-row kernels' reach runs the single-row driver inside the call.  Chunks
+ * (UNMEASURED): sign and verify_each min(4096, 2^17 / (L + 1)) rows, the proof call half the rows of min(4096, 2^17 / (L + 2)), the batch
+ * min(65536, 2^20 / L); dgpu_set_many_chunk_rows of the development surface cuts all four (the proof call keeps whole pairs of MSM rows: an odd forced count is
+ * rounded down, one row up to two).  Stage timers ps.sign_rows, ps.rows, ps.lines, ps.columns,
+ * ps.pok_rows, ps.mul_add, ps.pok_verdict beside the BBS+ block's. */
+int32_t dgpu_ps_sign_many_g1(uint64_t g_table, size_t L, const uint64_t *sk /* (1+L)*4: x, y_1..y_L */, const uint64_t *messages /* n rows */, size_t row_stride,
+                             const uint64_t *r /* n*4 */, size_t n, int32_t montgomery, uint64_t *out_sig /* n*2*12 */, uint8_t *bad /* n */);
+int32_t dgpu_ps_verify_each(uint64_t pk_g2, size_t L, const uint64_t *g_tilde_pc, const uint64_t *sigs /* n*2*12 */, const uint64_t *messages /* n rows */,
+                            size_t row_stride, size_t n, int32_t montgomery, uint8_t *ok /* n */);
+int32_t dgpu_ps_verify_batch(uint64_t pk_g2, size_t L, const uint64_t *all_pc /* (L+2) * DGPU_G2_PREPARED_WORDS */, const uint64_t *sigs /* n*2*12 */,
+                             const uint64_t *messages /* n rows */, size_t row_stride, size_t n, int32_t montgomery, const uint64_t random[4], int32_t *ok);
+int32_t dgpu_ps_pok_verify_each(uint64_t pk_g2, size_t L, const uint64_t *g_tilde_pc, const uint64_t *sigs /* n*2*12: sigma_1', sigma_2' */,
+                                const uint64_t *g2_points /* n*2*24: k_i, t_i */, const uint64_t *resp_r /* n*4 */, const uint64_t *values /* n rows */,
+                                size_t row_stride, const uint8_t *revealed /* n*L */, const uint64_t *challenge /* n*4 */, size_t n, int32_t montgomery,
+                                uint8_t *status /* n */);
+
 /* ---- the LegoGroth16 prover as one call ----
  * replaces create_proof_and_committed_witnesses_with_assignment (legogroth16/src/prover.rs:267-383, with calculate_coeff :585-594) and — when
  * the circuit is resident (r1cs != 0) — the QAP::witness_map call in front of it (create_proof_with_reduction, :153-180): the whole schedule

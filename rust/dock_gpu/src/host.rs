@@ -160,6 +160,9 @@ impl WindowTableG1 {
         if unsafe { dgpu_window_table_g1(xy.as_ptr(), &mut h) } != DGPU_OK { return None; }
         Some(WindowTableG1 { handle: h })
     }
+    pub(crate) fn raw_handle(&self) -> u64 {      // (src/coconut.rs: dgpu_ps_sign_many_g1 takes the table of g)
+        self.handle
+    }
     /// `multiply_many(&[Fr])` (utils/src/msm.rs:40-42) — the products as affine points (the reference normalises them next: generator.rs:424-431)
     pub fn multiply_many(&self, elements: &[Fr]) -> Option<Vec<G1Affine>> {
         let n = elements.len();
@@ -394,6 +397,31 @@ pub(crate) fn raw_bbs23_pok_ietf_verify_batch(params: u64, l: usize, pk_pc: &[u6
                                               challenge: &[Fr], random: &Fr, ok: &mut i32) -> i32 {
     unsafe { dgpu_bbs23_pok_ietf_verify_batch_g1(params, l, pk_pc.as_ptr(), g2_pc.as_ptr(), points.as_ptr(), resp_fixed.as_ptr() as *const u64, values.as_ptr() as *const u64, l,
                                                  revealed.as_ptr(), challenge.as_ptr() as *const u64, challenge.len(), 1, random as *const Fr as *const u64, ok) }
+}
+
+// ---- PS (Coconut) signatures in bulk: the raw callers behind src/coconut.rs (the typed API and its documentation live there).  `pk`: a plain G2 bases handle
+// holding `[alpha_tilde, beta_tilde .., g_tilde]`, l + 2 points; a signature is 2 x 12 words (sigma_1, sigma_2)
+/// `(sigma_1, sigma_2)_i = (r_i g, (r_i (x + sum_j y_j m_ij)) g)`; `g_table`: a `WindowTableG1` of `g`; `sk`: (x, y_1 .. y_l); `messages`: n rows of `l`, packed;
+/// `out_sig`: n x 24 words, `bad`: n bytes
+pub(crate) fn raw_ps_sign_many(g_table: u64, l: usize, sk: &[Fr], messages: &[Fr], r: &[Fr], out_sig: &mut [u64], bad: &mut [u8]) -> i32 {
+    unsafe { dgpu_ps_sign_many_g1(g_table, l, sk.as_ptr() as *const u64, messages.as_ptr() as *const u64, l, r.as_ptr() as *const u64, r.len(), 1, out_sig.as_mut_ptr(),
+                                  bad.as_mut_ptr()) }
+}
+/// `ok[i] = (no element of signature i is the identity and e(sigma_1, alpha_tilde + sum_j m_ij beta_tilde_j) e(-sigma_2, g_tilde) == 1)`; `g_tilde_pc`: the
+/// prepared coefficients of `g_tilde`
+pub(crate) fn raw_ps_verify_each(pk: u64, l: usize, g_tilde_pc: &[u64], sigs: &[u64], messages: &[Fr], ok: &mut [u8]) -> i32 {
+    unsafe { dgpu_ps_verify_each(pk, l, g_tilde_pc.as_ptr(), sigs.as_ptr(), messages.as_ptr() as *const u64, l, ok.len(), 1, ok.as_mut_ptr()) }
+}
+/// one verdict for all rows under the weights `random^i`; `all_pc`: the prepared coefficients of the handle's l + 2 points, in its order
+pub(crate) fn raw_ps_verify_batch(pk: u64, l: usize, all_pc: &[u64], sigs: &[u64], n: usize, messages: &[Fr], random: &Fr, ok: &mut i32) -> i32 {
+    unsafe { dgpu_ps_verify_batch(pk, l, all_pc.as_ptr(), sigs.as_ptr(), messages.as_ptr() as *const u64, l, n, 1, random as *const Fr as *const u64, ok) }
+}
+/// `SignaturePoK::verify` per proof: `status[i]` = 0, or the first failing check in the reference's order: 3 the Schnorr check, 1 ZeroSignature, 4 the pairing.
+/// `sigs`: n x 24 words (sigma_1', sigma_2'); `g2_points`: n x 48 words (k, t); `resp_r`: n; `values`: n rows of `l`, packed; `revealed`: n x l bytes
+pub(crate) fn raw_ps_pok_verify_each(pk: u64, l: usize, g_tilde_pc: &[u64], sigs: &[u64], g2_points: &[u64], resp_r: &[Fr], values: &[Fr], revealed: &[u8], challenge: &[Fr],
+                                     status: &mut [u8]) -> i32 {
+    unsafe { dgpu_ps_pok_verify_each(pk, l, g_tilde_pc.as_ptr(), sigs.as_ptr(), g2_points.as_ptr(), resp_r.as_ptr() as *const u64, values.as_ptr() as *const u64, l,
+                                     revealed.as_ptr(), challenge.as_ptr() as *const u64, challenge.len(), 1, status.as_mut_ptr()) }
 }
 
 // ---- R1CS -> QAP witness map (legogroth16/src/r1cs_to_qap.rs:150-210) ---------------------------------------------------------------------------------

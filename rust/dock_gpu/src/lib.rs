@@ -34,6 +34,8 @@ pub mod accumulator_issue;      // (issuing membership / non-membership witnesse
 pub mod accumulator_proofs;     // (verifying membership / non-membership proofs in bulk behind the reference's own types: src/accumulator_proofs.rs; the case in tests/parity.rs runs under the same feature)
 #[cfg(feature = "bbs-plus")]
 pub mod bbs_plus;               // (BBS+ signatures in bulk behind the reference's own types: src/bbs_plus.rs; the case in tests/parity.rs runs under the same feature)
+#[cfg(feature = "coconut")]
+pub mod coconut;                // (PS / Coconut signatures in bulk behind the reference's own types: src/coconut.rs; the case in tests/parity.rs runs under the same feature)
 
 pub type G2Prepared = ArkG2Prepared<ark_bls12_381::Config>;
 

@@ -970,3 +970,72 @@ fn accumulator_proofs_bulk_equal_the_reference() {
         assert_eq!(non_membership_verify_batch(&key, &v, &q, &bad, &bad_c, None, &rho), Some(false));
     }
 }
+
+// PS (Coconut) signatures in bulk behind the reference's own types (src/coconut.rs) against the reference's `Signature::new` / `verify` and `SignaturePoK::verify`
+#[cfg(feature = "coconut")]
+#[test]
+fn ps_bulk_equals_the_reference() {
+    use ark_serialize::CanonicalSerialize;
+    use coconut_crypto::setup::{PublicKey, SecretKey, SignatureParams};
+    use coconut_crypto::{CommitMessage, Signature, SignaturePoK, SignaturePoKGenerator};
+    use dock_gpu::coconut::{pok_verify_each, sign_many, verify_batch, verify_each, GpuPsParams};
+    use std::collections::BTreeMap;
+    setup();
+    let mut rng = StdRng::seed_from_u64(0xC0C0);
+    let bytes_of = |s: &Signature<Bls12_381>| { let mut b = vec![]; s.serialize_compressed(&mut b).unwrap(); b };
+    for &(l, n) in &[(1usize, 3usize), (5, 65), (30, 257)] {
+        let sk = SecretKey::<Fr>::rand(&mut rng, l as u32);
+        let params = SignatureParams::<Bls12_381>::new::<blake2::Blake2b512>(b"dock_gpu parity", l as u32);
+        let pk = PublicKey::new(&sk, &params);
+        let msgs: Vec<Vec<Fr>> = (0..n).map(|_| frs(&mut rng, l)).collect();
+        let rows: Vec<&[Fr]> = msgs.iter().map(|m| m.as_slice()).collect();
+        let gp = GpuPsParams::new(&params, &pk).expect("parameters");
+        assert_eq!(gp.supported_message_count(), l);
+        // Signature::new draws r with Fr::rand as its only use of the generator: the same seed gives the reference the r handed to sign_many
+        let r: Vec<Fr> = (0..n).map(|i| Fr::rand(&mut StdRng::seed_from_u64(1000 + i as u64))).collect();
+        let sigs: Vec<Signature<Bls12_381>> = (0..n).map(|i| Signature::new(&mut StdRng::seed_from_u64(1000 + i as u64), &msgs[i], &sk, &params).unwrap()).collect();
+        let mine = sign_many(&gp, &sk, &rows, &r).expect("sign_many");
+        for i in 0..n { assert_eq!(bytes_of(&mine[i]), bytes_of(&sigs[i]), "l = {l}, row {i}"); }
+        let mut r0 = r.clone(); r0[n - 1] = Fr::from(0u64);
+        assert!(sign_many(&gp, &sk, &rows, &r0).expect("sign_many")[n - 1].is_zero());
+        let mut bad = sigs.clone();
+        let mut bad_msgs = msgs.clone();
+        bad_msgs[0][0] += Fr::from(1u64);
+        if n > 2 { bad.swap(n - 1, n - 2); }
+        let bad_rows: Vec<&[Fr]> = bad_msgs.iter().map(|m| m.as_slice()).collect();
+        let want: Vec<bool> = bad.iter().zip(bad_msgs.iter()).map(|(x, m)| x.verify(m, &pk, &params).is_ok()).collect();
+        assert_eq!(verify_each(&gp, &bad, &bad_rows).expect("verify_each"), want);
+        assert!(verify_each(&gp, &sigs, &rows).expect("verify_each").iter().all(|&k| k));
+        let rho = Fr::rand(&mut rng);
+        assert_eq!(verify_batch(&gp, &sigs, &rows, &rho), Some(true));
+        assert_eq!(verify_batch(&gp, &bad, &bad_rows, &rho), Some(false));
+
+        // proofs over the same signatures, every proof its own pattern: nothing revealed, everything, every (i % 5 + 2)-th message
+        let (mut proofs, mut revealed, mut challenges): (Vec<SignaturePoK<Bls12_381>>, Vec<BTreeMap<usize, Fr>>, Vec<Fr>) = (vec![], vec![], vec![]);
+        for i in 0..n {
+            let shown = |j: usize| match i % 3 { 0 => false, 1 => true, _ => j % (i % 5 + 2) == 0 };
+            let c = Fr::rand(&mut rng);
+            let commit = msgs[i].iter().enumerate().map(|(j, m)| if shown(j) { CommitMessage::RevealMessage } else { CommitMessage::BlindMessageRandomly(*m) });
+            proofs.push(SignaturePoKGenerator::init(&mut rng, commit, &sigs[i], &pk, &params).unwrap().gen_proof(&c).unwrap());
+            revealed.push((0..l).filter(|&j| shown(j)).map(|j| (j, msgs[i][j])).collect());
+            challenges.push(c);
+        }
+        let maps: Vec<&BTreeMap<usize, Fr>> = revealed.iter().collect();
+        assert!(pok_verify_each(&gp, &proofs, &maps, &challenges).expect("pok_verify_each").iter().all(|r| r.is_ok()), "l = {l}");
+        // a wrong challenge, a wrong revealed message, a proof checked against another row's messages: the reference's verdict beside ours
+        let (mut bad_c, mut bad_rev) = (challenges.clone(), revealed.clone());
+        bad_c[0] += Fr::from(1u64);
+        if let Some(v) = bad_rev[1].values_mut().next() { *v += Fr::from(1u64); }
+        let mut bad_proofs = proofs.clone();
+        if n > 4 { bad_proofs.swap(3, 4); }
+        let bad_maps: Vec<&BTreeMap<usize, Fr>> = bad_rev.iter().collect();
+        let mine = pok_verify_each(&gp, &bad_proofs, &bad_maps, &bad_c);
+        if let Some(mine) = mine {                                   // (None: a swapped proof's response count does not fit its row's mask — the reference errs there too)
+            for i in 0..n {
+                let theirs = bad_proofs[i].verify(&bad_c[i], bad_rev[i].iter().map(|(j, m)| (*j, m)), &pk, &params);
+                assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "l = {l}, proof {i}");
+            }
+            assert!(mine[0].is_err());
+        }
+    }
+}
