@@ -12,6 +12,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("DGPU_LIB") or os.path.join(_HERE, "libdock_gpu.so")   # DGPU_LIB: development override (make g1only)
 _DEV_SO = os.environ.get("DGPU_DEV_LIB") or os.path.join(_HERE, "libdock_gpu_dev.so")   # DGPU_DEV_LIB: development override (A/B builds)
+# include/dock_gpu_saver.h: the product's objects plus the SAVER calls, and the same over the twin's objects (a third and fourth image, each with its own contexts)
+_SAVER_SO = os.path.join(_HERE, "libdock_gpu_saver.so")
+_SAVER_DEV_SO = os.path.join(_HERE, "libdock_gpu_saver_dev.so")
 
 ERR = {0: "DGPU_OK", -1: "DGPU_E_NODEVICE", -2: "DGPU_E_OOM", -3: "DGPU_E_BADARG", -4: "DGPU_E_HIP",
        -5: "DGPU_E_ZERO", -6: "DGPU_E_TOO_SMALL", -7: "DGPU_E_LENGTH"}
@@ -86,7 +89,7 @@ _init_args = None    # ("init", device, min_gpu_n) / ("list", [devices], min_gpu
 # every symbol include/dock_gpu_dev.h adds (the twin only)
 DEV_SYMBOLS = ["dgpu_set_window_bits", "dgpu_set_chunk", "dgpu_set_many_chunk_rows", "dgpu_set_msm_segments", "dgpu_set_reduce_shift", "dgpu_set_reduce_lanes", "dgpu_set_miller_pipeline", "dgpu_set_gt_pow", "dgpu_set_wm_many",
                "dgpu_prof_enable", "dgpu_prof_reset", "dgpu_prof_read", "dgpu_selftest_fp_mul", "dgpu_selftest_g1_sum", "dgpu_selftest_arith", "dgpu_selftest_glv_decompose", "dgpu_selftest_gls4_decompose",
-               "dgpu_dev_fail_alloc_after", "dgpu_dev_set_acc_split", "dgpu_dev_get_acc_split", "dgpu_dev_set_acc_d_pass", "dgpu_dev_set_acc_d_unroll", "dgpu_dev_get_acc_d_unroll", "dgpu_dev_set_ntt", "dgpu_dev_get_ntt_last"]
+               "dgpu_dev_fail_alloc_after", "dgpu_dev_set_acc_split", "dgpu_dev_get_acc_split", "dgpu_dev_set_acc_d_pass", "dgpu_dev_set_acc_d_unroll", "dgpu_dev_get_acc_d_unroll", "dgpu_dev_set_ntt", "dgpu_dev_get_ntt_last", "dgpu_dev_set_saver_fp_bits"]
 
 # every symbol include/dock_gpu.h declares
 SYMBOLS = [
@@ -113,6 +116,11 @@ SYMBOLS = [
 ]
 
 
+# every symbol include/dock_gpu_saver.h declares (libdock_gpu_saver.so and its development build only)
+SAVER_SYMBOLS = ["dgpu_saver_dk_create", "dgpu_saver_dk_free", "dgpu_saver_dk_powers", "dgpu_saver_decrypt_many", "dgpu_saver_verify_decryption_each",
+                 "dgpu_saver_verify_commitment_each", "dgpu_saver_verify_commitments_batch"]
+
+
 def lib():
     """the library the wrappers call: the product, or the twin inside `with twin():`"""
     global _lib
@@ -127,7 +135,32 @@ def dev_lib():
 
 
 def is_twin():
-    return _lib is not None and _lib is _loaded.get(_DEV_SO)
+    return _lib is not None and (_lib is _loaded.get(_DEV_SO) or _lib is _loaded.get(_SAVER_DEV_SO))
+
+
+def _bring_up(T):
+    """T on the device(s) the product was initialised on"""
+    import numpy as np
+    kind, devs, min_n = _init_args or ("init", 0, 0)
+    if kind == "init":
+        rc = T.dgpu_init(devs)
+    else:
+        arr = np.ascontiguousarray(devs, dtype=np.int32)
+        rc = T.dgpu_init_device_list(arr.ctypes.data_as(C.c_void_p), len(arr)) if T.dgpu_context_count() != len(arr) else 0
+    if rc:
+        raise DockGpuError(rc, "twin: dgpu_init")
+    T.dgpu_set_min_gpu_n(min_n)
+
+
+def saver_lib(bring_up=True):
+    """the library that serves include/dock_gpu_saver.h: the current one if it does (inside `with twin(saver=True):`), else libdock_gpu_saver.so, brought up
+    on the product's device(s) the first time.  Its handles live in it: crypto_amd.saver makes and uses them there."""
+    if _lib is not None and hasattr(_lib, "dgpu_saver_dk_create"):
+        return _lib
+    S = _load(_SAVER_SO)
+    if bring_up and S.dgpu_context_count() == 0:
+        _bring_up(S)
+    return S
 
 
 def note_init(*args):
@@ -137,23 +170,15 @@ def note_init(*args):
 
 
 @contextlib.contextmanager
-def twin():
+def twin(saver=False):
     """Inside the block every wrapper of this package calls the development twin (include/dock_gpu_dev.h: knobs, stage timers, self-tests), brought up
-    on the same device(s) as the product.  Nests; handles do not cross the border."""
+    on the same device(s) as the product.  Nests; handles do not cross the border.  saver: the twin that serves include/dock_gpu_saver.h too
+    (libdock_gpu_saver_dev.so), for what cuts or times the SAVER calls."""
     global _lib
     prev = lib()
-    T = dev_lib()
+    T = _load(_SAVER_DEV_SO) if saver else dev_lib()
     if T is not prev:
-        import numpy as np
-        kind, devs, min_n = _init_args or ("init", 0, 0)
-        if kind == "init":
-            rc = T.dgpu_init(devs)
-        else:
-            arr = np.ascontiguousarray(devs, dtype=np.int32)
-            rc = T.dgpu_init_device_list(arr.ctypes.data_as(C.c_void_p), len(arr)) if T.dgpu_context_count() != len(arr) else 0
-        if rc:
-            raise DockGpuError(rc, "twin: dgpu_init")
-        T.dgpu_set_min_gpu_n(min_n)
+        _bring_up(T)
     _lib = T
     try:
         yield T
@@ -308,6 +333,16 @@ def _load(path):
         L.dgpu_ps_verify_each.argtypes = [u64, sz, vp, vp, vp, sz, sz, C.c_int32, vp]
         L.dgpu_ps_verify_batch.argtypes = [u64, sz, vp, vp, vp, sz, sz, C.c_int32, vp, C.POINTER(C.c_int32)]
         L.dgpu_ps_pok_verify_each.argtypes = [u64, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, C.c_int32, vp]
+        if hasattr(L, "dgpu_saver_dk_create"):                # libdock_gpu_saver.so and its development build (include/dock_gpu_saver.h)
+            for s in SAVER_SYMBOLS:
+                getattr(L, s).restype = C.c_int32
+            L.dgpu_saver_dk_create.argtypes = [vp, vp, vp, vp, vp, C.c_int32, sz, C.POINTER(u64)]
+            L.dgpu_saver_dk_free.argtypes = [u64]
+            L.dgpu_saver_dk_powers.argtypes = [u64, sz, sz, sz, vp]
+            L.dgpu_saver_decrypt_many.argtypes = [u64, vp, sz, vp, C.c_int32, vp, vp, vp]
+            L.dgpu_saver_verify_decryption_each.argtypes = [u64, vp, sz, vp, vp, vp]
+            L.dgpu_saver_verify_commitment_each.argtypes = [vp, sz, vp, sz, vp]
+            L.dgpu_saver_verify_commitments_batch.argtypes = [vp, sz, vp, sz, vp, C.c_int32, C.POINTER(C.c_int32)]
         L.dgpu_witness_map.argtypes = [vp, vp, vp, sz] * 3 + [vp, sz, sz, sz, C.c_int32, vp, C.POINTER(u64), C.POINTER(sz)]
         for name in ("dgpu_window_table_g1", "dgpu_window_table_g2"):
             getattr(L, name).argtypes = [vp, C.POINTER(u64)]
@@ -353,6 +388,7 @@ def _load(path):
             L.dgpu_selftest_g1_sum.argtypes = [vp, vp, sz, vp]
             L.dgpu_selftest_arith.argtypes = [C.c_int32, C.c_int32, vp, sz, sz, vp, sz]
             L.dgpu_dev_fail_alloc_after.argtypes = [C.c_int64, C.c_int64]
+            L.dgpu_dev_set_saver_fp_bits.argtypes = [C.c_int32]
             L.dgpu_dev_set_acc_split.argtypes = [C.c_int32]
             L.dgpu_dev_get_acc_split.argtypes = []
             L.dgpu_dev_set_acc_d_pass.argtypes = [C.c_int32]

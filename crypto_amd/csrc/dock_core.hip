@@ -121,6 +121,7 @@ int choose_chunk(size_t E, int min_chunk, size_t max_chunks, int lanes_per_chunk
     return ch;
 }
 
+void (*g_free_saver_dk)(void *p) = nullptr;
 int32_t upload_scalars(Slot &sl, const uint64_t *h, size_t n, bool mont, uint32_t *d_out) {
     HIPCHK(hipMemcpyAsync(d_out, h, n * 32, hipMemcpyHostToDevice, sl.stream));
     if (mont) ntt::launch_fr_mont_to_canonical(sl.stream, d_out, n);     // Fr::into_bigint on the device (ark-ec msm_unchecked does it on rayon)
@@ -258,6 +259,7 @@ int32_t dgpu_shutdown(void) {
         else if (hd.kind == 10 || hd.kind == 11) { PreTable *pt = (PreTable *)hd.p; (void)hipFree(pt->tab); delete pt; }
         else if (hd.kind == 12) { SortedScalars *ss = (SortedScalars *)hd.p; (void)hipFree(ss->off); (void)hipFree(ss->entries); delete ss; }
         else if (hd.kind == 13 || hd.kind == 14) { FoldTab *ft = (FoldTab *)hd.p; (void)hipFree(ft->tab); delete ft; }
+        else if (hd.kind == 15) { if (g_free_saver_dk) g_free_saver_dk(hd.p); }
         else if (hd.kind >= 7) delete (ShardSet *)hd.p;                 // its per-device parts are table entries of their own
         else { if (hd.aux) (void)hipFree(hd.aux); (void)hipFree(hd.p); }
     }

@@ -37,7 +37,7 @@ struct Buf {
 
 // kind: 1 = G1 bases, 2 = G2 bases, 3 = scalars, 4 = R1CS (DevR1cs*), 5 / 6 = G1 / G2 window table, 7 / 8 = G1 / G2 bases sharded over
 // several devices (ShardSet*), 9 = scalars sharded like a bases set (ShardSet*), 10 / 11 = G1 / G2 precomputed-multiples table (PreTable*),
-// 12 = sorted scalars (SortedScalars*), 13 / 14 = G1 / G2 fold table (FoldTab*, dock_fixed.hip).  `ctx` = the device context that owns the allocation;
+// 12 = sorted scalars (SortedScalars*), 13 / 14 = G1 / G2 fold table (FoldTab*, dock_fixed.hip), 15 = SAVER decryption key (dock_saver.hip).  `ctx` = the device context that owns the allocation;
 // `inflight` = calls currently using it (a free waits for them: no use-after-free when dgpu_*_free races an MSM on the same handle).
 struct Handle { void *p; size_t n; int kind; int ctx; int inflight; void *aux = nullptr; int small_uses = 0; };   // aux: the small-MSM table of a plain bases handle (msm_driver.hip.h small_sub_for)
 struct PreTable { void *tab; size_t n; int c, W; };      // kind 10 / 11: tab[w * n + i] = prepared record of 2^(c w) P_i (pre_kernels.hip.h)
@@ -121,6 +121,7 @@ struct Shared {
     std::atomic<int> wm_many_chunk{0}, wm_many_rpb{0};   // dgpu_set_wm_many: rows per chunk and statements per block of dgpu_witness_map_r1cs_many (dock_qap.hip; 0 = automatic)
     std::atomic<int> acc_split{0}, acc_last_split{0};   // dgpu_dev_set_acc_split: chunks per element of the accumulator witness update (dock_accumulator.hip; 0 = automatic), and the count the last call ran with
     std::atomic<int> acc_d_pass{0}, acc_d_unroll{0}, acc_d_last_unroll{0};    // dgpu_dev_set_acc_d_pass / dgpu_dev_set_acc_d_unroll: members per pass and non-members per lane of dgpu_accumulator_d_for_batch (dock_accumulator.hip; 0 = automatic), and the non-members per lane the last call ran with
+    std::atomic<int> saver_fp_bits{0};       // dgpu_dev_set_saver_fp_bits: bits of the table fingerprints of the SAVER keys created from now on (dock_saver.hip; 0 = all 64, -1 = none)
     std::atomic<int> reduce_lanes{0};        // dgpu_set_reduce_lanes: 0 = the shared bucket set by bit marginals (reduce_kernels.hip.h; the plain pipeline then takes 4); 1 / 4: the scan form with k_reduce_top / k_reduce_top_quad (members per point in the last kernel)
     std::atomic<int> reduce_shift{-1};        // dgpu_set_reduce_shift: log2 buckets per lane of k_reduce_l0 on the table pipeline (-1 = automatic)
     std::atomic<int> ml_mode{31};             // dgpu_set_miller_pipeline: bit 0 the two-launch line kernel of small Miller loops, bit 1 the 18-role product tree, bit 2 sixteen lanes per pair in the line kernel, bit 3 (with bit 2) a wave per role, bit 4 three waves per sparse product while the chip is nearly empty (pairing_launch.hip.h: the launchers take this word)
@@ -305,6 +306,7 @@ template <class Pred> inline bool take_handle(uint64_t id, Pred kind_ok, Handle 
     }
 }
 void free_r1cs_object(void *p);      // dock_qap.hip
+extern void (*g_free_saver_dk)(void *p);   // set by dock_saver.hip where it is linked in (libdock_gpu_saver.so): frees a kind-15 handle's allocations and the object
 // the context's cached NTT tables of the domain of size 2^logn (logn >= 1), built on the slot's stream the first time a size is asked for (dock_qap.hip)
 int32_t get_domain(Slot &sl, int logn, NttDomain &out);
 // the window table of a G1 point (what dgpu_window_table_g1 builds) into `tab`, FIXED_TABLE_ENTRIES prepared records the caller owns, queued on the caller's

@@ -34,6 +34,7 @@ int32_t dgpu_dev_get_ntt_last(int32_t *path, int32_t *groups, int32_t cap) {
     int route = 0; const int n = ntt::dev_get_ntt_last(&route, groups, cap);
     *path = route; return n;
 }
+int32_t dgpu_dev_set_saver_fp_bits(int32_t bits) { if (bits < -1 || bits > 63) return DGPU_E_BADARG; gs.saver_fp_bits = bits; return DGPU_OK; }
 int32_t dgpu_set_reduce_lanes(int32_t lanes) { if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4) return DGPU_E_BADARG; gs.reduce_lanes = lanes; return DGPU_OK; }
 int32_t dgpu_set_reduce_shift(int32_t sh) { if (sh < -1 || sh > 6) return DGPU_E_BADARG; gs.reduce_shift = sh; return DGPU_OK; }
 int32_t dgpu_set_miller_pipeline(int32_t mode) {       // bits 0-4: forms; bits 8-13 / 16-21: where the chain is cut (0: default); bits 24-27: slice length of the last piece's products (0: automatic); bits 28-29: log2 of the factor on the block limit of k_line_products3
@@ -74,7 +75,7 @@ int32_t dgpu_selftest_g1_sum(const uint64_t *pts, const uint8_t *neg, size_t n, 
     void *dp, *dn, *dout, *dinf;
     HIPCHK(dev_malloc(&dp, n * 96 + 16)); HIPCHK(dev_malloc(&dn, n + 16)); HIPCHK(dev_malloc(&dout, 4 * 48)); HIPCHK(dev_malloc(&dinf, 16));
     HIPCHK(hipMemcpy(dp, pts, n * 96, hipMemcpyHostToDevice));
-    if (neg) HIPCHK(hipMemcpy(dn, neg, n, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(dn, 0, n + 16));
+    if (neg) HIPCHK(hipMemcpy(dn, neg, n, hipMemcpyHostToDevice)); else HIPCHK(hipMemsetAsync(dn, 0, n + 16, sl.stream));      // (on the kernel's stream, as below)
     selftest::launch_selftest_g1_sum(sl.stream, (const uint32_t *)dp, (const uint8_t *)dn, n, (uint32_t *)dout, (uint8_t *)dinf);
     HIPCHK(hipStreamSynchronize(sl.stream));
     uint64_t w[24]; uint8_t inf;
@@ -95,7 +96,7 @@ int32_t dgpu_selftest_arith(int32_t op, int32_t stress, const uint64_t *in, size
     void *din, *dout;
     HIPCHK(dev_malloc(&din, n * iw * 8 + 16)); HIPCHK(dev_malloc(&dout, n * ow * 8 + 16));
     HIPCHK(hipMemcpy(din, in, n * iw * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dout, 0, n * ow * 8));
+    HIPCHK(hipMemsetAsync(dout, 0, n * ow * 8, sl.stream));      // (on the kernel's stream: the slot streams do not wait for the null stream, and a memset there can land on the kernel's output)
     selftest::launch_selftest_arith(sl.stream, op, stress, (const uint32_t *)din, n, (uint32_t *)dout);
     HIPCHK(hipStreamSynchronize(sl.stream));
     HIPCHK(hipMemcpy(out, dout, n * ow * 8, hipMemcpyDeviceToHost));

@@ -25,7 +25,7 @@
 #include "bbs_launch.hip.h"
 #include "ps_launch.hip.h"
 #include "acc_host_tables.hpp"
-#include "pair_check.hip.h"             // zero_words, ws_check, coeffs_up, launch_check, check_tail, add_jac
+#include "pair_check.hip.h"             // zero_words, ws_check, coeffs_up, launch_check, check_tail, add_jac, merged_multi_verdict
 using namespace dock;
 using namespace acch;
 using namespace mlk;
@@ -46,13 +46,6 @@ bool bad_shape(size_t L, size_t stride, size_t n) {
 bool pk_ok(const HandleRef &hb, size_t L) { return hb.ok && hb.h.kind == 2 && hb.h.n == L + 2; }
 // rows per chunk of a call that runs no many-row MSM: the many-row kernels' rule all the same (dgpu_set_many_chunk_rows of the development surface cuts it)
 size_t sign_chunk(size_t n, size_t L) { return std::min(n, std::min(psk::PS_EACH_CHUNK, many_chunk_rows(L + 1))); }
-// -P on affine Montgomery words (y -> p - y; the identity, zero words, stays)
-void neg_g1(uint64_t *out, const uint64_t *p) {
-    memcpy(out, p, 48);
-    hostf::Fq y; memcpy(&y, p + 6, 48);
-    y = y.neg();
-    memcpy(out + 6, &y, 48);
-}
 // [sigma_1 | -sigma_2] of the rows [r0, r0 + rows) of n x 2 x 12 words, to dst (rows x 24 u32 words each, the second block right behind the first)
 void sides(const uint64_t *sigs, size_t r0, size_t rows, uint64_t *dst) {
     for (size_t i = 0; i < rows; i++) {
@@ -190,8 +183,6 @@ int32_t verify_batch(uint64_t pk, size_t L, const uint64_t *all_pc, const uint64
     if ((rc = ensure_workspace(sl, ws))) return rc;
     hipStream_t s = sl.stream;
     std::vector<HPoint> P(np, HPoint::identity());
-    std::vector<uint64_t> pts(np * 12 + (np + 7) / 8, 0);
-    uint8_t verdict = 0;
     DrainUnlessDone guard(sl);
     uint32_t *d_cols = sl.q[9].as<uint32_t>(), *d_rec1 = sl.q[10].as<uint32_t>(), *d_rec2 = d_rec1 + chunk * G1::AFF_STRIDE;
     uint64_t jac[18];
@@ -211,31 +202,9 @@ int32_t verify_batch(uint64_t pk, size_t L, const uint64_t *all_pc, const uint64
         }
         if (gs.prof) prof_flush(sl);
     }
-    uint8_t *sk = (uint8_t *)(pts.data() + np * 12);
-    for (size_t k = 0; k < np; k++) {
-        sk[k] = P[k].inf ? 1 : 0;
-        if (P[k].inf) continue;
-        hostf::Fq X, Y, Z; P[k].to_normalised_jacobian(X, Y, Z);
-        memcpy(pts.data() + 12 * k, &X, 48); memcpy(pts.data() + 12 * k + 6, &Y, 48);
-    }
-    // ONE multi-pairing of L + 2 pairs, each against its own prepared point: one segment, one slice, one final exponentiation
-    static const hostf::Fq12 one = hostf::Fq12::one();
-    uint32_t *dP = sl.q[4].as<uint32_t>(), *fout = sl.ml_out.as<uint32_t>();
-    HIPCHK(hipMemcpyAsync(dP, pts.data(), np * PT + np, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(sl.ml_coeffs.p, all_pc, np * cw * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(sl.ml_out.as<uint8_t>() + 576, &one, 576, hipMemcpyHostToDevice, s));
-    { StageTimer st(sl, "ps.lines"); launch_lines_from_prepared(s, dP, sl.ml_coeffs.as<uint32_t>(), (const uint8_t *)(dP + np * 24), np, sl.ml_lines.as<uint32_t>(), np, nullptr, false); }
-    { StageTimer st(sl, "bbs.products");
-      launch_line_products(s, gs.ml_mode.load(), sl.ml_lines.as<uint32_t>(), np, (int)np, 1, sl.ml_partial.as<uint32_t>(), nullptr, 1, 0, N_LINES, nullptr, false); }
-    { StageTimer st(sl, "bbs.tail"); gtk::launch_miller_tail(s, sl.ml_partial.as<uint32_t>(), 1, fout); }
-    { StageTimer st(sl, "bbs.final_exp"); gtk::launch_final_exp(s, fout, 1, (uint32_t *)nullptr, (uint8_t *)nullptr, fout + 144, sl.flags.as<uint8_t>()); }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&verdict, sl.flags.p, 1, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    guard.done = true;
-    if (gs.prof) prof_flush(sl);
-    *ok = verdict ? 1 : 0;
-    return DGPU_OK;
+    guard.done = true;                                                   // (every chunk's MSMs were waited for)
+    // ONE multi-pairing of L + 2 pairs, each against its own prepared point
+    return merged_multi_verdict(sl, P, all_pc, sl.q[4], "ps.lines", ok);
 }
 
 // ---- SignaturePoK::verify for n proofs (proof.rs:32-56) -------------------------------------------------------------------------------------------------------------

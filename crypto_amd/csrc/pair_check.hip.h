@@ -1,5 +1,6 @@
 // crypto_amd/csrc/pair_check.hip.h — the two-pair pairing check with shared lines and the merged verdict of a batch, for the bulk verifiers that end in
-// e(P1_i, w) e(P2_i, g2) == 1 (dock_bbs.hip: BBS+ signatures and proofs of knowledge; dock_acc_pok.hip: accumulator proofs).  Host code of a driver unit: it is
+// e(P1_i, w) e(P2_i, g2) == 1 (dock_bbs.hip: BBS+ signatures and proofs of knowledge; dock_acc_pok.hip: accumulator proofs; dock_ps.hip; dock_saver.hip, which
+// takes the pairing VALUES of its slices and a product of K + 2 pairs per slice from the same tail).  Host code of a driver unit: it is
 // included after msm_many.hip.h and lives in the unit's anonymous namespace, as it did while dock_bbs.hip was its only user.
 #pragma once
 #include "msm_many.hip.h"
@@ -11,6 +12,13 @@ using namespace mlk;
 namespace {
 
 bool zero_words(const uint64_t *w, int k) { uint64_t o = 0; for (int i = 0; i < k; i++) o |= w[i]; return o == 0; }
+// -P on affine Montgomery words (y -> p - y; the identity, zero words, stays)
+void neg_g1(uint64_t *out, const uint64_t *p) {
+    memcpy(out, p, 48);
+    hostf::Fq y; memcpy(&y, p + 6, 48);
+    y = y.neg();
+    memcpy(out + 6, &y, 48);
+}
 
 // ---- the pairing check of m <= `cols` rows on the device: e(P1_i, w) e(P2_i, g2) == 1 ---------------------------------------------------------------------------
 // dP: [P1 | P2], cols affine points each; dsk: their skip flags in the same order (an identity contributes one, as everywhere in the library).  The coefficients
@@ -33,15 +41,25 @@ int32_t coeffs_up(Slot &sl, const uint64_t *pk_pc, const uint64_t *g2_pc, size_t
     HIPCHK(hipMemcpyAsync(sl.ml_out.as<uint8_t>() + cols * 576, &one, 576, hipMemcpyHostToDevice, sl.stream));
     return DGPU_OK;
 }
-// what follows the 2 m pairs' lines in sl.ml_lines, whoever wrote them: one "segment" of 2 m pairs with slices of 2 — slice i is the pairs i and i + m, i.e. the
-// two lines of row i — the loop's tail, the final exponentiation compared with one.  pxy: the pairs' px, py where the lines came unevaluated, else nullptr
-void check_tail(Slot &sl, size_t m, size_t cols, const uint32_t *pxy) {
+// What follows the pairs' lines in sl.ml_lines, whoever wrote them: one "segment" of slice_len m pairs in m slices (slice i is the pairs i, i + m, ..), the loop's
+// tail, the final exponentiation.  out_gt != nullptr receives the m pairing VALUES (144 words each); want != nullptr (an element on the device) sets the verdict
+// bytes sl.flags[i] = (value i == want).  The Miller outputs go to the head of sl.ml_out.  pxy: the pairs' px, py where the lines came unevaluated, else nullptr
+void pair_tail(Slot &sl, size_t m, int slice_len, const uint32_t *pxy, uint32_t *out_gt, const uint32_t *want) {
     hipStream_t s = sl.stream;
     uint32_t *fout = sl.ml_out.as<uint32_t>();
     { StageTimer st(sl, "bbs.products");
-      launch_line_products(s, gs.ml_mode.load(), sl.ml_lines.as<uint32_t>(), 2 * m, 2, (int)m, sl.ml_partial.as<uint32_t>(), nullptr, 1, 0, N_LINES, pxy, false); }
+      launch_line_products(s, gs.ml_mode.load(), sl.ml_lines.as<uint32_t>(), (size_t)slice_len * m, slice_len, (int)m, sl.ml_partial.as<uint32_t>(), nullptr, 1, 0, N_LINES, pxy, false); }
     { StageTimer st(sl, "bbs.tail"); gtk::launch_miller_tail(s, sl.ml_partial.as<uint32_t>(), m, fout); }
-    { StageTimer st(sl, "bbs.final_exp"); gtk::launch_final_exp(s, fout, m, (uint32_t *)nullptr, (uint8_t *)nullptr, fout + cols * 144, sl.flags.as<uint8_t>()); }
+    { StageTimer st(sl, "bbs.final_exp"); gtk::launch_final_exp(s, fout, m, out_gt, (uint8_t *)nullptr, want, want ? sl.flags.as<uint8_t>() : nullptr); }
+}
+// the check of m two-pair rows: slice i is the pairs i and i + m, i.e. the two lines of row i, compared with the one behind the `cols` Miller outputs
+void check_tail(Slot &sl, size_t m, size_t cols, const uint32_t *pxy) { pair_tail(sl, m, 2, pxy, nullptr, sl.ml_out.as<uint32_t>() + cols * 144); }
+// the value-returning sibling (dock_saver.hip: a pairing value per slice goes on to a table lookup): the values behind the m Miller outputs in sl.ml_out
+// (which holds 2 m elements then); want as above, or nullptr
+uint32_t *value_tail(Slot &sl, size_t m, const uint32_t *want) {
+    uint32_t *gt = sl.ml_out.as<uint32_t>() + m * 144;
+    pair_tail(sl, m, 2, nullptr, gt, want);
+    return gt;
 }
 void launch_check(Slot &sl, const uint32_t *dP1, const uint32_t *dP2, const uint8_t *dsk, size_t m, size_t cols) {
     hipStream_t s = sl.stream;
@@ -95,6 +113,37 @@ int32_t merged_pair_verdict(Slot &sl, const HPoint &P1, const HPoint &P2, const 
     HIPCHK(hipMemcpyAsync(dP, pts, sizeof pts, hipMemcpyHostToDevice, s));
     if ((rc = coeffs_up(sl, pk_pc, g2_pc, 1))) return rc;
     launch_check(sl, dP, dP + 24, (const uint8_t *)(dP + 48), 1, 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&verdict, sl.flags.p, 1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    own.done = true;
+    if (gs.prof) prof_flush(sl);
+    *ok = verdict ? 1 : 0;
+    return DGPU_OK;
+}
+// *ok = [prod_k e(P_k, Q_k) == 1] for the np merged points of a batch, each against its own prepared G2 point (all_pc: np coefficient blocks on the host):
+// ONE multi-pairing — one segment, one slice, one final exponentiation (dock_ps.hip, dock_saver.hip: the column sums of a batch against the key).  An identity
+// member is skipped.  scratch: np PT + np + 64 bytes of the slot; sl.ml_coeffs holds np blocks, sl.ml_lines np pairs' lines, the rest as ws_check(sl, 1).
+int32_t merged_multi_verdict(Slot &sl, const std::vector<HPoint> &P, const uint64_t *all_pc, Buf &scratch, const char *lines_stage, int32_t *ok) {
+    hipStream_t s = sl.stream;
+    const size_t np = P.size(), cw = (size_t)DGPU_G2_PREPARED_WORDS;
+    std::vector<uint64_t> pts(np * 12 + (np + 7) / 8, 0);
+    uint8_t *sk = (uint8_t *)(pts.data() + np * 12);
+    for (size_t k = 0; k < np; k++) {
+        sk[k] = P[k].inf ? 1 : 0;
+        if (P[k].inf) continue;
+        hostf::Fq X, Y, Z; P[k].to_normalised_jacobian(X, Y, Z);
+        memcpy(pts.data() + 12 * k, &X, 48); memcpy(pts.data() + 12 * k + 6, &Y, 48);
+    }
+    static const hostf::Fq12 one = hostf::Fq12::one();
+    uint8_t verdict = 0;
+    DrainUnlessDone own(sl);                                             // (pts and verdict are this frame's)
+    uint32_t *dP = scratch.as<uint32_t>(), *fout = sl.ml_out.as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(dP, pts.data(), np * 96 + np, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sl.ml_coeffs.p, all_pc, np * cw * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sl.ml_out.as<uint8_t>() + 576, &one, 576, hipMemcpyHostToDevice, s));
+    { StageTimer st(sl, lines_stage); launch_lines_from_prepared(s, dP, sl.ml_coeffs.as<uint32_t>(), (const uint8_t *)(dP + np * 24), np, sl.ml_lines.as<uint32_t>(), np, nullptr, false); }
+    pair_tail(sl, 1, (int)np, nullptr, nullptr, fout + 144);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&verdict, sl.flags.p, 1, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));

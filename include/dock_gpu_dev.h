@@ -62,6 +62,10 @@ int32_t dgpu_dev_get_acc_d_unroll(void);
  * groups in launch order (per stage: n = log2 D ones); returns n (0: no transform yet). */
 int32_t dgpu_dev_set_ntt(int32_t path, const int32_t *split, int32_t n_split);
 int32_t dgpu_dev_get_ntt_last(int32_t *path, int32_t *groups, int32_t cap);
+/* Bits of the table fingerprints of the SAVER keys created from now on (dgpu_saver_dk_create of include/dock_gpu_saver.h: libdock_gpu_saver_dev.so serves both; existing keys keep theirs): 1 .. 63 keeps the low bits, 0 restores
+ * all 64, -1 keeps none, so that a whole column is ONE run of equal fingerprints.  Any setting gives the same chunks: the fingerprint only finds candidates
+ * (tests make runs exist by pigeonhole with 3 bits at b = 4). */
+int32_t dgpu_dev_set_saver_fp_bits(int32_t bits);
 /* log2 of the buckets one lane of the bucket reduction sums serially on the table pipeline (0..6; -1 = automatic: 3 for a 2^19-bucket table when the
  * call runs alone, 4 when three or more calls are in flight on the device context).  Any value gives the same point. */
 int32_t dgpu_set_reduce_shift(int32_t log2_buckets_per_lane);

@@ -9,6 +9,8 @@ fn main() {
         format!("{}/../../crypto_amd", here)
     });
     println!("cargo:rustc-link-search=native={}", dir);
-    println!("cargo:rustc-link-lib=dylib=dock_gpu");
+    // the feature `saver` (src/saver.rs, include/dock_gpu_saver.h) needs libdock_gpu_saver.so: the product's objects plus the SAVER calls, linked INSTEAD of it
+    let name = if std::env::var("CARGO_FEATURE_SAVER").is_ok() { "dock_gpu_saver" } else { "dock_gpu" };
+    println!("cargo:rustc-link-lib=dylib={}", name);
     println!("cargo:rustc-link-arg=-Wl,-rpath,{}", dir);
 }

@@ -37,6 +37,9 @@ pub mod bbs_plus;               // (BBS+ signatures in bulk behind the reference
 #[cfg(feature = "coconut")]
 pub mod coconut;                // (PS / Coconut signatures in bulk behind the reference's own types: src/coconut.rs; the case in tests/parity.rs runs under the same feature)
 
+#[cfg(feature = "saver")]
+pub mod saver;                  // (SAVER decryption and its checks in bulk behind the reference's own types: src/saver.rs; the case in tests/parity.rs runs under the same feature)
+
 pub type G2Prepared = ArkG2Prepared<ark_bls12_381::Config>;
 
 pub mod ffi;

@@ -1039,3 +1039,58 @@ fn ps_bulk_equals_the_reference() {
         }
     }
 }
+
+// SAVER in bulk behind the reference's own types (src/saver.rs) against the reference's decrypt_to_chunks_given_pairing_powers, verify_decryption,
+// verify_ciphertext_commitment and verify_commitments_in_batch.  NOT compiled where it was written (no toolchain there).
+#[cfg(feature = "saver")]
+#[test]
+fn saver_bulk_equals_the_reference() {
+    use dock_gpu::saver::{decrypt_many, verify_commitment_each, verify_commitments_batch, verify_decryption_each, GpuCommitmentKey, GpuDecryptionKey};
+    use saver::encryption::{Ciphertext, Encryption};
+    use saver::keygen::{keygen, PreparedDecryptionKey};
+    use saver::setup::EncryptionGens;
+    use saver::utils::{chunks_count, decompose};
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5A7E);
+    for &(b, n) in &[(4u8, 3usize), (8, 17)] {
+        let k = chunks_count::<Fr>(b) as usize;
+        let gens = EncryptionGens::<Bls12_381>::new_using_rng(&mut rng);
+        let g_i: Vec<G1Affine> = (0..k).map(|_| G1Projective::rand(&mut rng).into_affine()).collect();
+        let (delta_g, gamma_g) = (G1Projective::rand(&mut rng).into_affine(), G1Projective::rand(&mut rng).into_affine());
+        let (sk, ek, dk) = keygen(&mut rng, b, &gens, &g_i, &delta_g, &gamma_g).unwrap();
+        let gdk = GpuDecryptionKey::new(&dk, &g_i, &gens.H, b).expect("decryption key");
+        assert_eq!(gdk.supported_chunks_count(), k);
+        let powers = PreparedDecryptionKey::from(dk.clone()).pairing_powers(b, &g_i).unwrap();
+        assert_eq!(gdk.pairing_powers().expect("powers"), powers);
+        let msgs = frs(&mut rng, n);
+        let mut cts: Vec<Ciphertext<Bls12_381>> = msgs.iter().map(|m| {
+            let (c, _r) = Encryption::<Bls12_381>::encrypt_decomposed_message(&mut rng, decompose(m, b).unwrap(), &ek, &g_i).unwrap();
+            Ciphertext { X_r: c[0], enc_chunks: c[1..k + 1].to_vec(), commitment: c[k + 1] }
+        }).collect();
+        cts[n - 1].enc_chunks[0] = g_i[0];                           // one ciphertext that does not decrypt, with a bad commitment
+        let mine = decrypt_many(&gdk, &cts, &sk).expect("decrypt_many");
+        let (mut all_chunks, mut all_nu) = (vec![], vec![]);
+        for i in 0..n {
+            let theirs = Encryption::<Bls12_381>::decrypt_to_chunks_given_pairing_powers(&cts[i].X_r, &cts[i].enc_chunks, &sk, dk.clone(), &g_i, b, Some(&powers));
+            assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "b = {b}, row {i}");
+            let (c, nu) = mine[i].clone().unwrap_or((vec![0u16; k], G1Affine::identity()));
+            all_chunks.push(c); all_nu.push(nu);
+        }
+        assert!(mine[n - 1].is_err());
+        let rows: Vec<&[u16]> = all_chunks.iter().map(|c| c.as_slice()).collect();
+        let ok = verify_decryption_each(&gdk, &cts, &rows, &all_nu).expect("verify_decryption_each");
+        for i in 0..n {
+            let theirs = Encryption::<Bls12_381>::verify_decryption(&all_chunks[i], &cts[i].X_r, &cts[i].enc_chunks, &all_nu[i], dk.clone(), &g_i, gens.clone());
+            assert_eq!(ok[i], theirs.is_ok(), "row {i}");
+        }
+        let ck = GpuCommitmentKey::new(&ek, &gens.H).expect("commitment key");
+        let each = verify_commitment_each(&ck, &cts).expect("verify_commitment_each");
+        for i in 0..n { assert_eq!(each[i], cts[i].verify_commitment(ek.clone(), gens.clone()).is_ok(), "row {i}"); }
+        assert!(!each[n - 1] && each[..n - 1].iter().all(|&v| v));
+        let rho = Fr::rand(&mut rng);
+        let r_powers: Vec<Fr> = (0..n).scan(Fr::from(1u64), |acc, _| { let v = *acc; *acc *= rho; Some(v) }).collect();
+        assert_eq!(verify_commitments_batch(&ck, &cts, &r_powers), Some(false));
+        assert_eq!(verify_commitments_batch(&ck, &cts[..n - 1], &r_powers[..n - 1]), Some(true));
+        assert_eq!(Encryption::<Bls12_381>::verify_commitments_in_batch(&cts[..n - 1], &r_powers[..n - 1], ek.clone(), gens.clone()).is_ok(), true);
+    }
+}
