@@ -39,6 +39,11 @@ pub mod coconut;                // (PS / Coconut signatures in bulk behind the r
 
 #[cfg(feature = "saver")]
 pub mod saver;                  // (SAVER decryption and its checks in bulk behind the reference's own types: src/saver.rs; the case in tests/parity.rs runs under the same feature)
+// libdock_gpu_saver.so and libdock_gpu_smc.so are separate images, each linked INSTEAD of the product (build.rs links one library): one of the two features a build
+#[cfg(all(feature = "saver", feature = "smc-range-proof"))]
+compile_error!("the features `saver` and `smc-range-proof` link different libraries (libdock_gpu_saver.so, libdock_gpu_smc.so): enable one of them");
+#[cfg(feature = "smc-range-proof")]
+pub mod smc_range_proof;       // (CLS / CCS range proofs over weak-BB signatures verified in bulk behind the reference's own types: src/smc_range_proof.rs; the case in tests/parity.rs runs under the same feature)
 
 pub type G2Prepared = ArkG2Prepared<ark_bls12_381::Config>;
 

@@ -1094,3 +1094,60 @@ fn saver_bulk_equals_the_reference() {
         assert_eq!(Encryption::<Bls12_381>::verify_commitments_in_batch(&cts[..n - 1], &r_powers[..n - 1], ek.clone(), gens.clone()).is_ok(), true);
     }
 }
+
+// CLS / CCS range proofs over weak-BB signatures verified in bulk behind the reference's own types (src/smc_range_proof.rs) against the reference's own verify.
+// NOT compiled where it was written (no toolchain there).
+#[cfg(feature = "smc-range-proof")]
+#[test]
+fn smc_range_proofs_bulk_equal_the_reference() {
+    use blake2::Blake2b512;
+    use dock_gpu::smc_range_proof::{ccs_statement, ccs_verify_batch, ccs_verify_each, cls_statement, cls_verify_batch, cls_verify_each, GpuRangeVerifier};
+    use smc_range_proof::ccs_set_membership::setup::{SetMembershipCheckParams, SetMembershipCheckParamsWithPairing};
+    use smc_range_proof::common::MemberCommitmentKey;
+    use smc_range_proof::prelude::{CCSArbitraryRangeProofProtocol, CLSRangeProofProtocol};
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5AC);
+    for &(base, min, max) in &[(2u16, 0u64, u64::MAX), (3, 5, 13), (3, 5, 12), (4, 10, 11), (16, 0, 65536), (4, 10, 1000)] {
+        let (params, _) = SetMembershipCheckParams::<Bls12_381>::new_for_range_proof::<_, Blake2b512>(&mut rng, b"test", base);
+        let pp = SetMembershipCheckParamsWithPairing::from(params.clone());
+        let comm_key = MemberCommitmentKey::<G1Affine>::generate_using_rng(&mut rng);
+        let key = GpuRangeVerifier::new(&pp, &comm_key).expect("verifier");
+        assert!(cls_statement(&key, max, min, base).is_err() && cls_statement(&key, min, max, base + 1).is_err());
+        let n = 5usize;
+        let values: Vec<u64> = (0..n as u64).map(|i| if i == 0 { min } else if i == 1 { max - 1 } else { min + (u64::rand(&mut rng) % (max - min)) }).collect();
+        let (rs, cs) = (frs(&mut rng, n), frs(&mut rng, n));
+        let comms: Vec<G1Affine> = values.iter().zip(&rs).map(|(v, r)| comm_key.commit(&Fr::from(*v), r)).collect();
+        let random = frs(&mut rng, n);
+        let rho = Fr::rand(&mut rng);
+
+        let st = cls_statement(&key, min, max, base).unwrap();
+        let mut proofs: Vec<_> = (0..n).map(|i| CLSRangeProofProtocol::init_given_base(&mut rng, values[i], rs[i], min, max, base, &comm_key, &params).unwrap().gen_proof(&cs[i])).collect();
+        assert_eq!(cls_verify_batch(&key, &st, &comms, &proofs, &cs, &rho), Some(true));
+        proofs[n - 1].D = comm_key.g;                                // InvalidRangeProof
+        if let Some(p) = proofs[2].pok_sigs.last_mut() { p.A_bar = comm_key.h; }      // ShortGroupSig(InvalidProof)
+        let mine = cls_verify_each(&key, &st, &comms, &proofs, &cs, None).expect("cls_verify_each");
+        let merged = cls_verify_each(&key, &st, &comms, &proofs, &cs, Some(&random)).expect("cls_verify_each merged");
+        for i in 0..n {
+            let theirs = proofs[i].verify(&comms[i], &cs[i], min, max, &comm_key, pp.clone());
+            assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "cls base {base}, proof {i}");
+            assert_eq!(merged[i].is_ok(), theirs.is_ok(), "cls merged base {base}, proof {i}");
+        }
+        assert!(mine[n - 1].is_err() && mine[0].is_ok());
+        assert_eq!(cls_verify_batch(&key, &st, &comms, &proofs, &cs, &rho), Some(false));
+
+        if max == u64::MAX || max == min + 1 { continue; }            // (base^l must fit the reference's u64; l = 0 is CLS's alone)
+        let st = ccs_statement(&key, min, max, base).unwrap();
+        let mut proofs: Vec<_> = (0..n).map(|i| CCSArbitraryRangeProofProtocol::init_given_base(&mut rng, values[i], rs[i], min, max, base, &comm_key, &params).unwrap().gen_proof(&cs[i])).collect();
+        assert_eq!(ccs_verify_batch(&key, &st, &comms, &proofs, &cs, &rho).unwrap(), Some(true));
+        proofs[n - 1].D_max = comm_key.g;
+        proofs[2].pok_sigs_max[0].A_bar = comm_key.h;
+        let mine = ccs_verify_each(&key, &st, &comms, &proofs, &cs, None).unwrap().expect("ccs_verify_each");
+        for i in 0..n {
+            let theirs = proofs[i].verify(&comms[i], &cs[i], min, max, &comm_key, pp.clone());
+            assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "ccs base {base}, proof {i}");
+        }
+        assert_eq!(ccs_verify_batch(&key, &st, &comms, &proofs, &cs, &rho).unwrap(), Some(false));
+        proofs[1].pok_sigs_min.pop();
+        assert!(ccs_verify_each(&key, &st, &comms, &proofs, &cs, None).is_err());      // ProofShorterThanExpected
+    }
+}
