@@ -18,6 +18,9 @@ _SAVER_DEV_SO = os.path.join(_HERE, "libdock_gpu_saver_dev.so")
 # include/dock_gpu_smc.h: the same pair for the range proofs over weak-BB signatures
 _SMC_SO = os.path.join(_HERE, "libdock_gpu_smc.so")
 _SMC_DEV_SO = os.path.join(_HERE, "libdock_gpu_smc_dev.so")
+# include/dock_gpu_bpp.h: the same pair for the Bulletproofs++ range proofs
+_BPP_SO = os.path.join(_HERE, "libdock_gpu_bpp.so")
+_BPP_DEV_SO = os.path.join(_HERE, "libdock_gpu_bpp_dev.so")
 
 ERR = {0: "DGPU_OK", -1: "DGPU_E_NODEVICE", -2: "DGPU_E_OOM", -3: "DGPU_E_BADARG", -4: "DGPU_E_HIP",
        -5: "DGPU_E_ZERO", -6: "DGPU_E_TOO_SMALL", -7: "DGPU_E_LENGTH"}
@@ -126,6 +129,9 @@ SAVER_SYMBOLS = ["dgpu_saver_dk_create", "dgpu_saver_dk_free", "dgpu_saver_dk_po
 # every symbol include/dock_gpu_smc.h declares (libdock_gpu_smc.so and its development build only)
 SMC_SYMBOLS = ["dgpu_smc_range_proofs_verify_each_g1", "dgpu_smc_range_proofs_verify_batch_g1"]
 
+# every symbol include/dock_gpu_bpp.h declares (libdock_gpu_bpp.so and its development build only)
+BPP_SYMBOLS = ["dgpu_bpp_range_proofs_verify_each_g1", "dgpu_bpp_range_proofs_verify_batch_g1"]
+
 
 def lib():
     """the library the wrappers call: the product, or the twin inside `with twin():`"""
@@ -141,7 +147,8 @@ def dev_lib():
 
 
 def is_twin():
-    return _lib is not None and (_lib is _loaded.get(_DEV_SO) or _lib is _loaded.get(_SAVER_DEV_SO) or _lib is _loaded.get(_SMC_DEV_SO))
+    return _lib is not None and (_lib is _loaded.get(_DEV_SO) or _lib is _loaded.get(_SAVER_DEV_SO) or _lib is _loaded.get(_SMC_DEV_SO) or
+                                 _lib is _loaded.get(_BPP_DEV_SO))
 
 
 def _bring_up(T):
@@ -186,14 +193,26 @@ def note_init(*args):
         _init_args = args
 
 
+def bpp_lib(bring_up=True):
+    """the library that serves include/dock_gpu_bpp.h: the current one if it does (inside `with twin(bpp=True):`), else libdock_gpu_bpp.so, brought up on the
+    product's device(s) the first time"""
+    if _lib is not None and hasattr(_lib, BPP_SYMBOLS[0]):
+        return _lib
+    S = _load(_BPP_SO)
+    if bring_up and S.dgpu_context_count() == 0:
+        _bring_up(S)
+    return S
+
+
 @contextlib.contextmanager
-def twin(saver=False, smc=False):
+def twin(saver=False, smc=False, bpp=False):
     """Inside the block every wrapper of this package calls the development twin (include/dock_gpu_dev.h: knobs, stage timers, self-tests), brought up
     on the same device(s) as the product.  Nests; handles do not cross the border.  saver: the twin that serves include/dock_gpu_saver.h too
-    (libdock_gpu_saver_dev.so), for what cuts or times the SAVER calls; smc: the one that serves include/dock_gpu_smc.h (libdock_gpu_smc_dev.so)."""
+    (libdock_gpu_saver_dev.so), for what cuts or times the SAVER calls; smc: the one that serves include/dock_gpu_smc.h (libdock_gpu_smc_dev.so); bpp: the one that
+    serves include/dock_gpu_bpp.h (libdock_gpu_bpp_dev.so)."""
     global _lib
     prev = lib()
-    T = _load(_SAVER_DEV_SO) if saver else _load(_SMC_DEV_SO) if smc else dev_lib()
+    T = _load(_SAVER_DEV_SO) if saver else _load(_SMC_DEV_SO) if smc else _load(_BPP_DEV_SO) if bpp else dev_lib()
     if T is not prev:
         _bring_up(T)
     _lib = T
@@ -365,6 +384,11 @@ def _load(path):
                 getattr(L, s).restype = C.c_int32
             L.dgpu_smc_range_proofs_verify_each_g1.argtypes = [vp] * 5 + [C.c_int32, sz] + [vp] * 8 + [sz, C.c_int32, vp, vp, vp]
             L.dgpu_smc_range_proofs_verify_batch_g1.argtypes = [vp] * 5 + [C.c_int32, sz] + [vp] * 8 + [sz, C.c_int32, vp, C.POINTER(C.c_int32)]
+        if hasattr(L, BPP_SYMBOLS[0]):                        # libdock_gpu_bpp.so and its development build (include/dock_gpu_bpp.h)
+            for s in BPP_SYMBOLS:
+                getattr(L, s).restype = C.c_int32
+            L.dgpu_bpp_range_proofs_verify_each_g1.argtypes = [u64] + [C.c_uint32] * 3 + [vp] * 5 + [sz, C.c_int32, vp]
+            L.dgpu_bpp_range_proofs_verify_batch_g1.argtypes = [u64] + [C.c_uint32] * 3 + [vp] * 5 + [sz, C.c_int32, vp, C.POINTER(C.c_int32)]
         L.dgpu_witness_map.argtypes = [vp, vp, vp, sz] * 3 + [vp, sz, sz, sz, C.c_int32, vp, C.POINTER(u64), C.POINTER(sz)]
         for name in ("dgpu_window_table_g1", "dgpu_window_table_g2"):
             getattr(L, name).argtypes = [vp, C.POINTER(u64)]

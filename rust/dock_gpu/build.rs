@@ -12,7 +12,8 @@ fn main() {
     // the feature `saver` (src/saver.rs, include/dock_gpu_saver.h) needs libdock_gpu_saver.so: the product's objects plus the SAVER calls, linked INSTEAD of it
     // the feature `smc-range-proof` (src/smc_range_proof.rs, include/dock_gpu_smc.h) needs libdock_gpu_smc.so in the same way; the two libraries are separate
     // images, so a host builds with one of the two features
-    let name = if std::env::var("CARGO_FEATURE_SAVER").is_ok() { "dock_gpu_saver" } else if std::env::var("CARGO_FEATURE_SMC_RANGE_PROOF").is_ok() { "dock_gpu_smc" } else { "dock_gpu" };
+    let name = if std::env::var("CARGO_FEATURE_SAVER").is_ok() { "dock_gpu_saver" } else if std::env::var("CARGO_FEATURE_SMC_RANGE_PROOF").is_ok() { "dock_gpu_smc" }
+               else if std::env::var("CARGO_FEATURE_BULLETPROOFS_PLUS_PLUS").is_ok() { "dock_gpu_bpp" } else { "dock_gpu" };      // (src/bpp_range_proof.rs, include/dock_gpu_bpp.h: libdock_gpu_bpp.so)
     println!("cargo:rustc-link-lib=dylib={}", name);
     println!("cargo:rustc-link-arg=-Wl,-rpath,{}", dir);
 }

@@ -42,6 +42,10 @@ pub mod saver;                  // (SAVER decryption and its checks in bulk behi
 // libdock_gpu_saver.so and libdock_gpu_smc.so are separate images, each linked INSTEAD of the product (build.rs links one library): one of the two features a build
 #[cfg(all(feature = "saver", feature = "smc-range-proof"))]
 compile_error!("the features `saver` and `smc-range-proof` link different libraries (libdock_gpu_saver.so, libdock_gpu_smc.so): enable one of them");
+#[cfg(all(feature = "bulletproofs-plus-plus", any(feature = "saver", feature = "smc-range-proof")))]
+compile_error!("the feature `bulletproofs-plus-plus` links libdock_gpu_bpp.so, `saver` and `smc-range-proof` link other libraries: enable one of them");
+#[cfg(feature = "bulletproofs-plus-plus")]
+pub mod bpp_range_proof;       // (Bulletproofs++ range proofs verified in bulk behind the reference's own types: src/bpp_range_proof.rs; the case in tests/parity.rs runs under the same feature)
 #[cfg(feature = "smc-range-proof")]
 pub mod smc_range_proof;       // (CLS / CCS range proofs over weak-BB signatures verified in bulk behind the reference's own types: src/smc_range_proof.rs; the case in tests/parity.rs runs under the same feature)
 

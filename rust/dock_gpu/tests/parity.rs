@@ -1151,3 +1151,43 @@ fn smc_range_proofs_bulk_equal_the_reference() {
         assert!(ccs_verify_each(&key, &st, &comms, &proofs, &cs, None).is_err());      // ProofShorterThanExpected
     }
 }
+
+// Bulletproofs++ range proofs verified in bulk behind the reference's own types (src/bpp_range_proof.rs) against the reference's own verify.
+// NOT compiled where it was written (no toolchain there).
+#[cfg(feature = "bulletproofs-plus-plus")]
+#[test]
+fn bpp_range_proofs_bulk_equal_the_reference() {
+    use blake2::Blake2b512;
+    use bulletproofs_plus_plus::range_proof::Prover;
+    use bulletproofs_plus_plus::setup::SetupParams;
+    use dock_crypto_utils::transcript::new_merlin_transcript;
+    use dock_gpu::bpp_range_proof::{challenges, verify_batch, verify_each, GpuSetup, Parts};
+    setup();
+    let mut rng = StdRng::seed_from_u64(0xB99);
+    for &(base, num_bits, m) in &[(2u16, 8u16, 1usize), (2, 8, 2), (16, 8, 1), (4, 16, 4), (2, 64, 2)] {
+        let sp = SetupParams::<G1Affine>::new_for_perfect_range_proof::<Blake2b512>(b"test", base, num_bits, m as u32);
+        let gs = GpuSetup::new(&sp).expect("setup");
+        let n = 5usize;
+        let (mut vs, mut proofs) = (Vec::new(), Vec::new());
+        for i in 0..n {
+            let v: Vec<u64> = (0..m).map(|_| if i == 0 { 0 } else { u64::rand(&mut rng) >> (64 - num_bits) }).collect();
+            let gamma = frs(&mut rng, m);
+            let comms: Vec<G1Affine> = v.iter().zip(&gamma).map(|(v, g)| sp.compute_pedersen_commitment(*v, g)).collect();
+            let mut t = new_merlin_transcript(b"BPP/tests");
+            proofs.push(Prover::new_with_given_base(base, num_bits, comms.clone(), v, gamma).unwrap().prove(&mut rng, sp.clone(), &mut t).unwrap());
+            vs.push(comms);
+        }
+        vs[n - 1][0] = sp.G;                                           // a commitment to another value
+        let parts: Vec<Parts> = proofs.iter().map(|p| Parts::of(p).expect("parts")).collect();
+        let chals: Vec<Vec<Fr>> = (0..n).map(|i| challenges(&mut new_merlin_transcript(b"BPP/tests"), num_bits, &vs[i], &parts[i])).collect();
+        let mine = verify_each(&gs, num_bits, &vs, &parts, &chals).expect("verify_each");
+        for i in 0..n {
+            let theirs = proofs[i].verify(num_bits, &vs[i], &sp, &mut new_merlin_transcript(b"BPP/tests"));
+            assert_eq!(mine[i].is_ok(), theirs.is_ok(), "base {base}, {num_bits} bits, {m} values, proof {i}");
+        }
+        assert!(mine[0].is_ok() && mine[n - 1] == Err(1));
+        let rho = Fr::rand(&mut rng);
+        assert_eq!(verify_batch(&gs, num_bits, &vs[..n - 1], &parts[..n - 1], &chals[..n - 1], &rho), Some(true));
+        assert_eq!(verify_batch(&gs, num_bits, &vs, &parts, &chals, &rho), Some(false));
+    }
+}
