@@ -10,25 +10,23 @@
 // and for both the pairing e(W', pk) e(-Wbar, P~) = 1 over the proof's first two points.  The scalar field has to
 //   write the own scalars where the segmented small MSM reads them                                                        k_acc_pok_own
 //   one verdict: the coefficients of the shared points and the weights over the proofs' own points (weights u_i on the long check, v_i on the short one,
-//   t_i on the pairing; membership: u_i = t_i = rho^i; non-membership: u_i = rho^2i, v_i = rho^(2i+1), t_i = rho^i)     k_acc_pok_col_sums, k_acc_pok_col_finish
+//   t_i on the pairing; membership: u_i = t_i = rho^i; non-membership: u_i = rho^2i, v_i = rho^(2i+1), t_i = rho^i)     k_acc_pok_col_sums, k_col_finish
 // and two kernels move words only: k_acc_pok_stage lays the points out for the segment MSM and the pairing (-Wbar by a flip of y), k_acc_pok_verdict folds a
 // row's checks into its status byte.  The per-lane routines are FRD functions over load / store functors, as bbs_pok_kernels.hip.h's are: the same text runs
-// on the host under -DFP29_CHECK (tests/native/acc_pok_dev_host_shim.cpp).  Operand classes as in bbs_routines.hip.h: "product" (limbs < 2^29, value < 2 r),
+// on the host under -DFP29_CHECK (tests/native/acc_pok_dev_host_shim.cpp).  Operand classes as in col_sums.hip.h: "product" (limbs < 2^29, value < 2 r),
 // "lazy sum" (one carry pass after every addition of a product).
 //
-// Bounds of the batch sums.  A lane's run of BBS_COL_RUN = 16 rows adds ONE product per row to its sum: at most 16 terms, value < 32 r, limbs
+// Bounds of the batch sums.  A lane's run of COL_RUN = 16 rows adds ONE product per row to its sum: at most 16 terms, value < 32 r, limbs
 // <= 2^29 + 1 after each carry pass.  The fixed tree of a block of 256 adds sums of equal depth: after its eight levels a slot holds at most 256 x 16 products,
 // value < 2^13 r — a first operand of fr_mul (limbs < 2^31, value x 2 r far below 2^34 r^2).  The second pass adds products, one per block, with a carry pass
 // each.  A weight is a product, the negation of a product (neg_product: 512 r - v < 514 r as a first operand) or -(a b) of two products.
 #pragma once
-#include "bbs_routines.hip.h"
+#include "col_sums.hip.h"
 
 namespace accpk {
 using namespace fr29;
-using bbsk::neg_product;
-using bbsk::pow_start;
-using bbsk::tree_step;
-using bbsk::col_finish;
+using colk::neg_product;
+using colk::pow_start;
 
 constexpr int FQW = 12;           // u32 words of a base-field element
 constexpr int MEMBERSHIP = 0, NON_MEMBERSHIP = 1;
@@ -134,8 +132,8 @@ FRD uint8_t nm_status(bool c_inf, bool j_inf, bool short_ok, bool long_ok, bool 
 
 #if defined(__HIPCC__)
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------------------
-using bbsk::ld_words;
-using bbsk::st_words;
+using colk::ld_words;
+using colk::st_words;
 // what the kernels below load: chal: rows x 8 words, resp: rows x (2 | 3) x 8 words
 struct ProofIn {
     const uint32_t *__restrict__ chal, *__restrict__ resp; int kind; bool mont;
@@ -191,16 +189,14 @@ __global__ void __launch_bounds__(256) k_acc_pok_verdict(const uint8_t *__restri
 // over the own points (q < pts), tp[8 i ..] = rho^(i0 + i), tn[8 i ..] = -rho^(i0 + i)
 // (KIND is a template parameter: the two proof shapes are two kernels, so neither carries the other's branches and registers)
 template <int KIND>
-__global__ void __launch_bounds__(256) k_acc_pok_col_sums(ProofIn in, bbsk::RhoWords rho_words, size_t rows, size_t i0, size_t run, uint32_t *__restrict__ part,
+__global__ void __launch_bounds__(256) k_acc_pok_col_sums(ProofIn in, colk::RhoWords rho_words, size_t rows, size_t i0, size_t run, uint32_t *__restrict__ part,
                                                           uint32_t *__restrict__ wts, uint32_t *__restrict__ tp, uint32_t *__restrict__ tn) {
-    __shared__ uint32_t sh[NL][256];
     in.kind = KIND;
-    const unsigned t = threadIdx.x, n_pts = (unsigned)shape_of(KIND).pts;
-    const size_t k = blockIdx.x, lo = ((size_t)blockIdx.y * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-    Fr rho, sum;
+    const unsigned n_pts = (unsigned)shape_of(KIND).pts;
+    const size_t k = blockIdx.x;
+    Fr rho;
     fr_from_words(rho, rho_words.w, in.mont);
-    fr_zero(sum);
-    if (cnt)
+    colk::col_block_sum(k, rows, run, part, [&](size_t lo, size_t cnt, Fr &sum) {
         col_run(KIND, rho, i0 + lo, cnt, k == 0,
                 [&](size_t j, const Fr &u, const Fr &v, Fr &s) { col_term(s, KIND, lo + j, k, u, v, [&](size_t r_, unsigned q_, Fr &x_) { in.r(r_, q_, x_); }); },
                 [&](size_t j, const Fr &u, const Fr &v, const Fr &tw) {
@@ -209,33 +205,7 @@ __global__ void __launch_bounds__(256) k_acc_pok_col_sums(ProofIn in, bbsk::RhoW
                                 [&](unsigned q, const Fr &x) { if (q < n_pts) st_words(wts, i * n_pts + q, x); else st_words(q == n_pts ? tp : tn, i, x); });
                 },
                 sum);
-#pragma unroll
-    for (int l = 0; l < NL; l++) sh[l][t] = sum.l[l];
-    __syncthreads();
-    for (unsigned d = 128; d >= 1; d >>= 1) {
-        if (t < d)
-            tree_step(t, d, [&](unsigned q, Fr &x) { for (int l = 0; l < NL; l++) x.l[l] = sh[l][q]; }, [&](unsigned q, const Fr &x) { for (int l = 0; l < NL; l++) sh[l][q] = x.l[l]; });
-        __syncthreads();
-    }
-    if (t == 0) {
-        Fr one, r0; fr_one(one);
-        for (int l = 0; l < NL; l++) r0.l[l] = sh[l][0];
-        fr_mul(r0, r0, one);
-        for (int l = 0; l < NL; l++) part[(k * gridDim.y + blockIdx.y) * NL + l] = r0.l[l];
-    }
-}
-// one lane per column: the chunk's block sums onto the running sum in block order; out_words[8 k ..] = the coefficient of shared point k so far: the sum, or
-// (bit k of neg_mask) minus it — the P of a non-membership proof enters its check as -s_d P
-__global__ void __launch_bounds__(64) k_acc_pok_col_finish(const uint32_t *__restrict__ part, size_t nparts, size_t n, int first, unsigned neg_mask, uint32_t *__restrict__ run_sums,
-                                                           uint32_t *__restrict__ out_words) {
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    Fr start, c, o;
-    if (first) fr_zero(start); else for (int l = 0; l < NL; l++) start.l[l] = run_sums[k * NL + l];
-    col_finish(start, nparts, [&](size_t b, Fr &v) { for (int l = 0; l < NL; l++) v.l[l] = part[(k * nparts + b) * NL + l]; }, c);
-    for (int l = 0; l < NL; l++) run_sums[k * NL + l] = c.l[l];
-    if ((neg_mask >> k) & 1) neg_product(o, c); else o = c;
-    st_words(out_words, k, o);
+    });
 }
 #endif
 

@@ -10,7 +10,7 @@ namespace accpk {
 //                        lines and per-step products per proof).  A non-membership chunk is 8192 segments and 32768 terms a launch of the segmented small MSM
 //   ACC_POK_BATCH_CHUNK  proofs per chunk of the two ..._proofs_verify_batch_g1 calls, at most: the variable-base MSM over the chunk's 3 n or 5 n own points
 //                        runs per chunk
-// A lane of k_acc_pok_col_sums takes bbs_launch.hip.h's BBS_COL_RUN rows.
+// A lane of k_acc_pok_col_sums takes col_launch.hip.h's COL_RUN rows.
 constexpr size_t ACC_POK_EACH_CHUNK = 4096, ACC_POK_BATCH_CHUNK = 65536;
 // kind: 0 membership (3 points A', Abar, T; 2 responses z1, z2; 4 own scalars in 1 segment; 1 shared point V), 1 non-membership (5 points C', Cbar, J, T1, T2;
 // 3 responses s_r, s_y, s_d; 8 own scalars in 2 segments; 3 shared points V, P, Q)

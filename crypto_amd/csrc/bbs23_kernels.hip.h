@@ -12,14 +12,14 @@
 //   write the rows where the many-row MSM reads them (msm_many.hip.h many_rows_resident)                                   k_bbs23_rows
 //   write the own scalars where the segmented small MSM reads them                                                        k_bbs23_own
 //   one verdict: the column sums C_k and the weights over the proofs' own points (CDL: u_i = rho^2i on the first check, v_i = rho^(2i+1) on the second,
-//   t_i = rho^i on the pairing; IETF: u_i = t_i = rho^i)                                                                 k_bbs23_col_sums, k_bbs23_col_finish
+//   t_i = rho^i on the pairing; IETF: u_i = t_i = rho^i)                                                                 k_bbs23_col_sums, k_col_finish
 // and two kernels move words only: k_bbs23_stage lays the points out for the segment MSM and the pairing (-Bbar by a flip of y), k_bbs23_verdict folds a
 // row's checks into its status byte.  The proof kind is a template parameter of every kernel that depends on it: two kernels, neither carries the other's
 // branches and registers.  The per-lane routines are FRD functions over load / store functors, as bbs_pok_kernels.hip.h's are: the same text runs on the
-// host under -DFP29_CHECK (tests/native/bbs23_dev_host_shim.cpp).  Operand classes as in bbs_routines.hip.h: "product" (limbs < 2^29, value < 2 r), "lazy
+// host under -DFP29_CHECK (tests/native/bbs23_dev_host_shim.cpp).  Operand classes as in col_sums.hip.h: "product" (limbs < 2^29, value < 2 r), "lazy
 // sum" (one carry pass after every addition of a product).
 //
-// Bounds of the batch sums.  Every column, C_0 included, adds ONE product per row to a lane's sum: a run of BBS_COL_RUN = 16 rows is at most 16
+// Bounds of the batch sums.  Every column, C_0 included, adds ONE product per row to a lane's sum: a run of COL_RUN = 16 rows is at most 16
 // terms, value < 32 r, limbs <= 2^29 + 1 after each carry pass.  The fixed tree of a block of 256 adds sums of equal depth: after its eight levels a slot
 // holds at most 256 x 16 products, value < 2^13 r — a first operand of fr_mul (limbs < 2^31, value x 2 r far below 2^34 r^2).  The second pass adds products,
 // one per block, with a carry pass each.  A weight is a product, the negation of a product (neg_product: 512 r - v < 514 r as a first operand) or, for CDL's d,
@@ -29,10 +29,8 @@
 
 namespace bbs23k {
 using namespace fr29;
-using bbsk::neg_product;
-using bbsk::pow_start;
-using bbsk::tree_step;
-using bbsk::col_finish;
+using colk::neg_product;
+using colk::pow_start;
 
 constexpr int FQW = 12;           // u32 words of a base-field element
 constexpr int CDL = 0, IETF = 1;
@@ -150,8 +148,8 @@ FRD uint8_t status_of(bool a_inf, bool first_ok, bool second_ok, bool pairing_ok
 
 #if defined(__HIPCC__)
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------------------
-using bbsk::ld_words;
-using bbsk::st_words;
+using colk::ld_words;
+using colk::st_words;
 // what the kernels below load: chal: rows x 8 words, resp: rows x nresp x 8 words, vals: rows x L x 8 words packed, rev: rows x L bytes
 struct ProofIn {
     const uint32_t *__restrict__ chal, *__restrict__ resp, *__restrict__ vals; const uint8_t *__restrict__ rev; size_t L; unsigned nresp; bool mont;
@@ -219,16 +217,13 @@ template <int KIND> __global__ void __launch_bounds__(256) k_bbs23_verdict(const
 // fixed tree in LDS, part[(k * gridDim.y + b) * NL ..] in the internal form).  Column 0 also writes the rows' weights as canonical words: wts[(pts i + q) * 8 ..]
 // over the own points (q < pts), tp[8 i ..] = rho^(i0 + i), tn[8 i ..] = -rho^(i0 + i)
 template <int KIND>
-__global__ void __launch_bounds__(256) k_bbs23_col_sums(ProofIn in, bbsk::RhoWords rho_words, size_t rows, size_t i0, size_t run, uint32_t *__restrict__ part,
+__global__ void __launch_bounds__(256) k_bbs23_col_sums(ProofIn in, colk::RhoWords rho_words, size_t rows, size_t i0, size_t run, uint32_t *__restrict__ part,
                                                         uint32_t *__restrict__ wts, uint32_t *__restrict__ tp, uint32_t *__restrict__ tn) {
-    __shared__ uint32_t sh[NL][256];
     constexpr unsigned n_pts = KIND == CDL ? 5 : 3;
-    const unsigned t = threadIdx.x;
-    const size_t k = blockIdx.x, lo = ((size_t)blockIdx.y * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-    Fr rho, sum;
+    const size_t k = blockIdx.x;
+    Fr rho;
     fr_from_words(rho, rho_words.w, in.mont);
-    fr_zero(sum);
-    if (cnt)
+    colk::col_block_sum(k, rows, run, part, [&](size_t lo, size_t cnt, Fr &sum) {
         col_run(KIND, rho, i0 + lo, cnt, k == 0,
                 [&](size_t j, const Fr &u, const Fr &v, Fr &s) {
                     if (KIND == CDL) col_term(s, lo + j, k, v, BBS23K_CHAL(in), BBS23K_VALS(in)); else col_term(s, lo + j, k, u, BBS23K_CHAL(in), BBS23K_VALS(in));
@@ -239,32 +234,7 @@ __global__ void __launch_bounds__(256) k_bbs23_col_sums(ProofIn in, bbsk::RhoWor
                                 [&](unsigned q, const Fr &x) { if (q < n_pts) st_words(wts, i * n_pts + q, x); else st_words(q == n_pts ? tp : tn, i, x); });
                 },
                 sum);
-#pragma unroll
-    for (int l = 0; l < NL; l++) sh[l][t] = sum.l[l];
-    __syncthreads();
-    for (unsigned d = 128; d >= 1; d >>= 1) {
-        if (t < d)
-            tree_step(t, d, [&](unsigned q, Fr &x) { for (int l = 0; l < NL; l++) x.l[l] = sh[l][q]; }, [&](unsigned q, const Fr &x) { for (int l = 0; l < NL; l++) sh[l][q] = x.l[l]; });
-        __syncthreads();
-    }
-    if (t == 0) {
-        Fr one, r0; fr_one(one);
-        for (int l = 0; l < NL; l++) r0.l[l] = sh[l][0];
-        fr_mul(r0, r0, one);
-        for (int l = 0; l < NL; l++) part[(k * gridDim.y + blockIdx.y) * NL + l] = r0.l[l];
-    }
-}
-// one lane per column: the chunk's block sums onto the running sum in block order (run_sums[k * NL ..], internal form; first: it starts from zero);
-// out_words[8 k ..] = C_k so far
-__global__ void __launch_bounds__(64) k_bbs23_col_finish(const uint32_t *__restrict__ part, size_t nparts, size_t n, int first, uint32_t *__restrict__ run_sums,
-                                                         uint32_t *__restrict__ out_words) {
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    Fr start, c;
-    if (first) fr_zero(start); else for (int l = 0; l < NL; l++) start.l[l] = run_sums[k * NL + l];
-    col_finish(start, nparts, [&](size_t b, Fr &v) { for (int l = 0; l < NL; l++) v.l[l] = part[(k * nparts + b) * NL + l]; }, c);
-    for (int l = 0; l < NL; l++) run_sums[k * NL + l] = c.l[l];
-    st_words(out_words, k, c);
+    });
 }
 #endif
 

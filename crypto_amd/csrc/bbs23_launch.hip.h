@@ -10,7 +10,7 @@ namespace bbs23k {
 //                      per-step products per proof).  A CDL chunk is 8192 segments and 24576 terms a launch of the segmented small MSM, an IETF chunk 4096 and 12288
 //   BBS23_BATCH_CHUNK  proofs per chunk of the two ..._verify_batch_g1 calls, at most, beside bbs_launch.hip.h's BBS_BATCH_TERMS scalars of values: the
 //                      variable-base MSM over the chunk's 5 n or 3 n own points runs per chunk
-// A lane of k_bbs23_col_sums takes bbs_launch.hip.h's BBS_COL_RUN rows.
+// A lane of k_bbs23_col_sums takes col_launch.hip.h's COL_RUN rows.
 constexpr size_t BBS23_EACH_CHUNK = 4096, BBS23_BATCH_CHUNK = 65536;
 // kind: 0 CDL (proof_23_cdl.rs: 5 points Abar, Bbar, d, T1, T2; 3 responses z1, z2, z3; 6 own scalars in 2 segments), 1 IETF (proof_23_ietf.rs: 3 points
 // Abar, Bbar, T; 2 responses z_a, z_b; 3 own scalars in 1 segment)
@@ -31,7 +31,7 @@ void launch_bbs23_stage(hipStream_t s, const uint32_t *points, int kind, size_t 
 void launch_bbs23_verdict(hipStream_t s, const uint32_t *seg, const uint8_t *seg_inf, const uint32_t *b, const uint8_t *b_inf, const uint8_t *pairing, const uint8_t *a_inf, int kind,
                           size_t rows, uint8_t *status);
 // The chunk [i0, i0 + rows) of a batch: C_k += this chunk's share for the n = L + 1 columns (run_sums: n x 10 words between chunks; first: from zero; part:
-// bbsk::bbs_col_part_words(rows, n) words), c_words[8 k ..] = C_k as it stands, wts[(pts i + q) * 8 ..] the weights over the own points, tp / tn[8 i ..] =
+// colk::col_part_words(rows, n) words), c_words[8 k ..] = C_k as it stands, wts[(pts i + q) * 8 ..] the weights over the own points, tp / tn[8 i ..] =
 // +- rho^(i0 + i).  Two launches, no atomics.
 void launch_bbs23_columns(hipStream_t s, const ProofDev &in, const uint32_t rho_words[8], size_t rows, size_t i0, bool first, uint32_t *part, uint32_t *run_sums, uint32_t *wts,
                           uint32_t *tp, uint32_t *tn, uint32_t *c_words);

@@ -6,11 +6,11 @@
 // and everything the scalar field has to do is to write such rows where the many-row MSM reads them (msm_many.hip.h many_rows_resident):
 //   signing        row i times t_i = 1 / (x + e_i), the host's inverse: the MSM then yields A_i = t_i b_i itself                     k_bbs_rows (mult = t_i)
 //   verification   row i as it stands: the MSM yields b_i, the addend of -((-e_i) A_i + b_i) = e_i A_i - b_i                          k_bbs_rows (mult = 1)
-//   one verdict    the L + 2 column sums c_k = sum_i rho^i row_ik, the weights rho^i and rho^i e_i of the two MSMs over the A_i       k_bbs_col_sums, k_bbs_col_finish
+//   one verdict    the L + 2 column sums c_k = sum_i rho^i row_ik, the weights rho^i and rho^i e_i of the two MSMs over the A_i       k_bbs_col_sums, colk::k_col_finish
 // The 2023 scheme (bbs_plus/src/signature_23.rs: no s, no h_0; parameters [g1, h_1 .. h_L], row (1, m_i1 .. m_iL)) is the same text with ONE fixed column in
 // front of the messages instead of two: k_bbs_rows and k_bbs_col_sums take the count (`fixed`: 2 here, 1 there) and n = L + fixed.
-// The per-lane routines (row_value, row_entry, neg_product, pow_start, col_run, tree_step, col_finish) are in bbs_routines.hip.h, shared with the proofs of
-// knowledge (bbs_pok_kernels.hip.h); the kernels here drive them.
+// The row's routines (row_value, row_entry) are in bbs_routines.hip.h, shared with the proofs of knowledge (bbs_pok_kernels.hip.h); the column sums' (pow_start,
+// col_run, the block frame col_block_sum, the second pass) in col_sums.hip.h, shared with every batch verifier; the kernels here drive them.
 #pragma once
 #include "bbs_routines.hip.h"
 
@@ -30,20 +30,16 @@ __global__ void __launch_bounds__(256) k_bbs_rows(const uint32_t *__restrict__ s
     row_entry(o, v, mult);
     st_words(out_rows, t, o);
 }
-// grid (L + 2, blocks): block (k, b) sums column k over the rows [b * 256 * run, ..) of the chunk, lane t the `run` rows from (b * 256 + t) * run on with a start
-// power of its own, rho^(i0 + that row); the block's 256 sums fold by a fixed tree in LDS and leave as part[(k * gridDim.y + b) * NL ..] in the internal form.
-// Column 0 also writes wts[8 i ..] = rho^(i0 + i) and we[8 i ..] = rho^(i0 + i) e_i as canonical words.  rho_words, e, s, msgs: the caller's form (mont).
-// fixed as in k_bbs_rows: the grid's first dimension is L + fixed.
+// grid (L + 2, blocks): block (k, b) sums column k over the rows [b * 256 * run, ..) of the chunk (col_sums.hip.h col_block_sum), a lane its `run` rows with a
+// start power of its own, rho^(i0 + its first row).  Column 0 also writes wts[8 i ..] = rho^(i0 + i) and we[8 i ..] = rho^(i0 + i) e_i as canonical words.
+// rho_words, e, s, msgs: the caller's form (mont). fixed as in k_bbs_rows: the grid's first dimension is L + fixed.
 __global__ void __launch_bounds__(256) k_bbs_col_sums(const uint32_t *__restrict__ e, const uint32_t *__restrict__ s, const uint32_t *__restrict__ msgs, RhoWords rho_words, int mont,
                                                       size_t rows, size_t n, size_t fixed, size_t i0, size_t run, uint32_t *__restrict__ part, uint32_t *__restrict__ wts,
                                                       uint32_t *__restrict__ we) {
-    __shared__ uint32_t sh[NL][256];
-    const unsigned t = threadIdx.x;
-    const size_t k = blockIdx.x, lo = ((size_t)blockIdx.y * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-    Fr rho, sum;
+    const size_t k = blockIdx.x;
+    Fr rho;
     fr_from_words(rho, rho_words.w, mont != 0);
-    fr_zero(sum);
-    if (cnt)
+    col_block_sum(k, rows, run, part, [&](size_t lo, size_t cnt, Fr &sum) {
         col_run(rho, i0 + lo, cnt,
                 [&](size_t j, Fr &v) {
                     row_value_fixed(v, lo + j, k, fixed, [&](size_t r, Fr &x) { ld_words(x, s, r, mont != 0); },
@@ -56,33 +52,7 @@ __global__ void __launch_bounds__(256) k_bbs_col_sums(const uint32_t *__restrict
                     st_words(wts, lo + j, w); st_words(we, lo + j, p);
                 },
                 sum);
-#pragma unroll
-    for (int l = 0; l < NL; l++) sh[l][t] = sum.l[l];
-    __syncthreads();
-    for (unsigned d = 128; d >= 1; d >>= 1) {
-        if (t < d)
-            tree_step(t, d, [&](unsigned q, Fr &x) { for (int l = 0; l < NL; l++) x.l[l] = sh[l][q]; }, [&](unsigned q, const Fr &x) { for (int l = 0; l < NL; l++) sh[l][q] = x.l[l]; });
-        __syncthreads();
-    }
-    if (t == 0) {
-        Fr one, r0; fr_one(one);
-        for (int l = 0; l < NL; l++) r0.l[l] = sh[l][0];
-        fr_mul(r0, r0, one);
-        for (int l = 0; l < NL; l++) part[(k * gridDim.y + blockIdx.y) * NL + l] = r0.l[l];
-    }
-}
-// one lane per column: the chunk's block sums onto the running sum (run_sums[k * NL ..], internal form; first: it starts from zero), in block order; the running
-// sum goes back, and out_words[8 k ..] = the canonical words of -c_k (neg) or c_k as they stand after this chunk.
-__global__ void __launch_bounds__(64) k_bbs_col_finish(const uint32_t *__restrict__ part, size_t nparts, size_t n, int first, int neg, uint32_t *__restrict__ run_sums,
-                                                       uint32_t *__restrict__ out_words) {
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    Fr start, c, o;
-    if (first) fr_zero(start); else for (int l = 0; l < NL; l++) start.l[l] = run_sums[k * NL + l];
-    col_finish(start, nparts, [&](size_t b, Fr &v) { for (int l = 0; l < NL; l++) v.l[l] = part[(k * nparts + b) * NL + l]; }, c);
-    for (int l = 0; l < NL; l++) run_sums[k * NL + l] = c.l[l];
-    if (neg) neg_product(o, c); else o = c;
-    st_words(out_words, k, o);
+    });
 }
 #endif
 

@@ -8,13 +8,13 @@
 //   write the rows where the many-row MSM reads them (msm_many.hip.h many_rows_resident)                                  k_bbs_pok_rows
 //   write the own-point scalars (z1, z2, -c, c, -1 | z3, -1) where the segmented small MSM reads them                     k_bbs_pok_own
 //   one verdict: the column sums C_k and the weights of the MSMs over the own points (weights u_i = rho^2i on the first check, v_i = rho^(2i+1) on the
-//   second, t_i = rho^i on the pairing)                                                                                 k_bbs_pok_col_sums, k_bbs_pok_col_finish
+//   second, t_i = rho^i on the pairing)                                                                                 k_bbs_pok_col_sums, k_col_finish
 // and two kernels move words only: k_bbs_pok_stage lays the points out for the segment MSM and the pairing (-Abar by a flip of y), k_bbs_pok_verdict folds
 // the four checks of a row into its status byte.  The per-lane routines are FRD functions over load / store functors, as bbs_kernels.hip.h's are: the same text
 // runs on the host under -DFP29_CHECK (tests/native/bbs_pok_dev_host_shim.cpp).  Operand classes as there: "product" (limbs < 2^29, value < 2 r), "lazy sum"
 // (one carry pass after every addition of a product).
 //
-// Bounds of the batch sums.  A lane's run of BBS_COL_RUN = 16 rows adds one product per row to its sum, two in column 1 (u_i z2_i and
+// Bounds of the batch sums.  A lane's run of COL_RUN = 16 rows adds one product per row to its sum, two in column 1 (u_i z2_i and
 // v_i z4_i): at most 32 terms, value < 64 r, limbs <= 2^29 + 1 after each carry pass.  The fixed tree of a block of 256 adds sums of equal depth: after its eight
 // levels a slot holds at most 256 x 32 products, value < 2^14 r — a first operand of fr_mul (limbs < 2^31, value x 2 r far below 2^34 r^2).  The second pass
 // adds products, one per block, with a carry pass each.
@@ -23,10 +23,8 @@
 
 namespace bbspk {
 using namespace fr29;
-using bbsk::neg_product;
-using bbsk::pow_start;
-using bbsk::tree_step;
-using bbsk::col_finish;
+using colk::neg_product;
+using colk::pow_start;
 
 constexpr int POK_OWN = 7;        // own-point scalars per row: five of the first check, two of the second
 constexpr int POK_PTS = 5;        // points per proof: A', Abar, d, T1, T2
@@ -128,8 +126,8 @@ FRD uint8_t pok_status(bool a_inf, bool first_ok, bool second_ok, bool pairing_o
 
 #if defined(__HIPCC__)
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------------------
-using bbsk::ld_words;
-using bbsk::st_words;
+using colk::ld_words;
+using colk::st_words;
 // what the kernels below load: chal: rows x 8 words, fixed: rows x 4 x 8 words (z1 .. z4), vals: rows x L x 8 words packed, rev: rows x L bytes
 struct PokIn {
     const uint32_t *__restrict__ chal, *__restrict__ fixed, *__restrict__ vals; const uint8_t *__restrict__ rev; size_t L; bool mont;
@@ -194,15 +192,12 @@ __global__ void __launch_bounds__(256) k_bbs_pok_verdict(const uint32_t *__restr
 // grid (L + 2, blocks): block (k, b) sums column k over the rows [b * 256 * run, ..) of the chunk as k_bbs_col_sums does (a lane's own start powers, a fixed
 // tree in LDS, part[(k * gridDim.y + b) * NL ..] in the internal form).  Column 0 also writes the rows' weights as canonical words: w5[(5 i + q) * 8 ..] over the
 // own points (q < 5), tp[8 i ..] = rho^(i0 + i), tn[8 i ..] = -rho^(i0 + i)
-__global__ void __launch_bounds__(256) k_bbs_pok_col_sums(PokIn in, bbsk::RhoWords rho_words, size_t rows, size_t i0, size_t run, uint32_t *__restrict__ part,
+__global__ void __launch_bounds__(256) k_bbs_pok_col_sums(PokIn in, colk::RhoWords rho_words, size_t rows, size_t i0, size_t run, uint32_t *__restrict__ part,
                                                           uint32_t *__restrict__ w5, uint32_t *__restrict__ tp, uint32_t *__restrict__ tn) {
-    __shared__ uint32_t sh[NL][256];
-    const unsigned t = threadIdx.x;
-    const size_t k = blockIdx.x, lo = ((size_t)blockIdx.y * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-    Fr rho, sum;
+    const size_t k = blockIdx.x;
+    Fr rho;
     fr_from_words(rho, rho_words.w, in.mont);
-    fr_zero(sum);
-    if (cnt)
+    colk::col_block_sum(k, rows, run, part, [&](size_t lo, size_t cnt, Fr &sum) {
         pok_col_run(rho, i0 + lo, cnt, k == 0,
                     [&](size_t j, const Fr &u, const Fr &v, Fr &s) { pok_col_term(s, lo + j, k, u, v, POK_FUNCTORS(in)); },
                     [&](size_t j, const Fr &u, const Fr &v, const Fr &tw) {
@@ -211,31 +206,7 @@ __global__ void __launch_bounds__(256) k_bbs_pok_col_sums(PokIn in, bbsk::RhoWor
                                     [&](unsigned q, const Fr &x) { if (q < POK_PTS) st_words(w5, i * POK_PTS + q, x); else st_words(q == 5 ? tp : tn, i, x); });
                     },
                     sum);
-#pragma unroll
-    for (int l = 0; l < NL; l++) sh[l][t] = sum.l[l];
-    __syncthreads();
-    for (unsigned d = 128; d >= 1; d >>= 1) {
-        if (t < d)
-            tree_step(t, d, [&](unsigned q, Fr &x) { for (int l = 0; l < NL; l++) x.l[l] = sh[l][q]; }, [&](unsigned q, const Fr &x) { for (int l = 0; l < NL; l++) sh[l][q] = x.l[l]; });
-        __syncthreads();
-    }
-    if (t == 0) {
-        Fr one, r0; fr_one(one);
-        for (int l = 0; l < NL; l++) r0.l[l] = sh[l][0];
-        fr_mul(r0, r0, one);
-        for (int l = 0; l < NL; l++) part[(k * gridDim.y + blockIdx.y) * NL + l] = r0.l[l];
-    }
-}
-// one lane per column: the chunk's block sums onto the running sum in block order (k_bbs_col_finish without the negation): out_words[8 k ..] = C_k so far
-__global__ void __launch_bounds__(64) k_bbs_pok_col_finish(const uint32_t *__restrict__ part, size_t nparts, size_t n, int first, uint32_t *__restrict__ run_sums,
-                                                           uint32_t *__restrict__ out_words) {
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    Fr start, c;
-    if (first) fr_zero(start); else for (int l = 0; l < NL; l++) start.l[l] = run_sums[k * NL + l];
-    col_finish(start, nparts, [&](size_t b, Fr &v) { for (int l = 0; l < NL; l++) v.l[l] = part[(k * nparts + b) * NL + l]; }, c);
-    for (int l = 0; l < NL; l++) run_sums[k * NL + l] = c.l[l];
-    st_words(out_words, k, c);
+    });
 }
 #endif
 

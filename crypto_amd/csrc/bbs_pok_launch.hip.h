@@ -11,7 +11,7 @@ namespace bbspk {
 //                    proof).  The two segments per proof make 8192 segments and 28672 terms a launch of the segmented small MSM: 0.12 GB of window sums, 51 MB of table
 //   POK_BATCH_CHUNK  proofs per chunk of dgpu_bbs_plus_pok_verify_batch_g1, at most, beside bbs_launch.hip.h's BBS_BATCH_TERMS scalars of values: the
 //                    variable-base MSM over the chunk's 5 n own points runs per chunk
-// A lane of k_bbs_pok_col_sums takes bbs_launch.hip.h's BBS_COL_RUN rows.
+// A lane of k_bbs_pok_col_sums takes col_launch.hip.h's COL_RUN rows.
 constexpr size_t POK_EACH_CHUNK = 4096, POK_BATCH_CHUNK = 65536;
 // the proofs of a chunk on the device, in the caller's form (mont: ark-ff Montgomery words, else any 256-bit value): chal rows x 8 words, fixed rows x 4 x 8
 // words (z1, z2, z3, z4), vals rows x L x 8 words packed, rev rows x L bytes
@@ -26,7 +26,7 @@ void launch_pok_stage(hipStream_t s, const uint32_t *points, const uint32_t h0[2
 void launch_pok_verdict(hipStream_t s, const uint32_t *seg, const uint8_t *seg_inf, const uint32_t *b, const uint8_t *b_inf, const uint8_t *pairing, const uint8_t *a_inf, size_t rows,
                         uint8_t *status);
 // The chunk [i0, i0 + rows) of a batch: C_k += this chunk's share for the n = L + 2 columns (run_sums: n x 10 words between chunks; first: from zero; part:
-// bbsk::bbs_col_part_words(rows, n) words), c_words[8 k ..] = C_k as it stands, w5[(5 i + q) * 8 ..] the weights over the own points, tp / tn[8 i ..] = +- rho^(i0 + i).
+// colk::col_part_words(rows, n) words), c_words[8 k ..] = C_k as it stands, w5[(5 i + q) * 8 ..] the weights over the own points, tp / tn[8 i ..] = +- rho^(i0 + i).
 // Two launches, no atomics.
 void launch_pok_columns(hipStream_t s, const PokDev &in, const uint32_t rho_words[8], size_t rows, size_t i0, bool first, uint32_t *part, uint32_t *run_sums, uint32_t *w5,
                         uint32_t *tp, uint32_t *tn, uint32_t *c_words);

@@ -16,10 +16,10 @@
 //   per proof: the inverses (ONE fr_inv: fr_batch_inv over t, q, e + 0 .. e + base - 1), the powers, v, g_off, the own scalars, a record for the lanes below,
 //   and the flag "an inverse does not exist" (status 2)                                                                     k_bpp_consts
 //   per (proof, shared slot): the row's canonical scalar where the many-row MSM reads it                                    k_bpp_shared
-//   one verdict: proof i of the batch weighs rho^i: the coefficients of the 9 + NG shared points, the own scalars times rho^i   k_bpp_col_sums, k_bpp_col_finish
+//   one verdict: proof i of the batch weighs rho^i: the coefficients of the 9 + NG shared points, the own scalars times rho^i   k_bpp_col_sums, k_col_finish
 // and two kernels move words only: k_bpp_stage lays a proof's own points and its P_i = <row_i, setup> out for the segment MSM, k_bpp_verdict makes the status
 // byte.  The per-lane routines are FRD functions over load / store functors, as smc_kernels.hip.h's are: the same text runs on the host under -DFP29_CHECK
-// (tests/native/bpp_dev_host_shim.cpp).  Operand classes as in bbs_routines.hip.h: "product" (limbs < 2^29, value < 2 r), "lazy sum" (one carry pass after
+// (tests/native/bpp_dev_host_shim.cpp).  Operand classes as in col_sums.hip.h: "product" (limbs < 2^29, value < 2 r), "lazy sum" (one carry pass after
 // every addition of a product).
 //
 // g_off's three sums over D <= 512 digits factor, because digit k = i dp + j carries lambda^i base^j q^+-(i dp + j + 1):
@@ -36,17 +36,15 @@
 //   pub_k                   3 products                     value < 6 r       reduced by a product with one before it is subtracted
 //   e + k                   a product plus one             value < 4 r       reduced by a product with one
 // Every difference a - b is fr_sub<512, 30> (a: limbs < 2^30; b: a product; result: limbs < 2^31, value < value(a) + 512 r), at once the first operand of a
-// product.  The batch's column sums are bbs_routines.hip.h's col_run / tree_step / col_finish with their bounds (a lane's run of BBS_COL_RUN = 16 proofs, a
+// product.  The batch's column sums are col_sums.hip.h's col_run / tree_step / col_finish with their bounds (a lane's run of COL_RUN = 16 proofs, a
 // block's fixed tree: value < 2^13 r).  q^-(k+1) is the product of at most lg + 1 <= 10 entries of the proof's table of squarings (binary expansion of k + 1):
 // at most 9 products a lane beside gm_k's 9, against 2 lg for a square-and-multiply of its own or NG serial products in the proof's lane for a full table.
 #pragma once
-#include "bbs_routines.hip.h"
+#include "col_sums.hip.h"
 
 namespace bppk {
 using namespace fr29;
-using bbsk::neg_product;
-using bbsk::tree_step;
-using bbsk::col_finish;
+using colk::neg_product;
 
 constexpr int FQW = 12;           // u32 words of a base-field element
 constexpr int NH = 8;             // |H_vec|
@@ -280,8 +278,8 @@ FRD size_t batch_weight_index(const Shape &s, size_t rows, size_t i, unsigned q)
 
 #if defined(__HIPCC__)
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------------------
-using bbsk::ld_words;
-using bbsk::st_words;
+using colk::ld_words;
+using colk::st_words;
 // the record of a chunk: word (idx * NL + limb) * rows + i
 struct RecDev {
     uint32_t *__restrict__ p; size_t rows;
@@ -338,17 +336,13 @@ __global__ void __launch_bounds__(256) k_bpp_verdict(const uint8_t *__restrict__
 // grid (9 + NG, blocks): block (k, b) sums column k of the packed rows over the proofs [b * 256 * run, ..) of the chunk, proof i weighing rho^(i0 + i) (a lane's
 // own start power, a fixed tree in LDS, part[(k * gridDim.y + b) * NL ..] in the internal form).  The lanes of column 0 also write the batch's weights over the
 // own points: wts[8 batch_weight_index(i, q) ..] = rho^(i0 + i) own[i][q] as canonical words.  rows_sc: k_bpp_shared's output; own: k_bpp_consts's, own scalars apart
-__global__ void __launch_bounds__(256) k_bpp_col_sums(Shape s, const uint32_t *__restrict__ rows_sc, const uint32_t *__restrict__ own, bbsk::RhoWords rho_words, bool mont, size_t rows,
+__global__ void __launch_bounds__(256) k_bpp_col_sums(Shape s, const uint32_t *__restrict__ rows_sc, const uint32_t *__restrict__ own, colk::RhoWords rho_words, bool mont, size_t rows,
                                                       size_t i0, size_t run, uint32_t *__restrict__ part, uint32_t *__restrict__ wts) {
-    __shared__ uint32_t sh[NL][256];
-    const unsigned t = threadIdx.x;
-    const size_t n = (size_t)(SHARED0 + s.NG), lo = ((size_t)blockIdx.y * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-    const size_t k = blockIdx.x;
-    Fr rho, sum;
+    const size_t n = (size_t)(SHARED0 + s.NG), k = blockIdx.x;
+    Fr rho;
     fr_from_words(rho, rho_words.w, mont);
-    fr_zero(sum);
-    if (cnt)
-        bbsk::col_run(rho, i0 + lo, cnt, [&](size_t j, Fr &v) { ld_words(v, rows_sc, (lo + j) * n + k, false); },
+    colk::col_block_sum(k, rows, run, part, [&](size_t lo, size_t cnt, Fr &sum) {
+        colk::col_run(rho, i0 + lo, cnt, [&](size_t j, Fr &v) { ld_words(v, rows_sc, (lo + j) * n + k, false); },
                       [&](size_t j, const Fr &w) {
                           if (k != 0) return;
                           for (int q = 0; q < s.own; q++) {
@@ -359,31 +353,7 @@ __global__ void __launch_bounds__(256) k_bpp_col_sums(Shape s, const uint32_t *_
                           }
                       },
                       sum);
-#pragma unroll
-    for (int q = 0; q < NL; q++) sh[q][t] = sum.l[q];
-    __syncthreads();
-    for (unsigned d = 128; d >= 1; d >>= 1) {
-        if (t < d)
-            tree_step(t, d, [&](unsigned q, Fr &x) { for (int j = 0; j < NL; j++) x.l[j] = sh[j][q]; }, [&](unsigned q, const Fr &x) { for (int j = 0; j < NL; j++) sh[j][q] = x.l[j]; });
-        __syncthreads();
-    }
-    if (t == 0) {
-        Fr one, r0; fr_one(one);
-        for (int j = 0; j < NL; j++) r0.l[j] = sh[j][0];
-        fr_mul(r0, r0, one);
-        for (int j = 0; j < NL; j++) part[(k * gridDim.y + blockIdx.y) * NL + j] = r0.l[j];
-    }
-}
-// one lane per column: the chunk's block sums onto the running sum in block order; out_words[8 k ..] = the coefficient of shared point k so far
-__global__ void __launch_bounds__(64) k_bpp_col_finish(const uint32_t *__restrict__ part, size_t nparts, size_t ncols, int first, uint32_t *__restrict__ run_sums,
-                                                       uint32_t *__restrict__ out_words) {
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= ncols) return;
-    Fr start, c;
-    if (first) fr_zero(start); else for (int j = 0; j < NL; j++) start.l[j] = run_sums[k * NL + j];
-    col_finish(start, nparts, [&](size_t b, Fr &v) { for (int j = 0; j < NL; j++) v.l[j] = part[(k * nparts + b) * NL + j]; }, c);
-    for (int j = 0; j < NL; j++) run_sums[k * NL + j] = c.l[j];
-    st_words(out_words, k, c);
+    });
 }
 #endif
 

@@ -8,7 +8,7 @@ namespace bppk {
 // How a call is cut (tests/perf/bpp_timing.py reports what they would be tuned from).  Both are UNMEASURED as constants:
 //   BPP_EACH_CHUNK    proofs per chunk of dgpu_bpp_range_proofs_verify_each_g1, at most, beside the many-row kernels' own rule for rows of 9 + NG terms
 //   BPP_BATCH_POINTS  own points per chunk of dgpu_bpp_range_proofs_verify_batch_g1, at most (at least one proof): the variable-base MSM over them runs per chunk
-// A lane of k_bpp_col_sums takes bbs_launch.hip.h's BBS_COL_RUN proofs.
+// A lane of k_bpp_col_sums takes col_launch.hip.h's COL_RUN proofs.
 constexpr size_t BPP_EACH_CHUNK = 4096, BPP_BATCH_POINTS = (size_t)1 << 16;
 // what a shape comes to (bpp_kernels.hip.h make_shape): ok = 0 for anything outside base in {2, 4, 8, 16}, num_bits a power of two in [log2 base, 64], m a power
 // of two in [1, 8], NG a power of two

@@ -8,7 +8,7 @@
 //           device  one 4-term segment per row, respectively a 3-term and a 5-term one                              k_small_table, k_seg_tree, k_seg_fold (seg_rows_resident)
 //           device  e(A'_i, pk) e(-Abar_i, P~): the lines of the two prepared points shared by every row            pair_check.hip.h launch_check
 //           device  the first failing check of the row                                                              k_acc_pok_verdict
-//   batch   device  the coefficients of the shared points, the weights over the own points, +-rho^i                 k_acc_pok_col_sums, k_acc_pok_col_finish
+//   batch   device  the coefficients of the shared points, the weights over the own points, +-rho^i                 k_acc_pok_col_sums, k_col_finish
 //           device  one MSM over the chunk's 3 n (5 n) own points, one each over the two pairing sides; ONE over the 1 (3) shared points; the host adds the
 //                   chunks' points
 //           device  e(sum rho^i A'_i, pk) e(-sum rho^i Abar_i, P~) against one                                      pair_check.hip.h merged_pair_verdict
@@ -22,8 +22,6 @@ using namespace acch;
 using namespace mlk;
 
 namespace {
-
-constexpr size_t PT = 96;                 // bytes of an affine G1 point of the ABI
 
 // what the four calls share: the proofs' inputs.  shared: V, then P and Q for non-membership
 struct Proofs {
@@ -61,15 +59,8 @@ int32_t proofs_up(Slot &sl, const Proofs &p, size_t r0, size_t rows, accpk::Proo
     dev = accpk::ProofDev{sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), p.kind, p.mont ? 1 : 0};
     return DGPU_OK;
 }
-// the segments of every row of a chunk — one of 4 terms, respectively one of 3 and one of 5: the layout depends on the row count alone
-void own_layout(const accpk::KindShape &sh, size_t rows, SegLayout &lay) {
-    std::vector<uint64_t> ends((size_t)sh.segs * rows);
-    for (size_t i = 0; i < rows; i++) {
-        if (sh.segs == 1) ends[i] = (size_t)sh.own * (i + 1);
-        else { ends[2 * i] = (size_t)sh.own * i + 3; ends[2 * i + 1] = (size_t)sh.own * (i + 1); }
-    }
-    seg_layout(ends.data(), 0, ends.size(), lay);
-}
+// the segments of every row of a chunk — one of 4 terms, respectively one of 3 and one of 5
+void own_layout(const accpk::KindShape &sh, size_t rows, SegLayout &lay) { row_layout(rows, (size_t)sh.own, sh.segs == 1 ? 0 : 3, lay); }
 void shared_words(const Proofs &p, uint64_t out[36]) {
     memset(out, 0, 36 * 8);
     for (int k = 0; k < p.sh().shared; k++) memcpy(out + 12 * k, p.shared[k], PT);
@@ -169,33 +160,25 @@ int32_t verify_batch(const uint64_t *pk_pc, const uint64_t *ptilde_pc, const Pro
     uint32_t *d_c = sl.q[8].as<uint32_t>(), *d_run = d_c + nsh * 8, *d_w = sl.q[6].as<uint32_t>(), *d_tp = sl.q[9].as<uint32_t>(), *d_tn = d_tp + chunk * 8;
     uint32_t *d_rec = sl.q[10].as<uint32_t>(), *d_reca = sl.q[11].as<uint32_t>(), *d_recb = d_reca + chunk * G1::AFF_STRIDE, *d_recs = sl.q[13].as<uint32_t>();
     HPoint Gsum = HPoint::identity(), P1 = HPoint::identity(), P2 = HPoint::identity();
-    uint64_t jac[18];
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t rows = std::min(chunk, n - r0);
         accpk::ProofDev dev;
         if ((rc = proofs_up(sl, p, r0, rows, dev))) return rc;
         const uint8_t *raw = sl.q[5].as<uint8_t>();
         { StageTimer st(sl, "msm.prep_bases");
-          msm::launch_prep_bases_raw<G1>(s, raw, PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, np * rows, d_rec);
-          msm::launch_prep_bases_raw<G1>(s, raw, np * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_reca);
-          msm::launch_prep_bases_raw<G1>(s, raw + PT, np * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_recb); }
+          prep_g1(s, raw, PT, np * rows, d_rec);
+          prep_g1(s, raw, np * PT, rows, d_reca);
+          prep_g1(s, raw + PT, np * PT, rows, d_recb); }
         { StageTimer st(sl, "acc.pok_columns");
           accpk::launch_acc_pok_columns(s, dev, (const uint32_t *)random, rows, r0, r0 == 0, sl.q[7].as<uint32_t>(), d_run, d_w, d_tp, d_tn, d_c); }
         HIPCHK(hipGetLastError());
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_w, np * rows, jac))) return rc;
-        add_jac(Gsum, jac);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_reca, d_tp, rows, jac))) return rc;
-        add_jac(P1, jac);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_recb, d_tn, rows, jac))) return rc;
-        add_jac(P2, jac);
+        if ((rc = msm_add(sl, d_rec, d_w, np * rows, Gsum))) return rc;
+        if ((rc = msm_add(sl, d_reca, d_tp, rows, P1))) return rc;
+        if ((rc = msm_add(sl, d_recb, d_tn, rows, P2))) return rc;
         if (gs.prof) prof_flush(sl);
     }
     // the shared points' terms: ONE small MSM over V [, P, Q] with the finished coefficients
-    HIPCHK(hipMemcpyAsync(sl.q[12].p, shared, nsh * PT, hipMemcpyHostToDevice, s));
-    { StageTimer st(sl, "msm.prep_bases"); msm::launch_prep_bases_raw<G1>(s, sl.q[12].as<uint8_t>(), PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, nsh, d_recs); }
-    HIPCHK(hipGetLastError());
-    if ((rc = msm_device<G1, hostf::Fq>(sl, d_recs, d_c, nsh, jac))) return rc;
-    add_jac(Gsum, jac);
+    if ((rc = shared_points_add(sl, shared, nsh, sl.q[12], d_recs, d_c, Gsum))) return rc;
     if (!Gsum.inf) { HIPCHK(hipStreamSynchronize(s)); guard.done = true; *ok = 0; return DGPU_OK; }      // the G1 equation fails: the pairing cannot mend it
     if ((rc = merged_pair_verdict(sl, P1, P2, pk_pc, ptilde_pc, sl.q[4], ok))) return rc;
     guard.done = true;

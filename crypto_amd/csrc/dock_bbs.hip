@@ -10,7 +10,7 @@
 //            device  d_i = -((-e_i) A_i + b_i) = e_i A_i - b_i: the kernel's negation of its result, free  k_g1_scale_quad
 //            device  e(A_i, w) e(d_i, g2): lines of the two prepared points shared by every row, the products of every slice (i, i + m), the loop's tail, the
 //                    final exponentiation compared with one                                                k_lines_from_prepared x 2, k_line_products, k_miller_tail, k_final_exp
-//   batch    device  c_k = sum_i rho^i row_ik, rho^i, rho^i e_i                                           k_bbs_col_sums, k_bbs_col_finish
+//   batch    device  c_k = sum_i rho^i row_ik, rho^i, rho^i e_i                                           k_bbs_col_sums, k_col_finish
 //            device  P1 = sum rho^i A_i, P2 = sum (rho^i e_i) A_i + sum (-c_k) H_k: two MSMs per chunk over the A_i, ONE over the parameters; the host adds the
 //                    chunks' points
 //            device  e(P1, w) e(P2, g2) against one, as above with one slice
@@ -21,7 +21,7 @@
 //              device  P_i = <row_i, params>                                                                      k_many_tree, k_many_fold
 //              device  [A', h_0, Abar, d, T1] . (z1, z2, -c, c, -1) and z3 d - T2 per row                         k_small_table, k_seg_tree, k_seg_fold (seg_rows_resident)
 //              device  e(A'_i, w) e(-Abar_i, g2), as above; the four checks into a status byte                    .., k_bbs_pok_verdict
-//   pok batch  device  C_k, the weights over the own points, +-rho^i                                              k_bbs_pok_col_sums, k_bbs_pok_col_finish
+//   pok batch  device  C_k, the weights over the own points, +-rho^i                                              k_bbs_pok_col_sums, k_col_finish
 //              device  one MSM over the chunk's 5 n own points, one each over the A' and the Abar; ONE over the parameters; the host adds the chunks' points
 //              device  e(sum rho^i A'_i, w) e(-sum rho^i Abar_i, g2) against one
 // The 2023 scheme (dgpu_bbs23_*: bbs_plus/src/signature_23.rs, proof_23_cdl.rs, proof_23_ietf.rs): parameters [g1, h_1 .. h_L], no s, no h_0.
@@ -29,7 +29,7 @@
 //   pok each   device  row i = (c_i, y_i ..), the own scalars (z1, z2, -c, -1 | z3, -1) (CDL) or (z_a, z_b, -1) (IETF)   k_bbs23_rows, k_bbs23_own
 //              device  the bases [Abar, d, Bbar, T1 | d, T2] or [Abar, Bbar, T], Abar and -Bbar for the pairing             k_bbs23_stage
 //              device  P_i, the segments, the pairing as above; the checks into a status byte                              .., k_bbs23_verdict
-//   pok batch  device  C_k, the weights over the own points, +-rho^i                                                        k_bbs23_col_sums, k_bbs23_col_finish
+//   pok batch  device  C_k, the weights over the own points, +-rho^i                                                        k_bbs23_col_sums, k_col_finish
 //              device  one MSM over the chunk's 5 n or 3 n own points, one each over the Abar and the Bbar; ONE over the parameters; the pairing as above
 // Only verdict bytes (each, batch) or the signatures (sign) come back.  The device copies of the inverses and of the rows that carry them are zeroed on every return
 // path before the slot is released, the host copy too.
@@ -42,14 +42,13 @@
 #include "bbs_pok_launch.hip.h"
 #include "bbs23_launch.hip.h"
 #include "acc_host_tables.hpp"
-#include "pair_check.hip.h"             // zero_words, ws_check, coeffs_up, launch_check, add_jac, merged_pair_verdict: shared with dock_acc_pok.hip
+#include "pair_check.hip.h"             // PT, row_layout, prep_g1, msm_add, params_msm, zero_words, ws_check, coeffs_up, launch_check, merged_pair_verdict: shared with the other bulk drivers
 using namespace dock;
 using namespace acch;
 using namespace mlk;
 
 namespace {
 
-constexpr size_t PT = 96;                // bytes of an affine G1 point of the ABI
 constexpr size_t NPTS = 5;                // points of a proof of knowledge: A', Abar, d, T1, T2
 
 // what the three calls share: the rows' inputs and how they are cut.  fixed: the columns in front of the messages — 2 for BBS+ (1, s_i), parameters
@@ -217,16 +216,6 @@ size_t batch_chunk(size_t n, size_t L, size_t cap) {
     const int forced = gs.many_chunk.load();
     return std::min(n, forced > 0 ? (size_t)forced : std::min(cap, std::max<size_t>(1, bbsk::BBS_BATCH_TERMS / L)));
 }
-// acc += sum_k c_k H_k: ONE MSM of nn = L + 2 terms over the parameters, the scalars at d_c
-int32_t params_msm(Slot &sl, uint64_t params, const Handle &h, const uint32_t *d_c, size_t nn, HPoint &acc) {
-    SmallSub sub;
-    uint64_t jac[18];
-    int32_t rc;
-    const bool have = small_sub_for<G1>(sl, params, h, 0, nn, sub, true);
-    if ((rc = msm_device<G1, hostf::Fq>(sl, (const uint32_t *)h.p, d_c, nn, jac, have ? &sub : nullptr))) return rc;
-    add_jac(acc, jac);
-    return DGPU_OK;
-}
 int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const uint64_t *sig_a, const Rows &r, const uint64_t *random, int32_t *ok) {
     if (r.n == 0) { if (ok) *ok = 1; return DGPU_OK; }
     if (bad_rows(r) || !pk_pc || !g2_pc || !sig_a || !random || !ok) return DGPU_E_BADARG;
@@ -250,7 +239,7 @@ int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_
         if ((e = o.q[1].ensure(chunk * 32))) return e;
         if ((e = o.q[2].ensure(chunk * r.L * 32))) return e;
         if ((e = o.q[3].ensure(2 * PT + 64))) return e;
-        if ((e = o.q[7].ensure(bbsk::bbs_col_part_words(chunk, nn) * 4))) return e;
+        if ((e = o.q[7].ensure(colk::col_part_words(chunk, nn) * 4))) return e;
         if ((e = o.q[8].ensure(nn * 40 + nn * 32 + 64))) return e;
         if ((e = o.q[9].ensure(2 * chunk * 32))) return e;
         if ((e = o.q[10].ensure(chunk * G1::AFF_STRIDE * 4))) return e;
@@ -264,7 +253,6 @@ int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_
     DrainUnlessDone guard(sl);
     uint32_t *d_c = sl.q[8].as<uint32_t>(), *d_run = d_c + nn * 8, *d_w = sl.q[9].as<uint32_t>(), *d_we = d_w + chunk * 8, *d_rec = sl.q[10].as<uint32_t>();
     HPoint P1 = HPoint::identity(), P2 = HPoint::identity();
-    uint64_t jac[18];
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t rows = std::min(chunk, n - r0);
         HIPCHK(hipMemcpyAsync(sl.q[0].p, r.e + 4 * r0, rows * 32, hipMemcpyHostToDevice, s));
@@ -274,10 +262,8 @@ int32_t verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_
           bbsk::launch_bbs_columns(s, sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), (const uint32_t *)random, r.mont ? 1 : 0, rows, nn, r.fixed, r0, r0 == 0,
                                    sl.q[7].as<uint32_t>(), d_run, d_w, d_we, d_c); }
         HIPCHK(hipGetLastError());
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_w, rows, jac))) return rc;
-        add_jac(P1, jac);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_we, rows, jac))) return rc;
-        add_jac(P2, jac);
+        if ((rc = msm_add(sl, d_rec, d_w, rows, P1))) return rc;
+        if ((rc = msm_add(sl, d_rec, d_we, rows, P2))) return rc;
         if (gs.prof) prof_flush(sl);
     }
     if ((rc = params_msm(sl, params, hb.h, d_c, nn, P2))) return rc;       // - sum_k c_k H_k
@@ -315,12 +301,6 @@ int32_t proofs_up(Slot &sl, const Proofs &p, size_t r0, size_t rows, bbspk::PokD
     dev = bbspk::PokDev{sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), sl.q[3].as<uint8_t>(), p.L, p.mont ? 1 : 0};
     return DGPU_OK;
 }
-// the two segments of every row of a chunk, 5 and 2 terms: the layout depends on the row count alone
-void own_layout(size_t rows, SegLayout &lay) {
-    std::vector<uint64_t> ends(2 * rows);
-    for (size_t i = 0; i < rows; i++) { ends[2 * i] = 7 * i + 5; ends[2 * i + 1] = 7 * i + 7; }
-    seg_layout(ends.data(), 0, 2 * rows, lay);
-}
 
 int32_t pok_verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const Proofs &p, uint8_t *status) {
     if (p.n == 0) return DGPU_OK;
@@ -336,8 +316,8 @@ int32_t pok_verify_each(uint64_t params, const uint64_t *pk_pc, const uint64_t *
     const size_t chunk = bp.chunk;
     int32_t rc;
     SegLayout lay, lay_tail;
-    own_layout(chunk, lay);
-    if (n % chunk) own_layout(n % chunk, lay_tail);
+    row_layout(chunk, 7, 5, lay);                                        // the two segments of every row, 5 and 2 terms
+    if (n % chunk) row_layout(n % chunk, 7, 5, lay_tail);
     // q[0 .. 3], q[5]: the proofs (ws_proofs); q[4]: [P | identity flags], q[6]: the own-point scalars, q[7]: the own points in segment order, q[8]: [A' | -Abar],
     // q[9]: [skip flags of (A', -Abar) | status]
     auto ws = [&](Slot &o) -> int32_t {
@@ -402,7 +382,7 @@ int32_t pok_verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t 
         if ((e = ws_proofs(o, p, chunk))) return e;
         if ((e = o.q[4].ensure(2 * PT + 64))) return e;
         if ((e = o.q[6].ensure(chunk * NPTS * 32))) return e;
-        if ((e = o.q[7].ensure(bbsk::bbs_col_part_words(chunk, nn) * 4))) return e;
+        if ((e = o.q[7].ensure(colk::col_part_words(chunk, nn) * 4))) return e;
         if ((e = o.q[8].ensure(nn * 40 + nn * 32 + 64))) return e;
         if ((e = o.q[9].ensure(2 * chunk * 32))) return e;
         if ((e = o.q[10].ensure(chunk * NPTS * G1::AFF_STRIDE * 4))) return e;
@@ -416,25 +396,21 @@ int32_t pok_verify_batch(uint64_t params, const uint64_t *pk_pc, const uint64_t 
     uint32_t *d_c = sl.q[8].as<uint32_t>(), *d_run = d_c + nn * 8, *d_w5 = sl.q[6].as<uint32_t>(), *d_tp = sl.q[9].as<uint32_t>(), *d_tn = d_tp + chunk * 8;
     uint32_t *d_rec = sl.q[10].as<uint32_t>(), *d_reca = sl.q[11].as<uint32_t>(), *d_recb = d_reca + chunk * G1::AFF_STRIDE;
     HPoint Gsum = HPoint::identity(), P1 = HPoint::identity(), P2 = HPoint::identity();
-    uint64_t jac[18];
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t rows = std::min(chunk, n - r0);
         bbspk::PokDev dev;
         if ((rc = proofs_up(sl, p, r0, rows, dev))) return rc;
         const uint8_t *raw = sl.q[5].as<uint8_t>();
         { StageTimer st(sl, "msm.prep_bases");
-          msm::launch_prep_bases_raw<G1>(s, raw, PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, NPTS * rows, d_rec);
-          msm::launch_prep_bases_raw<G1>(s, raw, NPTS * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_reca);
-          msm::launch_prep_bases_raw<G1>(s, raw + PT, NPTS * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_recb); }
+          prep_g1(s, raw, PT, NPTS * rows, d_rec);
+          prep_g1(s, raw, NPTS * PT, rows, d_reca);
+          prep_g1(s, raw + PT, NPTS * PT, rows, d_recb); }
         { StageTimer st(sl, "bbs.pok_columns");
           bbspk::launch_pok_columns(s, dev, (const uint32_t *)random, rows, r0, r0 == 0, sl.q[7].as<uint32_t>(), d_run, d_w5, d_tp, d_tn, d_c); }
         HIPCHK(hipGetLastError());
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_w5, NPTS * rows, jac))) return rc;
-        add_jac(Gsum, jac);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_reca, d_tp, rows, jac))) return rc;
-        add_jac(P1, jac);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_recb, d_tn, rows, jac))) return rc;
-        add_jac(P2, jac);
+        if ((rc = msm_add(sl, d_rec, d_w5, NPTS * rows, Gsum))) return rc;
+        if ((rc = msm_add(sl, d_reca, d_tp, rows, P1))) return rc;
+        if ((rc = msm_add(sl, d_recb, d_tn, rows, P2))) return rc;
         if (gs.prof) prof_flush(sl);
     }
     if ((rc = params_msm(sl, params, hb.h, d_c, nn, Gsum))) return rc;     // sum_k C_k H_k
@@ -474,15 +450,8 @@ int32_t proofs23_up(Slot &sl, const Proofs23 &p, int kind, const bbs23k::KindSha
     dev = bbs23k::ProofDev{sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), sl.q[2].as<uint32_t>(), sl.q[3].as<uint8_t>(), p.L, kind, p.mont ? 1 : 0};
     return DGPU_OK;
 }
-// the segments of every row of a chunk — CDL: 4 and 2 terms, IETF: 3: the layout depends on the kind and the row count alone
-void own_layout23(const bbs23k::KindShape &ks, size_t rows, SegLayout &lay) {
-    std::vector<uint64_t> ends(ks.segs * rows);
-    for (size_t i = 0; i < rows; i++) {
-        if (ks.segs == 2) { ends[2 * i] = ks.own * i + 4; ends[2 * i + 1] = ks.own * (i + 1); }
-        else ends[i] = ks.own * (i + 1);
-    }
-    seg_layout(ends.data(), 0, ks.segs * rows, lay);
-}
+// the segments of every row of a chunk — CDL: 4 and 2 terms, IETF: 3
+void own_layout23(const bbs23k::KindShape &ks, size_t rows, SegLayout &lay) { row_layout(rows, (size_t)ks.own, ks.segs == 2 ? 4 : 0, lay); }
 
 int32_t pok23_verify_each(int kind, uint64_t params, const uint64_t *pk_pc, const uint64_t *g2_pc, const Proofs23 &p, uint8_t *status) {
     if (p.n == 0) return DGPU_OK;
@@ -569,7 +538,7 @@ int32_t pok23_verify_batch(int kind, uint64_t params, const uint64_t *pk_pc, con
         if ((e = ws_proofs23(o, p, ks, chunk))) return e;
         if ((e = o.q[4].ensure(2 * PT + 64))) return e;
         if ((e = o.q[6].ensure(chunk * npts * 32))) return e;
-        if ((e = o.q[7].ensure(bbsk::bbs_col_part_words(chunk, nn) * 4))) return e;
+        if ((e = o.q[7].ensure(colk::col_part_words(chunk, nn) * 4))) return e;
         if ((e = o.q[8].ensure(nn * 40 + nn * 32 + 64))) return e;
         if ((e = o.q[9].ensure(2 * chunk * 32))) return e;
         if ((e = o.q[10].ensure(chunk * npts * G1::AFF_STRIDE * 4))) return e;
@@ -583,25 +552,21 @@ int32_t pok23_verify_batch(int kind, uint64_t params, const uint64_t *pk_pc, con
     uint32_t *d_c = sl.q[8].as<uint32_t>(), *d_run = d_c + nn * 8, *d_wts = sl.q[6].as<uint32_t>(), *d_tp = sl.q[9].as<uint32_t>(), *d_tn = d_tp + chunk * 8;
     uint32_t *d_rec = sl.q[10].as<uint32_t>(), *d_reca = sl.q[11].as<uint32_t>(), *d_recb = d_reca + chunk * G1::AFF_STRIDE;
     HPoint Gsum = HPoint::identity(), P1 = HPoint::identity(), P2 = HPoint::identity();
-    uint64_t jac[18];
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t rows = std::min(chunk, n - r0);
         bbs23k::ProofDev dev;
         if ((rc = proofs23_up(sl, p, kind, ks, r0, rows, dev))) return rc;
         const uint8_t *raw = sl.q[5].as<uint8_t>();
         { StageTimer st(sl, "msm.prep_bases");
-          msm::launch_prep_bases_raw<G1>(s, raw, PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, npts * rows, d_rec);
-          msm::launch_prep_bases_raw<G1>(s, raw, npts * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_reca);
-          msm::launch_prep_bases_raw<G1>(s, raw + PT, npts * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_recb); }
+          prep_g1(s, raw, PT, npts * rows, d_rec);
+          prep_g1(s, raw, npts * PT, rows, d_reca);
+          prep_g1(s, raw + PT, npts * PT, rows, d_recb); }
         { StageTimer st(sl, "bbs23.pok_columns");
           bbs23k::launch_bbs23_columns(s, dev, (const uint32_t *)random, rows, r0, r0 == 0, sl.q[7].as<uint32_t>(), d_run, d_wts, d_tp, d_tn, d_c); }
         HIPCHK(hipGetLastError());
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_wts, npts * rows, jac))) return rc;
-        add_jac(Gsum, jac);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_reca, d_tp, rows, jac))) return rc;
-        add_jac(P1, jac);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_recb, d_tn, rows, jac))) return rc;
-        add_jac(P2, jac);
+        if ((rc = msm_add(sl, d_rec, d_wts, npts * rows, Gsum))) return rc;
+        if ((rc = msm_add(sl, d_reca, d_tp, rows, P1))) return rc;
+        if ((rc = msm_add(sl, d_recb, d_tn, rows, P2))) return rc;
         if (gs.prof) prof_flush(sl);
     }
     if ((rc = params_msm(sl, params, hb.h, d_c, nn, Gsum))) return rc;     // sum_k C_k H_k

@@ -8,7 +8,7 @@
 //           device  the segment [V .., D, M, R, S, X .., R .., P_i] of every proof                                                  k_bpp_stage
 //           device  one (own + 1)-term segment per proof                                             k_small_table, k_seg_tree, k_seg_fold (seg_rows_resident)
 //           device  the status byte from the segment's identity flag and the status-2 flag                                          k_bpp_verdict
-//   batch   device  constants and rows as above; the coefficients of the shared points and the own scalars times rho^i              k_bpp_col_sums, k_bpp_col_finish
+//   batch   device  constants and rows as above; the coefficients of the shared points and the own scalars times rho^i              k_bpp_col_sums, k_col_finish
 //           device  one MSM over the chunk's own points; ONE over the setup at the end; the host adds the chunks' points and tests for the identity
 // Only status bytes (each) or one verdict (batch) come back.  No pairing is run.  Nothing secret passes through: nothing is wiped.
 #include "msm_many.hip.h"
@@ -21,8 +21,6 @@ using namespace acch;
 
 namespace {
 
-constexpr size_t PT = 96;                 // bytes of an affine G1 point of the ABI
-
 // what the two calls share: the shape and the proofs' inputs
 struct Proofs {
     uint64_t setup; uint32_t base, num_bits, m; const uint64_t *values, *round_points, *wnla_points, *l_n, *challenges; size_t n; bool mont;
@@ -34,12 +32,6 @@ bool bad_proofs(const Proofs &p, bppk::ShapeInfo &sh) {
     return !sh.ok;
 }
 bool setup_ok(const HandleRef &hb, const bppk::ShapeInfo &sh) { return hb.ok && hb.h.kind == 1 && hb.h.n == sh.shared; }
-// proofs per chunk of the batch: the largest count with rows * per <= limit, at least one (dgpu_set_many_chunk_rows of the development surface cuts it further)
-size_t chunk_rows(size_t n, size_t limit, size_t per) {
-    const int forced = gs.many_chunk.load();
-    const size_t cap = std::max<size_t>(1, limit / per);
-    return std::min(n, forced > 0 ? std::min((size_t)forced, cap) : cap);
-}
 // q[0]: the challenges, q[1]: l0, n0, q[2]: V, q[3]: D, M, R, S, q[4]: X .., R .., q[5]: the record
 int32_t ws_proofs(Slot &o, const Proofs &p, const bppk::ShapeInfo &sh, size_t chunk) {
     int32_t e;
@@ -62,12 +54,6 @@ int32_t proofs_up(Slot &sl, const Proofs &p, const bppk::ShapeInfo &sh, size_t r
     dev = bppk::ProofDev{sl.q[0].as<uint32_t>(), sl.q[1].as<uint32_t>(), p.base, p.num_bits, p.m, p.mont ? 1 : 0};
     return DGPU_OK;
 }
-// one segment of `terms` terms per proof: the layout depends on the counts alone
-void own_layout(size_t rows, size_t terms, SegLayout &lay) {
-    std::vector<uint64_t> ends(rows);
-    for (size_t k = 0; k < rows; k++) ends[k] = terms * (k + 1);
-    seg_layout(ends.data(), 0, rows, lay);
-}
 
 int32_t verify_each(const Proofs &p, uint8_t *status) {
     if (p.n == 0) return DGPU_OK;
@@ -84,8 +70,8 @@ int32_t verify_each(const Proofs &p, uint8_t *status) {
     const size_t chunk = bp.chunk;
     int32_t rc;
     SegLayout lay, lay_tail;
-    own_layout(chunk, T, lay);
-    if (n % chunk) own_layout(n % chunk, T, lay_tail);
+    row_layout(chunk, T, 0, lay);                                        // one segment of T terms per proof
+    if (n % chunk) row_layout(n % chunk, T, 0, lay_tail);
     // q[0] .. q[5]: the proofs and the record (ws_proofs); q[6]: the own scalars and the one behind them, q[7]: the segments' bases, q[8]: [P | identity flags],
     // q[9]: [status-2 flags | status]
     auto ws = [&](Slot &o) -> int32_t {
@@ -162,34 +148,27 @@ int32_t verify_batch(const Proofs &p, const uint64_t *random, int32_t *ok) {
     uint8_t *dflag = sl.q[9].as<uint8_t>();
     std::vector<uint8_t> hflag(chunk);
     HPoint sum = HPoint::identity();
-    uint64_t jac[18];
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t rows = std::min(chunk, n - r0);
         bppk::ProofDev dev;
         if ((rc = proofs_up(sl, p, sh, r0, rows, dev))) return rc;
         { StageTimer st(sl, "msm.prep_bases");
-          msm::launch_prep_bases_raw<G1>(s, sl.q[2].as<uint8_t>(), PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows * p.m, d_rec);
-          msm::launch_prep_bases_raw<G1>(s, sl.q[3].as<uint8_t>(), PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows * 4, d_rec + rows * p.m * G1::AFF_STRIDE);
-          msm::launch_prep_bases_raw<G1>(s, sl.q[4].as<uint8_t>(), PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows * 2 * sh.K, d_rec + rows * (p.m + 4) * G1::AFF_STRIDE); }
+          prep_g1(s, sl.q[2].p, PT, rows * p.m, d_rec);
+          prep_g1(s, sl.q[3].p, PT, rows * 4, d_rec + rows * p.m * G1::AFF_STRIDE);
+          prep_g1(s, sl.q[4].p, PT, rows * 2 * sh.K, d_rec + rows * (p.m + 4) * G1::AFF_STRIDE); }
         { StageTimer st(sl, "bpp.consts"); bppk::launch_bpp_consts(s, dev, rows, d_recd, own, d_own, dflag); }
         { StageTimer st(sl, "bpp.shared"); bppk::launch_bpp_shared(s, dev, rows, d_recd, d_rows); }
         { StageTimer st(sl, "bpp.columns");
           bppk::launch_bpp_columns(s, dev, d_rows, d_own, (const uint32_t *)random, rows, r0, r0 == 0, sl.q[7].as<uint32_t>(), d_run, d_w, d_c); }
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(hflag.data(), dflag, rows, hipMemcpyDeviceToHost, s));
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_w, rows * own, jac))) return rc;
-        add_jac(sum, jac);
+        if ((rc = msm_add(sl, d_rec, d_w, rows * own, sum))) return rc;
         HIPCHK(hipStreamSynchronize(s));                                 // (hflag is this frame's; the next chunk's operands overwrite this one's)
         if (gs.prof) prof_flush(sl);
         for (size_t i = 0; i < rows; i++) if (hflag[i]) { guard.done = true; *ok = 0; return DGPU_OK; }      // a proof of status 2 refuses the batch
     }
     // the shared points' terms: ONE MSM over the setup with the finished coefficients
-    {
-        SmallSub sub;
-        const bool have = small_sub_for<G1>(sl, p.setup, hb.h, 0, cols, sub, true);
-        if ((rc = msm_device<G1, hostf::Fq>(sl, (const uint32_t *)hb.h.p, d_c, cols, jac, have ? &sub : nullptr))) return rc;
-        add_jac(sum, jac);
-    }
+    if ((rc = params_msm(sl, p.setup, hb.h, d_c, cols, sum))) return rc;
     HIPCHK(hipStreamSynchronize(s));
     guard.done = true;
     *ok = sum.inf ? 1 : 0;

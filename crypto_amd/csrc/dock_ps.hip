@@ -36,8 +36,6 @@ template <class C> int32_t table_mul_device(Slot &sl, const void *table, const u
 
 namespace {
 
-constexpr size_t PT = 96, PT2 = 192;      // bytes of an affine G1 / G2 point of the ABI
-
 // the argument checks that come before the device is looked at (n > 0)
 bool bad_shape(size_t L, size_t stride, size_t n) {
     return L == 0 || stride < L || n >= (1ull << 31) || L >= (1ull << 31) - 2 || stride >= (1ull << 31);
@@ -185,21 +183,17 @@ int32_t verify_batch(uint64_t pk, size_t L, const uint64_t *all_pc, const uint64
     std::vector<HPoint> P(np, HPoint::identity());
     DrainUnlessDone guard(sl);
     uint32_t *d_cols = sl.q[9].as<uint32_t>(), *d_rec1 = sl.q[10].as<uint32_t>(), *d_rec2 = d_rec1 + chunk * G1::AFF_STRIDE;
-    uint64_t jac[18];
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t rows = std::min(chunk, n - r0);
         const uint8_t *raw = sl.q[3].as<uint8_t>();
         HIPCHK(hipMemcpyAsync(sl.q[3].p, sigs + 24 * r0, 2 * rows * PT, hipMemcpyHostToDevice, s));
         if ((rc = upload_rows_packed(s, sl.q[2].p, messages + r0 * stride * 4, L, stride, rows))) return rc;
         { StageTimer st(sl, "msm.prep_bases");
-          msm::launch_prep_bases_raw<G1>(s, raw, 2 * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_rec1);
-          msm::launch_prep_bases_raw<G1>(s, raw + PT, 2 * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_rec2); }
+          prep_g1(s, raw, 2 * PT, rows, d_rec1);
+          prep_g1(s, raw + PT, 2 * PT, rows, d_rec2); }
         { StageTimer st(sl, "ps.columns"); psk::launch_ps_col_scalars(s, sl.q[2].as<uint32_t>(), (const uint32_t *)random, mont ? 1 : 0, rows, L, r0, chunk, d_cols); }
         HIPCHK(hipGetLastError());
-        for (size_t k = 0; k < np; k++) {
-            if ((rc = msm_device<G1, hostf::Fq>(sl, k == L + 1 ? d_rec2 : d_rec1, d_cols + k * chunk * 8, rows, jac))) return rc;
-            add_jac(P[k], jac);
-        }
+        for (size_t k = 0; k < np; k++) if ((rc = msm_add(sl, k == L + 1 ? d_rec2 : d_rec1, d_cols + k * chunk * 8, rows, P[k]))) return rc;
         if (gs.prof) prof_flush(sl);
     }
     guard.done = true;                                                   // (every chunk's MSMs were waited for)

@@ -32,7 +32,7 @@ using namespace mlk;
 
 namespace {
 
-constexpr size_t PT = 96, PT2 = 192, GTB = 576;      // bytes of an affine G1 / G2 point and of a GT element of the ABI
+constexpr size_t GTB = 576;               // bytes of a GT element of the ABI
 constexpr size_t CW = (size_t)DGPU_G2_PREPARED_WORDS;   // u64 words of one prepared G2 point
 
 // kind 15.  coeffs: 2 K + 2 blocks in the order H, V_0, V_1[K], V_2[K]
@@ -51,8 +51,9 @@ void release(SaverDk *d) {
     delete d;
 }
 bool dk_ok(const HandleRef &h) { return h.ok && h.h.kind == 15; }
-// pairing rows per chunk (dgpu_set_many_chunk_rows of the development surface cuts it) -> ciphertexts per chunk when each takes `per` of them
-size_t chunk_rows(size_t n, size_t limit, size_t per) {
+// pairing rows per chunk (dgpu_set_many_chunk_rows of the development surface REPLACES the limit, unlike pair_check.hip.h chunk_rows, where it cuts the
+// row count) -> ciphertexts per chunk when each takes `per` of them
+size_t ct_chunk_rows(size_t n, size_t limit, size_t per) {
     const int forced = gs.many_chunk.load();
     const size_t lim = forced > 0 ? (size_t)forced : limit;
     return std::min(n, std::max<size_t>(1, lim / per));
@@ -183,7 +184,7 @@ int32_t dec_pipeline(uint64_t handle, const DecCall &c) {
     CtxScope on_owner(h.h.ctx);
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    const size_t chunk = chunk_rows(n, saverk::SAVER_PAIR_ROWS, K), chunk0 = verify ? chunk_rows(n, saverk::SAVER_PAIR_ROWS, 1) : 0, big = std::max(chunk, chunk0);
+    const size_t chunk = ct_chunk_rows(n, saverk::SAVER_PAIR_ROWS, K), chunk0 = verify ? ct_chunk_rows(n, saverk::SAVER_PAIR_ROWS, 1) : 0, big = std::max(chunk, chunk0);
     int32_t rc;
     // q[0]: the GLV split of -rho, q[1]: the c_0, q[2]: the second sides (-rho c_0 | -nu) and their identity flags, q[3]: the c_ij column-major,
     // q[5]: chunks | miss bytes | status, q[6]: the verdicts of the V_0 column (verify)
@@ -291,7 +292,7 @@ int32_t commitment_each(const uint64_t *all_pc, size_t K, const uint64_t *ct, si
     const size_t nc = K + 2, rw = nc * 12;
     SLOT_ACQUIRE(LK, sl);
     HIPCHK(hipSetDevice(cur().device));
-    const size_t chunk = chunk_rows(n, saverk::SAVER_COMMIT_PAIRS, nc);
+    const size_t chunk = ct_chunk_rows(n, saverk::SAVER_COMMIT_PAIRS, nc);
     int32_t rc;
     auto ws = [&](Slot &o) -> int32_t {
         int32_t e;
@@ -356,17 +357,15 @@ int32_t commitments_batch(const uint64_t *all_pc, size_t K, const uint64_t *ct, 
     std::vector<HPoint> P(nc, HPoint::identity());
     DrainUnlessDone guard(sl);
     uint32_t *d_w = sl.q[9].as<uint32_t>(), *d_rec = sl.q[10].as<uint32_t>();
-    uint64_t jac[18];
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t rows = std::min(chunk, n - r0);
         const uint8_t *raw = sl.q[3].as<uint8_t>();
         HIPCHK(hipMemcpyAsync(sl.q[3].p, ct + r0 * nc * 12, rows * nc * PT, hipMemcpyHostToDevice, s));
         if ((rc = upload_scalars(sl, r_powers + 4 * r0, rows, mont, d_w))) return rc;
         for (size_t k = 0; k < nc; k++) {
-            { StageTimer st(sl, "msm.prep_bases"); msm::launch_prep_bases_raw<G1>(s, raw + k * PT, nc * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows, d_rec); }
+            { StageTimer st(sl, "msm.prep_bases"); prep_g1(s, raw + k * PT, nc * PT, rows, d_rec); }
             HIPCHK(hipGetLastError());
-            if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_w, rows, jac))) return rc;
-            add_jac(P[k], jac);
+            if ((rc = msm_add(sl, d_rec, d_w, rows, P[k]))) return rc;
         }
         if (gs.prof) prof_flush(sl);
     }

@@ -10,7 +10,7 @@
 //           device  (status, detail) of the proof: its first failure in the reference's order                                        k_smc_verdict
 //   merged  (each with random_i) as each, but the proof's pairings become ONE: the weights random_i^d, two more segments of S l terms over the staged A'
 //           and -Abar in the SAME segment launch, their sums as the pairing's two sides               k_smc_merge_weights, k_smc_merged_sides, launch_check
-//   batch   device  the own scalars as above; the coefficients of g1, g, h, the weights over the own points, +-rho^slice             k_smc_own, k_smc_col_sums, k_smc_col_finish
+//   batch   device  the own scalars as above; the coefficients of g1, g, h, the weights over the own points, +-rho^slice             k_smc_own, k_smc_col_sums, k_col_finish
 //           device  one MSM over the chunk's C and D points, one over its 3 S l n digit points, one each over the two pairing sides; ONE over g1, g, h; the
 //                   host adds the chunks' points
 //           device  e(sum t A', pk) e(-sum t Abar, g2) against one                                                                   pair_check.hip.h merged_pair_verdict
@@ -26,8 +26,6 @@ using namespace mlk;
 
 namespace {
 
-constexpr size_t PT = 96;                 // bytes of an affine G1 point of the ABI
-
 // what the two calls share: the statement and the proofs' inputs
 struct Proofs {
     const uint64_t *g1, *ck_g, *ck_h, *pk_pc, *g2_pc; int32_t sides; size_t l; const uint64_t *weights, *side_consts;
@@ -42,12 +40,6 @@ bool bad_proofs(const Proofs &p) {
     if (p.l > (size_t)smck::SMC_MAX_L || p.n >= (1ull << 31)) return true;
     if (!p.g1 || !p.ck_g || !p.ck_h || !p.pk_pc || !p.g2_pc || !p.side_consts || !p.commitments || !p.side_points || !p.side_resp || !p.challenge) return true;
     return p.l > 0 && (!p.weights || !p.digit_points || !p.digit_resp);
-}
-// proofs per chunk: the largest count with rows * per <= limit, at least one (dgpu_set_many_chunk_rows of the development surface cuts it further)
-size_t chunk_rows(size_t n, size_t limit, size_t per) {
-    const int forced = gs.many_chunk.load();
-    const size_t cap = std::max<size_t>(1, limit / per);
-    return std::min(n, forced > 0 ? std::min((size_t)forced, cap) : cap);
 }
 // q[0]: the challenges, q[1]: the sides' responses, q[2]: the digits' responses, q[3]: the statement, q[4]: [C | D] (the scratch of the merged verdict afterwards),
 // q[5]: the digits' points, q[6]: the own scalars
@@ -210,7 +202,6 @@ int32_t verify_batch(const Proofs &p, const uint64_t *random, int32_t *ok) {
     uint32_t *d_wside = sl.q[14].as<uint32_t>(), *d_wdig = d_wside + nside * 8;
     uint32_t *d_rec = sl.q[10].as<uint32_t>(), *d_reca = sl.q[11].as<uint32_t>(), *d_recb = d_reca + ndig * G1::AFF_STRIDE, *d_recs = sl.q[13].as<uint32_t>(), *d_recside = sl.q[15].as<uint32_t>();
     HPoint Gsum = HPoint::identity(), P1 = HPoint::identity(), P2 = HPoint::identity();
-    uint64_t jac[18];
     if ((rc = statement_up(sl, p))) return rc;
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t rows = std::min(chunk, n - r0);
@@ -218,34 +209,26 @@ int32_t verify_batch(const Proofs &p, const uint64_t *random, int32_t *ok) {
         if ((rc = proofs_up(sl, p, r0, rows, dev))) return rc;
         const uint8_t *raw = sl.q[5].as<uint8_t>();
         { StageTimer st(sl, "msm.prep_bases");
-          msm::launch_prep_bases_raw<G1>(s, sl.q[4].as<uint8_t>(), PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, rows * (1 + S), d_recside);
+          prep_g1(s, sl.q[4].p, PT, rows * (1 + S), d_recside);
           if (D) {
-              msm::launch_prep_bases_raw<G1>(s, raw, PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, 3 * D * rows, d_rec);
-              msm::launch_prep_bases_raw<G1>(s, raw, 3 * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, D * rows, d_reca);
-              msm::launch_prep_bases_raw<G1>(s, raw + PT, 3 * PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, D * rows, d_recb);
+              prep_g1(s, raw, PT, 3 * D * rows, d_rec);
+              prep_g1(s, raw, 3 * PT, D * rows, d_reca);
+              prep_g1(s, raw + PT, 3 * PT, D * rows, d_recb);
           } }
         { StageTimer st(sl, "smc.own"); smck::launch_smc_own(s, dev, rows, d_own); }
         { StageTimer st(sl, "smc.columns");
           smck::launch_smc_columns(s, d_own, (const uint32_t *)random, p.sides, (int)p.l, p.mont ? 1 : 0, rows, r0, r0 == 0, sl.q[7].as<uint32_t>(), d_run, d_wside, d_wdig, d_tp, d_tn, d_c); }
         HIPCHK(hipGetLastError());
-        if ((rc = msm_device<G1, hostf::Fq>(sl, d_recside, d_wside, rows * (1 + S), jac))) return rc;
-        add_jac(Gsum, jac);
+        if ((rc = msm_add(sl, d_recside, d_wside, rows * (1 + S), Gsum))) return rc;
         if (D) {
-            if ((rc = msm_device<G1, hostf::Fq>(sl, d_rec, d_wdig, 3 * D * rows, jac))) return rc;
-            add_jac(Gsum, jac);
-            if ((rc = msm_device<G1, hostf::Fq>(sl, d_reca, d_tp, D * rows, jac))) return rc;
-            add_jac(P1, jac);
-            if ((rc = msm_device<G1, hostf::Fq>(sl, d_recb, d_tn, D * rows, jac))) return rc;
-            add_jac(P2, jac);
+            if ((rc = msm_add(sl, d_rec, d_wdig, 3 * D * rows, Gsum))) return rc;
+            if ((rc = msm_add(sl, d_reca, d_tp, D * rows, P1))) return rc;
+            if ((rc = msm_add(sl, d_recb, d_tn, D * rows, P2))) return rc;
         }
         if (gs.prof) prof_flush(sl);
     }
     // the shared points' terms: ONE small MSM over g1, g, h with the finished coefficients
-    HIPCHK(hipMemcpyAsync(sl.q[12].p, shared, 3 * PT, hipMemcpyHostToDevice, s));
-    { StageTimer st(sl, "msm.prep_bases"); msm::launch_prep_bases_raw<G1>(s, sl.q[12].as<uint8_t>(), PT, 0, PT / 2, msm::NO_INF_OFF, nullptr, 3, d_recs); }
-    HIPCHK(hipGetLastError());
-    if ((rc = msm_device<G1, hostf::Fq>(sl, d_recs, d_c, 3, jac))) return rc;
-    add_jac(Gsum, jac);
+    if ((rc = shared_points_add(sl, shared, 3, sl.q[12], d_recs, d_c, Gsum))) return rc;
     if (!Gsum.inf || !D) { HIPCHK(hipStreamSynchronize(s)); guard.done = true; *ok = Gsum.inf ? 1 : 0; return DGPU_OK; }      // the G1 equation fails: the pairing cannot mend it (l = 0: there is none)
     if ((rc = merged_pair_verdict(sl, P1, P2, p.pk_pc, p.g2_pc, sl.q[4], ok))) return rc;
     guard.done = true;

@@ -1,6 +1,6 @@
 // crypto_amd/csrc/k_acc_pok.hip — translation unit of the kernels of accumulator proofs in bulk (acc_pok_kernels.hip.h).
 #include "acc_pok_kernels.hip.h"
-#include "bbs_launch.hip.h"
+#include "col_launch.hip.h"
 #include "acc_pok_launch.hip.h"
 namespace accpk {
 static_assert(KIND_MEMBERSHIP == MEMBERSHIP && KIND_NON_MEMBERSHIP == NON_MEMBERSHIP, "one numbering of the proof kinds");
@@ -19,13 +19,14 @@ void launch_acc_pok_stage(hipStream_t s, const uint32_t *points, const uint32_t 
 void launch_acc_pok_verdict(hipStream_t s, const uint8_t *seg_inf, const uint8_t *pairing, const uint8_t *skip, int kind, size_t rows, uint8_t *status) {
     hipLaunchKernelGGL(k_acc_pok_verdict, dim3(blocks_for(rows)), dim3(256), 0, s, seg_inf, pairing, skip, kind, rows, status);
 }
-size_t acc_pok_part_words(size_t rows, int kind) { return bbsk::bbs_col_part_words(rows, (size_t)shape_of(kind).shared); }
+size_t acc_pok_part_words(size_t rows, int kind) { return colk::col_part_words(rows, (size_t)shape_of(kind).shared); }
 void launch_acc_pok_columns(hipStream_t s, const ProofDev &in, const uint32_t rho_words[8], size_t rows, size_t i0, bool first, uint32_t *part, uint32_t *run_sums, uint32_t *wts,
                             uint32_t *tp, uint32_t *tn, uint32_t *c_words) {
-    bbsk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
-    const size_t n = (size_t)shape_of(in.kind).shared, nb = bbsk::bbs_col_blocks(rows);
-    if (in.kind == MEMBERSHIP) hipLaunchKernelGGL(k_acc_pok_col_sums<MEMBERSHIP>, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, bbsk::BBS_COL_RUN, part, wts, tp, tn);
-    else hipLaunchKernelGGL(k_acc_pok_col_sums<NON_MEMBERSHIP>, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, bbsk::BBS_COL_RUN, part, wts, tp, tn);
-    hipLaunchKernelGGL(k_acc_pok_col_finish, dim3(1), dim3(64), 0, s, (const uint32_t *)part, nb, n, first ? 1 : 0, in.kind == MEMBERSHIP ? 0u : 2u, run_sums, c_words);
+    colk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
+    const size_t n = (size_t)shape_of(in.kind).shared, nb = colk::col_blocks(rows);
+    if (in.kind == MEMBERSHIP) hipLaunchKernelGGL(k_acc_pok_col_sums<MEMBERSHIP>, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, colk::COL_RUN, part, wts, tp, tn);
+    else hipLaunchKernelGGL(k_acc_pok_col_sums<NON_MEMBERSHIP>, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, colk::COL_RUN, part, wts, tp, tn);
+    // the P of a non-membership proof (column 1) enters its check as -s_d P
+    colk::launch_col_finish(s, part, nb, n, first, in.kind == MEMBERSHIP ? 0 : 1, in.kind == MEMBERSHIP ? 0 : 2, run_sums, c_words);
 }
 }  // namespace accpk

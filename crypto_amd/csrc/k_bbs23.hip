@@ -1,6 +1,6 @@
 // crypto_amd/csrc/k_bbs23.hip — translation unit of the kernels of BBS (2023) proofs of knowledge in bulk (bbs23_kernels.hip.h).
 #include "bbs23_kernels.hip.h"
-#include "bbs_launch.hip.h"
+#include "col_launch.hip.h"
 #include "bbs23_launch.hip.h"
 namespace bbs23k {
 static_assert(KIND_CDL == CDL && KIND_IETF == IETF, "one numbering of the proof kinds");
@@ -25,10 +25,10 @@ void launch_bbs23_verdict(hipStream_t s, const uint32_t *seg, const uint8_t *seg
 }
 void launch_bbs23_columns(hipStream_t s, const ProofDev &in, const uint32_t rho_words[8], size_t rows, size_t i0, bool first, uint32_t *part, uint32_t *run_sums, uint32_t *wts,
                           uint32_t *tp, uint32_t *tn, uint32_t *c_words) {
-    bbsk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
-    const size_t n = in.L + 1, nb = bbsk::bbs_col_blocks(rows);
-    if (in.kind == CDL) hipLaunchKernelGGL(k_bbs23_col_sums<CDL>, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, bbsk::BBS_COL_RUN, part, wts, tp, tn);
-    else hipLaunchKernelGGL(k_bbs23_col_sums<IETF>, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, bbsk::BBS_COL_RUN, part, wts, tp, tn);
-    hipLaunchKernelGGL(k_bbs23_col_finish, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const uint32_t *)part, nb, n, first ? 1 : 0, run_sums, c_words);
+    colk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
+    const size_t n = in.L + 1, nb = colk::col_blocks(rows);
+    if (in.kind == CDL) hipLaunchKernelGGL(k_bbs23_col_sums<CDL>, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, colk::COL_RUN, part, wts, tp, tn);
+    else hipLaunchKernelGGL(k_bbs23_col_sums<IETF>, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, colk::COL_RUN, part, wts, tp, tn);
+    colk::launch_col_finish(s, part, nb, n, first, 0, 0, run_sums, c_words);
 }
 }  // namespace bbs23k

@@ -1,6 +1,6 @@
 // crypto_amd/csrc/k_bbs_pok.hip — translation unit of the kernels of BBS+ proofs of knowledge in bulk (bbs_pok_kernels.hip.h).
 #include "bbs_pok_kernels.hip.h"
-#include "bbs_launch.hip.h"
+#include "col_launch.hip.h"
 #include "bbs_pok_launch.hip.h"
 namespace bbspk {
 static inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
@@ -20,9 +20,9 @@ void launch_pok_verdict(hipStream_t s, const uint32_t *seg, const uint8_t *seg_i
 }
 void launch_pok_columns(hipStream_t s, const PokDev &in, const uint32_t rho_words[8], size_t rows, size_t i0, bool first, uint32_t *part, uint32_t *run_sums, uint32_t *w5,
                         uint32_t *tp, uint32_t *tn, uint32_t *c_words) {
-    bbsk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
-    const size_t n = in.L + 2, nb = bbsk::bbs_col_blocks(rows);
-    hipLaunchKernelGGL(k_bbs_pok_col_sums, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, bbsk::BBS_COL_RUN, part, w5, tp, tn);
-    hipLaunchKernelGGL(k_bbs_pok_col_finish, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const uint32_t *)part, nb, n, first ? 1 : 0, run_sums, c_words);
+    colk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
+    const size_t n = in.L + 2, nb = colk::col_blocks(rows);
+    hipLaunchKernelGGL(k_bbs_pok_col_sums, dim3((unsigned)n, (unsigned)nb), dim3(256), 0, s, dev_in(in), w, rows, i0, colk::COL_RUN, part, w5, tp, tn);
+    colk::launch_col_finish(s, part, nb, n, first, 0, 0, run_sums, c_words);
 }
 }  // namespace bbspk

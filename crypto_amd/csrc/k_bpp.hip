@@ -1,6 +1,6 @@
 // crypto_amd/csrc/k_bpp.hip — translation unit of the kernels of Bulletproofs++ range proofs in bulk (bpp_kernels.hip.h).
 #include "bpp_kernels.hip.h"
-#include "bbs_launch.hip.h"
+#include "col_launch.hip.h"
 #include "bpp_launch.hip.h"
 namespace bppk {
 static inline unsigned blocks_for(size_t n, unsigned per = 256) { return (unsigned)((n + per - 1) / per); }
@@ -26,13 +26,13 @@ void launch_bpp_stage(hipStream_t s, const ProofDev &in, const uint32_t *values,
 void launch_bpp_verdict(hipStream_t s, const uint8_t *seg_inf, const uint8_t *bad, size_t rows, uint8_t *status) {
     hipLaunchKernelGGL(k_bpp_verdict, dim3(blocks_for(rows)), dim3(256), 0, s, seg_inf, bad, rows, status);
 }
-size_t bpp_part_words(size_t rows, size_t shared) { return bbsk::bbs_col_part_words(rows, shared); }
+size_t bpp_part_words(size_t rows, size_t shared) { return colk::col_part_words(rows, shared); }
 void launch_bpp_columns(hipStream_t s, const ProofDev &in, const uint32_t *rows_sc, const uint32_t *own, const uint32_t rho_words[8], size_t rows, size_t i0, bool first, uint32_t *part,
                         uint32_t *run_sums, uint32_t *wts, uint32_t *c_words) {
     const Shape sh = shape_of(in);
-    bbsk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
-    const size_t nb = bbsk::bbs_col_blocks(rows), cols = (size_t)(SHARED0 + sh.NG);
-    hipLaunchKernelGGL(k_bpp_col_sums, dim3((unsigned)cols, (unsigned)nb), dim3(256), 0, s, sh, rows_sc, own, w, in.mont != 0, rows, i0, bbsk::BBS_COL_RUN, part, wts);
-    hipLaunchKernelGGL(k_bpp_col_finish, dim3(blocks_for(cols, 64)), dim3(64), 0, s, (const uint32_t *)part, nb, cols, first ? 1 : 0, run_sums, c_words);
+    colk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
+    const size_t nb = colk::col_blocks(rows), cols = (size_t)(SHARED0 + sh.NG);
+    hipLaunchKernelGGL(k_bpp_col_sums, dim3((unsigned)cols, (unsigned)nb), dim3(256), 0, s, sh, rows_sc, own, w, in.mont != 0, rows, i0, colk::COL_RUN, part, wts);
+    colk::launch_col_finish(s, part, nb, cols, first, 0, 0, run_sums, c_words);
 }
 }  // namespace bppk

@@ -11,7 +11,7 @@ void launch_ps_pok_rows(hipStream_t s, const PokDev &in, size_t rows, uint32_t *
     hipLaunchKernelGGL(k_ps_pok_rows, dim3(blocks_for(2 * rows * (in.L + 2))), dim3(256), 0, s, k, rows, out_rows);
 }
 void launch_ps_col_scalars(hipStream_t s, const uint32_t *msgs, const uint32_t rho_words[8], int mont, size_t rows, size_t L, size_t i0, size_t cstride, uint32_t *cols) {
-    bbsk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
+    colk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
     const size_t nb = (rows + 256 * PS_COL_RUN - 1) / (256 * PS_COL_RUN);
     hipLaunchKernelGGL(k_ps_col_scalars, dim3((unsigned)(L + 2), (unsigned)nb), dim3(256), 0, s, msgs, w, mont, rows, L, i0, PS_COL_RUN, cstride, cols);
 }

@@ -1,6 +1,6 @@
 // crypto_amd/csrc/k_smc.hip — translation unit of the kernels of range proofs over weak-BB signatures in bulk (smc_kernels.hip.h).
 #include "smc_kernels.hip.h"
-#include "bbs_launch.hip.h"
+#include "col_launch.hip.h"
 #include "smc_launch.hip.h"
 namespace smck {
 static_assert(SMC_MAX_L == MAX_L && SMC_STMT_CONSTS == (size_t)STMT_CONSTS, "one shape of the statement");
@@ -25,13 +25,13 @@ void launch_smc_merge_weights(hipStream_t s, const uint32_t *random, int sides, 
 void launch_smc_merged_sides(hipStream_t s, const uint32_t *sums, const uint8_t *inf, size_t rows, uint32_t *pa, uint32_t *pb, uint8_t *skip) {
     hipLaunchKernelGGL(k_smc_merged_sides, dim3(blocks_for(2 * rows)), dim3(256), 0, s, sums, inf, rows, pa, pb, skip);
 }
-size_t smc_part_words(size_t rows, int sides, int l) { return bbsk::bbs_col_part_words(rows * eq_count(sides, l), 3); }
+size_t smc_part_words(size_t rows, int sides, int l) { return colk::col_part_words(rows * eq_count(sides, l), 3); }
 void launch_smc_columns(hipStream_t s, const uint32_t *own, const uint32_t rho_words[8], int sides, int l, int mont, size_t rows, size_t i0, bool first, uint32_t *part,
                         uint32_t *run_sums, uint32_t *w_side, uint32_t *w_digit, uint32_t *tp, uint32_t *tn, uint32_t *c_words) {
-    bbsk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
-    const size_t nb = bbsk::bbs_col_blocks(rows * eq_count(sides, l));
-    hipLaunchKernelGGL(k_smc_col_sums, dim3(3, (unsigned)nb), dim3(256), 0, s, own, w, sides, l, mont != 0, rows, i0 * eq_count(sides, l), i0 * digit_count(sides, l), bbsk::BBS_COL_RUN,
+    colk::RhoWords w; for (int k = 0; k < 8; k++) w.w[k] = rho_words[k];
+    const size_t nb = colk::col_blocks(rows * eq_count(sides, l));
+    hipLaunchKernelGGL(k_smc_col_sums, dim3(3, (unsigned)nb), dim3(256), 0, s, own, w, sides, l, mont != 0, rows, i0 * eq_count(sides, l), i0 * digit_count(sides, l), colk::COL_RUN,
                        part, w_side, w_digit, tp, tn);
-    hipLaunchKernelGGL(k_smc_col_finish, dim3(1), dim3(64), 0, s, (const uint32_t *)part, nb, first ? 1 : 0, run_sums, c_words);
+    colk::launch_col_finish(s, part, nb, 3, first, 0, 0, run_sums, c_words);
 }
 }  // namespace smck

@@ -1,7 +1,8 @@
 // crypto_amd/csrc/pair_check.hip.h — the two-pair pairing check with shared lines and the merged verdict of a batch, for the bulk verifiers that end in
 // e(P1_i, w) e(P2_i, g2) == 1 (dock_bbs.hip: BBS+ signatures and proofs of knowledge; dock_acc_pok.hip: accumulator proofs; dock_ps.hip; dock_saver.hip, which
-// takes the pairing VALUES of its slices and a product of K + 2 pairs per slice from the same tail).  Host code of a driver unit: it is
-// included after msm_many.hip.h and lives in the unit's anonymous namespace, as it did while dock_bbs.hip was its only user.
+// takes the pairing VALUES of its slices and a product of K + 2 pairs per slice from the same tail); and, in front, the small parts every bulk driver shares
+// (dock_smc.hip and dock_bpp.hip too): PT / PT2, chunk_rows, row_layout, prep_g1, and beside add_jac: msm_add, params_msm, shared_points_add.  Host code of a
+// driver unit: it is included after msm_many.hip.h and lives in the unit's anonymous namespace, as it did while dock_bbs.hip was its only user.
 #pragma once
 #include "msm_many.hip.h"
 #include "pairing_launch.hip.h"
@@ -10,6 +11,31 @@ using namespace dock;
 using namespace mlk;
 
 namespace {
+
+// ---- the small parts the bulk drivers share (a unit uses those it needs: chunk_rows serves dock_smc.hip and dock_bpp.hip, params_msm dock_bbs.hip and
+// dock_bpp.hip, shared_points_add dock_acc_pok.hip and dock_smc.hip, PT2 dock_ps.hip and dock_saver.hip) --------------------------------------------------------------
+constexpr size_t PT = 96, PT2 = 192;      // bytes of an affine G1 / G2 point of the ABI
+// rows per chunk: the largest count with rows * per <= limit, at least one (dgpu_set_many_chunk_rows of the development surface cuts it further)
+size_t chunk_rows(size_t n, size_t limit, size_t per) {
+    const int forced = gs.many_chunk.load();
+    const size_t cap = std::max<size_t>(1, limit / per);
+    return std::min(n, forced > 0 ? std::min((size_t)forced, cap) : cap);
+}
+// the segments of every row of a chunk — `own` terms a row, in one segment (first = 0) or in two, of `first` and own - first terms: the layout depends on the
+// counts alone
+void row_layout(size_t rows, size_t own, size_t first, SegLayout &lay) {
+    const size_t segs = first ? 2 : 1;
+    std::vector<uint64_t> ends(segs * rows);
+    for (size_t i = 0; i < rows; i++) {
+        if (first) ends[2 * i] = own * i + first;
+        ends[segs * i + segs - 1] = own * (i + 1);
+    }
+    seg_layout(ends.data(), 0, ends.size(), lay);
+}
+// the prepared records of n affine G1 points of the ABI on the device, `stride` bytes apart, none marked as the identity
+void prep_g1(hipStream_t s, const void *raw, size_t stride, size_t n, uint32_t *out) {
+    msm::launch_prep_bases_raw<G1>(s, (const uint8_t *)raw, stride, 0, PT / 2, msm::NO_INF_OFF, nullptr, n, out);
+}
 
 bool zero_words(const uint64_t *w, int k) { uint64_t o = 0; for (int i = 0; i < k; i++) o |= w[i]; return o == 0; }
 // -P on affine Montgomery words (y -> p - y; the identity, zero words, stays)
@@ -93,6 +119,29 @@ void add_jac(HPoint &acc, const uint64_t *jac) {
     const hostf::Fq zz = z * z;
     HPoint p; p.x = x; p.y = y; p.zz = zz; p.zzz = zz * z; p.inf = false;
     acc.add_in_place(p);
+}
+// acc += sum_k scalars_k rec_k: one MSM of n terms over prepared records on the device (sub: msm_device's), waited for
+int32_t msm_add(Slot &sl, const uint32_t *rec, const uint32_t *scalars, size_t n, HPoint &acc, const SmallSub *sub = nullptr) {
+    uint64_t jac[18];
+    int32_t rc;
+    if ((rc = msm_device<G1, hostf::Fq>(sl, rec, scalars, n, jac, sub))) return rc;
+    add_jac(acc, jac);
+    return DGPU_OK;
+}
+// acc += sum_k c_k H_k: ONE MSM of nn terms over a resident base set (handle `params`), the scalars at d_c
+int32_t params_msm(Slot &sl, uint64_t params, const Handle &h, const uint32_t *d_c, size_t nn, HPoint &acc) {
+    SmallSub sub;
+    const bool have = small_sub_for<G1>(sl, params, h, 0, nn, sub, true);
+    return msm_add(sl, (const uint32_t *)h.p, d_c, nn, acc, have ? &sub : nullptr);
+}
+// the close of a batch's G1 equation: the nsh <= 3 shared points (host words) onto the device at `raw`, their prepared records at d_recs, and
+// acc += sum_k c_k shared_k with the finished coefficients d_c — ONE small MSM
+int32_t shared_points_add(Slot &sl, const uint64_t *shared, size_t nsh, Buf &raw, uint32_t *d_recs, const uint32_t *d_c, HPoint &acc) {
+    hipStream_t s = sl.stream;
+    HIPCHK(hipMemcpyAsync(raw.p, shared, nsh * PT, hipMemcpyHostToDevice, s));
+    { StageTimer st(sl, "msm.prep_bases"); prep_g1(s, raw.p, PT, nsh, d_recs); }
+    HIPCHK(hipGetLastError());
+    return msm_add(sl, d_recs, d_c, nsh, acc);
 }
 // *ok = [e(P1, w) e(P2, g2) == 1] for the two merged points of a batch (an identity member is skipped); scratch: 2 PT + 64 bytes of the slot
 int32_t merged_pair_verdict(Slot &sl, const HPoint &P1, const HPoint &P2, const uint64_t *pk_pc, const uint64_t *g2_pc, Buf &scratch, int32_t *ok) {

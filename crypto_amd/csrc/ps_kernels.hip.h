@@ -11,9 +11,9 @@
 //   proof       two rows of L + 2 entries per proof over the whole key: S_i = (0, hidden ? z_ij : 0 .., z_r,i) and
 //               R_i = (1, revealed ? m_ij : 0 .., 0)                                                                              k_ps_pok_rows
 //               the Schnorr comparison, the identity flags and the pairing byte into a status                                     k_ps_verdict
-// Blocks are 256 independent lanes; scalars move as two 16-byte words (bbs_routines.hip.h ld_words / st_words).  The per-lane routines are FRD functions over
+// Blocks are 256 independent lanes; scalars move as two 16-byte words (col_sums.hip.h ld_words / st_words).  The per-lane routines are FRD functions over
 // load / store functors: the same text runs on the host under -DFP29_CHECK, where every product asserts its operand contract
-// (tests/native/ps_dev_host_shim.cpp).  Operand classes as in bbs_routines.hip.h: "product" (limbs < 2^29, value < 2 r), "lazy sum" (one carry pass after every
+// (tests/native/ps_dev_host_shim.cpp).  Operand classes as in col_sums.hip.h: "product" (limbs < 2^29, value < 2 r), "lazy sum" (one carry pass after every
 // addition of a product: limbs <= 2^29 + 3 below the top limb, value < 2 r per term).
 //
 // Bounds.  u_i's inner sum is x plus L products, a lazy sum of L + 1 terms: value < 2 (L + 1) r, the top limb < (L + 1) / 32 + 1.  It enters
@@ -26,8 +26,8 @@
 
 namespace psk {
 using namespace fr29;
-using bbsk::neg_product;
-using bbsk::pow_start;
+using colk::neg_product;
+using colk::pow_start;
 
 constexpr int G2W = 48;           // u32 words of an affine G2 point of the ABI
 
@@ -84,8 +84,8 @@ FRD uint8_t status_of(bool schnorr_ok, bool sigma_1_inf, bool sigma_2_inf, bool 
 
 #if defined(__HIPCC__)
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------------------
-using bbsk::ld_words;
-using bbsk::st_words;
+using colk::ld_words;
+using colk::st_words;
 // One lane per row: out[16 i ..] = r_i, out[16 i + 8 ..] = u_i as canonical words (below r), the order (sigma_1_i, sigma_2_i) leaves the fixed-base kernel in.
 // sk: (1 + L) x 8 words (x, y_1 .. y_L), r: rows x 8 words, msgs: rows x L x 8 words packed, all in the caller's form (mont)
 __global__ void __launch_bounds__(256) k_ps_sign_rows(const uint32_t *__restrict__ sk, const uint32_t *__restrict__ r, const uint32_t *__restrict__ msgs, int mont, size_t rows, size_t L,
@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(256) k_ps_pok_rows(PokIn in, size_t rows, uint
 // grid (L + 2, blocks): lane t of block (k, b) writes the `run` rows from (b * 256 + t) * run on of column k, with a start power of its own:
 // cols[(k * cstride + i) * 8 ..] = the column's scalar of row i of the chunk (col_scalars), canonical words.  msgs: rows x L x 8 words packed; i0: the chunk's
 // first row in the batch
-__global__ void __launch_bounds__(256) k_ps_col_scalars(const uint32_t *__restrict__ msgs, bbsk::RhoWords rho_words, int mont, size_t rows, size_t L, size_t i0, size_t run,
+__global__ void __launch_bounds__(256) k_ps_col_scalars(const uint32_t *__restrict__ msgs, colk::RhoWords rho_words, int mont, size_t rows, size_t L, size_t i0, size_t run,
                                                         size_t cstride, uint32_t *__restrict__ cols) {
     const size_t k = blockIdx.x, lo = ((size_t)blockIdx.y * 256 + threadIdx.x) * run;
     if (lo >= rows) return;

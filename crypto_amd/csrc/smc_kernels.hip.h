@@ -10,26 +10,24 @@
 // and per digit the pairing e(A'_d, pk) e(-Abar_d, g2) = 1.  The scalar field has to
 //   write the own scalars where the segmented small MSM reads them, one lane per equation                                k_smc_own
 //   one verdict: equation e = i M + m of the batch weighs rho^e, pairing slice i S l + d weighs rho^(i S l + d): the coefficients of the shared points g1, g, h
-//   and the weights over the proofs' own points                                                                          k_smc_col_sums, k_smc_col_finish
+//   and the weights over the proofs' own points                                                                          k_smc_col_sums, k_col_finish
 // and two kernels move words only: k_smc_stage lays the points out for the segment MSM and the pairing (-Abar by a flip of y), k_smc_verdict folds a proof's
 // flags into (status, detail).  The per-lane routines are FRD functions over load / store functors, as acc_pok_kernels.hip.h's are: the same text runs on the
-// host under -DFP29_CHECK (tests/native/smc_dev_host_shim.cpp).  Operand classes as in bbs_routines.hip.h: "product" (limbs < 2^29, value < 2 r), "lazy sum"
+// host under -DFP29_CHECK (tests/native/smc_dev_host_shim.cpp).  Operand classes as in col_sums.hip.h: "product" (limbs < 2^29, value < 2 r), "lazy sum"
 // (one carry pass after every addition of a product).
 //
 // Bounds.  The inner product of a side adds b_s c and l <= 64 products w_j z2_sj, a carry pass after each: 65 terms, limbs <= 2^29 + 1, value
-// < 130 r — a first operand of fr_mul (limbs < 2^31, value x 2 r far below 2^34 r^2), which reduces it to a product.  A lane's run of BBS_COL_RUN = 16
+// < 130 r — a first operand of fr_mul (limbs < 2^31, value x 2 r far below 2^34 r^2), which reduces it to a product.  A lane's run of COL_RUN = 16
 // equations adds at most ONE product per equation to its sum: value < 32 r.  The fixed tree of a block of 256 adds sums of equal depth: after its eight levels
 // a slot holds at most 256 x 16 products, value < 2^13 r.  The second pass adds products, one per block, with a carry pass each.  A weight is a product of two
 // products; the C of a CCS proof takes the sum of two, carried once (value < 4 r) and reduced by a product with one.
 #pragma once
-#include "bbs_routines.hip.h"
+#include "col_sums.hip.h"
 
 namespace smck {
 using namespace fr29;
-using bbsk::neg_product;
-using bbsk::pow_start;
-using bbsk::tree_step;
-using bbsk::col_finish;
+using colk::neg_product;
+using colk::pow_start;
 
 constexpr int FQW = 12;           // u32 words of a base-field element
 constexpr int MAX_L = 64, MAX_SIDES = 2;
@@ -164,8 +162,8 @@ FRD void merge_weight(Fr &t, const Fr &random, unsigned d) { pow_start(t, random
 
 #if defined(__HIPCC__)
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------------------
-using bbsk::ld_words;
-using bbsk::st_words;
+using colk::ld_words;
+using colk::st_words;
 // what the kernels below load: chal: rows x 8 words, zr: rows x S x 8, z: rows x S l x 2 x 8, stmt: (6 + l) x 8 (in the caller's form, as the proofs are)
 struct ProofIn {
     const uint32_t *__restrict__ chal, *__restrict__ zr, *__restrict__ z, *__restrict__ stmt; int sides, l; bool mont;
@@ -250,47 +248,20 @@ __global__ void __launch_bounds__(256) k_smc_merged_sides(const uint32_t *__rest
 // grid (3, blocks): block (k, b) sums column k over the equations [b * 256 * run, ..) of the chunk's rows * M (a lane's own start powers, a fixed tree in LDS,
 // part[(k * gridDim.y + b) * NL ..] in the internal form).  Column 0 also writes the weights as canonical words: w_side[8 i ..] over C, w_side[8 (rows + i S + s) ..]
 // over D, w_digit[8 (3 slice + q) ..] over A', Abar, T, tp / tn[8 slice ..] = +- rho^(p0 + slice).  own: k_smc_own's output
-__global__ void __launch_bounds__(256) k_smc_col_sums(const uint32_t *__restrict__ own, bbsk::RhoWords rho_words, int sides, int l, bool mont, size_t rows, size_t e0, size_t p0, size_t run,
+__global__ void __launch_bounds__(256) k_smc_col_sums(const uint32_t *__restrict__ own, colk::RhoWords rho_words, int sides, int l, bool mont, size_t rows, size_t e0, size_t p0, size_t run,
                                                       uint32_t *__restrict__ part, uint32_t *__restrict__ w_side, uint32_t *__restrict__ w_digit, uint32_t *__restrict__ tp,
                                                       uint32_t *__restrict__ tn) {
-    __shared__ uint32_t sh[NL][256];
-    const unsigned t = threadIdx.x;
-    const size_t neq = rows * eq_count(sides, l), lo = ((size_t)blockIdx.y * 256 + t) * run, cnt = lo >= neq ? 0 : (neq - lo < run ? neq - lo : run);
     const int k = (int)blockIdx.x;
-    Fr rho, sum;
+    Fr rho;
     fr_from_words(rho, rho_words.w, mont);
-    fr_zero(sum);
-    if (cnt)
+    colk::col_block_sum((size_t)k, rows * eq_count(sides, l), run, part, [&](size_t lo, size_t cnt, Fr &sum) {
         col_run(sides, l, rho, e0, p0, lo, cnt, k, k == 0, [&](size_t e, unsigned q, Fr &x) { ld_words(x, own, e * EQ_TERMS + q, false); },
                 [&](int kind, size_t idx, const Fr &x) {
                     if (kind == 0) st_words(w_side, idx, x); else if (kind == 1) st_words(w_side, rows + idx, x); else if (kind == 2) st_words(w_digit, idx, x);
                     else st_words(kind == 3 ? tp : tn, idx, x);
                 },
                 sum);
-#pragma unroll
-    for (int q = 0; q < NL; q++) sh[q][t] = sum.l[q];
-    __syncthreads();
-    for (unsigned d = 128; d >= 1; d >>= 1) {
-        if (t < d)
-            tree_step(t, d, [&](unsigned q, Fr &x) { for (int j = 0; j < NL; j++) x.l[j] = sh[j][q]; }, [&](unsigned q, const Fr &x) { for (int j = 0; j < NL; j++) sh[j][q] = x.l[j]; });
-        __syncthreads();
-    }
-    if (t == 0) {
-        Fr one, r0; fr_one(one);
-        for (int j = 0; j < NL; j++) r0.l[j] = sh[j][0];
-        fr_mul(r0, r0, one);
-        for (int j = 0; j < NL; j++) part[((size_t)k * gridDim.y + blockIdx.y) * NL + j] = r0.l[j];
-    }
-}
-// one lane per column: the chunk's block sums onto the running sum in block order; out_words[8 k ..] = the coefficient of shared point k so far
-__global__ void __launch_bounds__(64) k_smc_col_finish(const uint32_t *__restrict__ part, size_t nparts, int first, uint32_t *__restrict__ run_sums, uint32_t *__restrict__ out_words) {
-    const size_t k = threadIdx.x;
-    if (k >= 3) return;
-    Fr start, c;
-    if (first) fr_zero(start); else for (int j = 0; j < NL; j++) start.l[j] = run_sums[k * NL + j];
-    col_finish(start, nparts, [&](size_t b, Fr &v) { for (int j = 0; j < NL; j++) v.l[j] = part[(k * nparts + b) * NL + j]; }, c);
-    for (int j = 0; j < NL; j++) run_sums[k * NL + j] = c.l[j];
-    st_words(out_words, k, c);
+    });
 }
 #endif
 

@@ -11,7 +11,7 @@ namespace smck {
 //                     same bound falls on the rows S segments
 //   SMC_BATCH_EQS     equations per chunk of dgpu_smc_range_proofs_verify_batch_g1, at most (at least one proof): the variable-base MSM over the chunk's
 //                     own points (fewer than 3 per equation) runs per chunk
-// A lane of k_smc_col_sums takes bbs_launch.hip.h's BBS_COL_RUN equations.
+// A lane of k_smc_col_sums takes col_launch.hip.h's COL_RUN equations.
 constexpr size_t SMC_EACH_SLICES = 4096, SMC_BATCH_EQS = 16384;
 constexpr int SMC_MAX_L = 64;
 constexpr size_t SMC_STMT_CONSTS = 6;       // the statement on the device: (a, b, e) of side 0, of side 1 (zeros for one side), then w_0 .. w_(l-1); 8 words each

@@ -659,7 +659,7 @@ int32_t dgpu_accumulator_membership_witnesses_g1(const uint64_t *members /* m*4 
  * Non-membership, u_i = rho^(2i) on check 4, v_i = rho^(2i+1) on check 3, t_i = rho^i on the pairing: *ok = 1 iff
  *     (sum u_i s_r_i) V - (sum u_i s_d_i) P + (sum v_i s_d_i) Q + sum_i [ -u_i s_y_i C'_i - u_i c_i Cbar_i - v_i c_i J_i - u_i T1_i - v_i T2_i ] = O
  *     e(sum t_i C'_i, pk) e(-sum t_i Cbar_i, P~) = 1
- * — the one (three) shared-point coefficients and every weight on the device (k_acc_pok_col_sums, k_acc_pok_col_finish: two passes, no atomics), one variable-base
+ * — the one (three) shared-point coefficients and every weight on the device (k_acc_pok_col_sums, k_col_finish: two passes, no atomics), one variable-base
  * MSM over the chunk's 3 n (5 n) own points and one each over the two pairing sides, ONE small MSM over the shared points, one two-pair Miller loop and final
  * exponentiation.  n = 0 gives *ok = 1.  For a random rho a batch with a failing proof passes with probability at most 2n / r per equation; rho = 1 adds the rows
  * up unweighted, so errors that cancel between rows pass, as they would in the reference with that scalar.
@@ -716,7 +716,7 @@ int32_t dgpu_accumulator_non_membership_proofs_verify_batch_g1(const uint64_t ac
  * (utils/src/randomized_pairing_check.rs:96-158); row i has the weight rho^i, rho = random (rho = 0 mod r: DGPU_E_BADARG, decided on the host).  The pairs that
  * share w and g2 are merged before the pairing:
  *     P1 = sum rho^i A_i,   P2 = sum rho^i e_i A_i - sum_k c_k H_k,   c = sum_i rho^i (1, s_i, m_i1 .. m_iL),   H = the L + 2 points of params
- * — the column sums c_k, the weights and rho^i e_i on the device (k_bbs_col_sums, k_bbs_col_finish: two passes, no atomics), two variable-base MSMs of n terms
+ * — the column sums c_k, the weights and rho^i e_i on the device (k_bbs_col_sums, k_col_finish: two passes, no atomics), two variable-base MSMs of n terms
  * over the A_i, ONE MSM of L + 2 terms over params, one two-pair Miller loop and one final exponentiation.  *ok = 1 iff the result is one and no A_i is the
  * identity; n = 0 gives *ok = 1.  rho = 1 adds the rows up unweighted: errors that cancel between rows pass, as they would in the reference with that scalar.
  *
@@ -765,7 +765,7 @@ int32_t dgpu_bbs_plus_verify_batch_g1(uint64_t params, size_t L, const uint64_t 
  *     sum_k C_k H_k + sum_i [ u_i z1_i A'_i - u_i c_i Abar_i + (u_i c_i + v_i z3_i) d_i - u_i T1_i - v_i T2_i ] = O,
  *         C_0 = sum v_i c_i,  C_1 = sum (u_i z2_i + v_i z4_i),  C_(j+1) = sum v_i y_ij,  H = the L + 2 points of params
  *     e(sum t_i A'_i, w) e(-sum t_i Abar_i, g2) = 1
- * — the C_k and every weight on the device (k_bbs_pok_col_sums, k_bbs_pok_col_finish: two passes, no atomics), one variable-base MSM over the chunk's 5 n own
+ * — the C_k and every weight on the device (k_bbs_pok_col_sums, k_col_finish: two passes, no atomics), one variable-base MSM over the chunk's 5 n own
  * points and one each over the A' and the Abar, ONE MSM over params, one two-pair Miller loop and final exponentiation.  n = 0 gives *ok = 1.  For a random
  * rho a batch with a failing proof passes with probability at most 3n / r per equation (the G1 equation is a polynomial of degree < 2n in rho, the pairing's of
  * degree < n); rho = 1 adds the rows up unweighted, so errors that cancel between rows pass, as they would in the reference with that scalar.
@@ -823,7 +823,7 @@ int32_t dgpu_bbs_plus_pok_verify_batch_g1(uint64_t params, size_t L, const uint6
  *   IETF, u_i = t_i = rho^i:
  *     sum_k C_k H_k + sum_i u_i [ z_a Abar + z_b Bbar - T ]_i = O,                              C_0 = sum u_i c_i,  C_j = sum u_i y_ij
  *   both: e(sum t_i Abar_i, w) e(-sum t_i Bbar_i, g2) = 1
- * (k_bbs23_col_sums, k_bbs23_col_finish: two passes, no atomics; one MSM over the chunk's own points, one each over the Abar and the Bbar, ONE over params; a
+ * (k_bbs23_col_sums, k_col_finish: two passes, no atomics; one MSM over the chunk's own points, one each over the Abar and the Bbar, ONE over params; a
  * G1 sum that is not the identity refuses before the pairing).  For a random rho a batch with a failing proof passes with probability at most 2n / r (CDL) or
  * n / r (IETF) per equation; rho = r - 1 makes every CDL u_i one and rho = 1 every IETF u_i: errors that cancel between rows then pass.
  *

@@ -1,11 +1,12 @@
 // tests/native/acc_pok_dev_host_shim.cpp — the __host__ __device__ routines of accumulator proofs in bulk (crypto_amd/csrc/acc_pok_kernels.hip.h: own_scalar,
-// col_run, col_term, row_weights, with bbs_routines.hip.h's tree_step, col_finish and neg_product; and the word routines fq_neg_words, stage_src, mem_status,
+// col_run, col_term, row_weights, with col_sums.hip.h's tree_step, col_finish and neg_product; and the word routines fq_neg_words, stage_src, mem_status,
 // nm_status) compiled for the host with -DFP29_CHECK (every product asserts its operand contract), driven the way k_acc_pok_own, k_acc_pok_stage,
-// k_acc_pok_col_sums / k_acc_pok_col_finish and dock_acc_pok.hip's chunks drive them.  Built and loaded by tests/test_acc_pok_device_code_on_host.py.
+// k_acc_pok_col_sums / k_col_finish and dock_acc_pok.hip's chunks drive them (col_frame_host.hpp).  Built and loaded by tests/test_acc_pok_device_code_on_host.py.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 #include "../../crypto_amd/csrc/acc_pok_kernels.hip.h"
+#include "col_frame_host.hpp"
 using namespace fr29;
 
 namespace {
@@ -45,55 +46,31 @@ void shim_acc_pok_stage(const uint32_t *points, const uint32_t *shared, int kind
         memcpy(dst, w, 96);
     }
 }
-// k_acc_pok_col_sums + k_acc_pok_col_finish over the rows in chunks of `chunk` (dock_acc_pok.hip verify_batch): blocks of 256 lanes with `run` rows each, the
-// block's fixed tree, the second pass onto the running sums.  c: shared x 8 canonical words after the last chunk; wts: total x pts x 8; tp, tn: total x 8
+// k_acc_pok_col_sums + k_col_finish over the rows in chunks of `chunk` (dock_acc_pok.hip verify_batch).  c: shared x 8 canonical words after the last chunk;
+// wts: total x pts x 8; tp, tn: total x 8
 void shim_acc_pok_columns(const uint32_t *chal, const uint32_t *resp, const uint32_t *rho_words, int kind, int mont, size_t total, size_t chunk, size_t run, uint32_t *c,
                           uint32_t *wts, uint32_t *tp, uint32_t *tn) {
     const accpk::Shape shp = accpk::shape_of(kind);
     const size_t n = (size_t)shp.shared, np = (size_t)shp.pts, nr = (size_t)shp.resp;
-    const unsigned neg_mask = kind == accpk::MEMBERSHIP ? 0u : 2u;
-    std::vector<Fr> run_sums(n);
     Fr rho; fr_from_words(rho, rho_words, mont != 0);
-    for (size_t i0 = 0; i0 < total; i0 += chunk) {
-        const size_t rows = total - i0 < chunk ? total - i0 : chunk, nb = (rows + 256 * run - 1) / (256 * run);
+    // the P of a non-membership proof (column 1) leaves negated
+    col_frame_walk(total, chunk, 1, run, n, kind == accpk::MEMBERSHIP ? 0 : 1, kind == accpk::MEMBERSHIP ? 0 : 2, [&](size_t i0, size_t, size_t k, size_t lo, size_t cnt, Fr &sum) {
         // the chunk's arrays start at its first row, as the driver uploads them
         const In in{chal + 8 * i0, resp + 8 * nr * i0, kind, mont};
         uint32_t *cw = wts + 8 * np * i0, *ctp = tp + 8 * i0, *ctn = tn + 8 * i0;
-        std::vector<Fr> part(n * nb);
-        for (size_t k = 0; k < n; k++)
-            for (size_t b = 0; b < nb; b++) {
-                Fr sh[256];
-                for (unsigned t = 0; t < 256; t++) {
-                    const size_t lo = (b * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-                    fr_zero(sh[t]);
-                    if (!cnt) continue;
-                    accpk::col_run(kind, rho, i0 + lo, cnt, k == 0,
-                                   [&](size_t j, const Fr &u, const Fr &v, Fr &s) {
-                                       accpk::col_term(s, kind, lo + j, k, u, v, [&](size_t r, unsigned q, Fr &x) { x = in.load(in.resp + 8 * (nr * r + q)); });
-                                   },
-                                   [&](size_t j, const Fr &u, const Fr &v, const Fr &tw) {
-                                       const size_t i = lo + j;
-                                       accpk::row_weights(kind, i, u, v, tw, FUNCTORS(in), [&](unsigned q, const Fr &x) {
-                                           if (q < (unsigned)np) fr_to_words(cw + 8 * (i * np + q), x, false);
-                                           else fr_to_words((q == (unsigned)np ? ctp : ctn) + 8 * i, x, false);
-                                       });
-                                   },
-                                   sh[t]);
-                }
-                for (unsigned d = 128; d >= 1; d >>= 1)
-                    for (unsigned t = 0; t < d; t++) bbsk::tree_step(t, d, [&](unsigned q, Fr &x) { x = sh[q]; }, [&](unsigned q, const Fr &x) { sh[q] = x; });
-                Fr one; fr_one(one);
-                fr_mul(part[k * nb + b], sh[0], one);
-            }
-        for (size_t k = 0; k < n; k++) {
-            Fr start, ck, o;
-            if (i0 == 0) fr_zero(start); else start = run_sums[k];
-            bbsk::col_finish(start, nb, [&](size_t b, Fr &v) { v = part[k * nb + b]; }, ck);
-            run_sums[k] = ck;
-            if ((neg_mask >> k) & 1) bbsk::neg_product(o, ck); else o = ck;
-            fr_to_words(c + 8 * k, o, false);
-        }
-    }
+        accpk::col_run(kind, rho, i0 + lo, cnt, k == 0,
+                       [&](size_t j, const Fr &u, const Fr &v, Fr &s) {
+                           accpk::col_term(s, kind, lo + j, k, u, v, [&](size_t r, unsigned q, Fr &x) { x = in.load(in.resp + 8 * (nr * r + q)); });
+                       },
+                       [&](size_t j, const Fr &u, const Fr &v, const Fr &tw) {
+                           const size_t i = lo + j;
+                           accpk::row_weights(kind, i, u, v, tw, FUNCTORS(in), [&](unsigned q, const Fr &x) {
+                               if (q < (unsigned)np) fr_to_words(cw + 8 * (i * np + q), x, false);
+                               else fr_to_words((q == (unsigned)np ? ctp : ctn) + 8 * i, x, false);
+                           });
+                       },
+                       sum);
+    }, c);
 }
 // the word routines of k_acc_pok_stage and k_acc_pok_verdict
 void shim_acc_fq_neg(const uint32_t *y, uint32_t *out) { accpk::fq_neg_words(out, y); }

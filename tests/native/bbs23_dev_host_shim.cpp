@@ -1,12 +1,13 @@
 // tests/native/bbs23_dev_host_shim.cpp — the __host__ __device__ routines of BBS (2023) in bulk compiled for the host with -DFP29_CHECK (every product asserts
-// its operand contract): bbs_routines.hip.h's row_value_fixed with ONE fixed column, driven the way k_bbs_rows and k_bbs_col_sums / k_bbs_col_finish drive it for
+// its operand contract): bbs_routines.hip.h's row_value_fixed with ONE fixed column, driven the way k_bbs_rows and k_bbs_col_sums / k_col_finish drive it for
 // the signature calls, and crypto_amd/csrc/bbs23_kernels.hip.h (row_entry, own_scalar, col_run, col_term, row_weights, stage_src, fq_neg_words, g1_is_negation,
-// status_of), driven the way k_bbs23_rows, k_bbs23_own, k_bbs23_stage, k_bbs23_verdict, k_bbs23_col_sums / k_bbs23_col_finish and dock_bbs.hip's chunks drive
-// them.  Built and loaded by tests/test_bbs23_device_code_on_host.py.
+// status_of), driven the way k_bbs23_rows, k_bbs23_own, k_bbs23_stage, k_bbs23_verdict, k_bbs23_col_sums / k_col_finish and dock_bbs.hip's chunks drive
+// them (col_frame_host.hpp).  Built and loaded by tests/test_bbs23_device_code_on_host.py.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 #include "../../crypto_amd/csrc/bbs23_kernels.hip.h"
+#include "col_frame_host.hpp"
 using namespace fr29;
 
 namespace {
@@ -15,14 +16,6 @@ struct In {
     const uint32_t *chal, *resp, *vals; const uint8_t *rev; size_t L; int kind, mont;
     size_t nresp() const { return (size_t)bbs23k::shape_of(kind).resp; }
 };
-// the block's fixed tree and its reduction to a product, as every column-sum kernel ends
-Fr block_sum(Fr *sh) {
-    for (unsigned d = 128; d >= 1; d >>= 1)
-        for (unsigned t = 0; t < d; t++) bbsk::tree_step(t, d, [&](unsigned q, Fr &x) { x = sh[q]; }, [&](unsigned q, const Fr &x) { sh[q] = x; });
-    Fr one, o; fr_one(one);
-    fr_mul(o, sh[0], one);
-    return o;
-}
 }  // namespace
 #define CHAL(in) [&](size_t r, Fr &x) { x = load(in.chal + 8 * r, in.mont); }
 #define RESP(in) [&](size_t r, unsigned q, Fr &x) { x = load(in.resp + 8 * (in.nresp() * r + q), in.mont); }
@@ -40,46 +33,25 @@ void shim_bbs23_sig_rows(const uint32_t *msgs, const uint32_t *t, int mont, size
         fr_to_words(out + 8 * lane, o, false);
     }
 }
-// k_bbs_col_sums + k_bbs_col_finish with fixed = 1 over the rows in chunks of `chunk` (dock_bbs.hip verify_batch): c: n x 8 canonical words of -c_k after the last
+// k_bbs_col_sums + k_col_finish with fixed = 1 over the rows in chunks of `chunk` (dock_bbs.hip verify_batch): c: n x 8 canonical words of -c_k after the last
 // chunk; wts, we: total x 8
 void shim_bbs23_sig_columns(const uint32_t *e, const uint32_t *msgs, const uint32_t *rho_words, int mont, size_t total, size_t n, size_t chunk, size_t run, uint32_t *c,
                             uint32_t *wts, uint32_t *we) {
-    std::vector<Fr> run_sums(n);
     const Fr rho = load(rho_words, mont);
-    for (size_t i0 = 0; i0 < total; i0 += chunk) {
-        const size_t rows = total - i0 < chunk ? total - i0 : chunk, nb = (rows + 256 * run - 1) / (256 * run);
+    col_frame_walk(total, chunk, 1, run, n, 0, n, [&](size_t i0, size_t, size_t k, size_t lo, size_t cnt, Fr &sum) {
         const uint32_t *ce = e + 8 * i0, *cm = msgs + 8 * (n - 1) * i0;
-        std::vector<Fr> part(n * nb);
-        for (size_t k = 0; k < n; k++)
-            for (size_t b = 0; b < nb; b++) {
-                Fr sh[256];
-                for (unsigned t = 0; t < 256; t++) {
-                    const size_t lo = (b * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-                    fr_zero(sh[t]);
-                    if (!cnt) continue;
-                    bbsk::col_run(rho, i0 + lo, cnt,
-                                  [&](size_t j, Fr &v) {
-                                      bbsk::row_value_fixed(v, lo + j, k, 1, [&](size_t, Fr &) { __builtin_trap(); },
-                                                            [&](size_t r, size_t q, Fr &x) { x = load(cm + 8 * (r * (n - 1) + q), mont); });
-                                  },
-                                  [&](size_t j, const Fr &w) {
-                                      if (k != 0) return;
-                                      Fr p; fr_mul(p, load(ce + 8 * (lo + j), mont), w);
-                                      fr_to_words(wts + 8 * (i0 + lo + j), w, false); fr_to_words(we + 8 * (i0 + lo + j), p, false);
-                                  },
-                                  sh[t]);
-                }
-                part[k * nb + b] = block_sum(sh);
-            }
-        for (size_t k = 0; k < n; k++) {
-            Fr start, ck, o;
-            if (i0 == 0) fr_zero(start); else start = run_sums[k];
-            bbsk::col_finish(start, nb, [&](size_t b, Fr &v) { v = part[k * nb + b]; }, ck);
-            run_sums[k] = ck;
-            bbsk::neg_product(o, ck);
-            fr_to_words(c + 8 * k, o, false);
-        }
-    }
+        colk::col_run(rho, i0 + lo, cnt,
+                      [&](size_t j, Fr &v) {
+                          bbsk::row_value_fixed(v, lo + j, k, 1, [&](size_t, Fr &) { __builtin_trap(); },
+                                                [&](size_t r, size_t q, Fr &x) { x = load(cm + 8 * (r * (n - 1) + q), mont); });
+                      },
+                      [&](size_t j, const Fr &w) {
+                          if (k != 0) return;
+                          Fr p; fr_mul(p, load(ce + 8 * (lo + j), mont), w);
+                          fr_to_words(wts + 8 * (i0 + lo + j), w, false); fr_to_words(we + 8 * (i0 + lo + j), p, false);
+                      },
+                      sum);
+    }, c);
 }
 // k_bbs23_rows and k_bbs23_own: rows x (L + 1) and rows x own canonical words-of-8
 void shim_bbs23_rows(const uint32_t *chal, const uint32_t *resp, const uint32_t *vals, const uint8_t *rev, size_t L, int kind, int mont, size_t rows, uint32_t *out_rows,
@@ -112,48 +84,28 @@ void shim_bbs23_stage(const uint32_t *points, int kind, size_t rows, uint32_t *o
         memcpy(dst, w, 96);
     }
 }
-// k_bbs23_col_sums + k_bbs23_col_finish over the rows in chunks of `chunk` (dock_bbs.hip pok23_verify_batch).  c: (L + 1) x 8 canonical words after the last
+// k_bbs23_col_sums + k_col_finish over the rows in chunks of `chunk` (dock_bbs.hip pok23_verify_batch).  c: (L + 1) x 8 canonical words after the last
 // chunk; wts: total x pts x 8; tp, tn: total x 8
 void shim_bbs23_columns(const uint32_t *chal, const uint32_t *resp, const uint32_t *vals, const uint8_t *rev, size_t L, const uint32_t *rho_words, int kind, int mont, size_t total,
                         size_t chunk, size_t run, uint32_t *c, uint32_t *wts, uint32_t *tp, uint32_t *tn) {
     const bbs23k::Shape shp = bbs23k::shape_of(kind);
     const size_t n = L + 1, np = (size_t)shp.pts, nr = (size_t)shp.resp;
-    std::vector<Fr> run_sums(n);
     const Fr rho = load(rho_words, mont);
-    for (size_t i0 = 0; i0 < total; i0 += chunk) {
-        const size_t rows = total - i0 < chunk ? total - i0 : chunk, nb = (rows + 256 * run - 1) / (256 * run);
+    col_frame_walk(total, chunk, 1, run, n, 0, 0, [&](size_t i0, size_t, size_t k, size_t lo, size_t cnt, Fr &sum) {
         // the chunk's arrays start at its first row, as the driver uploads them
         const In in{chal + 8 * i0, resp + 8 * nr * i0, vals + 8 * L * i0, rev + L * i0, L, kind, mont};
         uint32_t *cw = wts + 8 * np * i0, *ctp = tp + 8 * i0, *ctn = tn + 8 * i0;
-        std::vector<Fr> part(n * nb);
-        for (size_t k = 0; k < n; k++)
-            for (size_t b = 0; b < nb; b++) {
-                Fr sh[256];
-                for (unsigned t = 0; t < 256; t++) {
-                    const size_t lo = (b * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-                    fr_zero(sh[t]);
-                    if (!cnt) continue;
-                    bbs23k::col_run(kind, rho, i0 + lo, cnt, k == 0,
-                                    [&](size_t j, const Fr &u, const Fr &v, Fr &s) { bbs23k::col_term(s, lo + j, k, kind == bbs23k::CDL ? v : u, CHAL(in), VALS(in)); },
-                                    [&](size_t j, const Fr &u, const Fr &v, const Fr &tw) {
-                                        const size_t i = lo + j;
-                                        bbs23k::row_weights(kind, i, u, v, tw, CHAL(in), RESP(in), [&](unsigned q, const Fr &x) {
-                                            if (q < (unsigned)np) fr_to_words(cw + 8 * (i * np + q), x, false);
-                                            else fr_to_words((q == (unsigned)np ? ctp : ctn) + 8 * i, x, false);
-                                        });
-                                    },
-                                    sh[t]);
-                }
-                part[k * nb + b] = block_sum(sh);
-            }
-        for (size_t k = 0; k < n; k++) {
-            Fr start, ck;
-            if (i0 == 0) fr_zero(start); else start = run_sums[k];
-            bbsk::col_finish(start, nb, [&](size_t b, Fr &v) { v = part[k * nb + b]; }, ck);
-            run_sums[k] = ck;
-            fr_to_words(c + 8 * k, ck, false);
-        }
-    }
+        bbs23k::col_run(kind, rho, i0 + lo, cnt, k == 0,
+                        [&](size_t j, const Fr &u, const Fr &v, Fr &s) { bbs23k::col_term(s, lo + j, k, kind == bbs23k::CDL ? v : u, CHAL(in), VALS(in)); },
+                        [&](size_t j, const Fr &u, const Fr &v, const Fr &tw) {
+                            const size_t i = lo + j;
+                            bbs23k::row_weights(kind, i, u, v, tw, CHAL(in), RESP(in), [&](unsigned q, const Fr &x) {
+                                if (q < (unsigned)np) fr_to_words(cw + 8 * (i * np + q), x, false);
+                                else fr_to_words((q == (unsigned)np ? ctp : ctn) + 8 * i, x, false);
+                            });
+                        },
+                        sum);
+    }, c);
 }
 // the word routines of k_bbs23_stage and k_bbs23_verdict
 void shim_bbs23_fq_neg(const uint32_t *y, uint32_t *out) { bbs23k::fq_neg_words(out, y); }

@@ -1,12 +1,13 @@
 // tests/native/bbs_pok_dev_host_shim.cpp — the __host__ __device__ routines of BBS+ proofs of knowledge in bulk (crypto_amd/csrc/bbs_pok_kernels.hip.h:
-// pok_value, pok_row_entry, pok_own_scalar, pok_col_run, pok_col_term, pok_weights, with bbs_routines.hip.h's tree_step, col_finish and neg_product; and the
+// pok_value, pok_row_entry, pok_own_scalar, pok_col_run, pok_col_term, pok_weights, with col_sums.hip.h's tree_step, col_finish and neg_product; and the
 // base-field word routines fq_neg_words, g1_is_negation, pok_status) compiled for the host with -DFP29_CHECK (every product asserts its operand contract), driven
-// the way k_bbs_pok_rows, k_bbs_pok_own, k_bbs_pok_col_sums / k_bbs_pok_col_finish and dock_bbs.hip's chunks drive them.  Built and loaded by
+// the way k_bbs_pok_rows, k_bbs_pok_own, k_bbs_pok_col_sums / k_col_finish and dock_bbs.hip's chunks drive them (col_frame_host.hpp).  Built and loaded by
 // tests/test_bbs_pok_device_code_on_host.py.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 #include "../../crypto_amd/csrc/bbs_pok_kernels.hip.h"
+#include "col_frame_host.hpp"
 using namespace fr29;
 
 namespace {
@@ -35,52 +36,29 @@ void shim_pok_rows(const uint32_t *chal, const uint32_t *fixed, const uint32_t *
         fr_to_words(own + 8 * lane, o, false);
     }
 }
-// k_bbs_pok_col_sums + k_bbs_pok_col_finish over the rows in chunks of `chunk` (dock_bbs.hip pok_verify_batch): blocks of 256 lanes with `run` rows each, the
-// block's fixed tree, the second pass onto the running sums.  c: (L + 2) x 8 canonical words of C_k after the last chunk; w5: total x 5 x 8; tp, tn: total x 8
+// k_bbs_pok_col_sums + k_col_finish over the rows in chunks of `chunk` (dock_bbs.hip pok_verify_batch).  c: (L + 2) x 8 canonical words of C_k after the last
+// chunk; w5: total x 5 x 8; tp, tn: total x 8
 void shim_pok_columns(const uint32_t *chal, const uint32_t *fixed, const uint32_t *vals, const uint8_t *rev, const uint32_t *rho_words, int mont, size_t total, size_t L,
                       size_t chunk, size_t run, uint32_t *c, uint32_t *w5, uint32_t *tp, uint32_t *tn) {
     const size_t n = L + 2;
-    std::vector<Fr> run_sums(n);
     Fr rho; fr_from_words(rho, rho_words, mont != 0);
-    for (size_t i0 = 0; i0 < total; i0 += chunk) {
-        const size_t rows = total - i0 < chunk ? total - i0 : chunk, nb = (rows + 256 * run - 1) / (256 * run);
+    col_frame_walk(total, chunk, 1, run, n, 0, 0, [&](size_t i0, size_t, size_t k, size_t lo, size_t cnt, Fr &sum) {
         // the chunk's arrays start at its first row, as the driver uploads them
         const In in{chal + 8 * i0, fixed + 32 * i0, vals + 8 * i0 * L, rev + i0 * L, L, mont};
         uint32_t *cw5 = w5 + 40 * i0, *ctp = tp + 8 * i0, *ctn = tn + 8 * i0;
-        std::vector<Fr> part(n * nb);
-        for (size_t k = 0; k < n; k++)
-            for (size_t b = 0; b < nb; b++) {
-                Fr sh[256];
-                for (unsigned t = 0; t < 256; t++) {
-                    const size_t lo = (b * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-                    fr_zero(sh[t]);
-                    if (!cnt) continue;
-                    bbspk::pok_col_run(rho, i0 + lo, cnt, k == 0,
-                                       [&](size_t j, const Fr &u, const Fr &v, Fr &s) { bbspk::pok_col_term(s, lo + j, k, u, v, FUNCTORS(in)); },
-                                       [&](size_t j, const Fr &u, const Fr &v, const Fr &tw) {
-                                           const size_t i = lo + j;
-                                           bbspk::pok_weights(i, u, v, tw, [&](size_t r, Fr &x) { x = in.load(in.chal + 8 * r); },
-                                                              [&](size_t r, unsigned q, Fr &x) { x = in.load(in.fixed + 8 * (4 * r + q)); },
-                                                              [&](unsigned q, const Fr &x) {
-                                                                  if (q < (unsigned)bbspk::POK_PTS) fr_to_words(cw5 + 8 * (i * bbspk::POK_PTS + q), x, false);
-                                                                  else fr_to_words((q == 5 ? ctp : ctn) + 8 * i, x, false);
-                                                              });
-                                       },
-                                       sh[t]);
-                }
-                for (unsigned d = 128; d >= 1; d >>= 1)
-                    for (unsigned t = 0; t < d; t++) bbsk::tree_step(t, d, [&](unsigned q, Fr &x) { x = sh[q]; }, [&](unsigned q, const Fr &x) { sh[q] = x; });
-                Fr one; fr_one(one);
-                fr_mul(part[k * nb + b], sh[0], one);
-            }
-        for (size_t k = 0; k < n; k++) {
-            Fr start, ck;
-            if (i0 == 0) fr_zero(start); else start = run_sums[k];
-            bbsk::col_finish(start, nb, [&](size_t b, Fr &v) { v = part[k * nb + b]; }, ck);
-            run_sums[k] = ck;
-            fr_to_words(c + 8 * k, ck, false);
-        }
-    }
+        bbspk::pok_col_run(rho, i0 + lo, cnt, k == 0,
+                           [&](size_t j, const Fr &u, const Fr &v, Fr &s) { bbspk::pok_col_term(s, lo + j, k, u, v, FUNCTORS(in)); },
+                           [&](size_t j, const Fr &u, const Fr &v, const Fr &tw) {
+                               const size_t i = lo + j;
+                               bbspk::pok_weights(i, u, v, tw, [&](size_t r, Fr &x) { x = in.load(in.chal + 8 * r); },
+                                                  [&](size_t r, unsigned q, Fr &x) { x = in.load(in.fixed + 8 * (4 * r + q)); },
+                                                  [&](unsigned q, const Fr &x) {
+                                                      if (q < (unsigned)bbspk::POK_PTS) fr_to_words(cw5 + 8 * (i * bbspk::POK_PTS + q), x, false);
+                                                      else fr_to_words((q == 5 ? ctp : ctn) + 8 * i, x, false);
+                                                  });
+                           },
+                           sum);
+    }, c);
 }
 // the base-field word routines of k_bbs_pok_stage and k_bbs_pok_verdict
 void shim_fq_neg(const uint32_t *y, uint32_t *out) { bbspk::fq_neg_words(out, y); }

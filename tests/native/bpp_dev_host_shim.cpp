@@ -1,11 +1,12 @@
 // tests/native/bpp_dev_host_shim.cpp — the __host__ __device__ routines of Bulletproofs++ range proofs in bulk (crypto_amd/csrc/bpp_kernels.hip.h: bpp_consts,
-// bpp_shared, batch_weight_index, shape_ok / make_shape, with bbs_routines.hip.h's col_run, tree_step, col_finish and neg_product) compiled for the host with
-// -DFP29_CHECK (every product asserts its operand contract), driven the way k_bpp_consts, k_bpp_shared, k_bpp_col_sums / k_bpp_col_finish and dock_bpp.hip's
-// chunks drive them.  Built and loaded by tests/test_bpp_device_code_on_host.py.
+// bpp_shared, batch_weight_index, shape_ok / make_shape, with col_sums.hip.h's col_run, tree_step, col_finish and neg_product) compiled for the host with
+// -DFP29_CHECK (every product asserts its operand contract), driven the way k_bpp_consts, k_bpp_shared, k_bpp_col_sums / k_col_finish and dock_bpp.hip's
+// chunks drive them (col_frame_host.hpp).  Built and loaded by tests/test_bpp_device_code_on_host.py.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 #include "../../crypto_amd/csrc/bpp_kernels.hip.h"
+#include "col_frame_host.hpp"
 using namespace fr29;
 
 namespace {
@@ -41,50 +42,28 @@ void shim_bpp_scalars(unsigned base, unsigned num_bits, unsigned m, const uint32
                       uint8_t *bad) {
     scalars(bppk::make_shape(base, num_bits, m), chal, l_n, mont, rows, own_stride, shared, own, bad);
 }
-// k_bpp_col_sums + k_bpp_col_finish over the proofs in chunks of `chunk` (dock_bpp.hip verify_batch): blocks of 256 lanes with `run` proofs each, the block's fixed
-// tree, the second pass onto the running sums.  shared / own: shim_bpp_scalars's with own_stride = own, of all `total` proofs.  c: (9 + NG) x 8 canonical words after
-// the last chunk; wts: total x own x 8, every chunk's part in the order [over values | over round points | over wnla points] of that chunk
+// k_bpp_col_sums + k_col_finish over the proofs in chunks of `chunk` (dock_bpp.hip verify_batch): a lane takes `run` proofs.  shared / own: shim_bpp_scalars's
+// with own_stride = own, of all `total` proofs.  c: (9 + NG) x 8 canonical words after the last chunk; wts: total x own x 8, every chunk's part in the order
+// [over values | over round points | over wnla points] of that chunk
 void shim_bpp_columns(unsigned base, unsigned num_bits, unsigned m, const uint32_t *shared, const uint32_t *own, const uint32_t *rho_words, int mont, size_t total, size_t chunk, size_t run,
                       uint32_t *c, uint32_t *wts) {
     const bppk::Shape s = bppk::make_shape(base, num_bits, m);
     const size_t n = (size_t)(bppk::SHARED0 + s.NG);
-    std::vector<Fr> run_sums(n);
     Fr rho; fr_from_words(rho, rho_words, mont != 0);
-    for (size_t i0 = 0; i0 < total; i0 += chunk) {
-        const size_t rows = total - i0 < chunk ? total - i0 : chunk, nb = (rows + 256 * run - 1) / (256 * run);
+    col_frame_walk(total, chunk, 1, run, n, 0, 0, [&](size_t i0, size_t rows, size_t k, size_t lo, size_t cnt, Fr &sum) {
         const uint32_t *csh = shared + 8 * n * i0, *cown = own + 8 * (size_t)s.own * i0;
         uint32_t *cw = wts + 8 * (size_t)s.own * i0;
-        for (size_t k = 0; k < n; k++) {
-            std::vector<Fr> part(nb);
-            for (size_t b = 0; b < nb; b++) {
-                Fr sh[256];
-                for (unsigned t = 0; t < 256; t++) {
-                    const size_t lo = (b * 256 + t) * run, cnt = lo >= rows ? 0 : (rows - lo < run ? rows - lo : run);
-                    fr_zero(sh[t]);
-                    if (!cnt) continue;
-                    bbsk::col_run(rho, i0 + lo, cnt, [&](size_t j, Fr &v) { fr_from_words(v, csh + 8 * ((lo + j) * n + k), false); },
-                                  [&](size_t j, const Fr &w) {
-                                      if (k != 0) return;
-                                      for (int q = 0; q < s.own; q++) {
-                                          Fr a, p;
-                                          fr_from_words(a, cown + 8 * ((lo + j) * (size_t)s.own + (size_t)q), false);
-                                          fr_mul(p, a, w);
-                                          fr_to_words(cw + 8 * bppk::batch_weight_index(s, rows, lo + j, (unsigned)q), p, false);
-                                      }
-                                  },
-                                  sh[t]);
-                }
-                for (unsigned d = 128; d >= 1; d >>= 1)
-                    for (unsigned t = 0; t < d; t++) bbsk::tree_step(t, d, [&](unsigned q, Fr &x) { x = sh[q]; }, [&](unsigned q, const Fr &x) { sh[q] = x; });
-                Fr one; fr_one(one);
-                fr_mul(part[b], sh[0], one);
-            }
-            Fr start, ck;
-            if (i0 == 0) fr_zero(start); else start = run_sums[k];
-            bbsk::col_finish(start, nb, [&](size_t b, Fr &v) { v = part[b]; }, ck);
-            run_sums[k] = ck;
-            fr_to_words(c + 8 * k, ck, false);
-        }
-    }
+        colk::col_run(rho, i0 + lo, cnt, [&](size_t j, Fr &v) { fr_from_words(v, csh + 8 * ((lo + j) * n + k), false); },
+                      [&](size_t j, const Fr &w) {
+                          if (k != 0) return;
+                          for (int q = 0; q < s.own; q++) {
+                              Fr a, p;
+                              fr_from_words(a, cown + 8 * ((lo + j) * (size_t)s.own + (size_t)q), false);
+                              fr_mul(p, a, w);
+                              fr_to_words(cw + 8 * bppk::batch_weight_index(s, rows, lo + j, (unsigned)q), p, false);
+                          }
+                      },
+                      sum);
+    }, c);
 }
 }

@@ -1,12 +1,13 @@
 // tests/native/smc_dev_host_shim.cpp — the __host__ __device__ routines of range proofs over weak-BB signatures in bulk (crypto_amd/csrc/smc_kernels.hip.h:
-// own_scalars, col_run, merge_weight, with bbs_routines.hip.h's tree_step, col_finish and neg_product; and the word routines fq_neg_words, stage_src,
+// own_scalars, col_run, merge_weight, with col_sums.hip.h's tree_step, col_finish and neg_product; and the word routines fq_neg_words, stage_src,
 // proof_verdict, ref_position) compiled for the host with -DFP29_CHECK (every product asserts its operand contract), driven the way k_smc_own, k_smc_stage,
-// k_smc_merge_weights, k_smc_verdict, k_smc_col_sums / k_smc_col_finish and dock_smc.hip's chunks drive them.  Built and loaded by
+// k_smc_merge_weights, k_smc_verdict, k_smc_col_sums / k_col_finish and dock_smc.hip's chunks drive them (col_frame_host.hpp).  Built and loaded by
 // tests/test_smc_device_code_on_host.py.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 #include "../../crypto_amd/csrc/smc_kernels.hip.h"
+#include "col_frame_host.hpp"
 using namespace fr29;
 
 namespace {
@@ -68,47 +69,24 @@ void shim_smc_merge_weights(const uint32_t *random, int sides, int l, int mont, 
         fr_to_words(tw + 8 * t, w, false); fr_to_words(tw + 8 * (slices + t), w, false);
     }
 }
-// k_smc_own + k_smc_col_sums + k_smc_col_finish over the proofs in chunks of `chunk` (dock_smc.hip verify_batch): blocks of 256 lanes with `run` equations each,
-// the block's fixed tree, the second pass onto the running sums.  own: total x M x 4 x 8 canonical words (shim_smc_own's); c: 3 x 8 canonical words after the last
-// chunk; w_c: total x 8, w_d: total x S x 8, w_digit: total x S l x 3 x 8, tp / tn: total x S l x 8
+// k_smc_own + k_smc_col_sums + k_col_finish over the proofs in chunks of `chunk` (dock_smc.hip verify_batch): a lane takes `run` equations.  own: total x M x 4
+// x 8 canonical words (shim_smc_own's); c: 3 x 8 canonical words after the last chunk; w_c: total x 8, w_d: total x S x 8, w_digit: total x S l x 3 x 8, tp /
+// tn: total x S l x 8
 void shim_smc_columns(const uint32_t *own, const uint32_t *rho_words, int sides, int l, int mont, size_t total, size_t chunk, size_t run, uint32_t *c, uint32_t *w_c, uint32_t *w_d,
                       uint32_t *w_digit, uint32_t *tp, uint32_t *tn) {
     const size_t M = smck::eq_count(sides, l), D = smck::digit_count(sides, l);
-    Fr run_sums[3];
     Fr rho; fr_from_words(rho, rho_words, mont != 0);
-    for (size_t i0 = 0; i0 < total; i0 += chunk) {
-        const size_t rows = total - i0 < chunk ? total - i0 : chunk, neq = rows * M, nb = (neq + 256 * run - 1) / (256 * run);
+    col_frame_walk(total, chunk, M, run, 3, 0, 0, [&](size_t i0, size_t, size_t k, size_t lo, size_t cnt, Fr &sum) {
         // the chunk's arrays start at its first proof, as the driver's do
         const uint32_t *cown = own + 8 * 4 * M * i0;
         uint32_t *cwc = w_c + 8 * i0, *cwd = w_d + 8 * sides * i0, *cwg = w_digit + 8 * 3 * D * i0, *ctp = tp + 8 * D * i0, *ctn = tn + 8 * D * i0;
-        std::vector<Fr> part(3 * nb);
-        for (int k = 0; k < 3; k++)
-            for (size_t b = 0; b < nb; b++) {
-                Fr sh[256];
-                for (unsigned t = 0; t < 256; t++) {
-                    const size_t lo = (b * 256 + t) * run, cnt = lo >= neq ? 0 : (neq - lo < run ? neq - lo : run);
-                    fr_zero(sh[t]);
-                    if (!cnt) continue;
-                    smck::col_run(sides, l, rho, i0 * M, i0 * D, lo, cnt, k, k == 0, [&](size_t e, unsigned q, Fr &x) { fr_from_words(x, cown + 8 * (e * 4 + q), false); },
-                                  [&](int kind, size_t idx, const Fr &x) {
-                                      uint32_t *dst = kind == 0 ? cwc : kind == 1 ? cwd : kind == 2 ? cwg : kind == 3 ? ctp : ctn;
-                                      fr_to_words(dst + 8 * idx, x, false);
-                                  },
-                                  sh[t]);
-                }
-                for (unsigned d = 128; d >= 1; d >>= 1)
-                    for (unsigned t = 0; t < d; t++) bbsk::tree_step(t, d, [&](unsigned q, Fr &x) { x = sh[q]; }, [&](unsigned q, const Fr &x) { sh[q] = x; });
-                Fr one; fr_one(one);
-                fr_mul(part[k * nb + b], sh[0], one);
-            }
-        for (int k = 0; k < 3; k++) {
-            Fr start, ck;
-            if (i0 == 0) fr_zero(start); else start = run_sums[k];
-            bbsk::col_finish(start, nb, [&](size_t b, Fr &v) { v = part[k * nb + b]; }, ck);
-            run_sums[k] = ck;
-            fr_to_words(c + 8 * k, ck, false);
-        }
-    }
+        smck::col_run(sides, l, rho, i0 * M, i0 * D, lo, cnt, (int)k, k == 0, [&](size_t e, unsigned q, Fr &x) { fr_from_words(x, cown + 8 * (e * 4 + q), false); },
+                      [&](int kind, size_t idx, const Fr &x) {
+                          uint32_t *dst = kind == 0 ? cwc : kind == 1 ? cwd : kind == 2 ? cwg : kind == 3 ? ctp : ctn;
+                          fr_to_words(dst + 8 * idx, x, false);
+                      },
+                      sum);
+    }, c);
 }
 // the word routines of k_smc_stage and k_smc_verdict
 void shim_smc_fq_neg(const uint32_t *y, uint32_t *out) { smck::fq_neg_words(out, y); }

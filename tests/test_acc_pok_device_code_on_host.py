@@ -1,6 +1,6 @@
 """CPU: the per-lane routines of accumulator proofs in bulk (crypto_amd/csrc/acc_pok_kernels.hip.h: own_scalar, col_run, col_term, row_weights, fq_neg_words,
 stage_src, mem_status, nm_status) compiled for the host with the FP29_CHECK operand asserts (tests/native/acc_pok_dev_host_shim.cpp) and driven as k_acc_pok_own,
-k_acc_pok_stage, k_acc_pok_col_sums, k_acc_pok_col_finish and the chunks of dock_acc_pok.hip drive them, against the big-integer model of tests/acc_pok_model.py:
+k_acc_pok_stage, k_acc_pok_col_sums, k_col_finish and the chunks of dock_acc_pok.hip drive them, against the big-integer model of tests/acc_pok_model.py:
 both proof kinds, both input forms, the values 0, 1, r - 1, r and 2^256 - 1, row counts on both sides of a lane's run (15, 16, 17), a wave (63, 64, 65), a block
 (4095, 4096, 4097) and a forced chunk, the batching scalars 1, 2 and r - 1, the y-flip, and the status routines on every flag combination.  (The model itself
 is checked against the oracle in tests/test_acc_pok_model.py.)  A green run shows the values are right and that no product leaves fr_mul's operand contract."""
@@ -27,7 +27,7 @@ p_ = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
 
 @pytest.fixture(scope="module")
 def shim():
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "bbs_routines.hip.h", "acc_pok_kernels.hip.h")]
+    deps = [SRC, os.path.join(HERE, "native", "col_frame_host.hpp")] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "col_sums.hip.h", "bbs_routines.hip.h", "acc_pok_kernels.hip.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-DFP29_CHECK", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", SO, SRC])
     L = C.CDLL(SO)
@@ -80,15 +80,15 @@ def arrays(raw, mont):
 
 
 def launcher_run():
-    hdr = open(os.path.join(CSRC, "bbs_launch.hip.h")).read()
-    return int(re.search(r"BBS_COL_RUN = (\d+)\b", hdr).group(1))
+    hdr = open(os.path.join(CSRC, "col_launch.hip.h")).read()
+    return int(re.search(r"\bCOL_RUN = (\d+)\b", hdr).group(1))
 
 
 def test_the_constants_are_the_launchers():
     assert launcher_run() == 16
     src = open(os.path.join(CSRC, "k_acc_pok.hip")).read()
-    assert "bbsk::bbs_col_blocks(rows)" in src and "bbsk::BBS_COL_RUN" in src and "dim3(256)" in src      # a block is 256 lanes of BBS_COL_RUN rows each: what the shim drives
-    assert "in.kind == MEMBERSHIP ? 0u : 2u" in src                                                       # the column that is negated when it is finished: P's
+    assert "colk::col_blocks(rows)" in src and "colk::COL_RUN" in src and "dim3(256)" in src      # a block is 256 lanes of COL_RUN rows each: what the shim drives
+    assert "in.kind == MEMBERSHIP ? 0 : 1, in.kind == MEMBERSHIP ? 0 : 2" in src                                                       # the column that is negated when it is finished: P's
     hdr = open(os.path.join(CSRC, "acc_pok_launch.hip.h")).read()
     assert "ACC_POK_EACH_CHUNK = 4096, ACC_POK_BATCH_CHUNK = 65536" in hdr
 
@@ -110,7 +110,7 @@ def test_own_scalars(shim, kind, mont):
 @pytest.mark.parametrize("rho", [1, 2, R - 1])
 @pytest.mark.parametrize("kind", [0, 1])
 def test_batch_columns_and_weights(shim, kind, rho, mont):
-    """k_acc_pok_col_sums / k_acc_pok_col_finish: the shared points' coefficients, the weights over the own points, rho^i and -rho^i for row counts on both sides
+    """k_acc_pok_col_sums / k_col_finish: the shared points' coefficients, the weights over the own points, rho^i and -rho^i for row counts on both sides
     of a lane's run (16), of a wave (64), of a block (256 x 16), in one chunk and in chunks that end inside a run, at a run's end and past a block"""
     run = launcher_run()
     assert 256 * run == 4096

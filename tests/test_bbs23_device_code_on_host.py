@@ -28,7 +28,7 @@ p_ = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
 
 @pytest.fixture(scope="module")
 def shim():
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "bbs_routines.hip.h", "bbs23_kernels.hip.h")]
+    deps = [SRC, os.path.join(HERE, "native", "col_frame_host.hpp")] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "col_sums.hip.h", "bbs_routines.hip.h", "bbs23_kernels.hip.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-DFP29_CHECK", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", SO, SRC])
     L = C.CDLL(SO)
@@ -97,14 +97,14 @@ def arrays(raw, mont):
 
 
 def launcher_run():
-    hdr = open(os.path.join(CSRC, "bbs_launch.hip.h")).read()
-    return int(re.search(r"BBS_COL_RUN = (\d+)\b", hdr).group(1))
+    hdr = open(os.path.join(CSRC, "col_launch.hip.h")).read()
+    return int(re.search(r"\bCOL_RUN = (\d+)\b", hdr).group(1))
 
 
 def test_the_constants_are_the_launchers():
     assert launcher_run() == 16
     src = open(os.path.join(CSRC, "k_bbs23.hip")).read()
-    assert "bbsk::bbs_col_blocks(rows)" in src and "bbsk::BBS_COL_RUN" in src and "dim3(256)" in src      # a block is 256 lanes of BBS_COL_RUN rows each: what the shim drives
+    assert "colk::col_blocks(rows)" in src and "colk::COL_RUN" in src and "dim3(256)" in src      # a block is 256 lanes of COL_RUN rows each: what the shim drives
     assert "n = in.L + 1" in src
     hdr = open(os.path.join(CSRC, "bbs23_launch.hip.h")).read()
     assert "BBS23_EACH_CHUNK = 4096, BBS23_BATCH_CHUNK = 65536" in hdr
@@ -136,7 +136,7 @@ def test_signature_rows_with_one_fixed_column(shim, mont):
 @pytest.mark.parametrize("mont", [0, 1])
 @pytest.mark.parametrize("rho", [1, 2, R - 1])
 def test_signature_columns_with_one_fixed_column(shim, rho, mont):
-    """k_bbs_col_sums / k_bbs_col_finish, fixed = 1: -c_k for the L + 1 columns, rho^i and rho^i e_i, in one chunk and in forced chunks"""
+    """k_bbs_col_sums / k_col_finish, fixed = 1: -c_k for the L + 1 columns, rho^i and rho^i e_i, in one chunk and in forced chunks"""
     run = launcher_run()
     shapes = ((1, 1, (1,)), (15, 1, (15, 7)), (16, 2, (16,)), (17, 30, (17, 16)), (63, 31, (63, 16)), (64, 32, (64, 17)), (65, 30, (65, 64)), (4095, 1, (4095,)),
               (4096, 1, (4096, 4095)), (4097, 1, (4097, 4096, 65)))
@@ -177,7 +177,7 @@ def test_rows_and_own_scalars(shim, kind, mont):
 @pytest.mark.parametrize("rho", [1, 2, R - 1])
 @pytest.mark.parametrize("kind", [CDL, IETF])
 def test_batch_columns_and_weights(shim, kind, rho, mont):
-    """k_bbs23_col_sums / k_bbs23_col_finish: C_k, the weights over the own points, rho^i and -rho^i for row counts on both sides of a lane's run (16), of a wave
+    """k_bbs23_col_sums / k_col_finish: C_k, the weights over the own points, rho^i and -rho^i for row counts on both sides of a lane's run (16), of a wave
     (64), of a block (256 x 16), in one chunk and in chunks that end inside a run, at a run's end and past a block"""
     run = launcher_run()
     assert 256 * run == 4096

@@ -1,5 +1,5 @@
 """CPU: the per-lane routines of BBS+ in bulk (crypto_amd/csrc/bbs_kernels.hip.h: row_value, row_entry, pow_start, col_run, tree_step, col_finish, neg_product)
-compiled for the host with the FP29_CHECK operand asserts (tests/native/bbs_dev_host_shim.cpp) and driven as k_bbs_rows, k_bbs_col_sums, k_bbs_col_finish and the
+compiled for the host with the FP29_CHECK operand asserts (tests/native/bbs_dev_host_shim.cpp) and driven as k_bbs_rows, k_bbs_col_sums, k_col_finish and the
 chunks of dock_bbs.hip drive them, against the big-integer model of tests/bbs_model.py: both input forms, the values 0, 1, r - 1, r and 2^256 - 1, rows of
 L + 2 = 3, 31, 32, 33 entries, row counts on both sides of a wave, a lane's run, a block and a chunk, the batching scalars 1, 2 and r - 1.  The host's batch
 inversion of x + e (acc_host_tables.hpp issue_inverses with its zero flags) against the same model, share by share.  The model itself is checked once against the
@@ -26,7 +26,7 @@ p_ = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
 
 @pytest.fixture(scope="module")
 def shim():
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "bbs_kernels.hip.h", "acc_host_tables.hpp", "host_field.hpp")]
+    deps = [SRC, os.path.join(HERE, "native", "col_frame_host.hpp")] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "col_sums.hip.h", "bbs_routines.hip.h", "bbs_kernels.hip.h", "acc_host_tables.hpp", "host_field.hpp")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-DFP29_CHECK", "-mbmi2", "-madx", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", SO, SRC])
     L = C.CDLL(SO)
@@ -56,14 +56,14 @@ def rand(rng, n):
 
 
 def launcher_run():
-    hdr = open(os.path.join(CSRC, "bbs_launch.hip.h")).read()
-    return int(re.search(r"BBS_COL_RUN = (\d+)\b", hdr).group(1))
+    hdr = open(os.path.join(CSRC, "col_launch.hip.h")).read()
+    return int(re.search(r"\bCOL_RUN = (\d+)\b", hdr).group(1))
 
 
 def test_the_constants_are_the_launchers():
     assert launcher_run() == 16
     src = open(os.path.join(CSRC, "k_bbs.hip")).read()
-    assert "256 * BBS_COL_RUN" in src and "dim3(256)" in src                      # a block is 256 lanes of BBS_COL_RUN rows each: what the shim drives
+    assert "colk::col_blocks(rows)" in src and "colk::COL_RUN" in src and "dim3(256)" in src and "256 * COL_RUN" in open(os.path.join(CSRC, "k_cols.hip")).read()      # a block is 256 lanes of COL_RUN rows each: what the shim drives
 
 
 def scenario(rows, L, seed, mont):
@@ -104,7 +104,7 @@ def test_rows(shim, n, mont):
 @pytest.mark.parametrize("mont", [0, 1])
 @pytest.mark.parametrize("rho", [1, 2, R - 1])
 def test_batch_columns(shim, rho, mont):
-    """k_bbs_col_sums / k_bbs_col_finish: -c_k, rho^i and rho^i e_i for row counts on both sides of a lane's run (16), of a wave (64), of a block (256 x 16), in
+    """k_bbs_col_sums / k_col_finish: -c_k, rho^i and rho^i e_i for row counts on both sides of a lane's run (16), of a wave (64), of a block (256 x 16), in
     one chunk and in chunks that end inside a run, at a run's end and past a block"""
     run = launcher_run()
     for rows, n, chunks in ((1, 3, (1,)), (2, 3, (2, 1)), (63, 31, (63, 16)), (64, 32, (64, 17)), (65, 33, (65, 64)), (257, 3, (257, 100)), (256 * run + 1, 3, (256 * run + 1, 256 * run))):

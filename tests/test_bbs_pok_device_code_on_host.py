@@ -1,6 +1,6 @@
 """CPU: the per-lane routines of BBS+ proofs of knowledge in bulk (crypto_amd/csrc/bbs_pok_kernels.hip.h: pok_value, pok_row_entry, pok_own_scalar, pok_col_run,
 pok_col_term, pok_weights, fq_neg_words, g1_is_negation, pok_status) compiled for the host with the FP29_CHECK operand asserts
-(tests/native/bbs_pok_dev_host_shim.cpp) and driven as k_bbs_pok_rows, k_bbs_pok_own, k_bbs_pok_col_sums, k_bbs_pok_col_finish and the chunks of dock_bbs.hip drive
+(tests/native/bbs_pok_dev_host_shim.cpp) and driven as k_bbs_pok_rows, k_bbs_pok_own, k_bbs_pok_col_sums, k_col_finish and the chunks of dock_bbs.hip drive
 them, against the big-integer model of tests/bbs_pok_model.py: both input forms, the values 0, 1, r - 1, r and 2^256 - 1, rows of L + 2 = 3, 31, 32, 33 entries, the
 masks all-hidden, all-revealed, only first, only last, alternating and differing per row, row counts on both sides of a lane's run, a wave, a block and a forced
 chunk, the batching scalars 1, 2 and r - 1.  (The model itself is checked against the oracle in tests/test_bbs_pok_model.py.)  A green run
@@ -28,7 +28,7 @@ p_ = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
 
 @pytest.fixture(scope="module")
 def shim():
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "bbs_routines.hip.h", "bbs_pok_kernels.hip.h")]
+    deps = [SRC, os.path.join(HERE, "native", "col_frame_host.hpp")] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "col_sums.hip.h", "bbs_routines.hip.h", "bbs_pok_kernels.hip.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-DFP29_CHECK", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", SO, SRC])
     L = C.CDLL(SO)
@@ -84,15 +84,15 @@ def arrays(raw, mont):
 
 
 def launcher_run():
-    hdr = open(os.path.join(CSRC, "bbs_launch.hip.h")).read()
-    return int(re.search(r"BBS_COL_RUN = (\d+)\b", hdr).group(1))
+    hdr = open(os.path.join(CSRC, "col_launch.hip.h")).read()
+    return int(re.search(r"\bCOL_RUN = (\d+)\b", hdr).group(1))
 
 
 def test_the_constants_are_the_launchers():
     assert launcher_run() == 16
     src = open(os.path.join(CSRC, "k_bbs_pok.hip")).read()
-    assert "bbsk::bbs_col_blocks(rows)" in src and "bbsk::BBS_COL_RUN" in src and "dim3(256)" in src      # a block is 256 lanes of BBS_COL_RUN rows each: what the shim drives
-    assert "256 * BBS_COL_RUN" in open(os.path.join(CSRC, "k_bbs.hip")).read()
+    assert "colk::col_blocks(rows)" in src and "colk::COL_RUN" in src and "dim3(256)" in src      # a block is 256 lanes of COL_RUN rows each: what the shim drives
+    assert "256 * COL_RUN" in open(os.path.join(CSRC, "k_cols.hip")).read()
 
 
 @pytest.mark.parametrize("mont", [0, 1])
@@ -113,7 +113,7 @@ def test_rows_and_own_point_scalars(shim, n, mont):
 @pytest.mark.parametrize("mont", [0, 1])
 @pytest.mark.parametrize("rho", [1, 2, R - 1])
 def test_batch_columns_and_weights(shim, rho, mont):
-    """k_bbs_pok_col_sums / k_bbs_pok_col_finish: C_k, the five weights over the own points, rho^i and -rho^i for row counts on both sides of a lane's run (16), of a
+    """k_bbs_pok_col_sums / k_col_finish: C_k, the five weights over the own points, rho^i and -rho^i for row counts on both sides of a lane's run (16), of a
     wave (64), of a block (256 x 16), in one chunk and in chunks that end inside a run, at a run's end and past a block"""
     run = launcher_run()
     shapes = ((1, 3, (1,), "revealed"), (2, 3, (2, 1), "hidden"), (15, 32, (15, 7), "first"), (17, 31, (17, 16), "last"), (63, 31, (63, 16), "per_row"),

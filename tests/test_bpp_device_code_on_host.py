@@ -1,6 +1,6 @@
 """CPU: the per-lane routines of Bulletproofs++ range proofs in bulk (crypto_amd/csrc/bpp_kernels.hip.h: bpp_consts, bpp_shared, batch_weight_index, shape_ok)
 compiled for the host with the FP29_CHECK operand asserts (tests/native/bpp_dev_host_shim.cpp, a stand-alone host build) and driven as k_bpp_consts, k_bpp_shared,
-k_bpp_col_sums, k_bpp_col_finish and the chunks of dock_bpp.hip drive them, against the closed form of tests/bpp_model.py: all 9 + NG shared and m + 4 + 2 K own
+k_bpp_col_sums, k_col_finish and the chunks of dock_bpp.hip drive them, against the closed form of tests/bpp_model.py: all 9 + NG shared and m + 4 + 2 K own
 scalars of every shape of the issue, both input forms, the values 0, 1, r - 1, r and 2^256 - 1 in every input position (each challenge, l0, n0), the status-2
 cases t = 0, r = 0, e = -k, and the batch's column sums and weights at proof counts on both sides of a lane's run (15, 16, 17) and of a wave (63, 64, 65), in
 forced chunks, under the batching scalars 1, 2 and r - 1.  A green run shows the values are right and that no product leaves fr_mul's operand contract."""
@@ -24,7 +24,7 @@ p_ = lambda a: a.ctypes.data_as(C.c_void_p)
 
 @pytest.fixture(scope="module")
 def shim():
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "bbs_routines.hip.h", "bpp_kernels.hip.h")]
+    deps = [SRC, os.path.join(HERE, "native", "col_frame_host.hpp")] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "col_sums.hip.h", "bbs_routines.hip.h", "bpp_kernels.hip.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-DFP29_CHECK", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", SO, SRC])
     L = C.CDLL(SO)

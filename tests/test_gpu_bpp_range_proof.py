@@ -3,6 +3,8 @@ come from known discrete logs (tests/bpp_model.py: the reference's prover, porte
 model computes and every expected status and verdict is decided in the exponent; one proof is confirmed by the oracle's own MSM on the reference's equation
 before any GPU verdict is trusted.  Every comparison is exact.  Points are computed once per discrete log and shared by every test."""
 from concurrent.futures import ThreadPoolExecutor
+import os
+import re
 import numpy as np
 import pytest
 import torch
@@ -16,6 +18,7 @@ from bbs_model import R
 pytestmark = pytest.mark.gpu
 R2 = pow(2, 256, R)
 G = O.G1
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "crypto_amd", "csrc")
 RHO = 0x1F2E3D4C5B6A79880123456789ABCDEF0FEDCBA9876543211234567
 # (2, 8, 1): NG = 8, K = 3, the smallest; (2, 8, 2): aggregation, lambda matters; (16, 8, 1): base > digits, pub_k reaches beyond D; (4, 16, 4); (2, 64, 2):
 # proof_system's shape, NG = 128, K = 7, rows of 137 terms (the many-row kernels' multi-block path), with 3 honest proofs
@@ -196,6 +199,39 @@ def test_row_counts_across_forced_chunks():
             assert each(W, shape, proofs[:5]) == want[:5] and batch(W, shape, good[:5], RHO) and not batch(W, shape, good[:4] + [proofs[15]], RHO)
         finally:
             T.dgpu_set_many_chunk_rows(0)
+
+
+def test_4097_proofs_in_one_chunk_two_blocks_a_column():
+    """4097 proofs of (2, 8, 2) in ONE batch call: own = 14, so BPP_BATCH_POINTS / own = 4681 > 4096 and one chunk holds them all, which k_bpp_col_sums runs
+    with two blocks a column (256 lanes x 16 proofs = 4096 a block) and k_col_finish adds.  The proofs are the 65 of the forced-chunk test, tiled, so the
+    model's work is that of 65 proofs; a batch is expected to pass exactly when the model gives status 0 to the source of every tile, and the model's statuses
+    are checked before any GPU verdict is read.  The honest batch verifies in both input forms; it is refused with one tampered proof in the second block
+    (proof 4096) and with one just before the border (proof 4095) — a scalar of the shared columns and an own point, at either place."""
+    W = world()
+    shape = (2, 8, 2)
+    s, setup, good, _, _ = W.case(shape, n=65)
+    points = int(re.search(r"BPP_BATCH_POINTS = \(size_t\)1 << (\d+)", open(os.path.join(CSRC, "bpp_launch.hip.h")).read()).group(1))
+    run = int(re.search(r"\bCOL_RUN = (\d+)\b", open(os.path.join(CSRC, "col_launch.hip.h")).read()).group(1))
+    n, border = 4097, 256 * run
+    assert border == 4096 and (1 << points) // s.own > border
+    src = list(good) + [BM.tamper(good[7], "n0"), BM.tamper(good[40], "M")]  # sources 65 and 66
+    status = [BM.status(s, setup, p) for p in src]
+    assert status[:65] == [0] * 65 and status[65] == 1 and status[66] == 1
+    tiles = np.arange(n) % 65
+    cases = [("honest", {})] + [("%s at %d" % (("n0", "M")[which - 65], at), {at: which}) for at in (border, border - 1) for which in (65, 66)]
+    for montgomery in (False, True):
+        P = W.pack(s, src, mont if montgomery else limbs)
+        rho = (mont if montgomery else limbs)([RHO])[0]
+        rows = lambda a, per: a.reshape(len(src), per, -1)
+        for name, put in cases:
+            idx = tiles.copy()
+            for at, which in put.items():
+                idx[at] = which
+            want = all(status[k] == 0 for k in idx)
+            assert want == (name == "honest")
+            T = BRP.Proofs(s.base, s.num_bits, s.m, rows(P.values, s.m)[idx], rows(P.round_points, 4)[idx], rows(P.wnla_points, 2 * s.K)[idx], rows(P.l_n, 2)[idx],
+                           rows(P.challenges, 7 + s.K)[idx])
+            assert BRP.verify_batch(W.setup(shape), s.base, s.num_bits, T, random=rho, montgomery=montgomery) == want, (name, montgomery)
 
 
 def test_two_threads_at_once_give_the_same_bytes():

@@ -3,6 +3,8 @@ key, the signatures and the proofs come from known discrete logs (tests/smc_mode
 model computes and every expected (status, detail) and verdict is decided in the exponent; two proofs are confirmed by the oracle's own MSM and pairing on the
 reference's equations before any GPU verdict is trusted.  Every comparison is exact.  Points are computed once per discrete log and shared by every test."""
 from concurrent.futures import ThreadPoolExecutor
+import os
+import re
 import numpy as np
 import pytest
 import torch
@@ -18,6 +20,7 @@ pytestmark = pytest.mark.gpu
 R2 = pow(2, 256, R)
 P_MOD = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
 G = O.G1
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "crypto_amd", "csrc")
 RHO = 0x1F2E3D4C5B6A79880123456789ABCDEF0FEDCBA9876543211234567
 # (kind, base, min, max): the statements of the issue — l = 64, rm = 2, rm = 1, l = 0, base 16; CCS with l = 5 and l = 64
 STATEMENTS = [(CLS, 2, 0, 2 ** 64 - 1), (CLS, 3, 5, 13), (CLS, 3, 5, 12), (CLS, 4, 10, 11), (CLS, 16, 0, 65536), (CCS, 4, 10, 1000), (CCS, 2, 0, 2 ** 63)]
@@ -81,6 +84,19 @@ class World:
             assert all(p.status(self.key, st) == (0, 0) for p in honest)
             self.cases[k] = (st, honest, forged)
         return self.cases[k]
+
+    def sixty_five(self):
+        """(statement 1, 65 honest proofs of it, its tampers, 65 scalars for the merged form): made once, shared by the tests that need them"""
+        if "65" not in self.cases:
+            st, honest, forged = self.case(1)
+            var = [p for _, p in variants(st, honest, forged)]
+            rng = np.random.default_rng(65)
+            good = []
+            for i in range(65):
+                b = rand(rng, 1 + st.sides * (1 + 3 * st.l) + 2)
+                good.append(SM.prove(self.key, st, st.min + i % (st.max - st.min), b[-1], b[-2], lambda j: b[j]))
+            self.cases["65"] = (st, good, var, rand(rng, 65))
+        return self.cases["65"]
 
     def pack(self, st, proofs, f=limbs):
         pts = self.points([p.C for p in proofs] + [v for p in proofs for v in p.D] + [v for p in proofs for d in p.digits for v in (d.ap, d.abar, d.t)])
@@ -199,19 +215,12 @@ def test_sixty_five_proofs_in_forced_chunks():
     """n = 65 with the chunks cut to 64 proofs and to 1 proof through the development surface: the statuses, the merged statuses and the batch verdicts are
     those of the uncut call"""
     W = world()
-    st, honest, forged = W.case(1)
-    var = [p for _, p in variants(st, honest, forged)]
-    rng = np.random.default_rng(65)
-    proofs = []
-    for i in range(65):
-        b = rand(rng, 1 + st.sides * (1 + 3 * st.l) + 2)
-        proofs.append(SM.prove(W.key, st, st.min + i % (st.max - st.min), b[-1], b[-2], lambda j: b[j]))
-    good = list(proofs)
+    st, good, var, rnd = W.sixty_five()
+    proofs = list(good)
     for i, v in zip((0, 1, 31, 63, 64), (var[0], var[3], var[1], var[2], var[5])):
         proofs[i] = v
     want = [p.status(W.key, st) for p in proofs]
     assert sum(1 for w in want if w != (0, 0)) == 5
-    rnd = rand(rng, 65)
     want_m = [p.status(W.key, st, random=r) for p, r in zip(proofs, rnd)]
     assert each(W, st, proofs) == want and each(W, st, proofs, random=rnd) == want_m and batch(W, st, good, RHO) and not batch(W, st, proofs, RHO)
     with twin(smc=True) as T:
@@ -224,6 +233,69 @@ def test_sixty_five_proofs_in_forced_chunks():
                 assert not batch(W, st, good[:64] + [proofs[64]], RHO), rows          # the bad proof alone in the last chunk
         finally:
             T.dgpu_set_many_chunk_rows(0)
+
+
+def tiled_batches(W, st, src, good, n, cases):
+    """every case's batch of n proofs — tile i is source i mod `good`, but for the places a case names — in both input forms: the GPU verdict is the model's,
+    a batch passing exactly when the model gives status (0, 0) to the source of every tile.  The model's statuses are taken before any GPU verdict is read"""
+    status = [p.status(W.key, st) for p in src]
+    assert status[:good] == [(0, 0)] * good and all(w != (0, 0) for w in status[good:])
+    tiles = np.arange(n) % good
+    for montgomery in (False, True):
+        f = mont if montgomery else limbs
+        P = W.pack(st, src, f)
+        rho = f([RHO])[0]
+        for name, put in cases:
+            idx = tiles.copy()
+            for at, which in put.items():
+                idx[at] = which
+            want = all(status[k] == (0, 0) for k in idx)
+            assert want == (not put), name
+            T = SRP.Proofs(st.as_tuple(), P.commitments[idx], P.challenge[idx], P.side_points.reshape(len(src), -1)[idx], P.side_responses.reshape(len(src), -1)[idx],
+                           P.digit_points.reshape(len(src), -1)[idx], P.digit_responses.reshape(len(src), -1)[idx])
+            assert SRP.verify_batch(W.params, st.as_tuple(), T, rho, montgomery=montgomery) == want, (name, montgomery)
+    return status
+
+
+def test_a_batch_across_the_border_of_a_block_of_equations():
+    """n proofs in ONE chunk whose n M equations fill more than one block of k_smc_col_sums (256 lanes x 16 equations = 4096): n = 4096 div M + 2, so that
+    4096 + M < n M <= SMC_BATCH_EQS: proof j = 4096 div M holds equation 4096 and proof j + 1 lies wholly in the second block.  The proofs are tiled from a few
+    sources, so the model's work is theirs alone.
+    Statement 1 (the 65 proofs of the forced-chunk test; M = 4): the honest batch verifies; it is refused with one tampered proof in the second block (j + 1),
+    with one just before the border (j - 1, equations 4092 .. 4095) and with one at it (j, equations 4096 .. 4099).  M = 4 divides 4096, so no proof of this
+    statement has equations on both sides of the border.
+    The CCS statement with l = 5 (M = 12; its 4 honest proofs): proof 341 holds equations 4092 .. 4103 and STRADDLES the border — its two side equations and its
+    first two digits' in the first block, the digits' from the third on in the second.  The honest batch verifies; it is refused when that proof has a side
+    equation wrong (below the border), when it has the third digit's wrong (equation 4096), and when it has both."""
+    W = world()
+    hdr = open(os.path.join(CSRC, "smc_launch.hip.h")).read()
+    eqs = int(re.search(r"SMC_BATCH_EQS = (\d+)\b", hdr).group(1))
+    run = int(re.search(r"\bCOL_RUN = (\d+)\b", open(os.path.join(CSRC, "col_launch.hip.h")).read()).group(1))
+    border = 256 * run
+    assert border == 4096
+
+    st, good, _, _ = W.sixty_five()
+    M = st.M
+    j = border // M                                                          # the proof that holds equation 4096
+    n = j + 2
+    assert border + M < n * M <= eqs and st.sides + st.D == M and st.D >= 1
+    assert (j - 1) * M + M - 1 < border <= j * M + M - 1 and (j + 1) * M > border       # j - 1 ends below the border, j holds it, j + 1 is behind it
+    # sources: 0 .. 64 the honest proofs; 65: a digit's response, 66: a side's point, 67: both (equations 0 and 1 of the proof)
+    src = good + [SM.tamper(good[3], "z1", st.D - 1), SM.tamper(good[4], "D", s=0), SM.tamper(SM.tamper(good[5], "z1", 0), "D", s=0)]
+    status = tiled_batches(W, st, src, 65, n, [("honest", {}), ("second block", {j + 1: 65}), ("before the border", {j - 1: 66}), ("at the border", {j: 67})])
+    assert status[65][0] == 2 and status[66][0] == 1 and status[67][0] == 1
+
+    st, honest, _ = W.case(5)
+    M, S = st.M, st.sides
+    j = border // M
+    n = j + 2
+    d = border - j * M - S                                                   # the digit of proof j whose equation is equation 4096
+    assert border + M < n * M <= eqs and border % M != 0 and j * M < border == j * M + S + d < (j + 1) * M and 0 <= d < st.D
+    # sources: 0 .. 3 the honest proofs; 4: side 0's point (equation j M, below the border), 5: digit d's response (equation 4096), 6: both
+    src = honest + [SM.tamper(honest[1], "D", s=0), SM.tamper(honest[2], "z1", d), SM.tamper(SM.tamper(honest[3], "z1", d), "D", s=0)]
+    status = tiled_batches(W, st, src, len(honest), n, [("honest", {}), ("straddling, wrong below the border", {j: len(honest)}),
+                                                        ("straddling, wrong behind the border", {j: len(honest) + 1}), ("straddling, wrong on both sides", {j: len(honest) + 2})])
+    assert [w[0] for w in status[len(honest):]] == [1, 2, 1]
 
 
 def test_two_threads_at_once_give_the_same_bytes():

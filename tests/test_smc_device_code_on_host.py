@@ -1,6 +1,6 @@
 """CPU: the per-lane routines of range proofs over weak-BB signatures in bulk (crypto_amd/csrc/smc_kernels.hip.h: own_scalars, col_run, merge_weight, fq_neg_words,
 stage_src, proof_verdict, ref_position) compiled for the host with the FP29_CHECK operand asserts (tests/native/smc_dev_host_shim.cpp, a stand-alone host build) and
-driven as k_smc_own, k_smc_stage, k_smc_merge_weights, k_smc_verdict, k_smc_col_sums, k_smc_col_finish and the chunks of dock_smc.hip drive them, against the
+driven as k_smc_own, k_smc_stage, k_smc_merge_weights, k_smc_verdict, k_smc_col_sums, k_col_finish and the chunks of dock_smc.hip drive them, against the
 big-integer model of tests/smc_model.py: one and two sides, l in {0, 1, 2, 16, 17, 64}, both input forms, the values 0, 1, r - 1, r and 2^256 - 1 among every kind
 of scalar (the statement's constants too), proof counts on both sides of a lane's run (15, 16, 17) and of a wave (63, 64, 65), forced chunks, the batching
 scalars 1, 2 and r - 1, the y-flip, and the verdict routine on planted flags.  A green run shows the values are right and that no product — the 65-term inner
@@ -28,7 +28,7 @@ p_ = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
 
 @pytest.fixture(scope="module")
 def shim():
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "bbs_routines.hip.h", "smc_kernels.hip.h")]
+    deps = [SRC, os.path.join(HERE, "native", "col_frame_host.hpp")] + [os.path.join(CSRC, h) for h in ("fr29.hip.h", "col_sums.hip.h", "bbs_routines.hip.h", "smc_kernels.hip.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-DFP29_CHECK", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", SO, SRC])
     L = C.CDLL(SO)
@@ -102,14 +102,14 @@ def own_words(shim, raw, stmt, sides, l, mont):
 
 
 def launcher_run():
-    hdr = open(os.path.join(CSRC, "bbs_launch.hip.h")).read()
-    return int(re.search(r"BBS_COL_RUN = (\d+)\b", hdr).group(1))
+    hdr = open(os.path.join(CSRC, "col_launch.hip.h")).read()
+    return int(re.search(r"\bCOL_RUN = (\d+)\b", hdr).group(1))
 
 
 def test_the_constants_are_the_launchers():
     assert launcher_run() == 16
     src = open(os.path.join(CSRC, "k_smc.hip")).read()
-    assert "bbsk::bbs_col_blocks(rows * eq_count(sides, l))" in src and "bbsk::BBS_COL_RUN" in src and "dim3(256)" in src      # what the shim drives
+    assert "colk::col_blocks(rows * eq_count(sides, l))" in src and "colk::COL_RUN" in src and "dim3(256)" in src      # what the shim drives
     assert "i0 * eq_count(sides, l), i0 * digit_count(sides, l)" in src                                                          # the chunk's first exponents
     hdr = open(os.path.join(CSRC, "smc_launch.hip.h")).read()
     assert "SMC_EACH_SLICES = 4096, SMC_BATCH_EQS = 16384" in hdr and "SMC_MAX_L = 64" in hdr and "SMC_STMT_CONSTS = 6" in hdr
@@ -130,7 +130,7 @@ def test_own_scalars(shim, l, sides, mont):
 @pytest.mark.parametrize("rho", [1, 2, R - 1])
 @pytest.mark.parametrize("sides", [1, 2])
 def test_batch_columns_and_weights(shim, sides, rho, mont):
-    """k_smc_col_sums / k_smc_col_finish: the coefficients of g1, g, h, the weights over C, D and the digits' points, +-rho^slice, for proof counts on both sides
+    """k_smc_col_sums / k_col_finish: the coefficients of g1, g, h, the weights over C, D and the digits' points, +-rho^slice, for proof counts on both sides
     of a lane's run, of a wave and of a block of 256 x 16 equations, in one chunk and in chunks that end inside a run"""
     run = launcher_run()
     shapes = [(0, 1, (1,)), (0, 17, (17, 5)), (0, 4097, (4097, 4096)), (1, 15, (15, 7)), (1, 16, (16,)), (1, 17, (17, 16)), (1, 63, (63, 16)), (1, 64, (64, 17)), (1, 65, (65, 64)),
