@@ -21,6 +21,9 @@ _SMC_DEV_SO = os.path.join(_HERE, "libdock_gpu_smc_dev.so")
 # include/dock_gpu_bpp.h: the same pair for the Bulletproofs++ range proofs
 _BPP_SO = os.path.join(_HERE, "libdock_gpu_bpp.so")
 _BPP_DEV_SO = os.path.join(_HERE, "libdock_gpu_bpp_dev.so")
+# include/dock_gpu_acc_gt.h: the same pair for the accumulator proofs with a GT commitment
+_ACC_GT_SO = os.path.join(_HERE, "libdock_gpu_acc_gt.so")
+_ACC_GT_DEV_SO = os.path.join(_HERE, "libdock_gpu_acc_gt_dev.so")
 
 ERR = {0: "DGPU_OK", -1: "DGPU_E_NODEVICE", -2: "DGPU_E_OOM", -3: "DGPU_E_BADARG", -4: "DGPU_E_HIP",
        -5: "DGPU_E_ZERO", -6: "DGPU_E_TOO_SMALL", -7: "DGPU_E_LENGTH"}
@@ -132,6 +135,10 @@ SMC_SYMBOLS = ["dgpu_smc_range_proofs_verify_each_g1", "dgpu_smc_range_proofs_ve
 # every symbol include/dock_gpu_bpp.h declares (libdock_gpu_bpp.so and its development build only)
 BPP_SYMBOLS = ["dgpu_bpp_range_proofs_verify_each_g1", "dgpu_bpp_range_proofs_verify_batch_g1"]
 
+# every symbol include/dock_gpu_acc_gt.h declares (libdock_gpu_acc_gt.so and its development build only)
+ACC_GT_SYMBOLS = ["dgpu_accumulator_gt_membership_proofs_verify_each_g1", "dgpu_accumulator_gt_membership_proofs_verify_batch_g1",
+                  "dgpu_accumulator_gt_non_membership_proofs_verify_each_g1", "dgpu_accumulator_gt_non_membership_proofs_verify_batch_g1"]
+
 
 def lib():
     """the library the wrappers call: the product, or the twin inside `with twin():`"""
@@ -148,7 +155,7 @@ def dev_lib():
 
 def is_twin():
     return _lib is not None and (_lib is _loaded.get(_DEV_SO) or _lib is _loaded.get(_SAVER_DEV_SO) or _lib is _loaded.get(_SMC_DEV_SO) or
-                                 _lib is _loaded.get(_BPP_DEV_SO))
+                                 _lib is _loaded.get(_BPP_DEV_SO) or _lib is _loaded.get(_ACC_GT_DEV_SO))
 
 
 def _bring_up(T):
@@ -204,15 +211,26 @@ def bpp_lib(bring_up=True):
     return S
 
 
+def acc_gt_lib(bring_up=True):
+    """the library that serves include/dock_gpu_acc_gt.h: the current one if it does (inside `with twin(acc_gt=True):`), else libdock_gpu_acc_gt.so, brought up
+    on the product's device(s) the first time"""
+    if _lib is not None and hasattr(_lib, ACC_GT_SYMBOLS[0]):
+        return _lib
+    S = _load(_ACC_GT_SO)
+    if bring_up and S.dgpu_context_count() == 0:
+        _bring_up(S)
+    return S
+
+
 @contextlib.contextmanager
-def twin(saver=False, smc=False, bpp=False):
+def twin(saver=False, smc=False, bpp=False, acc_gt=False):
     """Inside the block every wrapper of this package calls the development twin (include/dock_gpu_dev.h: knobs, stage timers, self-tests), brought up
     on the same device(s) as the product.  Nests; handles do not cross the border.  saver: the twin that serves include/dock_gpu_saver.h too
     (libdock_gpu_saver_dev.so), for what cuts or times the SAVER calls; smc: the one that serves include/dock_gpu_smc.h (libdock_gpu_smc_dev.so); bpp: the one that
-    serves include/dock_gpu_bpp.h (libdock_gpu_bpp_dev.so)."""
+    serves include/dock_gpu_bpp.h (libdock_gpu_bpp_dev.so); acc_gt: the one that serves include/dock_gpu_acc_gt.h (libdock_gpu_acc_gt_dev.so)."""
     global _lib
     prev = lib()
-    T = _load(_SAVER_DEV_SO) if saver else _load(_SMC_DEV_SO) if smc else _load(_BPP_DEV_SO) if bpp else dev_lib()
+    T = _load(_SAVER_DEV_SO) if saver else _load(_SMC_DEV_SO) if smc else _load(_BPP_DEV_SO) if bpp else _load(_ACC_GT_DEV_SO) if acc_gt else dev_lib()
     if T is not prev:
         _bring_up(T)
     _lib = T
@@ -389,6 +407,13 @@ def _load(path):
                 getattr(L, s).restype = C.c_int32
             L.dgpu_bpp_range_proofs_verify_each_g1.argtypes = [u64] + [C.c_uint32] * 3 + [vp] * 5 + [sz, C.c_int32, vp]
             L.dgpu_bpp_range_proofs_verify_batch_g1.argtypes = [u64] + [C.c_uint32] * 3 + [vp] * 5 + [sz, C.c_int32, vp, C.POINTER(C.c_int32)]
+        if hasattr(L, ACC_GT_SYMBOLS[0]):                     # libdock_gpu_acc_gt.so and its development build (include/dock_gpu_acc_gt.h)
+            for s in ACC_GT_SYMBOLS:
+                getattr(L, s).restype = C.c_int32
+            L.dgpu_accumulator_gt_membership_proofs_verify_each_g1.argtypes = [vp] * 8 + [sz, C.c_int32, vp]
+            L.dgpu_accumulator_gt_membership_proofs_verify_batch_g1.argtypes = [vp] * 8 + [sz, C.c_int32, vp, C.POINTER(C.c_int32)]
+            L.dgpu_accumulator_gt_non_membership_proofs_verify_each_g1.argtypes = [vp] * 9 + [sz, C.c_int32, vp]
+            L.dgpu_accumulator_gt_non_membership_proofs_verify_batch_g1.argtypes = [vp] * 9 + [sz, C.c_int32, vp, C.POINTER(C.c_int32)]
         L.dgpu_witness_map.argtypes = [vp, vp, vp, sz] * 3 + [vp, sz, sz, sz, C.c_int32, vp, C.POINTER(u64), C.POINTER(sz)]
         for name in ("dgpu_window_table_g1", "dgpu_window_table_g2"):
             getattr(L, name).argtypes = [vp, C.POINTER(u64)]

@@ -13,7 +13,9 @@ fn main() {
     // the feature `smc-range-proof` (src/smc_range_proof.rs, include/dock_gpu_smc.h) needs libdock_gpu_smc.so in the same way; the two libraries are separate
     // images, so a host builds with one of the two features
     let name = if std::env::var("CARGO_FEATURE_SAVER").is_ok() { "dock_gpu_saver" } else if std::env::var("CARGO_FEATURE_SMC_RANGE_PROOF").is_ok() { "dock_gpu_smc" }
-               else if std::env::var("CARGO_FEATURE_BULLETPROOFS_PLUS_PLUS").is_ok() { "dock_gpu_bpp" } else { "dock_gpu" };      // (src/bpp_range_proof.rs, include/dock_gpu_bpp.h: libdock_gpu_bpp.so)
+               else if std::env::var("CARGO_FEATURE_BULLETPROOFS_PLUS_PLUS").is_ok() { "dock_gpu_bpp" }      // (src/bpp_range_proof.rs, include/dock_gpu_bpp.h: libdock_gpu_bpp.so)
+               // the feature `vb-accumulator` alone: libdock_gpu_acc_gt.so (src/accumulator_gt_proofs.rs, include/dock_gpu_acc_gt.h), which serves src/accumulator_proofs.rs as well
+               else if std::env::var("CARGO_FEATURE_VB_ACCUMULATOR").is_ok() { "dock_gpu_acc_gt" } else { "dock_gpu" };
     println!("cargo:rustc-link-lib=dylib={}", name);
     println!("cargo:rustc-link-arg=-Wl,-rpath,{}", dir);
 }

@@ -32,8 +32,13 @@ pub mod host;
 pub mod accumulator_issue;      // (issuing membership / non-membership witnesses: src/accumulator_issue.rs; cargo-side cases in tests/parity_accumulator_issue.rs)
 #[cfg(feature = "vb-accumulator")]
 pub mod accumulator_proofs;     // (verifying membership / non-membership proofs in bulk behind the reference's own types: src/accumulator_proofs.rs; the case in tests/parity.rs runs under the same feature)
+// (the proofs with a GT commitment, vb_accumulator/src/proofs.rs, verified in bulk: src/accumulator_gt_proofs.rs over include/dock_gpu_acc_gt.h.  Its calls live in
+// libdock_gpu_acc_gt.so, which build.rs links INSTEAD of the product under this feature — it exports all of the product — unless `saver`, `smc-range-proof` or
+// `bulletproofs-plus-plus` has picked another library: then the module is left out.  The case in tests/parity.rs runs under the same condition.)
+#[cfg(all(feature = "vb-accumulator", not(any(feature = "saver", feature = "smc-range-proof", feature = "bulletproofs-plus-plus"))))]
+pub mod accumulator_gt_proofs;
 #[cfg(feature = "bbs-plus")]
-pub mod bbs_plus;               // (BBS+ signatures in bulk behind the reference's own types: src/bbs_plus.rs; the case in tests/parity.rs runs under the same feature)
+pub mod bbs_plus;              // (BBS+ signatures in bulk behind the reference's own types: src/bbs_plus.rs; the case in tests/parity.rs runs under the same feature)
 #[cfg(feature = "coconut")]
 pub mod coconut;                // (PS / Coconut signatures in bulk behind the reference's own types: src/coconut.rs; the case in tests/parity.rs runs under the same feature)
 

@@ -971,6 +971,98 @@ fn accumulator_proofs_bulk_equal_the_reference() {
     }
 }
 
+// the accumulator proofs with a GT commitment in bulk (src/accumulator_gt_proofs.rs) against the reference's own `MembershipProof::verify` /
+// `NonMembershipProof::verify` of vb_accumulator/src/proofs.rs: the same error per proof, or one verdict.  NOT compiled in the build image.
+#[cfg(all(feature = "vb-accumulator", not(any(feature = "saver", feature = "smc-range-proof", feature = "bulletproofs-plus-plus"))))]
+#[test]
+fn accumulator_gt_proofs_bulk_equal_the_reference() {
+    use ark_ec::pairing::PairingOutput;
+    use ark_ff::Field;
+    use dock_gpu::accumulator_gt_proofs::{membership_verify_batch, membership_verify_each, non_membership_verify_batch, non_membership_verify_each, GpuAccumulatorGtVerifier};
+    use vb_accumulator::proofs::{MembershipProof, MembershipProofProtocol, NonMembershipProof, NonMembershipProofProtocol};
+    use vb_accumulator::setup::{Keypair, NonMembershipProvingKey, SetupParams};
+    use vb_accumulator::witness::{MembershipWitness, NonMembershipWitness};
+    setup();
+    let mut rng = StdRng::seed_from_u64(0x5EED0AC6);
+    let params = SetupParams::<Bls12_381>::generate_using_rng(&mut rng);
+    let keypair = Keypair::<Bls12_381>::generate_using_rng(&mut rng, &params);
+    let alpha = keypair.secret_key.0;
+    let nm_prk = NonMembershipProvingKey::<G1Affine>::generate_using_rng(&mut rng);
+    let prk = nm_prk.derive_membership_proving_key();
+    let key = GpuAccumulatorGtVerifier::new(&params, &keypair.public_key).expect("key");
+    let v = (params.P * Fr::rand(&mut rng)).into_affine();
+    for &n in &[3usize, 65, 257] {
+        // membership: C = 1 / (y + alpha) V
+        let (mut proofs, mut challenges): (Vec<MembershipProof<Bls12_381>>, Vec<Fr>) = (vec![], vec![]);
+        for _ in 0..n {
+            let y = Fr::rand(&mut rng);
+            let wit = MembershipWitness((v * (y + alpha).inverse().unwrap()).into_affine());
+            let c = Fr::rand(&mut rng);
+            proofs.push(MembershipProofProtocol::<Bls12_381>::init(&mut rng, y, None, &wit, &keypair.public_key, &params, &prk).gen_proof(&c).unwrap());
+            challenges.push(c);
+        }
+        let rho = Fr::rand(&mut rng);
+        assert!(membership_verify_each(&key, &v, &prk.0, &proofs, &challenges, None).expect("membership_verify_each").iter().all(|r| r.is_ok()), "n = {n}");
+        assert_eq!(membership_verify_batch(&key, &v, &prk.0, &proofs, &challenges, None, &rho), Some(true));
+        // every error of the reference's order, and a valid proof whose commitment is the identity is none
+        let (mut bad, mut bad_c) = (proofs.clone(), challenges.clone());
+        bad[0].schnorr_response.0.s_sigma += Fr::from(1u64);
+        bad[1].schnorr_commit.0.R_rho = bad[0].schnorr_commit.0.R_rho;
+        bad[2].schnorr_commit.0.R_E = PairingOutput(bad[2].schnorr_commit.0.R_E.0 * bad[0].schnorr_commit.0.R_E.0);
+        if n > 3 {
+            bad[3].schnorr_response.0.s_delta_sigma += Fr::from(1u64);
+            bad[4].schnorr_commit.0.R_delta_rho = G1Affine::zero();
+            bad[5].randomized_witness.0.E_C = bad[6].randomized_witness.0.E_C;
+            bad_c[7] += Fr::from(1u64);
+        }
+        let mine = membership_verify_each(&key, &v, &prk.0, &bad, &bad_c, None).expect("membership_verify_each");
+        for i in 0..n {
+            let theirs = bad[i].verify(&v, &bad_c[i], keypair.public_key.clone(), params.clone(), &prk);
+            assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "n = {n}, membership proof {i}");
+        }
+        assert!(mine[0].is_err() && mine[2].is_err());
+        assert_eq!(membership_verify_batch(&key, &v, &prk.0, &bad, &bad_c, None, &rho), Some(false));
+        // a partial proof: the element's response travels beside it
+        let y = Fr::rand(&mut rng);
+        let wit = MembershipWitness((v * (y + alpha).inverse().unwrap()).into_affine());
+        let (c, blinding) = (Fr::rand(&mut rng), Fr::rand(&mut rng));
+        let partial = MembershipProofProtocol::<Bls12_381>::init(&mut rng, y, Some(blinding), &wit, &keypair.public_key, &params, &prk).gen_partial_proof(&c).unwrap();
+        let resp = blinding + c * y;
+        assert!(membership_verify_each(&key, &v, &prk.0, &[partial.clone()], &[c], Some(&[resp])).expect("partial")[0].is_ok());
+        assert!(membership_verify_each(&key, &v, &prk.0, &[partial.clone()], &[c], Some(&[resp + Fr::from(1u64)])).expect("partial")[0].is_err());
+        assert!(membership_verify_each(&key, &v, &prk.0, &[partial], &[c], None).is_none());      // MissingSchnorrResponseForElement stays with the caller
+
+        // non-membership: C (y + alpha) + d P = V
+        let (mut proofs, mut challenges): (Vec<NonMembershipProof<Bls12_381>>, Vec<Fr>) = (vec![], vec![]);
+        for _ in 0..n {
+            let (y, d) = (Fr::rand(&mut rng), Fr::rand(&mut rng));
+            let wit = NonMembershipWitness { d, C: ((v.into_group() - params.P * d) * (y + alpha).inverse().unwrap()).into_affine() };
+            let c = Fr::rand(&mut rng);
+            proofs.push(NonMembershipProofProtocol::<Bls12_381>::init(&mut rng, y, None, &wit, &keypair.public_key, &params, &nm_prk).gen_proof(&c).unwrap());
+            challenges.push(c);
+        }
+        assert!(non_membership_verify_each(&key, &v, &nm_prk, &proofs, &challenges, None).expect("non_membership_verify_each").iter().all(|r| r.is_ok()), "n = {n}");
+        assert_eq!(non_membership_verify_batch(&key, &v, &nm_prk, &proofs, &challenges, None, &rho), Some(true));
+        let (mut bad, mut bad_c) = (proofs.clone(), challenges.clone());
+        bad[0].schnorr_response.s_v += Fr::from(1u64);
+        bad[1].schnorr_commit.R_B = bad[0].schnorr_commit.R_B;
+        bad[2].schnorr_commit.C.R_E = PairingOutput(bad[2].schnorr_commit.C.R_E.0 * bad[0].schnorr_commit.C.R_E.0);
+        if n > 3 {
+            bad[3].schnorr_response.C.s_rho += Fr::from(1u64);
+            bad[4].randomized_witness.E_d_inv = G1Affine::zero();
+            bad[5].schnorr_commit.C.R_delta_sigma = bad[6].schnorr_commit.C.R_delta_sigma;
+            bad_c[7] += Fr::from(1u64);
+        }
+        let mine = non_membership_verify_each(&key, &v, &nm_prk, &bad, &bad_c, None).expect("non_membership_verify_each");
+        for i in 0..n {
+            let theirs = bad[i].verify(&v, &bad_c[i], keypair.public_key.clone(), params.clone(), &nm_prk);
+            assert_eq!(format!("{:?}", mine[i]), format!("{:?}", theirs), "n = {n}, non-membership proof {i}");
+        }
+        assert!(mine[0].is_err() && mine[2].is_err());
+        assert_eq!(non_membership_verify_batch(&key, &v, &nm_prk, &bad, &bad_c, None, &rho), Some(false));
+    }
+}
+
 // PS (Coconut) signatures in bulk behind the reference's own types (src/coconut.rs) against the reference's `Signature::new` / `verify` and `SignaturePoK::verify`
 #[cfg(feature = "coconut")]
 #[test]
