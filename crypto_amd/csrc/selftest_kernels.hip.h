@@ -10,6 +10,10 @@
 // tracker (shim_selftest_arith), which is what decides the operand classes (`stress`) an op may be given.  tests/test_gpu_device_arith.py holds the
 // operand tables and the big-integer expectations, and mirrors the ST_* numbers below.
 //
+// Families: Fp, Fs, Fp2 / Fs2 (one lane and lane pairs), Fr, the group law over all four fields (one lane, two and four lanes), the Fp12 products and the
+// one-lane line steps of pairing29.hip.h (ST_LINE_*), and — numbered here, wrapped in selftest_gt_kernels.hip.h — the six-lane GT group arithmetic of
+// gt_kernels.hip.h / gt_lanes.hip.h (ST_GT_*: six lanes per row behind GT_GROUP_PROLOGUE, k_selftest_gt<ID>, stress = reps | G << 8).
+//
 // Row layout (u64 words in the ABI of include/dock_gpu.h; the wrappers see them as u32 pairs):
 //   Fp / Fs element: 6 words (value * 2^384 mod p), Fp2 / Fs2: 12 (c0, c1), Fr: 4 (canonical or * 2^256, per op), Fp12: 72
 //   chain rows: word 0 = count | sign bits << 32, then ST_MAXP affine points (x, y); point outputs are X, Y, ZZ, ZZZ — all-zero = identity
@@ -53,7 +57,10 @@ enum : int {
     // ec29_two_lane.hip.h (two lanes per G1 point, four per G2 point), xyzz_phi, fp_inv.hip.h's xyzz_to_affine
     ST_G1_MADD_2L = 88, ST_G1_DBL_2L, ST_G2_MADD_4L, ST_G2_DBL_4L, ST_G1_PHI, ST_G1_TO_AFFINE, ST_G2H_TO_AFFINE = 95,
     // pairing29.hip.h
-    ST_F12_MUL = 100, ST_F12_MUL_ROLES, ST_F12_MUL_BY_014,
+    ST_F12_MUL = 100, ST_F12_MUL_ROLES, ST_F12_MUL_BY_014, ST_LINE_DBL = 104, ST_LINE_ADD,
+    // gt_kernels.hip.h / gt_lanes.hip.h (the wrappers are in selftest_gt_kernels.hip.h): six lanes per row, but for the digits
+    ST_GT_ROUNDTRIP = 110, ST_GT_CONJ, ST_GT_NEG, ST_GT_MUL, ST_GT_SQR_BY_MUL, ST_GT_CYC_SQR, ST_GT_FROB1, ST_GT_FROB2, ST_GT_INV, ST_GT_EXP_BY_X, ST_GT_FINAL_EXP,
+    ST_GT_MEMBERSHIP, ST_GT_SHRINK, ST_GT_TAIL_STEP, ST_GT_DIGITS,
     ST_OP_END
 };
 
@@ -291,6 +298,25 @@ ST_OP(ST_F12_MUL_BY_014, 1, 108, 72) {
     Fp12d x; st_ld_f12(x, in); Fp2 k0, k1, k4; st_ld(k0, in + 144); st_ld(k1, in + 168); st_ld(k4, in + 192);
     for (int i = 0; i < stress; i++) f12_mul_by_014(x, k0, k1, k4);
     st_st_f12(out, x);
+}
+
+// ---- the line steps (pairing29.hip.h; what k_miller_lines and k_g2_prepare call): a row is R = (X, Y, Z), plus Q = (x, y) for the addition; the step is
+// applied `stress` times with R fed back; out = R', then the last step's three line coefficients ----
+FD void st_ld_proj(G2Proj &R, const uint32_t *w) { st_ld(R.x, w); st_ld(R.y, w + 24); st_ld(R.z, w + 48); }
+FD void st_st_step(uint32_t *out, const G2Proj &R, const Line &l) {
+    st_st(out, R.x); st_st(out + 24, R.y); st_st(out + 48, R.z); st_st(out + 72, l.c0); st_st(out + 96, l.c1); st_st(out + 120, l.c2);
+}
+ST_OP(ST_LINE_DBL, 1, 36, 72) {
+    G2Proj R; Line l; st_ld_proj(R, in); fzero(l.c0); fzero(l.c1); fzero(l.c2);
+#pragma unroll 1
+    for (int i = 0; i < stress; i++) line_dbl_step(R, l);
+    st_st_step(out, R, l);
+}
+ST_OP(ST_LINE_ADD, 1, 60, 72) {
+    G2Proj R; Line l; Aff<Fp2> Q; st_ld_proj(R, in); st_ld_aff(Q, in + 72); fzero(l.c0); fzero(l.c1); fzero(l.c2);
+#pragma unroll 1
+    for (int i = 0; i < stress; i++) line_add_step(R, Q, l);
+    st_st_step(out, R, l);
 }
 
 #if defined(__HIPCC__)

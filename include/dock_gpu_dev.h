@@ -103,7 +103,9 @@ int32_t dgpu_selftest_g1_sum(const uint64_t *pts_xy /* n*12 */, const uint8_t *n
 /* One arithmetic function of the device headers per call, one kernel per op (crypto_amd/csrc/selftest_kernels.hip.h lists the ops and their row
  * shapes): n rows of in_words u64 in and out_words u64 out, in the ABI forms of dock_gpu.h (field elements * 2^384 mod p, Fr as 256-bit words,
  * points out as X, Y, ZZ, ZZZ).  stress = k: an operand is added to itself k - 1 times, un-normalised, before the operation (for the Fr word ops
- * it is the Montgomery flag, for the chains a repetition count).  DGPU_E_BADARG: unknown op, or a row shape that is not the op's. */
+ * it is the Montgomery flag, for the chains a repetition count).  For the six-lane GT group ops (selftest_gt_kernels.hip.h) stress = reps | G << 8:
+ * reps = how many times the output is fed back (at most 64), G = groups of six lanes per 64-lane wave, one of 1, 3 and 10.
+ * DGPU_E_BADARG: unknown op, a row shape that is not the op's, or a stress the op does not take (any other G among them). */
 int32_t dgpu_selftest_arith(int32_t op, int32_t stress, const uint64_t *in, size_t in_words, size_t n, uint64_t *out, size_t out_words);
 
 /* ---- fault injection (tests/test_gpu_fault_paths.py): the k-th hipMalloc from now and the count - 1 after it fail ---- */

@@ -258,6 +258,26 @@ void shim_miller_lines_ws(const uint32_t *p, const uint32_t *q, uint32_t *out) {
     }
     for (size_t s = 0; s < ls.size(); s++) { const Fp *c = reinterpret_cast<const Fp *>(&ls[s]); for (int k = 0; k < 6; k++) fp_to_abi(out + (s * 6 + k) * 12, c[k]); }
 }
+// the steps in the forms the lane-distributed kernels run, one lane (these have no one-lane kernel on the device): form 0 line_dbl_step_fast, 1 line_dbl_step_ws,
+// 2 line_add_step_ws.  Rows and outputs as ST_LINE_DBL / ST_LINE_ADD of selftest_kernels.hip.h; the step is applied `stress` times, R fed back, norm_y false
+// between steps and true on the last, so the un-normalised Y' feeds the next doubling as in the kernels.  0: done, -3: no such form or row shape
+int shim_line_steps(int form, int stress, const uint64_t *in, size_t in_words, size_t n, uint64_t *out, size_t out_words) {
+    if (form < 0 || form > 2 || stress < 1 || stress > 64 || in_words != (form == 2 ? 60u : 36u) || out_words != 72) return -3;
+    for (size_t r = 0; r < n; r++) {
+        const uint32_t *w = reinterpret_cast<const uint32_t *>(in + r * in_words);
+        G2Proj R; Line l; Aff<Fp2> Q;
+        selftest::st_ld_proj(R, w);
+        if (form == 2) selftest::st_ld_aff(Q, w + 72);
+        for (int i = 0; i < stress; i++) {
+            if (form == 0) line_dbl_step_fast(R, l, i == stress - 1);
+            else if (form == 1) line_dbl_step_ws(R, l, i == stress - 1);
+            else line_add_step_ws(R, Q, l);
+        }
+        fnorm(l.c0, l.c0); fnorm(l.c1, l.c1); fnorm(l.c2, l.c2);
+        selftest::st_st_step(reinterpret_cast<uint32_t *>(out + r * out_words), R, l);
+    }
+    return 0;
+}
 // 12 a by the scaled carry pass, from a lazily reduced operand (k a, carry-passed)
 void shim_fp_mul12(const uint32_t *a, int k, uint32_t *out) {
     Fp x, t, r; fp_from_abi(x, a); t = x; for (int i = 1; i < k; i++) fp_add(t, t, x); fp_norm(t, t);
@@ -315,7 +335,7 @@ extern "C" int shim_selftest_arith(int op, int stress, const uint64_t *in, size_
         X(ST_FR_ROUNDTRIP) X(ST_FR_MUL) X(ST_FR_BUTTERFLIES) X(ST_FR_CANON) X(ST_FR_INV)
         X(ST_G1_MADD) X(ST_G1_TREE) X(ST_G1_DBL) X(ST_G1S_MADD) X(ST_G1S_TREE) X(ST_G1S_DBL) X(ST_G1S_TREE_ROUNDS) X(ST_G1S_DBL_ROUNDS)
         X(ST_G2_MADD) X(ST_G2_TREE) X(ST_G2_DBL) X(ST_G2S_MADD) X(ST_G2S_MADD_EARLY) X(ST_G2S_TREE) X(ST_G2S_DBL) X(ST_G2S_TREE_ROUNDS) X(ST_G2S_DBL_ROUNDS)
-        X(ST_F12_MUL) X(ST_F12_MUL_ROLES) X(ST_F12_MUL_BY_014)
+        X(ST_F12_MUL) X(ST_F12_MUL_ROLES) X(ST_F12_MUL_BY_014) X(ST_LINE_DBL) X(ST_LINE_ADD)
 #undef X
         case ST_FR_BATCH_INV: {
             if (stress < 1 || stress > ST_MAX_SHARE || in_words != 4 * (size_t)stress || out_words != in_words) return -3;

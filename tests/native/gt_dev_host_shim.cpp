@@ -4,6 +4,7 @@
 // the oracles; an assertion that fires inside means a lazy-limb overflow is possible for some input.
 #define FP29_CHECK 1
 #include "../../crypto_amd/csrc/gt_kernels.hip.h"
+#include "../../crypto_amd/csrc/selftest_gt_kernels.hip.h"
 #include <string.h>
 #include <condition_variable>
 #include <mutex>
@@ -87,4 +88,33 @@ void shim_miller_tail(const uint64_t *L, uint64_t *out) {
         store(out, e, r);
     });
 }
+}
+
+// ---- the wrappers of the device self-tests (selftest_gt_kernels.hip.h), the same bodies k_selftest_gt runs, a group of six threads per row: n rows of
+// in_words u64 in, out_words u64 out; stress = reps | G << 8 as on the device (G, the groups per wave, means nothing here).  0: done; -3: no such op,
+// or a row shape that is not the op's ----
+template <int OP> static int gt_rows(int reps, const uint64_t *in, size_t in_words, size_t n, uint64_t *out, size_t out_words) {
+    using O = selftest::StOp<OP>;
+    if (in_words != (size_t)O::IN64 || out_words != (size_t)O::OUT64) return -3;
+    for (size_t i = 0; i < n; i++)
+        run_group([&](HostLanes &x, int) { O::run(x, reinterpret_cast<const uint32_t *>(in + i * in_words), reinterpret_cast<uint32_t *>(out + i * out_words), reps); });
+    return 0;
+}
+extern "C" int shim_selftest_gt(int op, int stress, const uint64_t *in, size_t in_words, size_t n, uint64_t *out, size_t out_words) {
+    using namespace selftest;
+    const int reps = stress & 0xff;
+    if (stress < 0 || reps > 64) return -3;
+    switch (op) {
+#define X(ID) case ID: return gt_rows<ID>(reps, in, in_words, n, out, out_words);
+        X(ST_GT_ROUNDTRIP) X(ST_GT_CONJ) X(ST_GT_NEG) X(ST_GT_MUL) X(ST_GT_SQR_BY_MUL) X(ST_GT_CYC_SQR) X(ST_GT_FROB1) X(ST_GT_FROB2) X(ST_GT_INV) X(ST_GT_EXP_BY_X)
+        X(ST_GT_FINAL_EXP) X(ST_GT_MEMBERSHIP) X(ST_GT_SHRINK) X(ST_GT_TAIL_STEP)
+#undef X
+        case ST_GT_DIGITS: {
+            using O = StOp<ST_GT_DIGITS>;
+            if (in_words != (size_t)O::IN64 || out_words != (size_t)O::OUT64) return -3;
+            for (size_t i = 0; i < n; i++) O::run(reinterpret_cast<const uint32_t *>(in + i * in_words), reinterpret_cast<uint32_t *>(out + i * out_words), stress);
+            return 0;
+        }
+        default: return -3;
+    }
 }

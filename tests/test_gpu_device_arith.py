@@ -11,6 +11,17 @@ Two halves over the SAME operand tables and expectations:
     it without an assertion.  The lane-shared forms have no host build; their operands are those of their one-lane twins.
   * test_gpu_* (-m gpu): the same rows on the device.  A failure that the host half does not share points at code generation or at a lane exchange.
 Rows interleave the operand classes (neighbouring lanes diverge in data-dependent branches) and their number is no multiple of 64 (a partial last wave).
+
+The layer above the field and curve headers follows the same pattern:
+  * test_host_gt_ops / test_gpu_gt_ops: the six-lane group functions of gt_kernels.hip.h (selftest_gt_kernels.hip.h) — gt_get_abi / gt_put / gt_get / gt_put_abi,
+    gt_conj, gt_neg, gt_mul (also aliased, as the Miller tail squares), gt_cyc_sqr, gt_frob1, gt_frob2, gt_inv, gt_exp_by_x, gt_final_exp, gt_in_cyclotomic /
+    gt_in_gt, gt_shrink on raw limbs up to the edge of its contract, k_miller_tail's load-shrink-square-multiply step, gt_signed_digits.  The host half runs
+    the wrappers with six threads as the lanes (tests/native/gt_dev_host_shim.cpp shim_selftest_gt); the device runs them behind GT_GROUP_PROLOGUE with 1, 3
+    and 10 groups per wave, and a row count that is no multiple of 3, 10 or 64, so GtLanesDev's slot offsets, ballots and early lane exits are all taken.
+    Elements carry zero, one and p - 1 coefficients, single w^e, subfield elements and equal / opposite neighbours: what a wrong select or constant needs to show.
+  * test_host_line_steps / test_gpu_line_steps: line_dbl_step and line_add_step against a transcription of the ark-ec formulas written here (which
+    test_host_line_transcription_is_the_miller_loops_step ties to the Miller loop); line_dbl_step_fast, line_dbl_step_ws and line_add_step_ws on the host only.
+Not covered per function: the lane-distributed line kernels (whole Miller loops only) and, on the device, one-lane G2 chains.
 """
 import ctypes as C
 import functools
@@ -26,6 +37,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "crypto_amd", "csrc")
 SRC = os.path.join(HERE, "native", "fp29_host_shim.cpp")
 SO = os.path.join(HERE, "native", "libfp29_host_shim.so")
+GT_SRC = os.path.join(HERE, "native", "gt_dev_host_shim.cpp")
+GT_SO = os.path.join(HERE, "native", "libgt_dev_host_shim.so")
 P, R = M.P, M.R
 MAXP = 24                                   # ST_MAXP: points per chain row
 
@@ -47,8 +60,14 @@ OPS = {
     "g2s_dbl_rounds": (83, _CH2, 48, 1),
     "g1_madd_2l": (88, _CH1, 24, 0), "g1_dbl_2l": (89, _CH1, 24, 0), "g2_madd_4l": (90, _CH2, 48, 0), "g2_dbl_4l": (91, _CH2, 48, 0), "g1_phi": (92, _CH1, 24, 0),
     "g1_to_affine": (93, _CH1, 13, 0), "g2h_to_affine": (95, _CH2, 25, 0),
-    "f12_mul": (100, 144, 72, 1), "f12_mul_roles": (101, 144, 72, 1), "f12_mul_by_014": (102, 108, 72, 1),
+    "f12_mul": (100, 144, 72, 1), "f12_mul_roles": (101, 144, 72, 1), "f12_mul_by_014": (102, 108, 72, 1), "line_dbl": (104, 36, 72, 1), "line_add": (105, 60, 72, 1),
+    "gt_roundtrip": (110, 72, 156, 1), "gt_conj": (111, 72, 72, 1), "gt_neg": (112, 72, 72, 1), "gt_mul": (113, 144, 72, 1), "gt_sqr_by_mul": (114, 72, 72, 1),
+    "gt_cyc_sqr": (115, 72, 72, 1), "gt_frob1": (116, 72, 72, 1), "gt_frob2": (117, 72, 72, 1), "gt_inv": (118, 72, 72, 1), "gt_exp_by_x": (119, 72, 72, 1),
+    "gt_final_exp": (120, 72, 73, 1), "gt_membership": (121, 72, 1, 1), "gt_shrink": (122, 84, 156, 1), "gt_tail_step": (123, 168, 72, 1), "gt_digits": (124, 4, 9, 1),
 }
+# the six-lane group ops (ST_GT_OP of selftest_gt_kernels.hip.h): stress = reps | G << 8; on the host they run through shim_selftest_gt
+GT_SIX = {k for k in OPS if k.startswith("gt_") and k != "gt_digits"}
+GT_GROUPS = (1, 3, 10)                      # groups per wave the twin accepts
 
 
 # ---- the two backends ----
@@ -60,6 +79,7 @@ def shim():
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SO, SRC])
     L = C.CDLL(SO)
     L.shim_selftest_arith.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.shim_line_steps.argtypes = L.shim_selftest_arith.argtypes
     return L
 
 
@@ -75,8 +95,24 @@ def _run(fn, name, stress, rows, out_words=None):
     return out
 
 
+@pytest.fixture(scope="module")
+def gt_shim():
+    """tests/native/gt_dev_host_shim.cpp: six threads as the six lanes of a group (the library test_gt_device_code_on_host.py builds, same flags)"""
+    deps = [GT_SRC] + [os.path.join(CSRC, f) for f in ("gt_kernels.hip.h", "pairing29.hip.h", "fp29.hip.h", "fp2_29.hip.h", "fp_safegcd.hip.h", "selftest_kernels.hip.h",
+                                                         "selftest_gt_kernels.hip.h")]
+    if not os.path.exists(GT_SO) or any(os.path.getmtime(d) > os.path.getmtime(GT_SO) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-o", GT_SO, GT_SRC])
+    L = C.CDLL(GT_SO)
+    L.shim_selftest_gt.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]
+    return L
+
+
 def host_backend(shim):
     return lambda name, stress, rows, out_words=None: _run(shim.shim_selftest_arith, name, stress, rows, out_words)
+
+
+def gt_host_backend(gt_shim):
+    return lambda name, stress, rows, out_words=None: _run(gt_shim.shim_selftest_gt, name, stress, rows, out_words)
 
 
 def gpu_backend(T):
@@ -461,10 +497,358 @@ F2_HOST = ("fp2_mul", "fp2_sqr", "fs2_mul", "fs2_sqr")
 F2_DEVICE = ("fp2_inv", "fp2h_mul", "fp2h_sqr", "fp2h_mul_sub", "fp2h_sqr_m", "fp2h_mul_xi_n", "fp2h_inv", "fs2h_mul", "fs2h_mul_two", "fs2h_sqr", "fs2h_mul_sub")
 
 
+# ---- the six-lane GT group arithmetic (gt_kernels.hip.h, gt_lanes.hip.h): expectations from bls12_381_model alone ----
+F2Z = (0, 0)
+F12_ZERO = ((F2Z,) * 3, (F2Z,) * 3)
+X_BITS = bin(M.X_ABS)[3:]                    # the bits of |x| below the top one
+
+
+GT_FIXED = [F12_ZERO, M.F12_ONE, (((P - 1, 0), F2Z, F2Z), (F2Z,) * 3)]          # zero, one, minus one
+
+
+def enc12(fs):
+    """model elements -> [n, 72] ABI words (tower order)"""
+    return np.hstack([enc_fp([_f12_flat(f)[k] for f in fs]) for k in range(12)])
+
+
+def from_w(c):
+    """the element sum c[e] w^e: coefficient e = 2 j + i is the tower's c_i.c_j (lane e of a group holds c[e])"""
+    return ((c[0], c[2], c[4]), (c[1], c[3], c[5]))
+
+
+def w_coeffs(f):
+    return [f[e & 1][e >> 1] for e in range(6)]
+
+
+def gt_odd(rows):
+    """no multiple of 3, of 10 or of 64: at every G the last wave is partial, and so is the last block's group count"""
+    rows = list(rows)
+    while len(rows) % 3 == 0 or len(rows) % 10 == 0 or len(rows) % 64 == 0:
+        rows.append(rows[len(rows) // 2])
+    return rows
+
+
+def carried(v):
+    """v as fully carried limbs of 29 bits, everything above bit 377 in the top one"""
+    return [(v >> (29 * i)) & (2 ** 29 - 1) for i in range(13)] + [v >> 377]
+
+
+def raw_words(limbs):
+    """14 u32 limbs -> 7 u64 words"""
+    return [limbs[2 * i] | (limbs[2 * i + 1] << 32) for i in range(7)]
+
+
+def limbs_value(l):
+    return sum(int(x) << (29 * i) for i, x in enumerate(l))
+
+
+@functools.lru_cache(None)
+def gt_elements():
+    """the element classes, interleaved: zero, one, minus one, every coefficient p - 1 and (p - 1) / 2; the six w^e alone and scaled by (1, 1); elements of Fp,
+    Fp2, Fp6 (odd w-coefficients zero) and c1 w (even ones zero); limb patterns in either half; neighbouring coefficients equal / negatives of each other; random"""
+    rng = random.Random(20266)
+    f2r = lambda: (rng.randrange(P), rng.randrange(P))
+    const = lambda v: from_w([(v, v)] * 6)
+    pat = _patterns(P, (29, 30), 381)
+    fixed = GT_FIXED + [const(P - 1), const((P - 1) // 2)]
+    basis = [from_w([s if k == e else F2Z for k in range(6)]) for e in range(6) for s in ((1, 0), (1, 1))]
+    sub = [from_w([(rng.randrange(P), 0)] + [F2Z] * 5), from_w([f2r()] + [F2Z] * 5), from_w([f2r(), F2Z, f2r(), F2Z, f2r(), F2Z]), from_w([F2Z, f2r(), F2Z, f2r(), F2Z, f2r()])]
+    limb = [from_w([(pat[(2 * e) % len(pat)], rng.randrange(P)) for e in range(6)]), from_w([(rng.randrange(P), pat[(2 * e + 1) % len(pat)]) for e in range(6)]),
+            from_w([(pat[e], pat[(e + 5) % len(pat)]) for e in range(6)])]
+    a, b, c = f2r(), f2r(), f2r()
+    n = M.f2_neg
+    neigh = [from_w([a] * 6), from_w([a, a, b, b, c, c]), from_w([(a[0], a[0]), (b[0], b[0]), (c[0], c[0]), a, b, c]),
+             from_w([a, n(a), b, n(b), c, n(c)]), from_w([(a[0], P - a[0]), (b[0], P - b[0]), a, n(a), c, c])]
+    rnd = [from_w([f2r() for _ in range(6)]) for _ in range(12)]
+    return interleave(fixed, basis, sub, limb, neigh, rnd)
+
+
+@functools.lru_cache(None)
+def gt_cyclotomic():
+    """u^((p^6 - 1)(p^2 + 1)) of the non-zero elements: conj(u) / u, then its p^2-power times itself"""
+    out = []
+    for u in gt_elements():
+        if u != F12_ZERO:
+            t = M.f12_mul(M.f12_conj(u), M.f12_inv(u))
+            out.append(M.f12_mul(M.f12_frob(t, 2), t))
+    return out
+
+
+@functools.lru_cache(None)
+def gt_members():
+    return [M.final_exponentiation(c) for c in [c for c in gt_cyclotomic() if c != M.F12_ONE][3::5][:6]]
+
+
+def _pow_by_mul(a, b, reps):
+    w = M.f12_mul(a, b)
+    for _ in range(reps - 1):
+        w = M.f12_mul(w, b)
+    return w
+
+
+GT_REPS = (1, 2, 5)
+
+
+@functools.lru_cache(None)
+def gt_table(op):
+    """(rows, labels, {reps: expected words}) of one op — built once, shared by both halves"""
+    els = gt_elements()
+    lab = lambda n: [("row %d" % i,) for i in range(n)]
+    if op in ("gt_roundtrip", "gt_conj", "gt_neg", "gt_sqr_by_mul", "gt_frob1", "gt_frob2", "gt_inv"):
+        rows = gt_odd(els)
+        fn = {"gt_roundtrip": lambda a: a, "gt_conj": M.f12_conj, "gt_neg": lambda a: tuple(tuple(M.f2_neg(c) for c in six) for six in a),
+              "gt_sqr_by_mul": lambda a: M.f12_mul(a, a), "gt_frob1": lambda a: M.f12_frob(a, 1), "gt_frob2": lambda a: M.f12_frob(a, 2),
+              "gt_inv": lambda a: a if a == F12_ZERO else M.f12_inv(a)}[op]
+        return enc12(rows), rows, {1: enc12([fn(a) for a in rows])}
+    if op == "gt_mul":
+        n = len(els)
+        pairs = gt_odd(interleave([(els[i], els[(7 * i + 3) % n]) for i in range(n)], [(a, a) for a in els[::3]], [(a, M.f12_conj(a)) for a in els[1::4]]))
+        rows = np.hstack([enc12([a for a, _ in pairs]), enc12([b for _, b in pairs])])
+        return rows, lab(len(pairs)), {r: enc12([_pow_by_mul(a, b, r) for a, b in pairs]) for r in GT_REPS}
+    if op in ("gt_cyc_sqr", "gt_exp_by_x"):
+        rows = gt_odd(interleave(gt_cyclotomic(), gt_members()))
+        if op == "gt_exp_by_x":
+            return enc12(rows), lab(len(rows)), {1: enc12([M.f12_conj(M.f12_pow(c, M.X_ABS)) for c in rows])}
+        want, cur = {}, rows
+        for r in range(1, max(GT_REPS) + 1):
+            cur = [M.f12_mul(c, c) for c in cur]
+            if r in GT_REPS:
+                want[r] = enc12(cur)
+        return enc12(rows), lab(len(rows)), want
+    if op == "gt_final_exp":
+        cyc = gt_cyclotomic()
+        rows = gt_odd(GT_FIXED + els[3:8] + els[17:23] + [cyc[-1], cyc[-2], gt_members()[0]])
+        assert len(rows) < 20
+        fe = [M.final_exponentiation(a) for a in rows]
+        want = np.hstack([enc12([F12_ZERO if w is None else w for w in fe]), np.array([[int(w is None)] for w in fe], np.uint64)])
+        return enc12(rows), lab(len(rows)), {1: want}
+    if op == "gt_tail_step":
+        n = len(els)
+        pairs = gt_odd([(els[i], els[(5 * i + 2) % n]) for i in range(31)])
+        ks = (0, 1, 2, 15, 16, 199)                     # k p + (the coefficient's Montgomery image): raw values up to 200 p, as the sparse products leave them
+        raw = lambda f, s: [w for j, c in enumerate(_f12_flat(f)) for w in raw_words(carried(ks[(s + j) % len(ks)] * P + c * 2 ** 406 % P))]
+        rows = np.array([raw(f, i) + raw(l, i + 3) for i, (f, l) in enumerate(pairs)], np.uint64)
+        want, cur = {}, [f for f, _ in pairs]
+        for r in range(1, max(GT_REPS) + 1):
+            cur = [M.f12_mul(M.f12_mul(f, f), l) for f, (_, l) in zip(cur, pairs)]
+            if r in GT_REPS:
+                want[r] = enc12(cur)
+        return rows, lab(len(pairs)), want
+    raise KeyError(op)
+
+
+@functools.lru_cache(None)
+def gt_membership_table():
+    """rows and verdicts (bit 0: in the cyclotomic subgroup, bit 1: in GT): zero 0, one 3, cyclotomic images 1 — or 3 where the model says f^r = 1 —, GT members 3,
+    each GT member with one word of one coefficient changed 0, elements outside the cyclotomic subgroup 0.  Minus one is 0 as well: the subgroup's order
+    p^4 - p^2 + 1 is odd, so it holds no element of order two — the model's power below says so, whatever one might expect of a norm-one element."""
+    els, cyc, gts = gt_elements(), gt_cyclotomic(), gt_members()
+    m1 = GT_FIXED[2]
+    assert M.f12_pow(m1, P ** 4 - P ** 2 + 1) == m1 != M.F12_ONE and M.f12_mul(m1, m1) == M.F12_ONE
+
+    def in_cyclotomic(f):                               # f^(p^4) f = f^(p^2), through the model's Frobenius
+        f2 = M.f12_frob(f, 2)
+        return f != F12_ZERO and M.f12_mul(M.f12_frob(f2, 2), f) == f2
+    assert all(M.f12_pow(g, R) == M.F12_ONE for g in gts)
+    fixed = list(zip(enc12(GT_FIXED), (0, 3, 0)))
+    images = [(w, 3 if M.f12_pow(c, R) == M.F12_ONE else 1) for w, c in zip(enc12(cyc), cyc)]
+    members = [(w, 3) for w in enc12(gts)]
+    broken = []
+    for i, w in enumerate(enc12(gts)):
+        w = w.copy()
+        w[6 * (2 * i + 1) + i] ^= np.uint64(1)          # word i of coefficient 2 i + 1
+        assert U.fp_int(w[6 * (2 * i + 1):6 * (2 * i + 2)]) < P
+        broken.append((w, 0))
+    outside = [a for a in els if a not in GT_FIXED and not in_cyclotomic(a)]
+    assert len(outside) >= 12
+    rows = gt_odd(interleave(fixed, images, members, broken, [(w, 0) for w in enc12(outside)]))
+    return np.stack([w for w, _ in rows]), np.array([v for _, v in rows], np.uint64)
+
+
+@functools.lru_cache(None)
+def gt_shrink_table():
+    """gt_shrink's inputs, twelve Fp per row (lane e: the row's Fp 2 e and 2 e + 1).  k p + d as carried limbs, k in 0, 1, 2, 15, 16, 199, 200, 5038 and d in 0, 1,
+    p - 1 and the limb patterns; and limbs written directly: every low limb 0, 2^29 - 1 or 2^29 + 7 under a top limb of 0, 1, 12, 13, 14, 25, 26, 27, 208, 2600,
+    2^16 - 1.  The host half (the function's own assertions: low limbs <= 2^29 + 7, top limb < 2^16) accepts every one of them, so all are kept — those with a top
+    limb of 2600 and more, the range k_miller_tail's comment speaks of, among them."""
+    ds = [0, 1, P - 1] + _patterns(P, (29, 30), 381)
+    kd = [carried(k * P + d) for k in (0, 1, 2, 15, 16, 199, 200, 5038) for d in ds]
+    direct = [[low] * 13 + [top] for low in (0, 2 ** 29 - 1, 2 ** 29 + 7) for top in (0, 1, 12, 13, 14, 25, 26, 27, 208, 2600, 2 ** 16 - 1)]
+    fps = interleave(kd, direct)
+    assert any(l[13] >= 2600 for l in fps)
+    while len(fps) % 12 or (len(fps) // 12) % 3 == 0 or (len(fps) // 12) % 10 == 0:
+        fps.append(fps[(5 * len(fps)) % len(kd)])
+    return np.array([w for l in fps for w in raw_words(l)], np.uint64).reshape(len(fps) // 12, 84), fps
+
+
+def check_gt_shrink(got, fps):
+    """per Fp: result = input mod p, limbs 0..12 < 2^29, value < 2 p; the canonical words are those of the value"""
+    o = np.ascontiguousarray(got).view(np.uint32).reshape(-1, 52)           # per lane: c0's 14 limbs, c1's, then 12 + 12 canonical words
+    i22 = pow(2 ** 22, -1, P)                                                 # limbs hold x 2^406, the ABI words x 2^384
+    for i, l in enumerate(fps):
+        lane, half = o[i // 2], i % 2
+        r = [int(x) for x in lane[14 * half:14 * half + 14]]
+        v, vin = limbs_value(r), limbs_value(l)
+        assert v % P == vin % P, ("gt_shrink: value", i, l, r)
+        assert all(x < 2 ** 29 for x in r[:13]) and v < 2 * P, ("gt_shrink: limbs carried, value < 2 p", i, l, r)
+        canon = sum(int(x) << (32 * j) for j, x in enumerate(lane[28 + 12 * half:40 + 12 * half]))
+        assert canon == vin * i22 % P, ("gt_shrink: canonical words", i, l)
+
+
+@functools.lru_cache(None)
+def gt_digits_table():
+    from test_gpu_gt_pow import EDGE                    # (the exponents the GT-power tests use)
+    rng = random.Random(20268)
+    exps = odd_rows(_uniq(EDGE + [int("8" * 64, 16), int("9" * 64, 16), int("7" * 63 + "9", 16), 2 ** 256 - 1] + [rng.randrange(2 ** 256) for _ in range(40)]))
+    want = []
+    for x in exps:                                      # v = nibble + carry; v > 8 gives v - 16 and a carry; digit 64 is the carry out of bit 255
+        d, c = [], 0
+        for w in range(64):
+            v = ((x >> (4 * w)) & 15) + c
+            c = 1 if v > 8 else 0
+            d.append(v - 16 * c)
+        d.append(c)
+        assert sum(v * 16 ** w for w, v in enumerate(d)) == x and all(-7 <= v <= 8 for v in d)
+        want.append(d)
+    return exps, want
+
+
+def check_gt(run, family, groups):
+    """one family of ops through either backend, every table at every G of `groups` (and at every reps for the ops that feed their output back)"""
+    def plain(op):
+        rows, lab, want = gt_table(op)
+        for G in groups:
+            for reps, w in want.items():
+                mismatch(run(op, reps | G << 8, rows), w, lab, "%s G=%d reps=%d" % (op, G, reps))
+    if family == "lane_local":
+        rows, els, want = gt_table("gt_roundtrip")
+        srows, fps = gt_shrink_table()
+        for G in groups:
+            got = run("gt_roundtrip", 1 | G << 8, rows)
+            mismatch(got[:, :72], want[1], [("row %d" % i,) for i in range(len(els))], "gt_roundtrip G=%d" % G)
+            raw = np.ascontiguousarray(got[:, 72:]).view(np.uint32).reshape(len(els), 6, 2, 14)          # the scratch element in the internal form
+            for i, f in enumerate(els):
+                for e, c in enumerate(w_coeffs(f)):
+                    for h in (0, 1):
+                        l = [int(x) for x in raw[i, e, h]]
+                        assert limbs_value(l) % P == c[h] * 2 ** 406 % P and limbs_value(l) < 2 * P and all(x <= 2 ** 29 + 7 for x in l[:13]), ("gt_put / gt_get", G, i, e, h)
+            check_gt_shrink(run("gt_shrink", 1 | G << 8, srows), fps)
+        for op in ("gt_conj", "gt_neg", "gt_frob1", "gt_frob2"):
+            plain(op)
+    elif family == "products":
+        for op in ("gt_mul", "gt_sqr_by_mul", "gt_tail_step"):
+            plain(op)
+    elif family == "cyclotomic":
+        for op in ("gt_cyc_sqr", "gt_exp_by_x"):
+            plain(op)
+    elif family == "inverse":
+        plain("gt_inv")
+    elif family == "final_exp":
+        plain("gt_final_exp")
+    elif family == "membership":
+        rows, want = gt_membership_table()
+        for G in groups:
+            got = run("gt_membership", 1 | G << 8, rows)[:, 0]
+            bad = np.nonzero(got != want)[0]
+            assert not len(bad), ("gt_membership G=%d: rows %s give %s, want %s" % (G, bad[:8], got[bad[:8]], want[bad[:8]]))
+    elif family == "digits":
+        exps, want = gt_digits_table()
+        got = run("gt_digits", 1, words(exps, 32))
+        d = np.ascontiguousarray(got).view(np.int8).reshape(len(exps), 72)
+        for i, x in enumerate(exps):
+            assert [int(v) for v in d[i, :65]] == want[i] and not d[i, 65:].any(), ("gt_signed_digits", hex(x))
+    else:
+        raise KeyError(family)
+
+
+GT_FAMILIES = ("lane_local", "products", "cyclotomic", "inverse", "final_exp", "membership", "digits")
+
+
+# ---- the line steps (pairing29.hip.h) against a transcription of the ark-ec M-twist formulas (bls12/g2.rs double_in_place / add_in_place) ----
+def line_dbl(Rp):
+    X, Y, Z = Rp
+    half = lambda t: M.f2_mul_fp(t, (P + 1) // 2)
+    a, b, c = half(M.f2_mul(X, Y)), M.f2_sqr(Y), M.f2_sqr(Z)
+    e = M.f2_mul_fp(M.f2_mul(c, (1, 1)), 12)
+    f = M.f2_mul_fp(e, 3)
+    g, h = half(M.f2_add(b, f)), M.f2_sub(M.f2_sqr(M.f2_add(Y, Z)), M.f2_add(b, c))
+    i, j = M.f2_sub(e, b), M.f2_sqr(X)
+    Rn = (M.f2_mul(a, M.f2_sub(b, f)), M.f2_sub(M.f2_sqr(g), M.f2_mul_fp(M.f2_sqr(e), 3)), M.f2_mul(b, h))
+    return Rn, (i, M.f2_mul_fp(j, 3), M.f2_neg(h))
+
+
+def line_add(Rp, Q):
+    X, Y, Z = Rp
+    theta, lam = M.f2_sub(Y, M.f2_mul(Q[1], Z)), M.f2_sub(X, M.f2_mul(Q[0], Z))
+    c, d = M.f2_sqr(theta), M.f2_sqr(lam)
+    e, f, g = M.f2_mul(lam, d), M.f2_mul(Z, c), M.f2_mul(X, d)
+    h = M.f2_sub(M.f2_add(e, f), M.f2_add(g, g))
+    Rn = (M.f2_mul(lam, h), M.f2_sub(M.f2_mul(theta, M.f2_sub(g, h)), M.f2_mul(e, Y)), M.f2_mul(Z, e))
+    return Rn, (M.f2_sub(M.f2_mul(theta, Q[0]), M.f2_mul(lam, Q[1])), M.f2_neg(theta), lam)
+
+
+LINE_STEPS = (1, 3)
+
+
+@functools.lru_cache(None)
+def line_tables():
+    """(doubling rows R, addition rows (R, Q)): R = Q with Z = 1 (the first step) over generator multiples 1 .. 6, their negatives and the off-subgroup points;
+    coordinates with a zero half, c0 = +-c1, limb patterns, Y = 0, random R; for the addition also R projectively equal to Q and to -Q (theta = lambda = 0, and
+    lambda = 0 alone).  The formulas are polynomial, so the degenerate rows have exact expected words too."""
+    rng = random.Random(20267)
+    f2r = lambda: (rng.randrange(P), rng.randrange(P))
+    off = U.off_subgroup_points()
+    pts = [M.g2_mul(M.G2_GEN, k) for k in range(1, 7)]
+    pts = pts + [M.g2_neg(q) for q in pts] + [off["T2"][0], off["S2"][0]]
+    pat = _patterns(P, (29, 30), 381)
+    a, b, c = (rng.randrange(P) for _ in range(3))
+    first = [(q[0], q[1], (1, 0)) for q in pts]
+    edge = [((a, 0), (0, b), (c, 0)), ((0, a), (b, 0), (0, c)), ((a, a), (b, P - b), (c, c)), ((a, P - a), (b, b), (c, P - c)),
+            ((pat[0], pat[1]), (pat[2], pat[3]), (pat[4], pat[5])), ((pat[5], pat[6]), (pat[7], pat[8]), (pat[9], pat[0])),
+            (f2r(), F2Z, f2r()), (pts[0][0], F2Z, (1, 0)), (F2Z, f2r(), f2r()), (f2r(), f2r(), F2Z)]
+    rnd = [(f2r(), f2r(), f2r()) for _ in range(10)]
+    dbl = odd_rows(interleave(first, edge, rnd))
+    scale = lambda q, z, s=1: (M.f2_mul(q[0], z), M.f2_mul(M.f2_mul_fp(q[1], s % P), z), z)
+    add = [(line_dbl(r)[0], (r[0], r[1])) for r in first]                                    # the loop's own first addition: R = 2 Q
+    add += [(scale(q, f2r()), q) for q in pts[:4]] + [(scale(q, f2r(), -1), q) for q in pts[:4]] + [((q[0], q[1], (1, 0)), q) for q in pts[4:6]]
+    add += [(r, (r[2], r[0])) for r in edge] + [(r, pts[i]) for i, r in enumerate(edge)] + [(r, pts[(3 * i) % len(pts)]) for i, r in enumerate(rnd)]
+    add += [((f2r(), f2r(), f2r()), (f2r(), f2r())) for _ in range(6)]
+    return dbl, odd_rows(add)
+
+
+@functools.lru_cache(None)
+def line_expected():
+    dbl, add = line_tables()
+    flat = lambda Rn, l: Rn + l
+    want = {}
+    for s in LINE_STEPS:
+        out = []
+        for r in dbl:
+            for _ in range(s):
+                r, l = line_dbl(r)
+            out.append(flat(r, l))
+        want["dbl", s] = cols(out, enc_f2)
+        out = []
+        for r, q in add:
+            for _ in range(s):
+                r, l = line_add(r, q)
+            out.append(flat(r, l))
+        want["add", s] = cols(out, enc_f2)
+    return cols(dbl, enc_f2), cols([r + q for r, q in add], enc_f2), want
+
+
+def check_lines(run, names=("line_dbl", "line_add")):
+    dbl, add = line_tables()
+    drows, arows, want = line_expected()
+    for s in LINE_STEPS:
+        mismatch(run(names[0], s, drows), want["dbl", s], dbl, "%s x %d" % (names[0], s))
+        mismatch(run(names[1], s, arows), want["add", s], add, "%s x %d" % (names[1], s))
+
+
 def test_op_table_matches_the_kernel_header():
-    """the numbers and row shapes above are those of selftest_kernels.hip.h (a mismatch would otherwise only show as a refused call)"""
+    """the numbers and row shapes above are those of selftest_kernels.hip.h and selftest_gt_kernels.hip.h (a mismatch would otherwise only show as a refused call)"""
     import re
-    src = open(os.path.join(CSRC, "selftest_kernels.hip.h")).read()
+    src = open(os.path.join(CSRC, "selftest_kernels.hip.h")).read() + open(os.path.join(CSRC, "selftest_gt_kernels.hip.h")).read()
     body = re.search(r"enum : int \{(.*?)ST_OP_END", src, re.S).group(1)
     body = re.sub(r"//[^\n]*", "", body)
     num, nxt = {}, 0
@@ -480,10 +864,16 @@ def test_op_table_matches_the_kernel_header():
     assert num == {k: v[0] for k, v in OPS.items()}
     val = lambda e: eval(re.sub(r"SW<(\w+)>::N", lambda m: {"Fp": "12", "Fs": "12", "Fp2": "24", "Fs2": "24"}[m.group(1)], e.replace("ST_CHAIN_IN(Fp)", str(_CH1)).replace("ST_CHAIN_IN(Fs)", str(_CH1))
                                  .replace("ST_CHAIN_IN(Fp2)", str(_CH2)).replace("ST_CHAIN_IN(Fs2)", str(_CH2)).replace("ST_PT_OUT(Fp)", "24").replace("ST_PT_OUT(Fs)", "24")
-                                 .replace("ST_PT_OUT(Fp2)", "48").replace("ST_PT_OUT(Fs2)", "48")))
+                                 .replace("ST_PT_OUT(Fp2)", "48").replace("ST_PT_OUT(Fs2)", "48").replace("ST_GT_RAW", "84").replace("ST_GT_SHRUNK", "26").replace("GT_LANES", "6")))
+    assert re.search(r"constexpr int ST_GT_RAW = GT_LANES \* NL;", src) and re.search(r"constexpr int ST_GT_SHRUNK = 26;", src)
     seen = {}
     for dev, name, lanes, iw, ow in re.findall(r"^ST_(DEV_)?OP\(ST_(\w+), (\d), (.+?), ([^,]+?)\) \{", src, re.M):
         seen[name.lower()] = (val(iw), val(ow), 0 if dev else 1)
+    six = {}
+    for name, iw, ow in re.findall(r"^ST_GT_OP\(ST_(\w+), (.+?), ([^,]+?)\) \{", src, re.M):        # the third macro: six lanes per row, host and device
+        six[name.lower()] = (val(iw), val(ow), 1)
+    assert set(six) == GT_SIX and not set(six) & set(seen)
+    seen.update(six)
     assert seen == {k: v[1:] for k, v in OPS.items() if v[1] is not None}
 
 
@@ -511,6 +901,53 @@ def test_host_fp12(shim):
 @pytest.mark.parametrize("g", [1, 2])
 def test_host_group_law(shim, g):
     check_group(host_backend(shim), g, G1_HOST if g == 1 else G2_HOST)
+
+
+@pytest.mark.parametrize("family", GT_FAMILIES)
+def test_host_gt_ops(gt_shim, family):
+    """the six-lane wrappers with six threads as the lanes, under the bound tracker (G means nothing on the host)"""
+    check_gt(gt_host_backend(gt_shim), family, (1,))
+
+
+def test_host_gt_refuses_other_ops_and_shapes(gt_shim):
+    z = np.zeros(256, np.uint64)
+    p = z.ctypes.data_as(C.c_void_p)
+    assert gt_shim.shim_selftest_gt(OPS["gt_conj"][0], 1 | 3 << 8, p, 72, 1, p, 72) == 0
+    assert gt_shim.shim_selftest_gt(OPS["gt_conj"][0], 1 | 1 << 8, p, 71, 1, p, 72) == -3
+    assert gt_shim.shim_selftest_gt(OPS["fp_mul"][0], 1 | 1 << 8, p, 12, 1, p, 6) == -3
+    assert gt_shim.shim_selftest_gt(OPS["gt_mul"][0], 65 | 1 << 8, p, 144, 1, p, 72) == -3
+
+
+def test_host_line_steps(shim):
+    """line_dbl_step / line_add_step (the wrappers the device runs), then the same rows through the forms the lane-distributed kernels run —
+    line_dbl_step_fast, line_dbl_step_ws, line_add_step_ws —, which have no one-lane kernel on the device"""
+    check_lines(host_backend(shim))
+    form = lambda k: (lambda name, stress, rows: _run(lambda op, *a: shim.shim_line_steps(k, *a), name, stress, rows))
+    fast, ws_dbl, ws_add = form(0), form(1), form(2)
+    check_lines(lambda name, s, rows: (fast if name == "line_dbl" else ws_add)(name, s, rows))
+    check_lines(lambda name, s, rows: (ws_dbl if name == "line_dbl" else ws_add)(name, s, rows))
+
+
+def test_host_line_transcription_is_the_miller_loops_step(shim):
+    """the transcription above is the function the loop uses: its 68 lines are those of shim_miller_lines, and folded they give the model's Miller loop"""
+    shim.shim_miller_lines.argtypes = [C.c_void_p] * 3
+    for Pa, Q in ((M.g1_mul(M.G1_GEN, 3), M.g2_mul(M.G2_GEN, 5)), (M.g1_mul(M.G1_GEN, 7), U.off_subgroup_points()["T2"][0])):
+        Rp, lines = (Q[0], Q[1], (1, 0)), []
+        for bit in X_BITS:
+            Rp, l = line_dbl(Rp); lines.append(l)
+            if bit == "1":
+                Rp, l = line_add(Rp, Q); lines.append(l)
+        assert len(lines) == 68
+        ev = [(l[0], M.f2_mul_fp(l[1], Pa[0]), M.f2_mul_fp(l[2], Pa[1])) for l in lines]
+        pw, qw, out = np.ascontiguousarray(enc_fp(list(Pa)).reshape(-1)), np.ascontiguousarray(enc_f2(list(Q)).reshape(-1)), np.zeros((68, 36), np.uint64)
+        shim.shim_miller_lines(pw.ctypes.data_as(C.c_void_p), qw.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        mismatch(out, cols(ev, enc_f2), [("line %d" % i,) for i in range(68)], "the Miller loop's lines")
+        f, it = M.F12_ONE, iter(ev)
+        for bit in X_BITS:
+            f = M.f12_mul_by_014(M.f12_mul(f, f), *next(it))
+            if bit == "1":
+                f = M.f12_mul_by_014(f, *next(it))
+        assert M.f12_conj(f) == M.multi_miller_loop([Pa], [Q])
 
 
 def test_host_refuses_what_it_cannot_run(shim):
@@ -562,6 +999,35 @@ def test_gpu_group_law_shared_lanes(twin, g):
     """ec29_two_lane.hip.h (two lanes per G1 point, four per G2 point), xyzz_phi and xyzz_to_affine: the chains of the one-lane test, P + P, P + (-P) and
     the identity partway among them, so the special branch is taken by some rows of a wave and not by their neighbours"""
     check_group(gpu_backend(twin), g, G1_DEVICE if g == 1 else G2_DEVICE)
+
+
+# Time limits of the GT tests: a call is one launch of at most 67 groups; the longest chain, gt_final_exp, is some 400 lane-group products and squarings
+# (milliseconds on the device).  What a test spends is the model's expectations (seconds, built once per table and shared with the host half) and the
+# first call's start-up, so 120 s is a limit only a hung kernel reaches.
+@pytest.mark.gpu
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("family", GT_FAMILIES)
+def test_gpu_gt_ops(twin, family):
+    """the six-lane wrappers behind GT_GROUP_PROLOGUE, every table at 1, 3 and 10 groups per wave: GtLanesDev's slots, ballots and early lane exits"""
+    check_gt(gpu_backend(twin), family, GT_GROUPS)
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(120)
+def test_gpu_line_steps(twin):
+    check_lines(gpu_backend(twin))
+
+
+@pytest.mark.gpu
+def test_gpu_gt_refuses_other_group_counts(twin):
+    z = np.zeros(256, np.uint64)
+    p = z.ctypes.data_as(C.c_void_p)
+    op = OPS["gt_conj"][0]
+    for G in range(0, 12):
+        assert twin.dgpu_selftest_arith(op, 1 | G << 8, p, 72, 0, p, 72) == (0 if G in GT_GROUPS else -3), G
+    assert twin.dgpu_selftest_arith(op, 65 | 1 << 8, p, 72, 0, p, 72) == -3
+    assert twin.dgpu_selftest_arith(op, 1 | 3 << 8, p, 71, 0, p, 72) == -3
+    assert twin.dgpu_selftest_arith(OPS["fp_mul"][0], 1 | 1 << 8, p, 12, 0, p, 6) == -3          # the plain ops take no G
 
 
 @pytest.mark.gpu
