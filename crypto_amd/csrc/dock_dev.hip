@@ -34,6 +34,28 @@ int32_t dgpu_dev_get_ntt_last(int32_t *path, int32_t *groups, int32_t cap) {
     int route = 0; const int n = ntt::dev_get_ntt_last(&route, groups, cap);
     *path = route; return n;
 }
+// the chunking and the heavy-bucket count the last bucket MSM left in its slot's accumulate workspace (sl.dyn, sl.heavy: grow-only, never cleared).  The slots
+// are handed out in turn (SlotLock: cx.rr), so with one call at a time the slot of the last call is rr - 1; read only, nothing of the product's state changes
+int32_t dgpu_dev_get_acc_last(uint32_t out[6]) {
+    if (!out) return DGPU_E_BADARG;
+    Ctx &cx = cur();
+    if (!cx.ready) return DGPU_E_NODEVICE;
+    const unsigned taken = cx.rr.load();
+    if (!taken) return DGPU_E_BADARG;                              // no call has taken a slot yet
+    Slot &sl = cx.slots[(taken - 1) % N_SLOTS];
+    std::lock_guard<std::mutex> lk(sl.mu);
+    if (!sl.stream || !sl.dyn.p || !sl.heavy.p || sl.dyn.cap < (size_t)msm::DYN_MULTI * 4 || sl.heavy.cap < 4) return DGPU_E_BADARG;
+    HIPCHK(hipSetDevice(cx.device));
+    HIPCHK(hipStreamSynchronize(sl.stream));
+    uint32_t w[6];
+    HIPCHK(hipMemcpy(w, sl.dyn.p, (size_t)msm::DYN_MULTI * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(w + 5, sl.heavy.p, 4, hipMemcpyDeviceToHost));
+    const uint32_t ch = w[msm::DYN_CH], E = w[msm::DYN_E];
+    // a workspace that was reserved but never used holds whatever the allocation held: k_dyn_chunk's words always satisfy these relations
+    if (ch < 16 || w[msm::DYN_HEAVY] != 16u * ch || w[msm::DYN_T] != (uint32_t)(((uint64_t)E + ch - 1) / ch)) return DGPU_E_BADARG;
+    out[0] = ch; out[1] = w[msm::DYN_T]; out[2] = w[msm::DYN_HEAVY]; out[3] = E; out[4] = w[msm::DYN_NMULTI]; out[5] = w[5];
+    return DGPU_OK;
+}
 int32_t dgpu_dev_set_saver_fp_bits(int32_t bits) { if (bits < -1 || bits > 63) return DGPU_E_BADARG; gs.saver_fp_bits = bits; return DGPU_OK; }
 int32_t dgpu_set_reduce_lanes(int32_t lanes) { if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4) return DGPU_E_BADARG; gs.reduce_lanes = lanes; return DGPU_OK; }
 int32_t dgpu_set_reduce_shift(int32_t sh) { if (sh < -1 || sh > 6) return DGPU_E_BADARG; gs.reduce_shift = sh; return DGPU_OK; }

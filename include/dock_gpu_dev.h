@@ -62,6 +62,16 @@ int32_t dgpu_dev_get_acc_d_unroll(void);
  * groups in launch order (per stage: n = log2 D ones); returns n (0: no transform yet). */
 int32_t dgpu_dev_set_ntt(int32_t path, const int32_t *split, int32_t n_split);
 int32_t dgpu_dev_get_ntt_last(int32_t *path, int32_t *groups, int32_t cap);
+/* What the accumulate stage of the last bucket MSM decided on the device (crypto_amd/csrc/dyn_chunk.hip.h, msm_kernels.hip.h K5 / K6), read back after the call
+ * has returned: out[0] = terms per chunk CH, out[1] = chunks with work T, out[2] = the heavy threshold 16 CH (a bucket of at least that many terms is folded by a
+ * block, k_fixup_heavy), out[3] = the sorted (bucket, term) pairs E, out[4] = heavy buckets of more than 512 pieces (folded range by range: k_fixup_heavy_ranges /
+ * _join), out[5] = heavy buckets in all (those of out[4] included).  Read only: it copies the words the call left in its slot's workspace, which only grows.
+ * WHICH slot: the calling thread's context hands its slots out in turn, and this reads the one handed out last — the last call's as long as calls are made one at
+ * a time on one context (what tests/test_gpu_heavy_buckets.py does); with calls in flight side by side, or after a call that takes a slot without accumulating
+ * (an upload, dgpu_scalars_sort, an MSM on the bucket-free small path), it reads another call's leftovers or fails.  A call of 2^19 terms or more with host
+ * scalars runs two term ranges and leaves the second one's words.  DGPU_E_BADARG: out is NULL, no call has taken a slot yet, or that slot's workspace holds no
+ * consistent words (no accumulation has run on it). */
+int32_t dgpu_dev_get_acc_last(uint32_t out[6]);
 /* Bits of the table fingerprints of the SAVER keys created from now on (dgpu_saver_dk_create of include/dock_gpu_saver.h: libdock_gpu_saver_dev.so serves both; existing keys keep theirs): 1 .. 63 keeps the low bits, 0 restores
  * all 64, -1 keeps none, so that a whole column is ONE run of equal fingerprints.  Any setting gives the same chunks: the fingerprint only finds candidates
  * (tests make runs exist by pigeonhole with 3 bits at b = 4). */

@@ -77,8 +77,10 @@ def test_vs_oracle_seeded(gname, n):
 
 @pytest.mark.parametrize("path", ["tree", "buckets"])
 def test_edge_cases_g1(path):
-    """P == Q and P == -Q inside a bucket, heavy buckets, identities: on the bucket pipeline these exercise k_accumulate's special cases, the heavy-bucket
-    folds and the reduction; on the tree path (what a 200-term call takes by default) the same inputs meet the general addition's"""
+    """P == Q and P == -Q inside a bucket, crowded buckets, identities: on the bucket pipeline these exercise k_accumulate's special cases, the one-lane
+    fix-up and the reduction; on the tree path (what a 200-term call takes by default) the same inputs meet the general addition's.  (The crowded buckets
+    here hold 50 and 200 terms: a bucket is heavy from 16 chunks of at least 16 terms, so none of them reaches k_fixup_heavy or the range folds — those are
+    tests/test_gpu_heavy_buckets.py's.)"""
     import contextlib
     with (U.bucket_pipeline() if path == "buckets" else contextlib.nullcontext()):
         _edge_cases_g1()
@@ -98,7 +100,7 @@ def _edge_cases_g1():
     sc[5] = sc[4]
     inf[7] = 1                                 # flagged identity base
     bases[8] = 0                               # all-zero words == identity
-    sc[10:60] = O.int_to_limbs(1, 4)           # many equal tiny scalars: one heavy bucket
+    sc[10:60] = O.int_to_limbs(1, 4)           # many equal tiny scalars: one crowded bucket (50 terms: cut by chunk borders, far from heavy)
     sc[60:90] = O.int_to_limbs(12345, 4)
     got = ca.msm_bigint(curve, bases, sc, inf)
     inf2 = inf.copy(); inf2[8] = 1

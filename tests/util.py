@@ -367,3 +367,79 @@ def edge_coverage_missing(scalars, c, part_log=None, per_window=False):
         have = set(abs(d) - 1 for w in ws for d in seen[w] if d)
         miss += [("bucket", ws[0], b) for b in borders if b not in have]
     return miss
+
+
+# ---- the chunking of the accumulate stage (crypto_amd/csrc/msm_kernels.hip.h K5 / K6, dyn_chunk.hip.h) as a model: which buckets chunk borders cut, and which
+# ---- of the three folds puts each together again (tests/test_acc_layout.py, tests/test_gpu_heavy_buckets.py) ---------------------------------------------
+HEAVY_CHUNKS = 16           # a bucket of at least 16 chunk lengths of terms is heavy (dyn[DYN_HEAVY] = 16 CH)
+HEAVY_RANGE = 512           # a heavy bucket of more pieces than this is folded range by range, the ranges cut at multiples of 512 chunk indices
+
+
+def closed_form_dlogs(G, scalars, dlogs):
+    """(sum s_i dlog_i) * generator as a model point: closed_form for bases that repeat (scalars: integers or limbs; dlogs: one integer per term)"""
+    tot = sum((s if isinstance(s, int) else O.limbs_to_int(s)) * k for s, k in zip(scalars, dlogs)) % R
+    return jac_to_model(G, G.mul(G.generator(), O.int_to_limbs(tot, 4)))
+
+
+class AccBucket:
+    """one occupied bucket of an AccLayout: terms, the chunks t0 .. t1 that hold its first and last term, pieces = t1 - t0 + 1, cls (below), and for a
+    `multi` bucket ranges = [(k, pieces of range k)] for k = t0 // 512 .. t1 // 512"""
+    __slots__ = ("b", "terms", "t0", "t1", "pieces", "cls", "ranges")
+
+    def __repr__(self):
+        return "AccBucket(b=%d, terms=%d, t0=%d, t1=%d, pieces=%d, cls=%s, ranges=%s)" % (self.b, self.terms, self.t0, self.t1, self.pieces, self.cls, self.ranges)
+
+
+class AccLayout:
+    """what acc_layout returns: ch, E (sorted pairs), T = ceil(E / ch) chunks, off[0 .. NB] (numpy, off[NB] = E), buckets {index: AccBucket} of the occupied
+    ones, heavy = the indices with at least 16 ch terms (class heavy or multi), multi = those of more than 512 pieces"""
+
+    def chunk_slots(self, t):
+        """(head_b, tail_b) of chunk t as k_accumulate leaves them: the bucket cut on the chunk's left border (its sum goes to the head slot, also when it is
+        cut on the right as well) and the one cut on the right border only (tail slot); None where the slot stays empty"""
+        start, end = t * self.ch, min((t + 1) * self.ch, self.E)
+        assert start < end
+        first = int(np.searchsorted(self.off, start, side="right")) - 1          # the largest b with off[b] <= start
+        last = int(np.searchsorted(self.off, end - 1, side="right")) - 1
+        head = first if self.off[first] < start else None
+        tail = last if self.off[last + 1] > end and not (last == first and head is not None) else None
+        return head, tail
+
+
+def acc_layout(scalars, c, ch, shared, identity_rows=()):
+    """The sorted list of an MSM over integer `scalars` at window width c, cut into chunks of ch terms: every non-zero signed digit d of window w is one
+    term of bucket w B + |d| - 1 (shared: of bucket |d| - 1 — the one bucket set of a table), buckets in index order.  identity_rows: terms the sort drops
+    (rows whose base is an identity, on the routes whose sort sees the bases).  Classes, as the kernels take them: `direct` = one piece (k_accumulate writes
+    the bucket itself), `fixup` = cut, fewer than 16 ch terms (one lane of k_fixup), `heavy` = at least 16 ch terms, at most 512 pieces (one block of
+    k_fixup_heavy), `multi` = more pieces (k_fixup_heavy_ranges / _join)."""
+    from collections import Counter
+    W, B, _, _ = window_shape(c)
+    NB = B if shared else W * B
+    skip = set(identity_rows)
+    cnt = np.zeros(NB, np.int64)
+    for s, k in Counter(s for i, s in enumerate(scalars) if s and i not in skip).items():
+        for w, d in enumerate(signed_digits(s, c)):
+            if d:
+                cnt[(0 if shared else w * B) + abs(d) - 1] += k
+    L = AccLayout()
+    L.c, L.ch, L.shared, L.NB = c, ch, shared, NB
+    L.off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    L.E = int(L.off[NB])
+    L.T = (L.E + ch - 1) // ch
+    L.buckets, L.heavy, L.multi = {}, [], []
+    for b in np.nonzero(cnt)[0].tolist():
+        k = AccBucket()
+        k.b, k.terms = b, int(cnt[b])
+        k.t0, k.t1 = int(L.off[b]) // ch, (int(L.off[b + 1]) - 1) // ch
+        k.pieces = k.t1 - k.t0 + 1
+        k.ranges = None
+        if k.terms >= HEAVY_CHUNKS * ch:
+            L.heavy.append(b)
+            k.cls = "multi" if k.pieces > HEAVY_RANGE else "heavy"
+            if k.cls == "multi":
+                L.multi.append(b)
+                k.ranges = [(r, min((r + 1) * HEAVY_RANGE - 1, k.t1) - max(r * HEAVY_RANGE, k.t0) + 1) for r in range(k.t0 // HEAVY_RANGE, k.t1 // HEAVY_RANGE + 1)]
+        else:
+            k.cls = "direct" if k.pieces == 1 else "fixup"
+        L.buckets[b] = k
+    return L
