@@ -98,7 +98,8 @@ _init_args = None    # ("init", device, min_gpu_n) / ("list", [devices], min_gpu
 # every symbol include/dock_gpu_dev.h adds (the twin only)
 DEV_SYMBOLS = ["dgpu_set_window_bits", "dgpu_set_chunk", "dgpu_set_many_chunk_rows", "dgpu_set_msm_segments", "dgpu_set_reduce_shift", "dgpu_set_reduce_lanes", "dgpu_set_miller_pipeline", "dgpu_set_gt_pow", "dgpu_set_wm_many",
                "dgpu_prof_enable", "dgpu_prof_reset", "dgpu_prof_read", "dgpu_selftest_fp_mul", "dgpu_selftest_g1_sum", "dgpu_selftest_arith", "dgpu_selftest_glv_decompose", "dgpu_selftest_gls4_decompose",
-               "dgpu_dev_fail_alloc_after", "dgpu_dev_set_acc_split", "dgpu_dev_get_acc_split", "dgpu_dev_set_acc_d_pass", "dgpu_dev_set_acc_d_unroll", "dgpu_dev_get_acc_d_unroll", "dgpu_dev_set_ntt", "dgpu_dev_get_ntt_last", "dgpu_dev_get_acc_last", "dgpu_dev_set_saver_fp_bits"]
+               "dgpu_dev_fail_alloc_after", "dgpu_dev_set_acc_split", "dgpu_dev_get_acc_split", "dgpu_dev_set_acc_d_pass", "dgpu_dev_set_acc_d_unroll", "dgpu_dev_get_acc_d_unroll", "dgpu_dev_set_ntt", "dgpu_dev_get_ntt_last", "dgpu_dev_get_acc_last", "dgpu_dev_set_saver_fp_bits",
+               "dgpu_selftest_psort", "dgpu_selftest_sort_sweep", "dgpu_selftest_scan", "dgpu_selftest_dyn_chunk", "dgpu_selftest_choose_chunk"]
 
 # every symbol include/dock_gpu.h declares
 SYMBOLS = [
@@ -468,5 +469,11 @@ def _load(path):
             L.dgpu_dev_set_ntt.argtypes = [C.c_int32, vp, C.c_int32]
             L.dgpu_dev_get_ntt_last.argtypes = [C.POINTER(C.c_int32), vp, C.c_int32]
             L.dgpu_dev_get_acc_last.argtypes = [vp]
+            u32, i32 = C.c_uint32, C.c_int32
+            L.dgpu_selftest_psort.argtypes = [vp, sz, i32, i32, u32, u32, u32, vp, u32, u32, u32, vp, i32, vp, vp, vp, vp, vp, C.POINTER(i32)]
+            L.dgpu_selftest_sort_sweep.argtypes = [vp, sz, i32, i32, vp, u32, u32, vp, vp, vp, vp, vp, vp]
+            L.dgpu_selftest_scan.argtypes = [vp, sz, i32, vp, vp]
+            L.dgpu_selftest_dyn_chunk.argtypes = [u32, u32, u32, u32, u32, u32, u32, vp]
+            L.dgpu_selftest_choose_chunk.argtypes = [u64, i32, u64, i32, u64]
         _loaded[path] = L
     return _loaded[path]

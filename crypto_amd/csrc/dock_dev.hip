@@ -9,6 +9,8 @@
 
 using namespace dock;
 
+#include "dev_sort_hooks.hip.h"      // dgpu_selftest_psort, _sort_sweep, _scan, _dyn_chunk, _choose_chunk: the MSM sort stage on its own
+
 extern "C" {
 
 int32_t dgpu_set_window_bits(int32_t c) { if (c != 0 && (c < 7 || c > 22)) return DGPU_E_BADARG; gs.window_bits = c; return DGPU_OK; }

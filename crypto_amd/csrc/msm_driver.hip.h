@@ -51,9 +51,10 @@ struct PlainGeom {
     AccGeom acc;
     bool psort;            // the two-level partition sort (psort_kernels.hip.h) instead of the per-window sweeps: large n
 };
-template <class C> int32_t plain_geometry(size_t n, PlainGeom &g) {
+// c: the window width (plain_geometry: choose_c's)
+template <class C> int32_t plain_geometry_at(size_t n, int c, PlainGeom &g) {
     if (n >= (1ull << 31)) return DGPU_E_BADARG;
-    g.c = choose_c(n, C::NFP == 2);
+    g.c = c;
     g.W = 255 / g.c + 1;
     g.B = 1u << (g.c - 1);
     if ((uint64_t)g.W * g.B >= (1ull << 31) || (uint64_t)n * g.W >= (1ull << 32)) return DGPU_E_BADARG;
@@ -72,9 +73,10 @@ template <class C> int32_t plain_geometry(size_t n, PlainGeom &g) {
     g.lds_bytes = ((size_t)1 << g.rb_log) * 4;
     // From 2^17 terms on the sweeps (every digit column re-read once per bucket range: 0.38 ms at n = 2^20) give way to the partition sort the table
     // pipeline uses (0.2 ms), with one bucket set per window in the key: key = w B + |digit| - 1
-    g.psort = g.W <= PS_MAX_W && n >= PLAIN_PSORT_MIN_N;
+    g.psort = n >= PLAIN_PSORT_MIN_N && plain_psort_fits(g.W, g.NB);
     return DGPU_OK;
 }
+template <class C> int32_t plain_geometry(size_t n, PlainGeom &g) { return plain_geometry_at<C>(n, choose_c(n, C::NFP == 2), g); }
 // grow-only workspace of one slot for the plain pipeline of that geometry (no-ops once the slot has seen the size: dgpu_reserve_*, uploads)
 template <class C> int32_t ws_plain(Slot &sl, const PlainGeom &g) {
     int32_t rc;

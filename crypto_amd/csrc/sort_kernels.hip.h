@@ -137,12 +137,15 @@ __global__ void __launch_bounds__(256) k_scan_add(uint32_t *__restrict__ out, ui
 __global__ void k_dyn_chunk(const uint32_t *__restrict__ total, uint32_t fixed_ch, uint32_t min_chunk, uint32_t max_chunks, uint32_t lanes_per_chunk, uint32_t T_max, uint32_t *__restrict__ dyn, uint32_t nb_shared) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const uint32_t E = *total;
+    // ceil(E / ch) in 64 bits: E + ch - 1 leaves 32 bits from E = 2^32 - ch + 1 on (plain_geometry admits every n W < 2^32), and the wrapped quotient
+    // was a chunk count of 0 or 1 — choose_chunk on the host, which computes in size_t, is the rule
+    const auto ceil_div = [](uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a + b - 1) / b); };
     uint32_t ch = fixed_ch;
     if (!ch) {
         ch = min_chunk;
         while (E / ch > max_chunks && ch < 4096) ch *= 2;
         const uint32_t resident = RESIDENT_ACC_LANES / lanes_per_chunk;
-        const uint32_t chunks = (E + ch - 1) / ch;
+        const uint32_t chunks = ceil_div(E, ch);
         if (chunks > resident) {            // whole rounds of the chip
             uint32_t rounds = (chunks + resident / 2) / resident;
             if (rounds < 1) rounds = 1;
@@ -157,8 +160,8 @@ __global__ void k_dyn_chunk(const uint32_t *__restrict__ total, uint32_t fixed_c
             if (one > ch && 2 * run >= one && one <= 4096) ch = one;
         }
     }
-    if (T_max && (E + ch - 1) / ch > T_max) ch = (E + T_max - 1) / T_max;      // never more chunks than partial slots
-    dyn[DYN_CH] = ch; dyn[DYN_T] = (E + ch - 1) / ch; dyn[DYN_HEAVY] = 16u * ch; dyn[DYN_E] = E; dyn[DYN_NMULTI] = 0;
+    if (T_max && ceil_div(E, ch) > T_max) ch = ceil_div(E, T_max);      // never more chunks than partial slots
+    dyn[DYN_CH] = ch; dyn[DYN_T] = ceil_div(E, ch); dyn[DYN_HEAVY] = 16u * ch; dyn[DYN_E] = E; dyn[DYN_NMULTI] = 0;
 }
 // buckets with at least dyn[DYN_HEAVY] terms -> heavy[] (the sweep sort counts before the pair total is known, so it cannot flag them itself)
 __global__ void __launch_bounds__(256) k_flag_heavy(const uint32_t *__restrict__ off, uint32_t NB, const uint32_t *__restrict__ dyn, uint32_t *__restrict__ heavy, uint32_t heavy_cap) {

@@ -45,9 +45,22 @@ struct PsParams {
 
 // about a thousand partitions (P4 runs one block per partition) while a partition keeps at least 32 buckets
 inline int ps_part_log(uint32_t NB) { int lg = 0; while ((1u << lg) < NB) lg++; int pl = lg - 10; return pl < 5 ? 5 : (pl > PS_PART_LOG_MAX ? PS_PART_LOG_MAX : pl); }
+// P4 with write combining when the average partition is long (n >= 2^23 at c = 20): decided from the worst-case pair count, the direct path is right for sparse vectors
+inline bool ps_use_wc(size_t n, int W, uint32_t P) { return ((uint64_t)n * (uint64_t)W) / P >= PS_WC_MIN_PAIRS; }
+// dynamic LDS of P3 (k_ps_scatter1): histogram, prefix, cursors and first slots of the P partitions, then the tile's staged pairs
+// (W = 13: 69 KB, two blocks per CU; sized for PS_MAX_W it was 81 KB and one)
+inline size_t ps_scatter_lds_bytes(uint32_t P, int W) { return ((size_t)4 * P + 2) * 4 + (size_t)PS_TILE * (size_t)W * 8; }
+constexpr size_t PS_SCATTER_LDS_MAX = 160 * 1024 - 2048;      // what launch_psort allows P3 (the CU's 160 KB less its static share); a shape beyond it cannot be launched
+// the partition sort serves a shape of W windows and NB buckets when its pairs fit the staging of P3 (PS_MAX_W) and P3's LDS fits a CU: the plain pipeline at a
+// forced width of 22 has 12288 partitions, whose four counter arrays alone are 192 KB — that launch would never run, so the sweeps serve it (plain_geometry)
+inline bool plain_psort_fits(int W, uint32_t NB) {
+    const int pl = ps_part_log(NB);
+    return W <= PS_MAX_W && ps_scatter_lds_bytes((NB + (1u << pl) - 1) >> pl, W) <= PS_SCATTER_LDS_MAX;
+}
 // cnt1 / off1: P * ntiles + 1 words; bsums: scan_blocks(P * ntiles) + 2 words; pairs: n * W x 8 B; off: NB + 1; entries: n * W
-void launch_psort(hipStream_t s, const PsParams &q, uint32_t NB, uint32_t *cnt1, uint32_t *off1, uint32_t *bsums, void *pairs, uint32_t *off, uint32_t *entries,
-                  uint32_t heavy_thr, uint32_t *heavy, uint32_t heavy_cap, const uint32_t *dyn_args = nullptr, uint32_t *dyn = nullptr);
+// place: P4's placement, 0 = by ps_use_wc (what every caller of the product takes), 1 = direct, 2 = write combining (development hooks); returns the form that ran (1 or 2)
+int launch_psort(hipStream_t s, const PsParams &q, uint32_t NB, uint32_t *cnt1, uint32_t *off1, uint32_t *bsums, void *pairs, uint32_t *off, uint32_t *entries,
+                  uint32_t heavy_thr, uint32_t *heavy, uint32_t heavy_cap, const uint32_t *dyn_args = nullptr, uint32_t *dyn = nullptr, int place = 0);
 // out[i] = (bases[i * aff_stride + flag_word] != 0): the identity flags of n prepared records as one byte each (built once per table)
 void launch_id_flags(hipStream_t s, const uint32_t *bases, int aff_stride, int flag_word, size_t n, uint8_t *out);
 // out[i] = fingerprint of raw point i (psort_kernels.hip.h k_raw_record_hash; the host-side twin is rec_fingerprint of bases_cache.hpp); words = 64-bit words per coordinate

@@ -118,6 +118,37 @@ int32_t dgpu_selftest_g1_sum(const uint64_t *pts_xy /* n*12 */, const uint8_t *n
  * DGPU_E_BADARG: unknown op, a row shape that is not the op's, or a stress the op does not take (any other G among them). */
 int32_t dgpu_selftest_arith(int32_t op, int32_t stress, const uint64_t *in, size_t in_words, size_t n, uint64_t *out, size_t out_words);
 
+/* ---- the sort stage of the bucket MSMs on its own (crypto_amd/csrc/dev_sort_hooks.hip.h; tests/test_gpu_sort_stage.py, tests/util.py sort_model / check_sort) ----
+ * Each device hook takes a slot, allocates its own buffers, fills every output buffer AND DGPU_SELFTEST_GUARD words behind it with DGPU_SELFTEST_SENTINEL on
+ * the slot's stream, runs the product's launchers (crypto_amd/csrc/sort_launch.hip.h) unchanged, copies everything back, guards included, and frees its buffers:
+ * every output array below is `its length + DGPU_SELFTEST_GUARD` words long.  The two words the product's drivers clear before a sort (heavy[0] and the bad
+ * word) are cleared here too. */
+#define DGPU_SELFTEST_GUARD 64
+#define DGPU_SELFTEST_SENTINEL 0xA5A5A5A5u
+/* The two-level partition sort (launch_psort) of n scalars (8 u32 each) at width c (16..22) with W = 255 / c + 1 windows.  key_wstride = 0: the one bucket set of
+ * a table (NB = 2^(c-1)); 2^(c-1): one set per window (NB = W 2^(c-1)).  val = (val_base + w val_wstride + i) | sign << 31.  idflag (flag_base + n bytes, or
+ * NULL: keep every row): idflag[flag_base + i] != 0 drops row i.  part_log, P and ntiles are computed as the product's drivers do.  dyn_args = NULL: the static
+ * heavy_thr (0xffffffff: nothing flagged) and no dyn; else the six words {fixed_ch, min_chunk, max_chunks, lanes_per_chunk, T_max, nb_shared} and dyn[0..4].
+ * place: 0 = the product's rule, 1 = direct placement, 2 = write combining; *placed = the one that ran (1 or 2).
+ * Out: off[NB + 1], entries[n W], heavy[1 + heavy_cap], dyn[5] (with dyn_args), bad[1], each followed by its guard.  DGPU_E_BADARG for a shape the product's
+ * drivers never launch (W > 16, a scatter whose LDS does not fit) or n > 2^22. */
+int32_t dgpu_selftest_psort(const uint32_t *scalars, size_t n, int32_t c, int32_t W, uint32_t key_wstride, uint32_t val_base, uint32_t val_wstride,
+                            const uint8_t *idflag, uint32_t flag_base, uint32_t heavy_thr, uint32_t heavy_cap, const uint32_t *dyn_args, int32_t place,
+                            uint32_t *off, uint32_t *entries, uint32_t *heavy, uint32_t *dyn, uint32_t *bad, int32_t *placed);
+/* The sweep route of the plain pipeline for n scalars (at most 2^20) at width c (7..22), with the geometry of plain_geometry (g2 != 0: G2's accumulate geometry),
+ * in the order msm_device_ranges launches it: digit codes (bases: n prepared base records of 32 (G1) / 64 (G2) words whose flag word drops a row, or NULL),
+ * count sweep, scan, chunk rule (fixed_ch: 0 = the rule, else kept as dgpu_set_chunk's), k_flag_heavy, scatter sweep.  heavy_cap = 0: the geometry's
+ * (n W / 256 + 1).  Out: off[NB + 1], cursor[NB], entries[n W], heavy[1 + heavy_cap], dyn[5], bad[1], each followed by its guard; NB = W 2^(c-1). */
+int32_t dgpu_selftest_sort_sweep(const uint32_t *scalars, size_t n, int32_t c, int32_t g2, const uint32_t *bases, uint32_t fixed_ch, uint32_t heavy_cap,
+                                 uint32_t *off, uint32_t *cursor, uint32_t *entries, uint32_t *heavy, uint32_t *dyn, uint32_t *bad);
+/* launch_scan over NB counters (1 .. 2^26): off[NB + 1] and, with_cursor != 0, cursor[NB], each followed by its guard; with_cursor = 0 passes no cursor buffer. */
+int32_t dgpu_selftest_scan(const uint32_t *cnt, size_t NB, int32_t with_cursor, uint32_t *off, uint32_t *cursor);
+/* launch_dyn_chunk on the pair count E: dyn[0..4] = chunk length, chunks, heavy threshold, E, 0, followed by the guard. */
+int32_t dgpu_selftest_dyn_chunk(uint32_t E, uint32_t fixed_ch, uint32_t min_chunk, uint32_t max_chunks, uint32_t lanes_per_chunk, uint32_t T_max, uint32_t nb_shared, uint32_t *dyn);
+/* host, no device: choose_chunk(E, min_chunk, max_chunks, lanes_per_chunk, nb_shared), the host's copy of the rule (a chunk forced by dgpu_set_chunk is returned
+ * as it is); DGPU_E_BADARG (negative) for min_chunk < 1 or lanes_per_chunk outside 1 .. 131072. */
+int32_t dgpu_selftest_choose_chunk(uint64_t E, int32_t min_chunk, uint64_t max_chunks, int32_t lanes_per_chunk, uint64_t nb_shared);
+
 /* ---- fault injection (tests/test_gpu_fault_paths.py): the k-th hipMalloc from now and the count - 1 after it fail ---- */
 int32_t dgpu_dev_fail_alloc_after(int64_t k, int64_t count);
 

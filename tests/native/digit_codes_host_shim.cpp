@@ -47,4 +47,9 @@ int shim_ps_digits(int shape, const uint32_t *scalars, size_t n, const uint8_t *
     return 0;
 }
 int shim_ps_part_log(uint32_t NB) { return msm::ps_part_log(NB); }
+// the two rules of launch_psort (the write-combining placement, P3's dynamic LDS with the limit it is launched under) and plain_geometry's condition on them
+int shim_ps_use_wc(size_t n, int W, uint32_t P) { return msm::ps_use_wc(n, W, P) ? 1 : 0; }
+size_t shim_ps_scatter_lds_bytes(uint32_t P, int W) { return msm::ps_scatter_lds_bytes(P, W); }
+size_t shim_ps_scatter_lds_max(void) { return msm::PS_SCATTER_LDS_MAX; }
+int shim_plain_psort_fits(int W, uint32_t NB) { return msm::plain_psort_fits(W, NB) ? 1 : 0; }
 }

@@ -208,3 +208,28 @@ def test_plain_pipeline_partition_sort(c, big_g1, twin):
     finally:
         lib().dgpu_set_window_bits(0)
         ca.bases_cache_clear()
+
+
+def test_plain_pipeline_forced_width_22_takes_the_sweeps(big_g1, twin):
+    """a forced width of 22 at 2^17 terms and more: the partition sort's scatter would need 245 KB of LDS for its 12288 partitions (sort_launch.hip.h
+    ps_scatter_lds_bytes, plain_psort_fits; tests/test_sort_stage_host.py has the arithmetic), a launch that cannot run — plain_geometry leaves the shape to the
+    sweeps.  The stage timers show the route, the closed form the point."""
+    G, curve, c = O.G1, ca.G1, 22
+    bases, k0, d = big_g1
+    W, B, _, _ = U.window_shape(c)
+    ec = EdgeCase(c, NP, 8600 + c, part_logs=[U.ps_part_log(B), U.ps_part_log(W * B)])
+    ints = ec.mixed
+    assert U.edge_coverage_missing([ints[p] for p in ec.pos], c, part_log=U.ps_part_log(W * B), per_window=True) == []
+    sc = limbs(ints)
+    assert lib().dgpu_set_window_bits(c) == 0
+    try:
+        ca.bases_cache_clear()
+        ca.prof.enable(True); ca.prof.reset()
+        r = ca.msm_bigint(curve, bases[:NP], sc)
+        stages = ca.prof.read()
+        assert U.jac_to_model(G, r) == U.closed_form(G, sc, k0, d)
+        assert "msm.count" in stages and "msm.scatter" in stages and "msm.psort" not in stages, sorted(stages)
+    finally:
+        ca.prof.enable(False)
+        lib().dgpu_set_window_bits(0)
+        ca.bases_cache_clear()

@@ -443,3 +443,128 @@ def acc_layout(scalars, c, ch, shared, identity_rows=()):
             k.cls = "direct" if k.pieces == 1 else "fixup"
         L.buckets[b] = k
     return L
+
+
+# ---- the sort stage of the bucket MSMs as a model (crypto_amd/csrc/psort_kernels.hip.h, sort_kernels.hip.h; the hooks dgpu_selftest_psort / _sort_sweep / _scan /
+# ---- _dyn_chunk of include/dock_gpu_dev.h; tests/test_gpu_sort_stage.py, tests/test_sort_stage_host.py) ------------------------------------------------------
+SORT_GUARD = 64                      # DGPU_SELFTEST_GUARD: words behind every output buffer of the hooks
+SORT_SENTINEL = 0xA5A5A5A5           # DGPU_SELFTEST_SENTINEL: what the hooks fill outputs and guards with before the launch
+RESIDENT_ACC_LANES = 131072          # the lanes k_accumulate keeps resident (dyn_chunk.hip.h)
+
+
+def scalar_words(vals):
+    """integers below 2^256 -> (n, 8) little-endian 32-bit words, the layout the kernels read"""
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint32).reshape(-1, 8).copy()
+
+
+def signed_digit_matrix(scalars, c):
+    """signed_digits for a whole vector at once: (n, W) int64 (bit 255 is masked, as the kernels do).  The windows come from the bit matrix of the scalars, the
+    carry runs window by window over all rows; a sample of rows is compared with signed_digits itself"""
+    W, B, M, _ = window_shape(c)
+    n = len(scalars)
+    raw = np.frombuffer(b"".join((int(s) & ((1 << 255) - 1)).to_bytes(32, "little") for s in scalars), dtype=np.uint8).reshape(n, 32)
+    bits = np.unpackbits(raw, axis=1, bitorder="little")
+    bits = np.concatenate([bits, np.zeros((n, W * c - 256), np.uint8)], axis=1) if W * c > 256 else bits[:, :W * c]
+    win = bits.reshape(n, W, c).astype(np.int64) @ (1 << np.arange(c, dtype=np.int64))
+    D = np.zeros((n, W), np.int64)
+    carry = np.zeros(n, np.int64)
+    for w in range(W):
+        v = win[:, w] + carry
+        carry = (v > B).astype(np.int64)
+        D[:, w] = v - (carry << c)
+    assert not carry.any()
+    for i in sorted(set(list(range(min(n, 24))) + [n - 1, n // 2, n // 3])):
+        assert D[i].tolist() == signed_digits(int(scalars[i]), c), i
+    return D
+
+
+def sort_model(scalars, c, key_wstride, val_base, val_wstride, idflag=None, flag_base=0):
+    """What the sort of the (bucket, term) pairs of integer `scalars` at width c must produce: (pairs, counts).  pairs: (E, 2) int64, sorted by (key, val), one
+    row per non-zero signed digit d of window w of row i: key = w key_wstride + |d| - 1 (key_wstride = 0: the one bucket set of a table; B: a set per window),
+    val = (val_base + w val_wstride + i) | sign << 31.  Rows with idflag[flag_base + i] != 0 are dropped.  counts: terms per bucket, NB = B or W B entries."""
+    W, B, _, _ = window_shape(c)
+    assert key_wstride in (0, B)
+    NB = W * B if key_wstride else B
+    n = len(scalars)
+    D = signed_digit_matrix(scalars, c)
+    live = np.ones(n, bool) if idflag is None else (np.asarray(idflag)[flag_base:flag_base + n] == 0)
+    on = (D != 0) & live[:, None]
+    i_idx, w_idx = np.nonzero(on)
+    d = D[i_idx, w_idx]
+    key = w_idx.astype(np.int64) * key_wstride + np.abs(d) - 1
+    val = (val_base + w_idx.astype(np.int64) * val_wstride + i_idx) | ((d < 0).astype(np.int64) << 31)
+    assert ((val & 0x7FFFFFFF) == val_base + w_idx * val_wstride + i_idx).all()          # the index stays below the sign bit
+    order = np.lexsort((val, key))
+    pairs = np.stack([key[order], val[order]], axis=1)
+    counts = np.bincount(key, minlength=NB).astype(np.int64)
+    assert len(counts) == NB
+    return pairs, counts
+
+
+def dyn_chunk_model(E, fixed_ch, min_chunk, max_chunks, lanes_per_chunk, T_max, nb_shared, trace=None):
+    """(ch, T, heavy, E, 0): the chunking of the accumulation for E sorted pairs, in unbounded integers, from the description of choose_chunk (dock_core.hip):
+    the shortest chunk of min_chunk terms, doubled (up to 4096) while there are more than max_chunks chunks; once the launch exceeds one round of the chip's
+    resident lanes the chunk count is snapped to whole rounds (rounded to nearest, at least one) and the length follows, if it lies in 16 .. 4096; on a shared
+    bucket set of nb_shared buckets ONE round is taken when the average run is at least half that round's chunk and the chunk is at most 4096.  A forced
+    length (fixed_ch) is kept.  On the device (k_dyn_chunk) there are never more chunks than T_max partial slots (T_max = 0: no cap); a bucket is heavy from
+    16 chunk lengths on.  trace: a set that receives the names of the branches taken."""
+    t = trace if trace is not None else set()
+    ceil = lambda a, b: -(-a // b)
+    ch = fixed_ch
+    if ch:
+        t.add("fixed")
+    else:
+        ch = min_chunk
+        while E // ch > max_chunks and ch < 4096:
+            ch *= 2
+            t.add("doubled")
+        if E // ch > max_chunks:
+            t.add("doubling stopped at 4096")
+        resident = RESIDENT_ACC_LANES // lanes_per_chunk
+        chunks = ceil(E, ch)
+        if chunks > resident:
+            rounds = max(1, (2 * chunks + resident) // (2 * resident))          # chunks / resident rounded to nearest, halves up
+            t.add("rounds up" if rounds * resident >= chunks else "rounds down")
+            length = ceil(E, rounds * resident)
+            if 16 <= length <= 4096:
+                ch = length
+                t.add("snapped")
+            else:
+                t.add("len below 16" if length < 16 else "len above 4096")
+        else:
+            t.add("one round or less")
+        if nb_shared:
+            run, one = E // nb_shared, ceil(E, resident)
+            if one > ch and 2 * run >= one and one <= 4096:
+                ch = one
+                t.add("shared: one round")
+            else:
+                t.add("shared: " + ("one <= ch" if one <= ch else "short runs" if 2 * run < one else "one > 4096"))
+    if T_max and ceil(E, ch) > T_max:
+        ch = ceil(E, T_max)
+        t.add("T_max binds")
+    elif T_max:
+        t.add("T_max free")
+    return ch, ceil(E, ch), 16 * ch, E, 0
+
+
+def check_sort(off, entries, NB, cap, pairs, counts, what=""):
+    """The device's off[NB + 1 + guard] and entries[cap + guard] (cap = n W slots) against sort_model's (pairs, counts): off starts at 0, never decreases and
+    ends at E; bucket by bucket the multiset of entries equals the model's (the order inside a bucket is the arrival order of LDS atomics); every slot from E
+    on and every guard word still holds the sentinel."""
+    off = np.asarray(off, np.uint32).astype(np.int64)
+    entries = np.asarray(entries, np.uint32).astype(np.int64)
+    E = len(pairs)
+    assert len(off) == NB + 1 + SORT_GUARD and len(entries) == cap + SORT_GUARD and E <= cap, what
+    assert off[0] == 0, (what, off[:4])
+    sizes = np.diff(off[:NB + 1])
+    assert (sizes >= 0).all(), (what, "off decreases at", np.nonzero(sizes < 0)[0][:8])
+    assert off[NB] == E, (what, "off[NB]", int(off[NB]), "model", E)
+    assert (sizes == counts).all(), (what, "bucket sizes differ at", np.nonzero(sizes != counts)[0][:8])
+    assert (off[NB + 1:] == SORT_SENTINEL).all(), (what, "guard of off[] written")
+    assert (entries[E:] == SORT_SENTINEL).all(), (what, "entries[] written at or past E", (E + np.nonzero(entries[E:] != SORT_SENTINEL)[0][:8]).tolist())
+    key = np.repeat(np.arange(NB, dtype=np.int64), sizes)
+    order = np.lexsort((entries[:E], key))
+    got = np.stack([key[order], entries[:E][order]], axis=1)
+    bad = np.nonzero((got != pairs).any(axis=1))[0]
+    assert len(bad) == 0, (what, "first differing pairs (device, model)", got[bad[:4]].tolist(), pairs[bad[:4]].tolist())
